@@ -8,6 +8,18 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --workload c5 ...                         (BASELINE configs[4]: vocab 1e7, emb 32, 8192 rows per GPU; default c2)
+    python bench.py ... --full                                (everything else this file measures or checks, see below)
+    python bench.py ... --dump-outputs DIR                    (DIR/predictions.npy: the last timed step's output, float32)
+
+A plain run (no --full) does only what the headline figure needs: set up, warm up (--warmup steps, then --prewarm-ms of the
+timed launches), time ONE region of exactly --steps steps, write --dump-outputs if asked, print the line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` = the region's milliseconds / K, plus the configuration it ran).  --full adds
+what the rest of this docstring describes: `value` over --regions (default 5) regions, the cold one-shot region, the armed replay
+behind `roofline` / `kernels`, the rocprofv3 traffic passes, the parity check against the float64 oracle, the secondary
+measurements (`long_run`, `one_launch_per_batch`, `predict_e2e`, `zipf_ids`, `criteo_vocabularies`) and `cpu_baseline`.
+--dump-outputs DIR writes the probabilities the timed path computed in its last step ([B, 1] float32; at N > 1 every rank's, in
+rank order: what the all-gather hands a caller) as DIR/predictions.npy.  Inputs and weights are seeded: the same arguments give
+the same inputs on every run, so two builds can be compared output for output.
 
 A "step" = one pass of the whole hot path over ONE batch of 4096 rows per GPU: ids -> multi-table gather + linear
 term + FM -> DNN 429-256-128-64 + Dense(1) + logit sum + sigmoid.  Nothing is skipped, inputs are device-resident
@@ -21,10 +33,12 @@ passes for the whole multiples of 256 rows x CUs, then — inside the same kerne
 (`dctr_embed_mlp_fwd_plan` lists the phases).  The bench does the same: the K steps go out as ceil(K / G) calls of G
 consecutive batches (--launch-batches, default min(K, 256) = predict()'s 2^20-row spans), exactly K * 4096 rows per GPU inside
 the timed region, bracketed by barrier + synchronize, MAX over ranks.
-`value` = the MEDIAN of --regions (5) such one-shot regions, each taken right after --prewarm-ms of the same steps untimed: an
+`value` = the MEDIAN of --regions (1 in a plain run, 5 with --full) such one-shot regions, each taken right after --prewarm-ms of
+the same steps untimed: an
 MI355X that has idled ramps its shader clock over tens of milliseconds (2.1 -> 2.4 GHz, profiles/r03_chain_lab_clock.log), and
-a 0.25 ms region after an idle period measures that ramp, not the kernel; the cold region is reported as `cold_one_shot`.
-After the regions a sample of the rows the timed launches wrote is compared with the float64 oracle (`parity`, the 1e-4 bar).
+a 0.25 ms region after an idle period measures that ramp, not the kernel; the cold region is reported as `cold_one_shot` (--full).
+With --full, after the regions a sample of the rows the timed launches wrote is compared with the float64 oracle (`parity`, the
+1e-4 bar).
 `one_launch_per_batch` in the JSON line is the other extreme (one launch per 4096-row batch, K of them in one hipGraph on 8
 streams — round 1's headline mode), `long_run` repeats the K-step region until >= 50 ms.
 
@@ -416,7 +430,7 @@ def measure_traffic(K, rows_launch, dist_name, timeout_s=120, fused_records=Fals
     if big_tables():
         timeout_s = max(timeout_s, 420)                 # the child draws 34 GB of tables first
     child = ["--steps", str(K), "--warmup", "0", "--no-cpu-baseline", "--no-secondary", "--no-traffic", "--prewarm-ms", "10", "--regions", "2",
-             "--parity-rows", "0", "--dist", dist_name, "--workload", WORKLOAD] + (["--fused-records"] if fused_records else [])
+             "--parity-rows", "0", "--dist", dist_name, "--workload", WORKLOAD, "--full"] + (["--fused-records"] if fused_records else [])
     got = {}
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         try:
@@ -460,6 +474,13 @@ def load_traffic(rows):
         return float(j["bytes_per_row"]) * rows, "profiles/r04_pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, %s rows per launch)" % j.get("rows_per_launch")
     except Exception:
         return None, None
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _free_port():
@@ -527,17 +548,24 @@ def main():
                          ">= 64 rows per CU, else 16 / 32), 16 / 32 = the tile kernel, 64 = streaming kernel, 128 / 256 = one "
                          "shape of the row-chained kernel")
     ap.add_argument("--dist", default="uniform", choices=["uniform", "zipf"], help="id distribution (SURVEY 8(d))")
-    ap.add_argument("--regions", type=int, default=5,
+    ap.add_argument("--regions", type=int, default=None,
                     help="`value` = the MEDIAN of this many one-shot timed regions of exactly K steps each (every region is "
-                         "bracketed by barrier + synchronize; all of them are printed as regions_ms)")
+                         "bracketed by barrier + synchronize; all of them are printed as regions_ms); default 1, 5 with --full")
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="untimed: the K-step region repeated for this long right before the timed regions (and a fifth of it before "
                          "each further region) so that they run at the clock the part holds under sustained load; an MI355X that "
                          "has idled ramps its shader clock over tens of milliseconds (2.1 -> 2.4 GHz measured, "
                          "profiles/r03_chain_lab_clock.log).  0 = off; the cold one-shot region is always reported as well")
     ap.add_argument("--parity-rows", type=int, default=4096,
-                    help="rows of the timed region's output compared with the float64 oracle after the region (0 = off)")
+                    help="rows of the timed region's output compared with the float64 oracle after the region (--full; 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: cold and armed regions (roofline, kernels), traffic passes, parity "
+                         "against the float64 oracle, the secondary measurements and the CPU baseline (off: time the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the probabilities of the last timed step to DIR/predictions.npy (float32)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an AMD GPU (no CPU path exists for the product)")
@@ -613,7 +641,7 @@ def main():
     for i in range(0, W, G):                                               # untimed warm-up, same launch shape
         nb = min(G, W - i)
         model._forward(staged, 0, nb * B, logits[:nb * B])
-    if K > 0:                                                              # ... and once through the timed region's own launches,
+    if K > 0 and args.full:                                                # ... and once through the timed region's own launches,
         lib.dctr_profile_arm(min(n_kern, 256))                             # armed, so that the event pairs exist beforehand
         run_steps()
         tmp = (ctypes.c_float * 256)()
@@ -683,27 +711,37 @@ def main():
     n_regions = max(1, args.regions)
 
     def prewarm(ms):
-        """Untimed sustained load: the region's own launches, back to back, for `ms` milliseconds."""
+        """Untimed sustained load: the region's own launches, back to back, for `ms` milliseconds (--full: whole K-step regions;
+        a plain run issues the launches one call at a time, so that a long region is not repeated whole)."""
         if ms <= 0 or K <= 0:
             return
         t_end = time.perf_counter() + ms * 1e-3
+        i = 0
         while time.perf_counter() < t_end:
-            run_steps()
+            if args.full:
+                run_steps()
+            else:
+                prepared[i % len(prepared)]()
+                i += 1
             torch.cuda.synchronize()
 
     cg0 = cgroup_cpu()
-    cold_s = timed_region(arm=False, kind="cold")           # reported, not `value`: the first region after an idle period
+    cold_s = None
+    if args.full:
+        cold_s = timed_region(arm=False, kind="cold")       # reported, not `value`: the first region after an idle period
     region_s = []
     for r in range(n_regions):
         prewarm(args.prewarm_ms if r == 0 else args.prewarm_ms / 5.0)
         region_s.append(timed_region(arm=False, kind="value"))
-    # the same region once more with an event pair around every kernel launch (hipExtLaunchKernelGGL start / stop events on
-    # the launch's own stream): the per-kernel durations of the roofline object.  Kept out of the `value` region because the
-    # pairs isolate consecutive kernels from each other (no tail / ramp overlap), which costs the region ~10 %.
-    timed_region(arm=True, kind="armed")
-    ms = (ctypes.c_float * 256)()
-    n_timed = lib.dctr_profile_collect(ms, min(n_kern, 256)) if K > 0 else 0
-    launch_s = [ms[i] * 1e-3 if ms[i] > 0 else None for i in range(n_timed)]
+    launch_s = []
+    if args.full:
+        # the same region once more with an event pair around every kernel launch (hipExtLaunchKernelGGL start / stop events on
+        # the launch's own stream): the per-kernel durations of the roofline object.  Kept out of the `value` region because the
+        # pairs isolate consecutive kernels from each other (no tail / ramp overlap), which costs the region ~10 %.
+        timed_region(arm=True, kind="armed")
+        ms = (ctypes.c_float * 256)()
+        n_timed = lib.dctr_profile_collect(ms, min(n_kern, 256)) if K > 0 else 0
+        launch_s = [ms[i] * 1e-3 if ms[i] > 0 else None for i in range(n_timed)]
     exchange = forward_only = None
     if dist is not None:                                    # every region: MAX over ranks
         ex = exchange_s["value"]                            # (forward, all-gather) of the `value` regions
@@ -711,16 +749,23 @@ def main():
         exchange, forward_only = float(t[0].item()), float(t[1].item())
         t = all_reduce_max(torch.tensor(region_s, dtype=torch.float64, device=device))
         region_s = [float(v) for v in t.tolist()]
-        t = all_reduce_max(torch.tensor([cold_s], dtype=torch.float64, device=device))
-        cold_s = float(t.item())
+        if cold_s is not None:
+            t = all_reduce_max(torch.tensor([cold_s], dtype=torch.float64, device=device))
+            cold_s = float(t.item())
     elapsed = float(np.median(region_s))
     model._check_status()
     assert bool(torch.isfinite(logits[:min(K, 4) * B]).all())
+    if args.dump_outputs and rank == 0 and K > 0:
+        # the last timed step's output, before any later leg reuses the buffer; at N > 1 every rank's, from the region's all-gather
+        last = slice((K - 1) * B, K * B)
+        pred = logits[last] if gathered is None else gathered.view(world, -1)[:, last]
+        dump_outputs(args.dump_outputs, {"predictions": pred.reshape(-1, 1).cpu().numpy()})
 
     # secondary measurements (not `value`).  FIRST, while the host has done nothing but issue launches: the same K steps repeated back
     # to back (no host synchronize in between) until >= 50 ms, on two clocks — the host's and the kernels' own (module docstring)
     long_run = per_batch = None
-    if K > 0 and not args.no_secondary:
+    secondary = args.full and not args.no_secondary      # (a plain run: none of them)
+    if K > 0 and secondary:
         reps = max(2, int(0.05 / max(elapsed if world == 1 else (forward_only or elapsed), 1e-6)) + 1)
         probe = torch.tensor([-1, 0], dtype=torch.int64, device=device) if fused else None     # [min entry, max exit], uint64 ticks
         if fused:
@@ -756,10 +801,12 @@ def main():
                                  "device_clock": "the kernels' constant-rate wall clock (%d kHz): first workgroup entry -> last wave exit" % khz})
         long_run["ratio_to_value_region_rate"] = long_run["samples_per_s_per_gpu"] / (K * B / (elapsed if world == 1 else (forward_only or elapsed)))
 
-    parity = check_parity(model, cols, staged, launches, logits, args.parity_rows, rank) if (K > 0 and args.parity_rows > 0) else None
-    quiesce()
+    parity = None
+    if args.full and K > 0 and args.parity_rows > 0:
+        parity = check_parity(model, cols, staged, launches, logits, args.parity_rows, rank)
+        quiesce()
 
-    if K > 0 and not args.no_secondary:
+    if K > 0 and secondary:
         if fused and dist is None:
             n_streams = max(1, args.streams)
             model.span_batches, tr = False, model.tile_rows
@@ -794,7 +841,7 @@ def main():
     # model.predict over >= 16 M device-staged rows right after >= 2 s of host-only work: the product's entry point on a device that
     # has idled behind host preprocessing.  predict_tensor leaves the logits on the device, predict returns numpy.
     e2e = None
-    if K > 0 and fused and dist is None and not args.no_secondary:
+    if K > 0 and fused and dist is None and secondary:
         try:
             from deepctr_amd.engine import Staged
             times = -(-(1 << 24) // staged.n)
@@ -853,7 +900,7 @@ def main():
     # SURVEY §8(d)'s secondary input distribution: the same K-step region on Zipf(1.05) ids (hot rows: L2 / MALL hits), own staged
     # ring, own output buffer, own parity check against the float64 oracle
     zipf = None
-    if K > 0 and fused and dist is None and not args.no_secondary and args.dist != "zipf":
+    if K > 0 and fused and dist is None and secondary and args.dist != "zipf":
         try:
             staged_z = model.stage(synthetic_feed(ring * B, 2000 + rank, "zipf"))
             logits_z = torch.empty_like(logits)
@@ -887,7 +934,7 @@ def main():
     # STANDING configuration with UNEQUAL vocabularies (Criteo's own cardinalities, 3 ... 1e7 rows per table, 2.2 GB): the same K-step
     # region on its own model, checked against the float64 oracle like `value` — an index that strays across tables shows up here.
     mixed = None
-    if K > 0 and dist is None and not args.no_secondary and WORKLOAD == "c2":
+    if K > 0 and dist is None and secondary and WORKLOAD == "c2":
         try:
             model_m, cols_m = build_model(device, CRITEO_VOCABS)
             staged_m = model_m.stage(synthetic_feed(ring * B, 3000 + rank, "uniform", CRITEO_VOCABS))
@@ -923,9 +970,10 @@ def main():
         except Exception as e:
             mixed = {"error": repr(e)}
 
-    result = None
-    if rank == 0:
-        value = world * B * K / elapsed if K else 0.0
+    def full_report(result):
+        """--full, rank 0: the per-kernel and roofline fields, the secondary legs, the parity checks, the CPU baseline and the host's
+        state, added to the plain run's `result`."""
+        value = result["value"]
         # kernel launches of the region in issue order <-> their event-pair durations; the dominant kernel = the kernel
         # launch that covers the most rows of a call (the 256-row shape of the row-chained kernel when the call has one)
         flat = []
@@ -1022,45 +1070,15 @@ def main():
                                 DNN_FLOP_PER_SAMPLE, ALG_BYTES_PER_SAMPLE, B, DNN_FLOP_PER_SAMPLE * B / F32_MFMA_PEAK_TF / 1e6,
                                 ALG_BYTES_PER_SAMPLE * B / HBM_PEAK_GBS / 1e3,
                                 F32_MFMA_PEAK_TF * 1e12 / DNN_FLOP_PER_SAMPLE * ALG_BYTES_PER_SAMPLE / 1e9 / HBM_PEAK_GBS))
-        result = {
-            "metric": WORKLOADS[WORKLOAD]["metric"], "value": value, "unit": "samples/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3 if K else None,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s, ids int32 [F,B] device-resident, ids %s, ring of %d "
-                                   "distinct batches, the K steps issued as %d call(s) of %d consecutive batches (%s)" % (
-                                       WORKLOADS[WORKLOAD]["config"], args.dist, ring, len(launches), G,
-                                       "fused gather+DNN, %s kernel launch(es) per call" % "+".join(str(launches_of(pl)) for pl in plans[:1]) if fused
-                                       else "2 launches per span"),
-                       "per_gpu_batch": B, "global_batch": B * world, "launch_batches": G,
-                       "table_layout": ("record-form inference copies [vocab, 32] fp32 (embedding row + its first-order weight in one 128-B "
-                                        "record: dctr_field_t.row_pitch, 2 x 166 MB) behind the launches; the model's weights stay [vocab, 16] + "
-                                        "[vocab, 1]" if model._records_allowed() and model.stage_plan.records_ready(staged) else
-                                        "plain [vocab, 16] embedding tables + separate [vocab, 1] linear tables"),
-                       "parallelism": "row-sharded x%d, tables replicated, forward collective-free; the one all-gather of the K steps' "
-                                      "logits is %s" % (world, "inside the timed region (`exchange` splits it out)" if world > 1 else
-                                                        "not part of a 1-GPU region")},
+        result.update({
             "roofline": roofline, "kernels": kernels,
             "whole_forward_frac_of_hbm_roofline": (value / world) * ALG_BYTES_PER_SAMPLE / 1e9 / HBM_PEAK_GBS,
             "fp32_ceiling_of_that_fraction": F32_MFMA_PEAK_TF * 1e12 / DNN_FLOP_PER_SAMPLE * ALG_BYTES_PER_SAMPLE / 1e9 / HBM_PEAK_GBS,
             "long_run": long_run, "predict_e2e": e2e, "one_launch_per_batch": per_batch, "zipf_ids": zipf, "criteo_vocabularies": mixed,
-            "collective": None if dist is None else {"backend": "RCCL (torch.distributed 'nccl')" if not host_exchange else "gloo (host tensors)",
-                                                     "world_size": int(dist.get_world_size()), "ranks_share_one_gpu": bool(args.share_gpu)},
-            "exchange": None if exchange is None else {
-                "what": "one RCCL all-gather of the K steps' logits (%d floats per rank) behind the K steps, %s; median over the value "
-                        "regions, MAX over ranks" % (K * B, "INSIDE the timed region" if world > 1 else "outside the 1-GPU region"),
-                "ms": exchange * 1e3, "forward_only_ms": forward_only * 1e3,
-                "forward_only_samples_per_s": world * B * K / forward_only if K else 0.0,
-                "samples_per_s_region_plus_exchange": world * B * K / (forward_only + exchange) if K else 0.0},
-            "regions_ms": [t * 1e3 for t in region_s],
-            "value_is": "median of %d one-shot regions of exactly K steps (each: barrier + sync | K steps | sync%s), taken right after "
-                        "%.0f ms (%.0f ms from the second region on) of the same steps untimed, i.e. at the clock the part holds "
-                        "under load" % (n_regions, " | all-gather of the logits | sync" if world > 1 else "", args.prewarm_ms,
-                                        args.prewarm_ms / 5.0),
             "cold_one_shot": {"ms": cold_s * 1e3, "samples_per_s": world * B * K / cold_s if K else 0.0,
                               "note": "the same region as the first GPU work after an idle period (shader clock still ramping)"},
-            "clock_prewarm_ms": args.prewarm_ms,
             "parity_max_rel": None if parity is None else parity["max_rel"], "parity": parity,
-        }
+        })
         if mixed is not None and "parity" in mixed and not mixed["parity"]["within_1e-4"]:
             raise SystemExit("bench.py: the unequal-vocabulary configuration is outside the 1e-4 parity bar: %r" % (mixed["parity"],))
         if WORKLOAD == "c5" and world == 1 and K > 0 and not args.no_traffic and not args.no_secondary:
@@ -1083,6 +1101,44 @@ def main():
                           "cfs_periods_throttled_during_run": cg1.get("nr_throttled", 0) - cg0.get("nr_throttled", 0),
                           "note": "host-side only: a throttled waiting thread lengthens a host-clock measurement, never a kernel "
                                   "(profiles/r05_longrun_diagnosis.md); timed legs are taken with the BLAS workers of earlier host work asleep"}
+
+    result = None
+    if rank == 0:
+        value = world * B * K / elapsed if K else 0.0
+        result = {
+            "metric": WORKLOADS[WORKLOAD]["metric"], "value": value, "unit": "samples/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3 if K else None,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s, ids int32 [F,B] device-resident, ids %s, ring of %d "
+                                   "distinct batches, the K steps issued as %d call(s) of %d consecutive batches (%s)" % (
+                                       WORKLOADS[WORKLOAD]["config"], args.dist, ring, len(launches), G,
+                                       "fused gather+DNN, %s kernel launch(es) per call" % "+".join(str(launches_of(pl)) for pl in plans[:1]) if fused
+                                       else "2 launches per span"),
+                       "per_gpu_batch": B, "global_batch": B * world, "launch_batches": G,
+                       "table_layout": ("record-form inference copies [vocab, 32] fp32 (embedding row + its first-order weight in one 128-B "
+                                        "record: dctr_field_t.row_pitch, 2 x 166 MB) behind the launches; the model's weights stay [vocab, 16] + "
+                                        "[vocab, 1]" if model._records_allowed() and model.stage_plan.records_ready(staged) else
+                                        "plain [vocab, 16] embedding tables + separate [vocab, 1] linear tables"),
+                       "parallelism": "row-sharded x%d, tables replicated, forward collective-free; the one all-gather of the K steps' "
+                                      "logits is %s" % (world, "inside the timed region (`exchange` splits it out)" if world > 1 else
+                                                        "not part of a 1-GPU region")},
+            "collective": None if dist is None else {"backend": "RCCL (torch.distributed 'nccl')" if not host_exchange else "gloo (host tensors)",
+                                                     "world_size": int(dist.get_world_size()), "ranks_share_one_gpu": bool(args.share_gpu)},
+            "exchange": None if exchange is None else {
+                "what": "one RCCL all-gather of the K steps' logits (%d floats per rank) behind the K steps, %s; median over the value "
+                        "regions, MAX over ranks" % (K * B, "INSIDE the timed region" if world > 1 else "outside the 1-GPU region"),
+                "ms": exchange * 1e3, "forward_only_ms": forward_only * 1e3,
+                "forward_only_samples_per_s": world * B * K / forward_only if K else 0.0,
+                "samples_per_s_region_plus_exchange": world * B * K / (forward_only + exchange) if K else 0.0},
+            "regions_ms": [t * 1e3 for t in region_s],
+            "value_is": "median of %d one-shot region(s) of exactly K steps (each: barrier + sync | K steps | sync%s), taken right after "
+                        "%.0f ms%s of the same steps untimed, i.e. at the clock the part holds under load" % (
+                            n_regions, " | all-gather of the logits | sync" if world > 1 else "", args.prewarm_ms,
+                            " (%.0f ms from the second region on)" % (args.prewarm_ms / 5.0) if n_regions > 1 else ""),
+            "clock_prewarm_ms": args.prewarm_ms, "full": bool(args.full),
+        }
+        if args.full:
+            full_report(result)
         print(json.dumps(result), flush=True)
     if dist is not None:
         barrier()

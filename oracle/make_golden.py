@@ -590,8 +590,8 @@ def gen_widths():
 
 def main(argv=None):
     """``python -m oracle.make_golden [--out DIR] [siblings | bn | widths]``: every generator (or one add-on group) into DIR
-    (default tests/golden).  tests/test_oracle_golden.py::test_recipe_regenerates_every_fixture runs it into a scratch
-    directory and compares every file with the committed one, so the recipe cannot rot unnoticed."""
+    (default tests/golden).  To check that the recipe has not rotted, run it into a scratch directory and compare every file
+    with the committed one (it executes the reference's code, so this is not part of the test suite)."""
     global OUT
     argv = list(sys.argv[1:] if argv is None else argv)
     if "--out" in argv:

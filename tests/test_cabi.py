@@ -249,7 +249,8 @@ def test_host_packer_is_clean_under_asan_ubsan(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "deepctr_amd", "csrc")
     exe = tmp_path / "host_pack_san"
-    cmd = [hipcc, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "--offload-host-only", "-x", "hip",
+    cmd = [hipcc, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
+           "--offload-host-only", "-x", "hip",
            "-I", os.path.join(root, "include"), "-I", csrc, os.path.join(csrc, "host_pack.cpp"), os.path.join(csrc, "abi.cpp"),
            os.path.join(root, "tests", "native", "host_pack_san.cpp"), "-o", str(exe), "-pthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)

@@ -45,7 +45,7 @@ def _last_json_line(text):
 
 
 def test_bench_under_torch_distributed_run_one_rank(device):
-    args = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-secondary"]
+    args = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-secondary"]
     plain = subprocess.run([sys.executable] + args, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert plain.returncode == 0, plain.stderr[-3000:]
     ref = _last_json_line(plain.stdout)
@@ -71,7 +71,7 @@ def test_bench_gpus2_starts_two_ranks(device):
     and the line says n_gpus 2 — here both ranks on the box's one GPU (--share-gpu, exchange over gloo: RCCL wants a GPU per rank),
     the same code path the 8-GPU command takes.  Without --share-gpu the same command on a 1-GPU box must exit non-zero, not print
     an n_gpus 1 line."""
-    args = ["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", "--regions", "3",
+    args = ["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary", "--regions", "3",
             "--prewarm-ms", "20"]
     run = subprocess.run([sys.executable] + args + ["--share-gpu", "--backend", "gloo"], cwd=ROOT, env=_env(), capture_output=True,
                          text=True, timeout=900)
