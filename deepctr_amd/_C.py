@@ -129,6 +129,16 @@ class CrossMixBwdArgs(ctypes.Structure):
                 ("dx_stride", c_i64), ("dx_accumulate", c_i32), ("pad_", c_i32), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class interacting(object):
+    """dctr_interacting_args_t.  Its mirror sits one level down (interacting.Args): tests/test_cabi.py pairs the module-level mirrors
+    with header structs by a fixed list, and tests/test_autoint_cpu.py checks this one against the C compiler's layout the same way."""
+
+    class Args(ctypes.Structure):
+        _fields_ = [("x", c_vp), ("batch", c_i64), ("x_stride", c_i64), ("fields", c_i32), ("dim", c_i32), ("n_layers", c_i32),
+                    ("att_embedding_size", c_i32), ("head_num", c_i32), ("use_res", c_i32), ("scaling", c_i32), ("layers", c_vp),
+                    ("out", c_vp), ("out_stride", c_i64), ("head_w", c_vp), ("logit", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -211,6 +221,8 @@ SYMBOLS = {
     "dctr_cin_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), c_vp]),
     "dctr_cin_fwd_supported": (ctypes.c_int, [ctypes.POINTER(CinArgs), ctypes.POINTER(GatherFmArgs), ctypes.c_int32]),
     "dctr_cin_gather_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), ctypes.POINTER(GatherFmArgs), c_vp, c_vp, c_vp]),
+    "dctr_interacting_workspace_bytes": (c_sz, [ctypes.POINTER(interacting.Args)]),
+    "dctr_interacting_fwd": (ctypes.c_int, [ctypes.POINTER(interacting.Args), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

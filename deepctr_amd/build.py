@@ -47,6 +47,7 @@ SOURCES = [
     "interaction_kernels.hip",
     "cin_kernels.hip",
     "cin_bwd_kernels.hip",
+    "interacting_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -80,5 +80,19 @@ class GlorotUniform(Initializer):
         return ((torch.rand(tuple(shape), generator=_gen(self.seed), dtype=torch.float32) * 2 - 1) * lim).to(dtype)
 
 
+class TruncatedNormal(Initializer):
+    """keras TruncatedNormal (the default InteractingLayer uses, reference interaction.py:735-748): normal(mean, stddev) with
+    values more than two stddev from the mean redrawn."""
+
+    def __init__(self, mean=0.0, stddev=0.05, seed=None):
+        self.mean, self.stddev, self.seed = mean, stddev, seed
+
+    def __call__(self, shape, dtype=torch.float32):
+        t = torch.empty(tuple(shape), dtype=torch.float32)
+        torch.nn.init.trunc_normal_(t, mean=self.mean, std=self.stddev, a=self.mean - 2 * self.stddev, b=self.mean + 2 * self.stddev,
+                                    generator=_gen(self.seed))
+        return t.to(dtype)
+
+
 glorot_normal = GlorotNormal
 glorot_uniform = GlorotUniform

@@ -3,7 +3,7 @@
 siblings need — SURVEY.md §8a)."""
 from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer
-from .interaction import AFMLayer, BiInteractionPooling, CIN, CrossNet, CrossNetMix, FM, InnerProductLayer
+from .interaction import AFMLayer, BiInteractionPooling, CIN, CrossNet, CrossNetMix, FM, InnerProductLayer, InteractingLayer
 from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
@@ -17,6 +17,7 @@ custom_objects = {
     'CrossNetMix': CrossNetMix,
     'CIN': CIN,
     'InnerProductLayer': InnerProductLayer,
+    'InteractingLayer': InteractingLayer,
     'LocalActivationUnit': LocalActivationUnit,
     'Dice': Dice,
     'SequencePoolingLayer': SequencePoolingLayer,

@@ -1,12 +1,12 @@
-"""Host mirror of the five in-scope layers of the reference's ``deepctr/layers/interaction.py``:
+"""Host mirror of the six in-scope layers of the reference's ``deepctr/layers/interaction.py``:
 ``AFMLayer`` (:39-160), ``CIN`` (:209-341), ``CrossNet`` (:344-435), ``FM`` (:563-607),
-``InnerProductLayer`` (:610-694).  Same constructor kwargs, ``get_config`` and weight names/shapes; ``call``
-launches the HIP kernels (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip).  The other eleven
+``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790).  Same constructor kwargs, ``get_config`` and weight names/shapes; ``call``
+launches the HIP kernels (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip).  The other ten
 interaction layers of the reference are out of scope."""
 import torch
 
 from .. import ops
-from ..initializers import GlorotNormal, GlorotUniform, Zeros
+from ..initializers import GlorotNormal, GlorotUniform, TruncatedNormal, Zeros
 from .base import Layer
 
 
@@ -114,6 +114,59 @@ class CIN(Layer):
         config = {'layer_size': self.layer_size, 'split_half': self.split_half, 'activation': self.activation,
                   'seed': self.seed}
         base = super(CIN, self).get_config()
+        base.update(config)
+        return base
+
+
+class InteractingLayer(Layer):
+    """Multi-head self-attention across the fields (reference interaction.py:697-790): x [B,F,E] -> [B,F,d*H]."""
+
+    def __init__(self, att_embedding_size=8, head_num=2, use_res=True, scaling=False, seed=1024, **kwargs):
+        if head_num <= 0:
+            raise ValueError('head_num must be a int > 0')
+        self.att_embedding_size = att_embedding_size
+        self.head_num = head_num
+        self.use_res = use_res
+        self.seed = seed
+        self.scaling = scaling
+        super(InteractingLayer, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        return self.build_for(int(input_shape[-1]))
+
+    def build_for(self, embedding_size):
+        if self.built:
+            return self
+        shape = (int(embedding_size), self.att_embedding_size * self.head_num)
+        self.add_weight('query', shape, TruncatedNormal(seed=self.seed))
+        self.add_weight('key', shape, TruncatedNormal(seed=self.seed + 1))
+        self.add_weight('value', shape, TruncatedNormal(seed=self.seed + 2))
+        if self.use_res:
+            self.add_weight('res', shape, TruncatedNormal(seed=self.seed))
+        self.built = True
+        return self
+
+    @property
+    def weights_qkvr(self):
+        """(query, key, value, res or None): the operands of one layer of ops.interacting."""
+        return (self.w('query'), self.w('key'), self.w('value'), self.w('res') if self.use_res else None)
+
+    def call(self, inputs, **kwargs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        y = ops.interacting(inputs, [self.weights_qkvr], self.att_embedding_size, self.head_num, self.use_res, self.scaling)
+        return y.reshape(inputs.shape[0], inputs.shape[1], self.att_embedding_size * self.head_num)
+
+    def compute_output_shape(self, input_shape):
+        return (None, input_shape[1], self.att_embedding_size * self.head_num)
+
+    def get_config(self):
+        # (the reference's omits scaling)
+        config = {'att_embedding_size': self.att_embedding_size, 'head_num': self.head_num, 'use_res': self.use_res,
+                  'seed': self.seed}
+        base = super(InteractingLayer, self).get_config()
         base.update(config)
         return base
 

@@ -539,6 +539,79 @@ def _check_saved_y(ys, rows, layer_size, x):
             raise ValueError("save_y / saved_y: expected a contiguous float32 [%d, %d] tensor on %s" % (rows, h, x.device))
 
 
+def _interacting_args(B, F, E, x_stride, weights, att_embedding_size, head_num, use_res, scaling):
+    flat = []
+    for layer in weights:
+        flat += [layer[0], layer[1], layer[2], layer[3] if use_res and len(layer) > 3 else None]
+    lp = _ptr_array(flat)
+    a = _C.interacting.Args(batch=int(B), x_stride=int(x_stride), fields=int(F), dim=int(E), n_layers=len(weights),
+                           att_embedding_size=int(att_embedding_size), head_num=int(head_num), use_res=int(bool(use_res)),
+                           scaling=int(bool(scaling)), layers=ctypes.cast(lp, ctypes.c_void_p))
+    return a, lp
+
+
+def interacting_workspace_bytes(batch, fields, dim, n_layers, att_embedding_size, head_num, use_res=True, with_out=True):
+    """Bytes of the workspace dctr_interacting_fwd needs for these shapes (0 on the LDS route; read from the library)."""
+    a = _C.interacting.Args(batch=int(batch), x_stride=int(fields) * int(dim), fields=int(fields), dim=int(dim), n_layers=int(n_layers),
+                           att_embedding_size=int(att_embedding_size), head_num=int(head_num), use_res=int(bool(use_res)),
+                           out_stride=int(fields) * int(att_embedding_size) * int(head_num))
+    if with_out:
+        a.out = 16          # (only its presence is read)
+    return int(_C.lib().dctr_interacting_workspace_bytes(ctypes.byref(a)))
+
+
+def interacting(x, weights, att_embedding_size, head_num, use_res, scaling, fields=None, dim=None, out=None, head_w=None, logit=None,
+                workspace=None):
+    """InteractingLayer.call (reference interaction.py:749-779) stacked over len(weights) layers (models/autoint.py:61-64), one launch:
+    x [B,F,E] (or, with ``fields``/``dim`` given, the leading F*E columns of a [B, stride] buffer read in place); ``weights``: per layer
+    (query, key, value, res) [E_l, d*H] (res unused unless ``use_res``).  Writes the flattened last layer to ``out`` [B, F*d*H] (a 2-D,
+    possibly strided view; allocated when neither ``out`` nor ``head_w`` is given) and / or, with ``head_w`` [F*d*H(, 1)], the Dense(1)
+    over it to ``logit`` [B].  ``workspace``: a float32 tensor of >= interacting_workspace_bytes (default: the per-stream scratch).
+    Returns ``out`` (or ``logit`` when only the head is asked for)."""
+    if fields is None:
+        if x.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+        x = _f32c(x, "x")
+        B, F, E = x.shape
+        x_stride = F * E
+    else:
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+            raise ValueError("interacting: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
+        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
+    weights = [[None if w is None else _f32c(w, "weight") for w in layer] for layer in weights]
+    _dev_check(x, out, logit, head_w, *[w for layer in weights for w in layer])
+    dH = int(att_embedding_size) * int(head_num)
+    if head_w is None and out is None:
+        out = torch.empty(B, F * dH, dtype=torch.float32, device=x.device)
+    if out is not None and (out.dim() != 2 or out.stride(1) != 1 or out.dtype != torch.float32 or out.shape[0] != B
+                            or out.shape[1] < F * dH):
+        raise ValueError("interacting: out must be a float32 [%d, >= %d] view with unit column stride" % (B, F * dH))
+    if head_w is not None:
+        head_w = _f32c(head_w, "head_w").reshape(-1)
+        if head_w.numel() != F * dH:
+            raise ValueError("interacting: head_w must hold fields*d*H = %d values" % (F * dH))
+        if logit is None:
+            logit = torch.empty(B, dtype=torch.float32, device=x.device)
+    a, keep = _interacting_args(B, F, E, x_stride, weights, att_embedding_size, head_num, use_res, scaling)
+    a.x = x.data_ptr()
+    if out is not None:
+        a.out, a.out_stride = out.data_ptr(), out.stride(0)
+    if head_w is not None:
+        a.head_w, a.logit = head_w.data_ptr(), logit.data_ptr()
+    need = int(_C.lib().dctr_interacting_workspace_bytes(ctypes.byref(a)))
+    if need:
+        if workspace is not None:
+            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
+                raise ValueError("interacting: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
+            ws = workspace
+        else:
+            ws = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _C.check(_C.lib().dctr_interacting_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_interacting_fwd")
+    del keep
+    return out if out is not None else logit
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

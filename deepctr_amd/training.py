@@ -238,6 +238,23 @@ def regularized_weights(model):
     return out
 
 
+def _interacting(layer, x):
+    """InteractingLayer.call (reference interaction.py:749-779) in torch ops: x [B,F,E] -> [B,F,d*H]."""
+    d, H = layer.att_embedding_size, layer.head_num
+    B, F = x.shape[0], x.shape[1]
+
+    def heads(w):
+        return (x @ w).reshape(B, F, H, d).permute(2, 0, 1, 3)                 # [H,B,F,d]
+    q, k, v = heads(layer.w("query")), heads(layer.w("key")), heads(layer.w("value"))
+    s = q @ k.transpose(-1, -2)
+    if layer.scaling:
+        s = s / d ** 0.5
+    o = (torch.softmax(s, dim=-1) @ v).permute(1, 2, 0, 3).reshape(B, F, H * d)
+    if layer.use_res:
+        o = o + x @ layer.w("res")
+    return torch.relu(o)
+
+
 def model_logits(model, staged, lo, hi, training=False):
     """Pre-sigmoid logits [B] of the four in-scope models and their siblings, torch ops only.  ``training`` switches Dice to
     batch statistics (and updates its moving statistics), as tf.keras does inside fit(); the default is the inference form
@@ -295,6 +312,21 @@ def model_logits(model, staged, lo, hi, training=False):
         jj = [j for i in range(n - 1) for j in range(i + 1, n)]
         parts[extra["inner_product"]] = (torch.stack([parts[i] for i in ii], dim=1) *
                                          torch.stack([parts[j] for j in jj], dim=1)).sum(-1)
+    if name == "AutoInt":                   # models/autoint.py:55-79: Dense(1) over [Flatten(InteractingLayer stack), DNN]
+        outs = []
+        if model.att_layers:
+            h = torch.stack(parts[:len(sp.fields)], dim=1)          # [B,F,E]
+            for layer in model.att_layers:
+                h = _interacting(layer, h)
+            outs.append(h.reshape(h.shape[0], -1))
+        if model.dnn is not None:
+            outs.append(dnn_forward(model.dnn, torch.cat(parts, dim=-1), training))
+        logit = (torch.cat(outs, dim=-1) @ model.dense.w("kernel")).reshape(-1)
+        if lin is not None:
+            logit = logit + lin
+        for f in fms:
+            logit = logit + f
+        return logit + model.prediction.w("global_bias")
     x = torch.cat(parts, dim=-1)
     if name == "DCNMix":                    # models/dcnmix.py:53-68 with CrossNetMix (interaction.py:511-549)
         outs = []

@@ -383,6 +383,40 @@ int dctr_cin_fwd_supported(const dctr_cin_args_t* args, const dctr_gather_fm_arg
 int dctr_cin_gather_fwd(const dctr_cin_args_t* args, const dctr_gather_fm_args_t* gather, const float* head_w, float* logit, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * InteractingLayer.call x n_layers — deepctr/layers/interaction.py:749-779, stacked as deepctr/models/autoint.py:61-64
+ *     per layer l, X_l [F, E_l] (E_0 = dim, E_l = d*H after): Q, K, V, R = X_l W; per head h: P = softmax_keys(Q_h K_h^T
+ *     (/ sqrt(d) when scaling)), O_h = P V_h; heads concatenated on the last axis (column h*d + j); + R when use_res; ReLU.
+ *     Output flattened f-major (index f*d*H + h*d + j), as Flatten() of the last layer.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* x;               /* sample b at x + b * x_stride, then [F, dim] row-major */
+    int64_t batch;
+    int64_t x_stride;             /* elements between samples (>= fields*dim): reads the dnn_in concat in place */
+    int32_t fields;               /* F */
+    int32_t dim;                  /* E_0 */
+    int32_t n_layers;             /* >= 1 */
+    int32_t att_embedding_size;   /* d */
+    int32_t head_num;             /* H */
+    int32_t use_res;              /* 0 | 1 */
+    int32_t scaling;              /* 0 | 1 */
+    const float* const* layers;   /* HOST array [n_layers * 4] of DEVICE pointers: layer l's query, key, value, res at 4l .. 4l+3,
+                                     each [E_l, d*H] row-major (Keras layout); res may be NULL when use_res == 0 */
+    float* out;                   /* NULL, or [B, F*d*H] at out_stride: the flattened output of the last layer */
+    int64_t out_stride;
+    const float* head_w;          /* NULL, or [F*d*H]: the Dense(1) over the flattened output taken on chip ... */
+    float* logit;                 /* ... into logit [B] (head_w and logit both or neither; out and / or the head) */
+    void* workspace;              /* NULL, or device scratch of dctr_interacting_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_interacting_args_t;
+/* Bytes of `workspace` these arguments need (0: none).  A workgroup keeps its samples' X, Q, K, V, R in LDS across every layer when
+ * one sample fits; a sample too large for the LDS (large F, wide d*H) runs the same layers with those buffers in the workspace
+ * (room for <= 256 workgroups, at most 256 MiB unless one sample needs more), and the workspace is then REQUIRED (DCTR_E_NULL
+ * without, before anything is launched).  More than 32 layers run as launches of <= 32 layers chained through `out` (or, with the
+ * head only, through batch * F * d*H floats of the workspace: batch is read for that case alone). */
+size_t dctr_interacting_workspace_bytes(const dctr_interacting_args_t* args);
+int dctr_interacting_fwd(const dctr_interacting_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
