@@ -139,6 +139,19 @@ class interacting(object):
                     ("out", c_vp), ("out_stride", c_i64), ("head_w", c_vp), ("logit", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class bilinear(object):
+    """dctr_bilinear_args_t, one level down for the same reason as interacting.Args (tests/test_fibinet_cpu.py checks its layout)."""
+    ALL, EACH, INTERACTION = 0, 1, 2
+    TYPES = {"all": ALL, "each": EACH, "interaction": INTERACTION}
+    MODE_MODEL, MODE_SENET, MODE_LAYER = 0, 1, 2
+
+    class Args(ctypes.Structure):
+        _fields_ = [("x", c_vp), ("batch", c_i64), ("x_stride", c_i64), ("fields", c_i32), ("dim", c_i32), ("bilinear_type", c_i32),
+                    ("mode", c_i32), ("reduction_size", c_i32), ("dense_cols", c_i32), ("senet_w1", c_vp), ("senet_w2", c_vp),
+                    ("senet_bilinear_w", c_vp), ("bilinear_w", c_vp), ("out", c_vp), ("out_stride", c_i64), ("workspace", c_vp),
+                    ("workspace_bytes", c_sz)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -223,6 +236,8 @@ SYMBOLS = {
     "dctr_cin_gather_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), ctypes.POINTER(GatherFmArgs), c_vp, c_vp, c_vp]),
     "dctr_interacting_workspace_bytes": (c_sz, [ctypes.POINTER(interacting.Args)]),
     "dctr_interacting_fwd": (ctypes.c_int, [ctypes.POINTER(interacting.Args), c_vp]),
+    "dctr_bilinear_workspace_bytes": (c_sz, [ctypes.POINTER(bilinear.Args)]),
+    "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

@@ -48,6 +48,7 @@ SOURCES = [
     "cin_kernels.hip",
     "cin_bwd_kernels.hip",
     "interacting_kernels.hip",
+    "bilinear_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -3,7 +3,8 @@
 siblings need — SURVEY.md §8a)."""
 from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer
-from .interaction import AFMLayer, BiInteractionPooling, CIN, CrossNet, CrossNetMix, FM, InnerProductLayer, InteractingLayer
+from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FM, InnerProductLayer,
+                          InteractingLayer, SENETLayer)
 from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
@@ -18,6 +19,8 @@ custom_objects = {
     'CIN': CIN,
     'InnerProductLayer': InnerProductLayer,
     'InteractingLayer': InteractingLayer,
+    'SENETLayer': SENETLayer,
+    'BilinearInteraction': BilinearInteraction,
     'LocalActivationUnit': LocalActivationUnit,
     'Dice': Dice,
     'SequencePoolingLayer': SequencePoolingLayer,

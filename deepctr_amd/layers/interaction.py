@@ -1,8 +1,11 @@
-"""Host mirror of the six in-scope layers of the reference's ``deepctr/layers/interaction.py``:
+"""Host mirror of the eight in-scope layers of the reference's ``deepctr/layers/interaction.py``:
 ``AFMLayer`` (:39-160), ``CIN`` (:209-341), ``CrossNet`` (:344-435), ``FM`` (:563-607),
-``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790).  Same constructor kwargs, ``get_config`` and weight names/shapes; ``call``
-launches the HIP kernels (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip).  The other ten
+``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790), ``SENETLayer`` (:1067-1139), ``BilinearInteraction`` (:1142-1221).
+Same constructor kwargs, ``get_config`` and weight names/shapes; ``call`` launches the HIP kernels
+(deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip).  The other eight
 interaction layers of the reference are out of scope."""
+import itertools
+
 import torch
 
 from .. import ops
@@ -167,6 +170,113 @@ class InteractingLayer(Layer):
         config = {'att_embedding_size': self.att_embedding_size, 'head_num': self.head_num, 'use_res': self.use_res,
                   'seed': self.seed}
         base = super(InteractingLayer, self).get_config()
+        base.update(config)
+        return base
+
+
+class SENETLayer(Layer):
+    """Squeeze-excitation reweighting of the fields (reference interaction.py:1067-1139): a list of F tensors [B,1,E] -> the same
+    list, each field scaled by A2[f] = relu(relu(mean_E(x) W_1) W_2)[f]."""
+
+    def __init__(self, reduction_ratio=3, seed=1024, **kwargs):
+        self.reduction_ratio = reduction_ratio
+        self.seed = seed
+        super(SENETLayer, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if not isinstance(input_shape, list) or len(input_shape) < 2:
+            raise ValueError('A `AttentionalFM` layer should be called on a list of at least 2 inputs')
+        return self.build_for(len(input_shape), int(input_shape[0][-1]))
+
+    def build_for(self, field_size, embedding_size):
+        if self.built:
+            return self
+        self.filed_size = int(field_size)
+        self.embedding_size = int(embedding_size)
+        reduction_size = max(1, self.filed_size // self.reduction_ratio)
+        self.add_weight("W_1", (self.filed_size, reduction_size), GlorotNormal(seed=self.seed))
+        self.add_weight("W_2", (reduction_size, self.filed_size), GlorotNormal(seed=self.seed))
+        self.built = True
+        return self
+
+    @property
+    def weights_w12(self):
+        return (self.w("W_1"), self.w("W_2"))
+
+    def call(self, inputs, training=None, **kwargs):
+        if inputs[0].dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs[0].dim()))
+        x = _stack_fields(inputs)
+        B, F, E = x.shape
+        y = ops.senet_bilinear(x, senet_w=self.weights_w12).reshape(B, F, E)
+        return list(torch.split(y, 1, dim=1))
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+    def compute_mask(self, inputs, mask=None):
+        return [None] * self.filed_size
+
+    def get_config(self):
+        config = {'reduction_ratio': self.reduction_ratio, 'seed': self.seed}
+        base = super(SENETLayer, self).get_config()
+        base.update(config)
+        return base
+
+
+class BilinearInteraction(Layer):
+    """Bilinear interaction of every field pair (reference interaction.py:1142-1221): a list of F tensors [B,1,E] -> [B, F(F-1)/2, E],
+    p_ij = (x_i W) * x_j over i < j in itertools.combinations order, W shared ('all'), per i ('each') or per pair ('interaction')."""
+
+    def __init__(self, bilinear_type="interaction", seed=1024, **kwargs):
+        self.bilinear_type = bilinear_type
+        self.seed = seed
+        super(BilinearInteraction, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if not isinstance(input_shape, list) or len(input_shape) < 2:
+            raise ValueError('A `AttentionalFM` layer should be called on a list of at least 2 inputs')
+        return self.build_for(len(input_shape), int(input_shape[0][-1]))
+
+    def build_for(self, field_size, embedding_size):
+        if self.built:
+            return self
+        F, E = int(field_size), int(embedding_size)
+        shape, init = (E, E), (lambda: GlorotNormal(seed=self.seed))
+        if self.bilinear_type == "all":
+            self.add_weight("bilinear_weight", shape, init())
+        elif self.bilinear_type == "each":
+            for i in range(F - 1):
+                self.add_weight("bilinear_weight" + str(i), shape, init())
+        elif self.bilinear_type == "interaction":
+            for i, j in itertools.combinations(range(F), 2):
+                self.add_weight("bilinear_weight" + str(i) + '_' + str(j), shape, init())
+        else:
+            raise NotImplementedError("bilinear_type %r: expected 'all', 'each' or 'interaction'" % (self.bilinear_type,))
+        self.filed_size = F
+        self.built = True
+        return self
+
+    @property
+    def matrices(self):
+        """The layer's [E,E] weights in the order ops.senet_bilinear takes them (creation order = the reference's)."""
+        return list(self._weights.values())
+
+    def call(self, inputs, **kwargs):
+        if inputs[0].dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs[0].dim()))
+        x = _stack_fields(inputs)
+        B, F, E = x.shape
+        y = ops.senet_bilinear(x, bilinear_w=self.matrices, bilinear_type=self.bilinear_type)
+        return y.reshape(B, F * (F - 1) // 2, E)
+
+    def compute_output_shape(self, input_shape):
+        filed_size = len(input_shape)
+        return (None, filed_size * (filed_size - 1) // 2, input_shape[0][-1])
+
+    def get_config(self):
+        config = {'bilinear_type': self.bilinear_type, 'seed': self.seed}
+        base = super(BilinearInteraction, self).get_config()
         base.update(config)
         return base
 

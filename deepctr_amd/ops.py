@@ -612,6 +612,125 @@ def interacting(x, weights, att_embedding_size, head_num, use_res, scaling, fiel
     return out if out is not None else logit
 
 
+_BILINEAR_TABLES = {}
+
+
+def bilinear_table(matrices):
+    """DEVICE int64 table of the matrices' addresses (dctr_bilinear_args_t.bilinear_w).  Cached per tuple of addresses: in-place
+    updates (set_weights, the optimiser) keep a table valid, and a reallocated weight gives a new key, hence a fresh table."""
+    key = tuple(m.data_ptr() for m in matrices)
+    t = _BILINEAR_TABLES.get(key)
+    if t is None:
+        if len(_BILINEAR_TABLES) >= 64:      # (tables of freed weights must not pile up)
+            _BILINEAR_TABLES.clear()
+        t = _BILINEAR_TABLES[key] = torch.tensor(key, dtype=torch.int64).to(matrices[0].device)
+    return t
+
+
+def bilinear_weight_count(bilinear_type, fields):
+    """Matrices of one BilinearInteraction over `fields` inputs (reference interaction.py:1174-1185)."""
+    if bilinear_type not in _C.bilinear.TYPES:
+        raise NotImplementedError("bilinear_type %r: expected 'all', 'each' or 'interaction'" % (bilinear_type,))
+    return {"all": 1, "each": fields - 1, "interaction": fields * (fields - 1) // 2}[bilinear_type]
+
+
+def _bilinear_args(B, F, E, x_stride, bilinear_type, mode, r, dense_cols, out_stride):
+    return _C.bilinear.Args(batch=int(B), x_stride=int(x_stride), fields=int(F), dim=int(E),
+                            bilinear_type=_C.bilinear.TYPES.get(bilinear_type, -1), mode=int(mode), reduction_size=int(r),
+                            dense_cols=int(dense_cols), out_stride=int(out_stride))
+
+
+def senet_bilinear_width(fields, dim, mode, dense_cols=0):
+    P = fields * (fields - 1) // 2
+    return {_C.bilinear.MODE_MODEL: 2 * P * dim + dense_cols, _C.bilinear.MODE_SENET: fields * dim,
+            _C.bilinear.MODE_LAYER: P * dim}[mode]
+
+
+def senet_bilinear_workspace_bytes(batch, fields, dim, bilinear_type="interaction", mode=0, reduction_size=1):
+    """Bytes of the workspace dctr_bilinear_fwd needs for these shapes (0 on the LDS route; read from the library)."""
+    a = _bilinear_args(batch, fields, dim, fields * dim, bilinear_type, mode, reduction_size, 0,
+                       senet_bilinear_width(fields, dim, mode))
+    return int(_C.lib().dctr_bilinear_workspace_bytes(ctypes.byref(a)))
+
+
+def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bilinear_type="interaction", fields=None, dim=None,
+                   dense_cols=0, out=None, workspace=None):
+    """SENETLayer.call and / or BilinearInteraction.call (reference interaction.py:1113-1209), one launch.  x [B,F,E] (or, with
+    ``fields`` / ``dim``, the leading F*E columns of a [B, stride] buffer read in place, ``dense_cols`` more columns behind them).
+    ``senet_w`` = (W_1 [F,r], W_2 [r,F]); ``senet_bilinear_w`` / ``bilinear_w``: one BilinearInteraction's matrices [E,E] each (1, F-1
+    or F(F-1)/2 of them, by ``bilinear_type``).  Which are given picks the mode:
+      * all three (FiBiNET, models/fibinet.py:50-58): out [B, >= 2*P*E + dense_cols] = per pair [bilinear over the SENET output,
+        E floats | bilinear over x, E floats] (the two outputs concatenated on their last axis, flattened), then the dense columns;
+      * ``senet_w`` alone: out [B, >= F*E] = the SENET output, flattened;
+      * ``bilinear_w`` alone: out [B, >= P*E] = the bilinear interaction over x.
+    ``out`` is a 2-D (possibly strided) view, allocated when not given; ``workspace``: a float32 tensor of
+    >= senet_bilinear_workspace_bytes (default: the per-stream scratch).  Returns ``out``."""
+    if fields is None:
+        if x.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+        x = _f32c(x, "x")
+        B, F, E = x.shape
+        x_stride = F * E
+    else:
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+            raise ValueError("senet_bilinear: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
+        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
+    if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
+        mode = _C.bilinear.MODE_MODEL
+    elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_SENET
+    elif senet_w is None and bilinear_w is not None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_LAYER
+    else:
+        raise ValueError("senet_bilinear: give senet_w + senet_bilinear_w + bilinear_w, senet_w alone, or bilinear_w alone")
+    if mode != _C.bilinear.MODE_MODEL and dense_cols:
+        raise ValueError("senet_bilinear: dense_cols are copied by the three-weight (FiBiNET) form only")
+    tensors = [x]
+    r = 0
+    if senet_w is not None:
+        w1, w2 = (_f32c(w, "senet_w") for w in senet_w)
+        r = w1.shape[1]
+        if tuple(w1.shape) != (F, r) or tuple(w2.shape) != (r, F):
+            raise ValueError("senet_bilinear: senet_w must be W_1 [%d, r] and W_2 [r, %d]" % (F, F))
+        tensors += [w1, w2]
+    tables = []
+    for ws in (senet_bilinear_w, bilinear_w):
+        if ws is None:
+            tables.append(None)
+            continue
+        ws = [_f32c(w, "bilinear weight") for w in ws]
+        if len(ws) != bilinear_weight_count(bilinear_type, F) or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("senet_bilinear: bilinear_type %r over %d fields takes %d matrices [%d, %d]"
+                             % (bilinear_type, F, bilinear_weight_count(bilinear_type, F), E, E))
+        tensors += ws
+        tables.append(bilinear_table(ws))
+    _dev_check(out, *tensors)
+    width = senet_bilinear_width(F, E, mode, dense_cols)
+    if out is None:
+        out = torch.empty(B, width, dtype=torch.float32, device=x.device)
+    if out.dim() != 2 or out.stride(1) != 1 or out.dtype != torch.float32 or out.shape[0] != B or out.shape[1] < width:
+        raise ValueError("senet_bilinear: out must be a float32 [%d, >= %d] view with unit column stride" % (B, width))
+    a = _bilinear_args(B, F, E, x_stride, bilinear_type, mode, max(r, 1), dense_cols, out.stride(0))
+    a.x, a.out = x.data_ptr(), out.data_ptr()
+    if senet_w is not None:
+        a.senet_w1, a.senet_w2 = w1.data_ptr(), w2.data_ptr()
+    if tables[0] is not None:
+        a.senet_bilinear_w = tables[0].data_ptr()
+    if tables[1] is not None:
+        a.bilinear_w = tables[1].data_ptr()
+    need = int(_C.lib().dctr_bilinear_workspace_bytes(ctypes.byref(a)))
+    if need:
+        if workspace is not None:
+            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
+                raise ValueError("senet_bilinear: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
+            ws_t = workspace
+        else:
+            ws_t = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
+        a.workspace, a.workspace_bytes = ws_t.data_ptr(), ws_t.numel() * 4
+    _C.check(_C.lib().dctr_bilinear_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_bilinear_fwd")
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -255,6 +255,21 @@ def _interacting(layer, x):
     return torch.relu(o)
 
 
+def _bilinear(layer, x):
+    """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
+    itertools.combinations order."""
+    F = x.shape[1]
+    ii = [i for i in range(F - 1) for _ in range(i + 1, F)]
+    jj = [j for i in range(F - 1) for j in range(i + 1, F)]
+    if layer.bilinear_type == "all":
+        vid = x[:, :F - 1] @ layer.w("bilinear_weight")
+    elif layer.bilinear_type == "each":
+        vid = torch.einsum("bfe,fed->bfd", x[:, :F - 1], torch.stack(layer.matrices))
+    else:
+        return torch.einsum("bpe,ped->bpd", x[:, ii], torch.stack(layer.matrices)) * x[:, jj]
+    return vid[:, ii] * x[:, jj]
+
+
 def model_logits(model, staged, lo, hi, training=False):
     """Pre-sigmoid logits [B] of the four in-scope models and their siblings, torch ops only.  ``training`` switches Dice to
     batch statistics (and updates its moving statistics), as tf.keras does inside fit(); the default is the inference form
@@ -322,6 +337,22 @@ def model_logits(model, staged, lo, hi, training=False):
         if model.dnn is not None:
             outs.append(dnn_forward(model.dnn, torch.cat(parts, dim=-1), training))
         logit = (torch.cat(outs, dim=-1) @ model.dense.w("kernel")).reshape(-1)
+        if lin is not None:
+            logit = logit + lin
+        for f in fms:
+            logit = logit + f
+        return logit + model.prediction.w("global_bias")
+    if name == "FiBiNET":                   # models/fibinet.py:50-63: DNN over [Flatten(bilinear(SENET(x)), bilinear(x)), dense]
+        F = len(sp.fields)
+        x = torch.stack(parts[:F], dim=1)                           # [B,F,E]
+        B = x.shape[0]
+        a2 = torch.relu(torch.relu(x.mean(-1) @ model.senet.w("W_1")) @ model.senet.w("W_2"))
+        # concat_func joins the two [B,P,E] outputs on the last axis (reference layers/utils.py:236), then Flatten
+        h = torch.cat([_bilinear(model.senet_bilinear, x * a2.unsqueeze(-1)), _bilinear(model.bilinear, x)], dim=-1)
+        h = torch.cat([h.reshape(B, -1)] + parts[F:], dim=-1)
+        if model.dnn is not None:
+            h = dnn_forward(model.dnn, h, training)
+        logit = (h @ model.dense.w("kernel")).reshape(-1)
         if lin is not None:
             logit = logit + lin
         for f in fms:

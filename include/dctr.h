@@ -417,6 +417,48 @@ size_t dctr_interacting_workspace_bytes(const dctr_interacting_args_t* args);
 int dctr_interacting_fwd(const dctr_interacting_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SENETLayer.call + BilinearInteraction.call — deepctr/layers/interaction.py:1067-1221, wired as deepctr/models/fibinet.py:50-58
+ *     x_f [dim] for f < F (F >= 2, one dim).  SENET: Z = mean(x_f) [F]; A1 = relu(Z W_1) [r]; A2 = relu(A1 W_2) [F];
+ *     v_f = A2[f] x_f.  Bilinear over inputs u: for each pair (i, j), i < j in itertools.combinations order (P = F(F-1)/2 pairs),
+ *     p_ij = (u_i W) (.) u_j with W = W_0 (ALL), W_i (EACH, i < F-1) or W_ij (INTERACTION, pair index) — output [P, dim] pair-major.
+ *   mode MODEL: out row = per pair p [p over v (senet_bilinear_w), dim floats | p over x (bilinear_w), dim floats], then the
+ *               dense_cols columns of x behind its F*dim embedding columns: FiBiNET's whole DNN input (Flatten of the two outputs
+ *               concatenated on their last axis, then the dense values), 2*P*dim + dense_cols floats;
+ *   mode SENET: out row = [v_0 .. v_{F-1}] (F*dim floats);
+ *   mode LAYER: out row = the bilinear over x with bilinear_w (P*dim floats), no SENET.
+ *   The (v_i W) (.) v_j of MODEL is computed as A2[i] A2[j] ((x_i W) (.) x_j): equal within fp32 rounding, not bit for bit.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_BILINEAR_ALL = 0, DCTR_BILINEAR_EACH = 1, DCTR_BILINEAR_INTERACTION = 2 };
+enum { DCTR_BILINEAR_MODE_MODEL = 0, DCTR_BILINEAR_MODE_SENET = 1, DCTR_BILINEAR_MODE_LAYER = 2 };
+typedef struct {
+    const float* x;               /* sample b at x + b * x_stride, then [F, dim] row-major (+ the dense columns in mode MODEL) */
+    int64_t batch;
+    int64_t x_stride;             /* elements between samples (>= fields*dim (+ dense_cols)): reads the dnn_in concat in place */
+    int32_t fields;               /* F >= 2 */
+    int32_t dim;                  /* >= 1 */
+    int32_t bilinear_type;        /* DCTR_BILINEAR_ALL | EACH | INTERACTION */
+    int32_t mode;                 /* DCTR_BILINEAR_MODE_MODEL | SENET | LAYER */
+    int32_t reduction_size;       /* r = columns of senet_w1 (>= 1; unused in mode LAYER) */
+    int32_t dense_cols;           /* mode MODEL: columns copied behind the two blocks (else 0) */
+    const float* senet_w1;        /* [F, r] row-major (modes MODEL, SENET) */
+    const float* senet_w2;        /* [r, F] */
+    const float* const* senet_bilinear_w;   /* DEVICE array of nW DEVICE pointers to [dim, dim] (Keras layout) matrices: the layer over
+                                               the SENET output (mode MODEL); nW = 1 (ALL), F-1 (EACH), P (INTERACTION) */
+    const float* const* bilinear_w;         /* DEVICE array [nW]: the layer over x (modes MODEL, LAYER) */
+    float* out;                   /* [B, width] at out_stride */
+    int64_t out_stride;
+    void* workspace;              /* NULL, or device scratch of dctr_bilinear_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_bilinear_args_t;
+/* Bytes of `workspace` these arguments need (0: none).  A workgroup keeps 16 samples' embeddings (and, for ALL / EACH, x_i W per
+ * field) in LDS; a shape too large for the LDS (large fields*dim) runs the same kernel with those buffers in the workspace (room
+ * for <= 256 workgroups, at most 256 MiB unless one tile needs more), and the workspace is then REQUIRED (DCTR_E_NULL without,
+ * before anything is launched).  Argument errors (null pointers, F < 2, unknown type or mode, dim < 1, short strides) are
+ * reported before any launch. */
+size_t dctr_bilinear_workspace_bytes(const dctr_bilinear_args_t* args);
+int dctr_bilinear_fwd(const dctr_bilinear_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */

@@ -1,0 +1,99 @@
+"""FiBiNET at the reference defaults on Criteo-shaped input (26 sparse fields of vocabulary 1e5, embedding_dim 16, 13 dense;
+bilinear_type 'interaction', reduction_ratio 3, DNN 256-128-64 over 2*325*16 + 13 = 10,413 columns): samples/s of the whole forward
+(staged ids -> probabilities: gather, bilinear kernel, DNN kernel) beside the same model's torch-ops forward (training.model_logits
+under no_grad), device-event timing after warm-up, then the bilinear kernel and the DNN kernel alone.  Prints one JSON line.
+
+    python scripts/bench_fibinet.py [--rows 4096,65536] [--iters 20]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+F32_MFMA_PEAK_TF = 157.3
+STORE_TBPS = 6.0             # plain-store HBM rate the cost model uses
+
+
+def _time(fn, iters):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def main():
+    from deepctr_amd import engine, ops, training
+    from deepctr_amd.feature_column import DenseFeat, SparseFeat
+    from deepctr_amd.models import FiBiNET
+    from deepctr_amd.models.fibinet import bilinear_flops
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", default="4096,65536")
+    ap.add_argument("--iters", type=int, default=20)
+    args = ap.parse_args()
+    device = torch.device("cuda:0")
+    rng = np.random.RandomState(0)
+    V, F, E, D = 100000, 26, 16, 13
+    cols = [SparseFeat("C%d" % i, V, E) for i in range(F)] + [DenseFeat("I%d" % i, 1) for i in range(D)]
+    model = FiBiNET(cols, cols, device=device)
+    model.set_weights_by_name({k: (rng.standard_normal(v.shape) * (0.05 if k.endswith("embeddings") else 0.1)).astype(np.float32)
+                               for k, v in model.get_weights_by_name().items()})
+    width = model.dnn_in_dim
+    units = [256, 128, 64]
+    dnn_flops = 2 * (width * units[0] + units[0] * units[1] + units[1] * units[2] + units[2])
+    bl_bytes = 4 * (F * E + D + width)          # reads the embeddings and the dense values, writes the DNN input
+    res = {"model": "FiBiNET", "fields": F, "embedding_dim": E, "dense": D, "bilinear_type": "interaction", "dnn_in_dim": width,
+           "bilinear_flop_per_sample": bilinear_flops(F, E, "interaction"), "bilinear_hbm_bytes_per_sample": bl_bytes,
+           "dnn_flop_per_sample": dnn_flops, "rows": {}}
+    for n in [int(r) for r in args.rows.split(",")]:
+        feed = {"C%d" % i: rng.randint(0, V, n).astype(np.int32) for i in range(F)}
+        feed.update({"I%d" % i: rng.rand(n).astype(np.float32) for i in range(D)})
+        staged = engine.Staged(n)
+        model._stage_inputs(feed, staged)
+        out = torch.empty(n, dtype=torch.float32, device=device)
+
+        def hip():
+            model._begin()
+            model._forward(staged, 0, n, out)
+
+        def torch_ops():
+            with torch.no_grad():
+                training.model_logits(model, staged, 0, n)
+        ms_hip = _time(hip, args.iters)
+        ms_torch = _time(torch_ops, max(3, args.iters // 4))
+        ws = model.stage_plan.run(staged, 0, n)
+        buf = model._dnn_input(n)
+
+        def bil():
+            ops.senet_bilinear(ws["dnn_in"], senet_w=model.senet.weights_w12, senet_bilinear_w=model.senet_bilinear.matrices,
+                               bilinear_w=model.bilinear.matrices, bilinear_type="interaction", fields=F, dim=E, dense_cols=D, out=buf)
+
+        def dnn():
+            ops.mlp(buf, model.dnn.kernels, model.dnn.biases, "relu", head_w=model.dense.w("kernel"),
+                    global_bias=model.prediction.w("global_bias"), sigmoid_out=True, in_dim=width, out=out)
+        ms_bil = _time(bil, args.iters)
+        ms_dnn = _time(dnn, args.iters)
+        bound_ms = bl_bytes * n / (STORE_TBPS * 1e12) * 1e3
+        dnn_tf = dnn_flops * n / (ms_dnn * 1e-3) / 1e12
+        res["rows"][str(n)] = {"forward_ms": round(ms_hip, 4), "samples_per_s": round(n / (ms_hip * 1e-3)),
+                               "torch_ops_ms": round(ms_torch, 4), "torch_ops_samples_per_s": round(n / (ms_torch * 1e-3)),
+                               "speedup_vs_torch_ops": round(ms_torch / ms_hip, 2), "bilinear_call_ms": round(ms_bil, 4),
+                               "bilinear_hbm_bound_ms": round(bound_ms, 4), "bilinear_share_of_hbm_bound": round(bound_ms / ms_bil, 3),
+                               "dnn_call_ms": round(ms_dnn, 4), "dnn_tflops": round(dnn_tf, 2),
+                               "dnn_share_of_f32_mfma_peak": round(dnn_tf / F32_MFMA_PEAK_TF, 3)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
