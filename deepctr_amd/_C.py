@@ -152,6 +152,16 @@ class bilinear(object):
                     ("workspace_bytes", c_sz)]
 
 
+class fieldpair(object):
+    """dctr_fieldpair_args_t, one level down for the same reason as interacting.Args (tests/test_fefm_cpu.py checks its layout)."""
+    FEFM, FWFM = 0, 1
+
+    class Args(ctypes.Structure):
+        _fields_ = [("x", c_vp), ("batch", c_i64), ("x_stride", c_i64), ("x_offset", c_i64), ("fields", c_i32), ("dim", c_i32),
+                    ("kind", c_i32), ("reserved", c_i32), ("weights", c_vp), ("pairs_out", c_vp), ("pairs_stride", c_i64),
+                    ("pairs_offset", c_i64), ("add", c_vp), ("logit_out", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -238,6 +248,8 @@ SYMBOLS = {
     "dctr_interacting_fwd": (ctypes.c_int, [ctypes.POINTER(interacting.Args), c_vp]),
     "dctr_bilinear_workspace_bytes": (c_sz, [ctypes.POINTER(bilinear.Args)]),
     "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
+    "dctr_fieldpair_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.Args)]),
+    "dctr_fieldpair_fwd": (ctypes.c_int, [ctypes.POINTER(fieldpair.Args), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

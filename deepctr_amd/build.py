@@ -49,6 +49,7 @@ SOURCES = [
     "cin_bwd_kernels.hip",
     "interacting_kernels.hip",
     "bilinear_kernels.hip",
+    "fieldpair_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

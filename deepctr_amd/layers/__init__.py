@@ -3,8 +3,8 @@
 siblings need — SURVEY.md §8a)."""
 from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer
-from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FM, InnerProductLayer,
-                          InteractingLayer, SENETLayer)
+from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FEFMLayer, FM, FwFMLayer,
+                          InnerProductLayer, InteractingLayer, SENETLayer)
 from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
@@ -21,6 +21,8 @@ custom_objects = {
     'InteractingLayer': InteractingLayer,
     'SENETLayer': SENETLayer,
     'BilinearInteraction': BilinearInteraction,
+    'FwFMLayer': FwFMLayer,
+    'FEFMLayer': FEFMLayer,
     'LocalActivationUnit': LocalActivationUnit,
     'Dice': Dice,
     'SequencePoolingLayer': SequencePoolingLayer,

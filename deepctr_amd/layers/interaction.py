@@ -1,9 +1,10 @@
-"""Host mirror of the eight in-scope layers of the reference's ``deepctr/layers/interaction.py``:
+"""Host mirror of the ten in-scope layers of the reference's ``deepctr/layers/interaction.py``:
 ``AFMLayer`` (:39-160), ``CIN`` (:209-341), ``CrossNet`` (:344-435), ``FM`` (:563-607),
-``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790), ``SENETLayer`` (:1067-1139), ``BilinearInteraction`` (:1142-1221).
+``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790), ``SENETLayer`` (:1067-1139), ``BilinearInteraction`` (:1142-1221),
+``FwFMLayer`` (:1351-1425), ``FEFMLayer`` (:1428-1499).
 Same constructor kwargs, ``get_config`` and weight names/shapes; ``call`` launches the HIP kernels
-(deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip).  The other eight
-interaction layers of the reference are out of scope."""
+(deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip,
+fieldpair_kernels.hip).  The other six interaction layers of the reference are out of scope."""
 import itertools
 
 import torch
@@ -277,6 +278,99 @@ class BilinearInteraction(Layer):
     def get_config(self):
         config = {'bilinear_type': self.bilinear_type, 'seed': self.seed}
         base = super(BilinearInteraction, self).get_config()
+        base.update(config)
+        return base
+
+
+class FwFMLayer(Layer):
+    """Field-weighted factorization machine (reference interaction.py:1351-1425): x [B,F,E] -> [B,1],
+    sum_{i<j} field_pair_strengths[i][j] <x_i, x_j>."""
+
+    def __init__(self, num_fields=4, regularizer=0.000001, **kwargs):
+        self.num_fields = num_fields
+        self.regularizer = regularizer
+        super(FwFMLayer, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        if input_shape[1] != self.num_fields:
+            raise ValueError("Mismatch in number of fields {} and concatenated embeddings dims {}".format(self.num_fields,
+                                                                                                         input_shape[1]))
+        return self.build_for()
+
+    def build_for(self):
+        if self.built:
+            return self
+        self.add_weight('field_pair_strengths', (self.num_fields, self.num_fields), TruncatedNormal())
+        self.built = True
+        return self
+
+    @property
+    def field_strengths(self):
+        return self.w('field_pair_strengths')
+
+    def call(self, inputs, **kwargs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        if inputs.shape[1] != self.num_fields:
+            raise ValueError("Mismatch in number of fields {} and concatenated embeddings dims {}".format(self.num_fields,
+                                                                                                         inputs.shape[1]))
+        _, logit = ops.fieldpair(inputs, self.field_strengths, kind="fwfm")
+        return logit.reshape(-1, 1)
+
+    def compute_output_shape(self, input_shape):
+        return (None, 1)
+
+    def get_config(self):
+        config = {'num_fields': self.num_fields, 'regularizer': self.regularizer}
+        base = super(FwFMLayer, self).get_config()
+        base.update(config)
+        return base
+
+
+class FEFMLayer(Layer):
+    """Field-embedded factorization machine (reference interaction.py:1428-1499): x [B,F,E] -> [B, F(F-1)/2], per pair i < j
+    (itertools.combinations order) x_i^T (W_ij + W_ij^T) x_j with one [E,E] matrix ``field_embeddings<i>-<j>`` per pair."""
+
+    def __init__(self, regularizer, **kwargs):
+        self.regularizer = regularizer
+        super(FEFMLayer, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        return self.build_for(int(input_shape[1]), int(input_shape[2]))
+
+    def build_for(self, num_fields, embedding_size):
+        if self.built:
+            return self
+        self.num_fields = int(num_fields)
+        shape = (int(embedding_size), int(embedding_size))
+        # (the reference's TruncatedNormal() is unseeded: every matrix its own draw — here the pair index seeds it)
+        for p, (fi, fj) in enumerate(itertools.combinations(range(self.num_fields), 2)):
+            self.add_weight('field_embeddings' + str(fi) + "-" + str(fj), shape, TruncatedNormal(seed=p))
+        self.built = True
+        return self
+
+    @property
+    def matrices(self):
+        """The pair matrices in the order ops.fieldpair takes them (creation order = itertools.combinations)."""
+        return list(self._weights.values())
+
+    def call(self, inputs, **kwargs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        pairs, _ = ops.fieldpair(inputs, self.matrices, kind="fefm", pairs=True)
+        return pairs
+
+    def compute_output_shape(self, input_shape):
+        num_fields = int(input_shape[1])
+        return (None, (num_fields * (num_fields - 1)) / 2)
+
+    def get_config(self):
+        config = {'regularizer': self.regularizer}
+        base = super(FEFMLayer, self).get_config()
         base.update(config)
         return base
 

@@ -1,14 +1,16 @@
 """In-scope model constructors under the reference's names (deepctr/models/__init__.py:1-27 exports 27;
 BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN, AFM, PNN, NFM and DCNMix
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
-SENET + bilinear-interaction kernel)."""
+SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
 from .dcnmix import DCNMix
+from .deepfefm import DeepFEFM
 from .deepfm import DeepFM
 from .fibinet import FiBiNET
 from .fnn import FNN
+from .fwfm import FwFM
 from .nfm import NFM
 from .pnn import PNN
 from .sequence import DIN

@@ -731,6 +731,105 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
     return out
 
 
+def _fieldpair_args(kind, B, F, E, x_stride, x_offset=0):
+    return _C.fieldpair.Args(batch=int(B), x_stride=int(x_stride), x_offset=int(x_offset), fields=int(F), dim=int(E), kind=int(kind))
+
+
+def fieldpair_workspace_bytes(batch, fields, dim, kind="fefm", pairs=True):
+    """Bytes of the workspace dctr_fieldpair_fwd needs for these shapes (0 on the LDS route; read from the library)."""
+    a = _fieldpair_args(_FIELDPAIR_KINDS[kind], batch, fields, dim, fields * dim)
+    P = fields * (fields - 1) // 2
+    if kind == "fefm" and pairs:
+        a.pairs_out, a.pairs_stride = 16, P         # (only whether it is null enters the plan)
+    return int(_C.lib().dctr_fieldpair_workspace_bytes(ctypes.byref(a)))
+
+
+_FIELDPAIR_KINDS = {"fefm": _C.fieldpair.FEFM, "fwfm": _C.fieldpair.FWFM}
+
+
+def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=None, pairs_offset=0, logit=None, add=None,
+              workspace=None):
+    """FEFMLayer.call / FwFMLayer.call (reference interaction.py:1351-1499), one launch.  x [B,F,E] (or, with ``fields`` / ``dim``, the
+    F*E columns from ``x_offset`` of a [B, stride] buffer read in place: one feature group's slice of dnn_in).
+      * kind "fefm": ``weights`` = the P = F(F-1)/2 matrices [E,E] in itertools.combinations order (the live per-name tensors: the
+        kernel forms W + W^T itself).  ``pairs``: True (a new [B,P] tensor), or a float32 2-D view whose row receives the P scalars
+        from column ``pairs_offset`` (e.g. dnn_in behind its dense columns); ``logit``: True or a float32 [B] tensor = their row sum.
+      * kind "fwfm": ``weights`` = field_pair_strengths [F,F] (only r[i][j], i < j is read); ``logit`` only (True by default).
+    ``add`` [B] is added to the logit in the same launch.  ``workspace``: a float32 tensor of >= fieldpair_workspace_bytes (default:
+    the per-stream scratch).  Returns (pairs, logit), None for an output not asked for."""
+    if kind not in _FIELDPAIR_KINDS:
+        raise ValueError("fieldpair: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
+    if fields is None:
+        if x.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+        x = _f32c(x, "x")
+        B, F, E = x.shape
+        x_stride, x_offset = F * E, 0
+    else:
+        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+            raise ValueError("fieldpair: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
+        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
+        if x_offset < 0 or x_offset + F * E > x.shape[1]:
+            raise ValueError("fieldpair: columns [%d, %d) are not inside x [%d, %d]" % (x_offset, x_offset + F * E, B, x.shape[1]))
+    if F < 2:
+        raise ValueError("fieldpair: %d field(s): a field pair needs at least 2" % F)
+    P = F * (F - 1) // 2
+    tensors = [x]
+    if kind == "fefm":
+        ws = [_f32c(w, "field_embeddings") for w in weights]
+        if len(ws) != P or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("fieldpair: FEFM over %d fields takes %d matrices [%d, %d]" % (F, P, E, E))
+        tensors += ws
+        wptr = bilinear_table(ws)
+        if pairs is None and logit is None:
+            pairs = True
+    else:
+        r = _f32c(weights, "field_pair_strengths")
+        if tuple(r.shape) != (F, F):
+            raise ValueError("fieldpair: FwFM over %d fields takes field_pair_strengths [%d, %d]" % (F, F, F))
+        if pairs is not None:
+            raise ValueError("fieldpair: the FwFM kind has no pair outputs")
+        tensors.append(r)
+        wptr = r
+        if logit is None:
+            logit = True
+    if pairs is True:
+        pairs, pairs_offset = torch.empty(B, P, dtype=torch.float32, device=x.device), 0
+    if logit is True:
+        logit = torch.empty(B, dtype=torch.float32, device=x.device)
+    if pairs is not None and (pairs.dim() != 2 or pairs.stride(1) != 1 or pairs.dtype != torch.float32 or pairs.shape[0] != B
+                              or pairs_offset < 0 or pairs.shape[1] < pairs_offset + P):
+        raise ValueError("fieldpair: pairs must be a float32 [%d, >= %d] view with unit column stride" % (B, pairs_offset + P))
+    if logit is not None and (logit.dtype != torch.float32 or not logit.is_contiguous() or logit.numel() != B):
+        raise ValueError("fieldpair: logit must be a contiguous float32 tensor of %d elements" % B)
+    if add is not None:
+        if logit is None:
+            raise ValueError("fieldpair: add needs a logit output")
+        add = _f32c(add, "add")
+        if add.numel() != B:
+            raise ValueError("fieldpair: add must hold %d elements" % B)
+    _dev_check(pairs, logit, add, *tensors)
+    a = _fieldpair_args(_FIELDPAIR_KINDS[kind], B, F, E, x_stride, x_offset)
+    a.x, a.weights = x.data_ptr(), wptr.data_ptr()
+    if pairs is not None:
+        a.pairs_out, a.pairs_stride, a.pairs_offset = pairs.data_ptr(), pairs.stride(0), int(pairs_offset)
+    if logit is not None:
+        a.logit_out = logit.data_ptr()
+    if add is not None:
+        a.add = add.data_ptr()
+    need = int(_C.lib().dctr_fieldpair_workspace_bytes(ctypes.byref(a)))
+    if need:
+        if workspace is not None:
+            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
+                raise ValueError("fieldpair: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
+            ws_t = workspace
+        else:
+            ws_t = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
+        a.workspace, a.workspace_bytes = ws_t.data_ptr(), ws_t.numel() * 4
+    _C.check(_C.lib().dctr_fieldpair_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_fieldpair_fwd")
+    return pairs, logit
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -204,7 +204,8 @@ def l2_penalty(model, regs=None):
 def regularized_weights(model):
     """[(tensor, l2)] for every weight the reference attaches ``l2(l2_reg_*)`` to: embedding tables (inputs.py:22-41), the
     linear part (feature_column.py:171-210, layers/utils.py:142-158), DNN kernels (core.py:160-166), CrossNet / CrossNetMix
-    kernels (interaction.py:387, :481-500), CIN filters (:258) and AFMLayer.attention_W (:100).  keras l2(l) adds
+    kernels (interaction.py:387, :481-500), CIN filters (:258), AFMLayer.attention_W (:100), FwFMLayer.field_pair_strengths (:1385-1389)
+    and FEFMLayer's pair matrices (:1459-1463).  keras l2(l) adds
     l * sum(w^2) to the loss — over the WHOLE table every step, as the HIP step's 2*l2*w term does."""
     reg = getattr(model, "regularizers", None) or {}
     out, seen = [], set()
@@ -235,6 +236,12 @@ def regularized_weights(model):
             add(f, reg.get("cin", 0.0))
     for layer in getattr(model, "afm_layers", None) or []:
         add(layer.w("attention_W"), getattr(layer, "l2_reg_w", 0.0))
+    for layer in getattr(model, "fwfm_layers", None) or []:     # the whole [F,F] variable, not the triangle the forward reads
+        add(layer.field_strengths, layer.regularizer)
+    fefm = getattr(model, "fefm", None)
+    if fefm is not None:
+        for m in fefm.matrices:
+            add(m, fefm.regularizer)
     return out
 
 
@@ -268,6 +275,16 @@ def _bilinear(layer, x):
     else:
         return torch.einsum("bpe,ped->bpd", x[:, ii], torch.stack(layer.matrices)) * x[:, jj]
     return vid[:, ii] * x[:, jj]
+
+
+def _fefm(layer, x):
+    """FEFMLayer.call (reference interaction.py:1469-1488) in torch ops: x [B,F,E] -> [B,P], pairs i < j in itertools.combinations
+    order, x_i^T (W + W^T) x_j."""
+    F = x.shape[1]
+    ii = [i for i in range(F - 1) for _ in range(i + 1, F)]
+    jj = [j for i in range(F - 1) for j in range(i + 1, F)]
+    w = torch.stack(layer.matrices)
+    return (torch.einsum("bpe,ped->bpd", x[:, ii], w + w.transpose(1, 2)) * x[:, jj]).sum(-1)
 
 
 def model_logits(model, staged, lo, hi, training=False):
@@ -341,6 +358,37 @@ def model_logits(model, staged, lo, hi, training=False):
             logit = logit + lin
         for f in fms:
             logit = logit + f
+        return logit + model.prediction.w("global_bias")
+    if name == "FwFM":                      # models/fwfm.py:51-66: linear + FwFMLayer per group (+ DNN over the plain DNN input)
+        logit = torch.zeros(hi - lo, device=sp.device)
+        for g, layer in zip(model.groups, model.fwfm_layers):
+            first, n, dim = sp.group_slices[g]
+            x = torch.stack([parts[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim], dim=1)
+            gram = torch.einsum("bie,bje->bij", x, x)
+            logit = logit + (gram * torch.triu(layer.field_strengths, diagonal=1)).sum((1, 2))
+        if model.dnn is not None:
+            h = dnn_forward(model.dnn, torch.cat(parts, dim=-1), training)
+            logit = logit + (h @ model.dense.w("kernel")).reshape(-1)
+        if lin is not None:
+            logit = logit + lin
+        return logit + model.prediction.w("global_bias")
+    if name == "DeepFEFM":                  # models/deepfefm.py:62-99: FEFM over the default group, the ablation switches
+        first, n, dim = model.group_first, model.n_fields, model.emb_dim
+        x = torch.stack([parts[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim], dim=1)
+        pairs = _fefm(model.fefm, x)
+        logit = torch.zeros(hi - lo, device=sp.device)
+        if model.dnn is not None:
+            if not model.pairs_in_dnn:
+                h = torch.cat(parts, dim=-1)
+            elif model.exclude_embed:
+                h = pairs
+            else:
+                h = torch.cat(parts + [pairs], dim=-1)
+            logit = logit + (dnn_forward(model.dnn, h, training) @ model.dense.w("kernel")).reshape(-1)
+        if model.use_fefm:
+            logit = logit + pairs.sum(-1)
+        if model.use_linear and lin is not None:
+            logit = logit + lin
         return logit + model.prediction.w("global_bias")
     if name == "FiBiNET":                   # models/fibinet.py:50-63: DNN over [Flatten(bilinear(SENET(x)), bilinear(x)), dense]
         F = len(sp.fields)

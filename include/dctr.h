@@ -459,6 +459,45 @@ size_t dctr_bilinear_workspace_bytes(const dctr_bilinear_args_t* args);
 int dctr_bilinear_fwd(const dctr_bilinear_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FwFMLayer.call / FEFMLayer.call — deepctr/layers/interaction.py:1351-1499, wired as deepctr/models/fwfm.py and deepfefm.py
+ *     x_f [dim] for f < F (F >= 2, one dim): the embeddings of ONE feature group.  Pairs (i, j), i < j, in itertools.combinations
+ *     order, P = F(F-1)/2 of them.
+ *   kind FEFM: s_p = x_i^T (W_p + W_p^T) x_j with one [dim, dim] matrix per pair; the kernel forms W + W^T from the live W.
+ *              pairs_out row b = [s_0 .. s_{P-1}] at pairs_out + b * pairs_stride + pairs_offset (optional);
+ *              logit_out[b] = sum_p s_p (+ add[b]) (optional).  At least one of the two outputs.
+ *   kind FWFM: logit_out[b] = sum_{i<j} r[i][j] <x_i, x_j> (+ add[b]) with r the [F, F] field_pair_strengths, of which only the
+ *              strict upper triangle is read.  pairs_out must be NULL.
+ *   The sums run in the kernel's own order: equal to the reference's within fp32 rounding, not bit for bit.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_FIELDPAIR_FEFM = 0, DCTR_FIELDPAIR_FWFM = 1 };
+typedef struct {
+    const float* x;               /* sample b's [F, dim] row-major block at x + b * x_stride + x_offset */
+    int64_t batch;
+    int64_t x_stride;             /* elements between samples (>= x_offset + fields*dim): reads a group's slice of dnn_in in place */
+    int64_t x_offset;             /* first column of the group (>= 0) */
+    int32_t fields;               /* F >= 2 */
+    int32_t dim;                  /* >= 1 */
+    int32_t kind;                 /* DCTR_FIELDPAIR_FEFM | DCTR_FIELDPAIR_FWFM */
+    int32_t reserved;             /* 0 */
+    const void* weights;          /* FEFM: DEVICE array of P DEVICE pointers to [dim, dim] row-major matrices, combinations order;
+                                     FWFM: const float* [F, F] row-major */
+    float* pairs_out;             /* FEFM: NULL, or [B, P] at pairs_stride / pairs_offset; FWFM: NULL */
+    int64_t pairs_stride;         /* elements between rows of pairs_out (>= pairs_offset + P) */
+    int64_t pairs_offset;         /* first column written (>= 0): lets the scalars land behind the dense columns of a DNN-input row */
+    const float* add;             /* NULL, or [B] added to logit_out (e.g. the linear logit) */
+    float* logit_out;             /* [B]; FEFM: optional, FWFM: required */
+    void* workspace;              /* NULL, or device scratch of dctr_fieldpair_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_fieldpair_args_t;
+/* Bytes of `workspace` these arguments need (0: none, also for invalid arguments).  A workgroup keeps its samples' embeddings in
+ * LDS; a shape too large for the LDS (large fields*dim) runs the same kernel with that tile in the workspace (room for <= 256
+ * workgroups), and the workspace is then REQUIRED (DCTR_E_NULL without, before anything is launched).  No shape is refused for its
+ * size.  Argument errors (null pointers, F < 2, dim < 1, unknown kind, short strides, misaligned workspace) are reported before
+ * any launch. */
+size_t dctr_fieldpair_workspace_bytes(const dctr_fieldpair_args_t* args);
+int dctr_fieldpair_fwd(const dctr_fieldpair_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
