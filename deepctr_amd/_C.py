@@ -162,6 +162,21 @@ class fieldpair(object):
                     ("pairs_offset", c_i64), ("add", c_vp), ("logit_out", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class ffm(object):
+    """dctr_ffm_field_t / dctr_ffm_args_t, one level down for the same reason as interacting.Args (tests/test_onn_cpu.py checks the layout)."""
+    ROUTE_AUTO, ROUTE_DIRECT, ROUTE_LDS = 0, 1, 2
+
+    class Field(ctypes.Structure):
+        _fields_ = [("rows", c_vp), ("ids", c_vp), ("vocab", c_i64), ("row_pitch", c_i64), ("ids_stride", c_i64), ("ids_is_i64", c_i32),
+                    ("identity", c_i32)]
+
+    class Args(ctypes.Structure):
+        _fields_ = [("fields", c_vp), ("batch", c_i64), ("n_fields", c_i32), ("dim", c_i32), ("reduce_sum", c_i32), ("n_dense", c_i32),
+                    ("scale", c_vp), ("shift", c_vp), ("dense", c_vp), ("dense_stride", c_i64), ("out", c_vp), ("out_stride", c_i64),
+                    ("out_offset", c_i64), ("status", c_vp), ("route", c_i32), ("reserved", c_i32), ("workspace", c_vp),
+                    ("workspace_bytes", c_sz)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -250,6 +265,9 @@ SYMBOLS = {
     "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
     "dctr_fieldpair_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.Args)]),
     "dctr_fieldpair_fwd": (ctypes.c_int, [ctypes.POINTER(fieldpair.Args), c_vp]),
+    "dctr_ffm_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.Args)]),
+    "dctr_ffm_route": (ctypes.c_int, [ctypes.POINTER(ffm.Args)]),
+    "dctr_ffm_fwd": (ctypes.c_int, [ctypes.POINTER(ffm.Args), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

@@ -50,6 +50,7 @@ SOURCES = [
     "interacting_kernels.hip",
     "bilinear_kernels.hip",
     "fieldpair_kernels.hip",
+    "ffm_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

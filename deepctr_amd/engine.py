@@ -40,6 +40,7 @@ class Staged(object):
         self.seq = {}            # varlen feature name -> [N, T] ids
         self.length = {}         # length_name -> [N] int32
         self.weight = {}         # weight_name -> [N, T] float32
+        self.extra = {}          # model-specific per-sample tensors, rows on axis 0 (ONN: its [N, F] id matrix, hashed sequences)
 
 
 def _column(x, name):

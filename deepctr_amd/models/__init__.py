@@ -1,7 +1,7 @@
 """In-scope model constructors under the reference's names (deepctr/models/__init__.py:1-27 exports 27;
 BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN, AFM, PNN, NFM and DCNMix
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
-SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel)."""
+SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -12,6 +12,7 @@ from .fibinet import FiBiNET
 from .fnn import FNN
 from .fwfm import FwFM
 from .nfm import NFM
+from .onn import ONN
 from .pnn import PNN
 from .sequence import DIN
 from .wdl import WDL

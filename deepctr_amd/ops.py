@@ -830,6 +830,135 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
     return pairs, logit
 
 
+_FFM_ROUTES = {None: _C.ffm.ROUTE_AUTO, "auto": _C.ffm.ROUTE_AUTO, "direct": _C.ffm.ROUTE_DIRECT}
+
+
+def _ffm_args(batch, fields, dim, reduce_sum=False, n_dense=0, route=None, out_stride=None, out_offset=0):
+    if route not in _FFM_ROUTES:
+        raise ValueError("ffm: route %r: expected None / 'auto' or 'direct'" % (route,))
+    F, d = int(fields), int(dim)
+    P = F * (F - 1) // 2
+    width = (P if reduce_sum else P * d) + int(n_dense)
+    if out_stride is None:
+        out_stride = (int(out_offset) + width + 3) // 4 * 4
+    return _C.ffm.Args(batch=int(batch), n_fields=F, dim=d, reduce_sum=int(bool(reduce_sum)), n_dense=int(n_dense),
+                       out_stride=int(out_stride), out_offset=int(out_offset), route=_FFM_ROUTES[route])
+
+
+def ffm_workspace_bytes(batch, fields, dim, reduce_sum=False, route=None):
+    """Bytes of workspace dctr_ffm_fwd needs for these shapes (read from the library: 0, both routes keep their state on chip)."""
+    a = _ffm_args(batch, fields, dim, reduce_sum, route=route)
+    return int(_C.lib().dctr_ffm_workspace_bytes(ctypes.byref(a)))
+
+
+def ffm_route(batch, fields, dim, reduce_sum=False, route=None):
+    """'lds' or 'direct': the route dctr_ffm_fwd takes for these shapes (the library's answer, dctr_ffm_route)."""
+    a = _ffm_args(batch, fields, dim, reduce_sum, route=route)
+    rc = int(_C.lib().dctr_ffm_route(ctypes.byref(a)))
+    if rc < 0:
+        _C.check(rc, "dctr_ffm_route")
+    return {_C.ffm.ROUTE_LDS: "lds", _C.ffm.ROUTE_DIRECT: "direct"}[rc]
+
+
+def make_ffm_fields(fields, device):
+    """fields: list of dicts(rows [V, >= (F-1)*d] float32 with unit column stride, ids 1-D id view or None = pre-pooled field whose row
+    is the sample index) -> uint8 device tensor holding the dctr_ffm_field_t array (kept alive by the caller)."""
+    arr = (_C.ffm.Field * max(1, len(fields)))()
+    for j, f in enumerate(fields):
+        rows, ids = f["rows"], f.get("ids")
+        arr[j].rows = rows.data_ptr()
+        arr[j].vocab = int(rows.shape[0])
+        arr[j].row_pitch = row_stride(rows)
+        if ids is None:
+            arr[j].identity = 1
+        else:
+            arr[j].ids = ids.data_ptr()
+            arr[j].ids_stride = int(ids.stride(0)) if ids.shape[0] != 1 else 1
+            arr[j].ids_is_i64 = int(ids.dtype == torch.int64)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None, reduce_sum=False, out=None, out_offset=0,
+        status=None, route=None, desc=None, batch=None):
+    """ONN's field-aware lookup + pair products (reference models/onn.py:59-99), one launch: ids [F, B] (int32 / int64; row j unused
+    for a pre-pooled field) and ``masters`` = per field the fused table [V_j, F-1, d] (or its [V_j, (F-1)*d] view), or for a pre-pooled
+    field a (buffer [B, >= (F-1)*d],) 1-tuple -> out [B, P*d (+ n_dense)] ([B, P (+ n_dense)] with ``reduce_sum``), pairs in
+    itertools.combinations order.  ``scale`` / ``shift``: the inference BatchNormalization over the pair columns; ``dense`` [B, >= n_dense]:
+    copied behind them.  ``out``: a float32 2-D view with unit column stride and a row stride that is a multiple of 4, written from
+    column ``out_offset``; other columns are not touched.  ``route='direct'`` forces the direct route.  ``desc``: a descriptor tensor
+    from make_ffm_fields (then ``ids`` / ``masters`` are not looked at; ``dim`` and ``batch`` are required)."""
+    F = len(masters)
+    if F < 2:
+        raise ValueError("ffm: %d field(s): a field pair needs at least 2" % F)
+    keep = []
+    if desc is None:
+        B = int(ids.shape[1]) if batch is None else int(batch)
+        if ids.dim() != 2 or ids.shape[0] != F or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError("ffm: ids must be an int32 / int64 [%d, B] matrix" % F)
+        fields = []
+        for j, m in enumerate(masters):
+            pooled = isinstance(m, tuple)
+            m = m[0] if pooled else m
+            if m.dtype != torch.float32:
+                raise TypeError("ffm: tables must be float32, got %s" % m.dtype)
+            if m.dim() == 3:
+                if dim is None:
+                    dim = int(m.shape[2])
+                if m.shape[1] != F - 1 or m.shape[2] != dim or not m.is_contiguous():
+                    raise ValueError("ffm: field %d: expected a contiguous [V, %d, %d] table, got %s" % (j, F - 1, dim, tuple(m.shape)))
+                m = m.view(m.shape[0], -1)
+            if dim is None:
+                raise ValueError("ffm: dim is required with 2-D tables")
+            if m.dim() != 2 or m.stride(1) != 1 or m.shape[1] < (F - 1) * dim:
+                raise ValueError("ffm: field %d: expected [rows, >= %d] with unit column stride" % (j, (F - 1) * dim))
+            if pooled and m.shape[0] < B:
+                raise ValueError("ffm: pre-pooled field %d holds %d rows for a batch of %d" % (j, m.shape[0], B))
+            keep.append(m)
+            fields.append(dict(rows=m, ids=None if pooled else ids[j]))
+        _dev_check(ids, *keep)
+        desc = make_ffm_fields(fields, ids.device)
+    else:
+        if dim is None or batch is None:
+            raise ValueError("ffm: desc needs dim and batch")
+        B = int(batch)
+    dim = int(dim)
+    P = F * (F - 1) // 2
+    W = P if reduce_sum else P * dim
+    if dense is not None:
+        # (a single column's stride is arbitrary: torch keeps (1, n) for the [n, 1] transpose of a staged [1, n] row)
+        if dense.dim() != 2 or dense.dtype != torch.float32 or (dense.shape[1] > 1 and dense.stride(1) != 1) or dense.shape[0] < B:
+            raise ValueError("ffm: dense must be a float32 [B, n] matrix with unit column stride")
+        n_dense = int(dense.shape[1]) if n_dense is None else int(n_dense)
+        if n_dense > dense.shape[1]:
+            raise ValueError("ffm: n_dense %d > %d dense columns" % (n_dense, dense.shape[1]))
+    else:
+        n_dense = 0
+    if (scale is None) != (shift is None):
+        raise ValueError("ffm: scale and shift come together")
+    if scale is not None:
+        scale, shift = _f32c(scale, "scale"), _f32c(shift, "shift")
+        if scale.numel() != W or shift.numel() != W:
+            raise ValueError("ffm: scale / shift must hold %d elements" % W)
+    width = W + n_dense
+    if out is None:
+        out = torch.empty(B, (out_offset + width + 3) // 4 * 4, dtype=torch.float32, device=desc.device)
+    if (out.dim() != 2 or out.dtype != torch.float32 or out.stride(1) != 1 or out.shape[0] < B or out_offset < 0
+            or out.shape[1] < out_offset + width):
+        raise ValueError("ffm: out must be a float32 [%d, >= %d] view with unit column stride" % (B, out_offset + width))
+    _dev_check(desc, scale, shift, dense, out, status)
+    a = _ffm_args(B, F, dim, reduce_sum, n_dense, route, out_stride=row_stride(out), out_offset=out_offset)
+    a.fields, a.out = desc.data_ptr(), out.data_ptr()
+    if scale is not None:
+        a.scale, a.shift = scale.data_ptr(), shift.data_ptr()
+    if n_dense:
+        a.dense, a.dense_stride = dense.data_ptr(), row_stride(dense)
+    if status is not None:
+        a.status = status.data_ptr()
+    _C.check(_C.lib().dctr_ffm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_ffm_fwd")
+    del keep
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

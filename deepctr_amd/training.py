@@ -359,6 +359,23 @@ def model_logits(model, staged, lo, hi, training=False):
         for f in fms:
             logit = logit + f
         return logit + model.prediction.w("global_bias")
+    if name == "ONN":                       # models/onn.py:59-105: field-aware pair products (+ BN) and the dense values -> DNN -> Dense(1)
+        embs = model.field_aware_rows(staged, lo, hi, _pool)
+        F = model.n_fields
+        prods = []
+        for i in range(F - 1):
+            for j in range(i + 1, F):
+                pr = embs[i][j] * embs[j][i]
+                prods.append(pr.sum(-1, keepdim=True) if model.reduce_sum else pr)
+        x = torch.cat(prods, dim=-1)
+        if model.bn is not None:
+            x = _batch_norm(model.bn, x, training)
+        x = torch.cat([x] + parts, dim=-1)
+        h = dnn_forward(model.dnn, x, training)
+        logit = (h @ model.dense.w("kernel")).reshape(-1)
+        if lin is not None:
+            logit = logit + lin
+        return logit + model.prediction.w("global_bias")
     if name == "FwFM":                      # models/fwfm.py:51-66: linear + FwFMLayer per group (+ DNN over the plain DNN input)
         logit = torch.zeros(hi - lo, device=sp.device)
         for g, layer in zip(model.groups, model.fwfm_layers):
@@ -508,7 +525,7 @@ def permute_staged_(staged, yt, perm, wt=None):
         staged.dense.copy_(staged.dense.index_select(0, perm))
     if getattr(staged, "hashed", None) is not None:
         staged.hashed.copy_(staged.hashed.index_select(1, perm))
-    for group in (staged.seq, staged.length, staged.weight):
+    for group in (staged.seq, staged.length, staged.weight, getattr(staged, "extra", None) or {}):
         for k in group:
             group[k].copy_(group[k].index_select(0, perm))
     yt.copy_(yt.index_select(0, perm))

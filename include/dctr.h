@@ -498,6 +498,58 @@ size_t dctr_fieldpair_workspace_bytes(const dctr_fieldpair_args_t* args);
 int dctr_fieldpair_fwd(const dctr_fieldpair_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ONN's field-aware embedding lookup + pair products — deepctr/models/onn.py:59-99 (no layer class in the reference)
+ *     F >= 2 fields of one embedding_dim d.  Field j owns ONE fused table [vocab_j, F-1, d] (rows row_pitch floats apart): row r holds
+ *     the embeddings of id r towards every partner field, slot k = partner i in field order with j itself skipped — the reference's
+ *     sparse_emb_<j>_<i>/embeddings is the strided view [:, k, :].  Per sample and pair (i, j), i < j, in itertools.combinations order
+ *     (P = F(F-1)/2 pairs):  out[p*d + e] = row_i[slot of j][e] * row_j[slot of i][e]   (reduce_sum: out[p] = the sum over e),
+ *     then optionally out = out * scale + shift (the inference form of the BatchNormalization over the P*d, or P, columns), then the
+ *     n_dense dense values — combined_dnn_input([ffm_out], dense): the model's whole DNN-input row, in one launch from the ids.
+ *     A field with identity != 0 is pre-pooled (a VarLenSparseFeat pooled over the whole fused row by dctr_embed_pool with
+ *     dim = (F-1)*d): its row is the sample index, vocab = the rows of that buffer.  An id outside [0, vocab) raises
+ *     DCTR_STATUS_INDEX_OOR and enters the products as a row of zeros; nothing outside the tables is read.
+ *     Without scale / shift an output is one fp32 product, with them one product and one fma, on both routes: the same bits.
+ *     Routes: tiles of samples gathered whole into LDS (every table byte read once, coalesced), or — rows beyond the LDS, or
+ *     route = DCTR_FFM_ROUTE_DIRECT — both operands read from global memory.  No shape is refused for its size up to 2^27 floats per
+ *     output row; neither route needs a workspace (dctr_ffm_workspace_bytes() = 0; the two members are reserved).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_FFM_ROUTE_AUTO = 0, DCTR_FFM_ROUTE_DIRECT = 1, DCTR_FFM_ROUTE_LDS = 2 };
+typedef struct {
+    const float* rows;            /* [vocab, row_pitch] fp32: the fused table (or the pre-pooled buffer); 16-B aligned rows are read 16 B at a time */
+    const void* ids;              /* sample b's id at ids[b * ids_stride]; unused when identity */
+    int64_t vocab;
+    int64_t row_pitch;            /* floats between rows, >= (F-1)*d */
+    int64_t ids_stride;           /* elements */
+    int32_t ids_is_i64;           /* 0: int32 ids, 1: int64 ids */
+    int32_t identity;             /* 1: row = sample index b */
+} dctr_ffm_field_t;
+typedef struct {
+    const dctr_ffm_field_t* fields;   /* DEVICE array [n_fields], in field order */
+    int64_t batch;
+    int32_t n_fields;             /* F >= 2 */
+    int32_t dim;                  /* d >= 1 */
+    int32_t reduce_sum;           /* 0 | 1 */
+    int32_t n_dense;              /* dense columns copied behind the pair block (0 = none) */
+    const float* scale;           /* NULL, or [P*d] ([P] with reduce_sum); scale and shift both or neither */
+    const float* shift;
+    const float* dense;           /* [B, dense_stride] or NULL */
+    int64_t dense_stride;
+    float* out;                   /* row b at out + b * out_stride + out_offset: P*d (or P) + n_dense floats */
+    int64_t out_stride;           /* elements, a multiple of 4 (DCTR_E_ALIGN), >= out_offset + width */
+    int64_t out_offset;           /* first column written (>= 0); columns outside [out_offset, out_offset + width) are not touched */
+    int32_t* status;              /* optional device word, DCTR_STATUS_* bits are OR-ed in */
+    int32_t route;                /* DCTR_FFM_ROUTE_AUTO | DCTR_FFM_ROUTE_DIRECT (force the direct route) */
+    int32_t reserved;             /* 0 */
+    void* workspace;              /* reserved: NULL, or 16-B aligned */
+    size_t workspace_bytes;
+} dctr_ffm_args_t;
+size_t dctr_ffm_workspace_bytes(const dctr_ffm_args_t* args);
+/* The route dctr_ffm_fwd takes for these arguments (DCTR_FFM_ROUTE_LDS / DCTR_FFM_ROUTE_DIRECT), or the DCTR_E_* its size checks
+ * answer.  Pointers are not looked at. */
+int dctr_ffm_route(const dctr_ffm_args_t* args);
+int dctr_ffm_fwd(const dctr_ffm_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
