@@ -177,6 +177,26 @@ class ffm(object):
                     ("workspace_bytes", c_sz)]
 
 
+class ifm(object):
+    """dctr_ifm_src_t / dctr_ifm_lin_t / dctr_ifm_args_t, one level down for the same reason as interacting.Args (tests/test_ifm_cpu.py
+    checks the layout)."""
+    ROUTE_AUTO, ROUTE_WORKSPACE, ROUTE_LDS = 0, 1, 2
+
+    class Src(ctypes.Structure):
+        _fields_ = [("act", c_vp), ("kernel", c_vp), ("act_stride", c_i64), ("K", c_i32), ("reserved", c_i32)]
+
+    class Lin(ctypes.Structure):
+        _fields_ = [("table", c_vp), ("ids", c_vp), ("vec", c_vp), ("vocab", c_i64), ("ids_stride", c_i64), ("vec_stride", c_i64),
+                    ("ids_is_i64", c_i32), ("reserved", c_i32)]
+
+
+ifm.Args = type("Args", (ctypes.Structure,), {"_fields_": [
+    ("batch", c_i64), ("n_fields", c_i32), ("dim", c_i32), ("x", c_vp), ("x_stride", c_i64), ("n_src", c_i32), ("softmax", c_i32),
+    ("src", ifm.Src * 2), ("mprime", c_vp), ("mprime_stride", c_i64), ("lin", c_vp), ("n_lin", c_i32), ("n_add", c_i32),
+    ("add", c_vp * 4), ("global_bias", c_vp), ("sigmoid_out", c_i32), ("route", c_i32), ("out", c_vp), ("factor_out", c_vp),
+    ("factor_stride", c_i64), ("status", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -268,6 +288,9 @@ SYMBOLS = {
     "dctr_ffm_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_route": (ctypes.c_int, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_fwd": (ctypes.c_int, [ctypes.POINTER(ffm.Args), c_vp]),
+    "dctr_ifm_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.Args)]),
+    "dctr_ifm_route": (ctypes.c_int, [ctypes.POINTER(ifm.Args)]),
+    "dctr_ifm_fwd": (ctypes.c_int, [ctypes.POINTER(ifm.Args), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

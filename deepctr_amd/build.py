@@ -51,6 +51,7 @@ SOURCES = [
     "bilinear_kernels.hip",
     "fieldpair_kernels.hip",
     "ffm_kernels.hip",
+    "ifm_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

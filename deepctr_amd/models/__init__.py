@@ -1,16 +1,19 @@
 """In-scope model constructors under the reference's names (deepctr/models/__init__.py:1-27 exports 27;
 BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN, AFM, PNN, NFM and DCNMix
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
-SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel)."""
+SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel,
+IFM and DIFM the input-aware FM kernel)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
 from .dcnmix import DCNMix
 from .deepfefm import DeepFEFM
 from .deepfm import DeepFM
+from .difm import DIFM
 from .fibinet import FiBiNET
 from .fnn import FNN
 from .fwfm import FwFM
+from .ifm import IFM
 from .nfm import NFM
 from .onn import ONN
 from .pnn import PNN

@@ -959,6 +959,145 @@ def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None
     return out
 
 
+_IFM_ROUTES = {None: _C.ifm.ROUTE_AUTO, "auto": _C.ifm.ROUTE_AUTO, "workspace": _C.ifm.ROUTE_WORKSPACE}
+
+
+def _ifm_args(batch, fields, dim, n_src=1, route=None):
+    if route not in _IFM_ROUTES:
+        raise ValueError("ifm: route %r: expected None / 'auto' or 'workspace'" % (route,))
+    F, d = int(fields), int(dim)
+    if F < 1 or d < 1:
+        raise ValueError("ifm: fields = %d, dim = %d" % (F, d))
+    if not 0 <= int(n_src) <= 2:
+        raise ValueError("ifm: %d factor sources: 0, 1 or 2" % int(n_src))
+    a = _C.ifm.Args(batch=int(batch), n_fields=F, dim=d, x_stride=F * d, n_src=int(n_src), mprime_stride=F, route=_IFM_ROUTES[route])
+    for s in range(int(n_src)):
+        a.src[s].K, a.src[s].act_stride = 1, 1
+    return a
+
+
+def ifm_workspace_bytes(batch, fields, dim, n_src=1, route=None):
+    """Bytes of workspace dctr_ifm_fwd needs for these shapes (read from the library: 0 on the LDS route and without factor sources)."""
+    a = _ifm_args(batch, fields, dim, n_src, route)
+    return int(_C.lib().dctr_ifm_workspace_bytes(ctypes.byref(a)))
+
+
+def ifm_route(batch, fields, dim, n_src=1, route=None):
+    """'lds' or 'workspace': the route dctr_ifm_fwd takes for these shapes (the library's answer, dctr_ifm_route)."""
+    a = _ifm_args(batch, fields, dim, n_src, route)
+    rc = int(_C.lib().dctr_ifm_route(ctypes.byref(a)))
+    if rc < 0:
+        _C.check(rc, "dctr_ifm_route")
+    return {_C.ifm.ROUTE_LDS: "lds", _C.ifm.ROUTE_WORKSPACE: "workspace"}[rc]
+
+
+def make_ifm_lin(terms, batch, device):
+    """terms: per position either (table [V] / [V, 1] float32, ids 1-D int32 / int64 view of >= batch elements) — gathered in the
+    kernel — or a float32 tensor of >= batch elements already pooled ([B] or [B, 1]; dctr_embed_pool's lin_out) -> uint8 device tensor
+    holding the dctr_ifm_lin_t array (kept alive by the caller, who also keeps the tensors alive)."""
+    arr = (_C.ifm.Lin * max(1, len(terms)))()
+    for k, t in enumerate(terms):
+        if isinstance(t, (tuple, list)):
+            table, ids = t
+            if table.dtype != torch.float32 or table.numel() != table.shape[0] or not table.is_contiguous():
+                raise ValueError("ifm: linear term %d: the table must be a contiguous float32 [V] or [V, 1] tensor" % k)
+            if ids.dim() != 1 or ids.dtype not in (torch.int32, torch.int64) or ids.shape[0] < batch:
+                raise ValueError("ifm: linear term %d: ids must be a 1-D int32 / int64 view of >= %d elements" % (k, batch))
+            _dev_check(table, ids)
+            arr[k].table, arr[k].vocab = table.data_ptr(), int(table.shape[0])
+            arr[k].ids, arr[k].ids_is_i64 = ids.data_ptr(), int(ids.dtype == torch.int64)
+            arr[k].ids_stride = int(ids.stride(0)) if ids.shape[0] != 1 else 1
+        else:
+            if t.dtype != torch.float32 or t.numel() != t.shape[0] or t.shape[0] < batch:
+                raise ValueError("ifm: linear term %d: a pre-pooled term must be a float32 [B] or [B, 1] tensor of >= %d rows" % (k, batch))
+            _dev_check(t)
+            arr[k].vec = t.data_ptr()
+            arr[k].vec_stride = int(t.stride(0)) if t.shape[0] != 1 else 1
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), global_bias=None, sigmoid_out=False, out=None,
+        factor_out=None, status=None, route=None, workspace=None, lin_desc=None):
+    """The input-aware FM of IFM / DIFM (reference models/ifm.py:55-72, difm.py:59-80), one launch from the factor's inputs to the
+    prediction.  x: float32 [B, >= fields*dim] with unit column stride, field f's embedding in columns [f*dim, (f+1)*dim) (dnn_in, read in
+    place).  ``sources``: 0, 1 or 2 pairs (act [B, K] row-strided, kernel [K, fields] Keras layout); ``mprime`` [B, fields] is added to
+    their products and required without sources.  m = fields * softmax(m') with ``softmax``, else m'.  ``lin``: per position (0 or
+    ``fields`` of them) a (table, ids) pair or a pre-pooled [B] vector (make_ifm_lin; ``lin_desc`` = its result, then ``lin`` is only
+    counted) — refined by m BY POSITION; ``add``: up to four [B] vectors added unrefined.  Returns out [B] = fm + lin + add + bias,
+    through a sigmoid with ``sigmoid_out``.  ``factor_out`` [B, >= fields]: receives m.  ``route='workspace'`` forces the route whose
+    m' goes through HBM; ``workspace``: a float32 tensor of >= ifm_workspace_bytes (default: the per-stream scratch)."""
+    F, d = int(fields), int(dim)
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1) or x.shape[1] < F * d:
+        raise ValueError("ifm: x must be a float32 [B, >= %d] buffer with unit column stride" % (F * d))
+    B = int(x.shape[0])
+    sources = list(sources)
+    a = _ifm_args(B, F, d, len(sources), route)
+    a.x, a.x_stride = x.data_ptr(), row_stride(x)
+    keep = []
+    for s, (act, kernel) in enumerate(sources):
+        if act.dim() != 2 or act.dtype != torch.float32 or (act.shape[1] > 1 and act.stride(1) != 1) or act.shape[0] != B:
+            raise ValueError("ifm: source %d: act must be a float32 [%d, K] matrix with unit column stride" % (s, B))
+        K = int(act.shape[1])
+        if K < 1 or kernel.dtype != torch.float32 or tuple(kernel.shape) != (K, F):
+            raise ValueError("ifm: source %d: kernel must be float32 [%d, %d], got %s" % (s, K, F, tuple(kernel.shape)))
+        kernel = _f32c(kernel, "kernel")
+        keep.append(kernel)
+        a.src[s].act, a.src[s].act_stride, a.src[s].K, a.src[s].kernel = act.data_ptr(), row_stride(act), K, kernel.data_ptr()
+    if mprime is None and not sources:
+        raise ValueError("ifm: neither a factor source nor mprime")
+    if mprime is not None:
+        if mprime.dim() != 2 or mprime.dtype != torch.float32 or (mprime.shape[1] > 1 and mprime.stride(1) != 1) \
+                or mprime.shape[0] != B or mprime.shape[1] < F:
+            raise ValueError("ifm: mprime must be a float32 [%d, >= %d] matrix with unit column stride" % (B, F))
+        a.mprime, a.mprime_stride = mprime.data_ptr(), row_stride(mprime)
+    n_lin = len(lin)
+    if n_lin not in (0, F):
+        raise ValueError("ifm: %d linear terms for %d fields: the factor refines them by position, 0 or one per field" % (n_lin, F))
+    if n_lin:
+        if lin_desc is None:
+            lin_desc = make_ifm_lin(lin, B, x.device)
+        a.lin, a.n_lin = lin_desc.data_ptr(), n_lin
+    add = [t for t in add if t is not None]
+    if len(add) > 4:
+        raise ValueError("ifm: %d add vectors: at most 4" % len(add))
+    for i, t in enumerate(add):
+        if t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous():
+            raise ValueError("ifm: add[%d] must be a contiguous float32 vector of %d elements" % (i, B))
+        a.add[i] = t.data_ptr()
+    a.n_add = len(add)
+    if global_bias is not None:
+        if global_bias.dtype != torch.float32 or global_bias.numel() != 1:
+            raise ValueError("ifm: global_bias must be a float32 scalar tensor")
+        a.global_bias = global_bias.data_ptr()
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.numel() != B or not out.is_contiguous():
+        raise ValueError("ifm: out must be a contiguous float32 vector of %d elements" % B)
+    if factor_out is not None:
+        if factor_out.dim() != 2 or factor_out.dtype != torch.float32 or (factor_out.shape[1] > 1 and factor_out.stride(1) != 1) \
+                or factor_out.shape[0] != B or factor_out.shape[1] < F:
+            raise ValueError("ifm: factor_out must be a float32 [%d, >= %d] matrix with unit column stride" % (B, F))
+        a.factor_out, a.factor_stride = factor_out.data_ptr(), row_stride(factor_out)
+    if status is not None:
+        if status.dtype != torch.int32:
+            raise ValueError("ifm: status must be an int32 tensor")
+        a.status = status.data_ptr()
+    _dev_check(x, mprime, lin_desc, global_bias, out, factor_out, status, workspace, *(add + keep + [s_[0] for s_ in sources]))
+    a.softmax, a.sigmoid_out, a.out = int(bool(softmax)), int(bool(sigmoid_out)), out.data_ptr()
+    need = int(_C.lib().dctr_ifm_workspace_bytes(ctypes.byref(a)))
+    if need:
+        if workspace is not None:
+            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
+                raise ValueError("ifm: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
+            ws = workspace
+        else:
+            ws = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _C.check(_C.lib().dctr_ifm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_ifm_fwd")
+    del keep
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -376,6 +376,22 @@ def model_logits(model, staged, lo, hi, training=False):
         if lin is not None:
             logit = logit + lin
         return logit + model.prediction.w("global_bias")
+    if name in ("IFM", "DIFM"):             # models/ifm.py:55-72, difm.py:59-80: input-aware factor -> refined FM + refined linear terms
+        x = torch.stack(parts[:len(sp.fields)], dim=1)              # [B,F,d]
+        h = dnn_forward(model.dnn, x.reshape(x.shape[0], -1), training)
+        if name == "IFM":
+            m = x.shape[1] * torch.softmax(h @ model.dense.w("kernel"), dim=1)
+        else:
+            att = _interacting(model.att, x)
+            m = att.reshape(att.shape[0], -1) @ model.dense.w("kernel") + h @ model.dense_1.w("kernel")
+        r = x * m.unsqueeze(-1)
+        logit = 0.5 * (r.sum(1).pow(2) - (r * r).sum(1)).sum(-1)
+        terms = model.linear_terms(staged, lo, hi, _pool)           # [B,F] in position order: paired with m by position
+        if terms is not None:
+            logit = logit + (terms * m).sum(-1)
+        if lin is not None:                                         # (the stage's linear part holds the DenseFeat only: not refined)
+            logit = logit + lin
+        return logit + model.prediction.w("global_bias")
     if name == "FwFM":                      # models/fwfm.py:51-66: linear + FwFMLayer per group (+ DNN over the plain DNN input)
         logit = torch.zeros(hi - lo, device=sp.device)
         for g, layer in zip(model.groups, model.fwfm_layers):

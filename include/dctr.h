@@ -550,6 +550,73 @@ int dctr_ffm_route(const dctr_ffm_args_t* args);
 int dctr_ffm_fwd(const dctr_ffm_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * IFM / DIFM: the input-aware factor, the refined FM and linear terms, the prediction — deepctr/models/ifm.py:55-72, difm.py:59-80
+ *     F >= 1 fields of one embedding_dim d, read in place from the leading F*d columns of x (e.g. dnn_in) at x_stride.  Per sample b:
+ *       m'[f] = mprime[b, f] (0 when NULL) + sum over the n_src sources of act[b, 0..K) . kernel[0..K, f]   (Keras layout [K, F], no bias)
+ *       m[f]  = softmax ? F * softmax_f(m')[f], the row maximum subtracted (IFM) : m'[f] (DIFM)
+ *       fm    = 0.5 * sum_c ((sum_f m[f] e[f, c])^2 - sum_f (m[f] e[f, c])^2)
+ *       lin   = sum_k m[k] * lin_k         n_lin = 0 or F first-order terms, paired with m BY POSITION as the reference pairs them
+ *       out[b] = act(fm + lin + add[0][b] + .. + *global_bias),  act = sigmoid when sigmoid_out
+ *     lin_k is gathered from a 1-wide table by id (int32 / int64), or read from a [B] vector already pooled (dctr_embed_pool's lin_out).
+ *     An id outside [0, vocab) raises DCTR_STATUS_INDEX_OOR and contributes zero; nothing outside the tables is read.  The add vectors
+ *     enter unrefined (the dense linear term is one of them).  m reaches memory only through the optional factor_out [B, F].
+ *     The products run on v_mfma_f32_16x16x4_f32 (exact fp32).  Routes: the [16, F] tile of m' of a wave's samples waits in LDS, or —
+ *     more than 560 fields, or route = DCTR_IFM_ROUTE_WORKSPACE — goes through a [B, F] workspace between two launches.  Both routes
+ *     give the same bits; K and d never decide the route (K is walked in chunks of 64, d by the lanes).  No shape is refused for its
+ *     size up to F*d < 2^27.  Without sources (mprime alone) there is nothing to project: one launch, no LDS, no workspace.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_IFM_ROUTE_AUTO = 0, DCTR_IFM_ROUTE_WORKSPACE = 1, DCTR_IFM_ROUTE_LDS = 2 };
+typedef struct {
+    const float* act;             /* [B, act_stride] fp32: the DNN's last hidden layer, the flattened attention output, ... */
+    const float* kernel;          /* [K, F] fp32, contiguous */
+    int64_t act_stride;           /* floats between rows, >= K */
+    int32_t K;                    /* >= 1 */
+    int32_t reserved;             /* 0 */
+} dctr_ifm_src_t;
+typedef struct {
+    const float* table;           /* [vocab] fp32 (a 1-wide linear embedding table); unused when vec */
+    const void* ids;              /* sample b's id at ids[b * ids_stride] */
+    const float* vec;             /* NULL, or the term itself: sample b's at vec[b * vec_stride] */
+    int64_t vocab;
+    int64_t ids_stride;           /* elements */
+    int64_t vec_stride;           /* floats */
+    int32_t ids_is_i64;           /* 0: int32 ids, 1: int64 ids */
+    int32_t reserved;             /* 0 */
+} dctr_ifm_lin_t;
+typedef struct {
+    int64_t batch;
+    int32_t n_fields;             /* F >= 1 */
+    int32_t dim;                  /* d >= 1 */
+    const float* x;               /* [B, x_stride]: field f's embedding at columns [f*d, (f+1)*d) */
+    int64_t x_stride;             /* floats, >= F*d */
+    int32_t n_src;                /* 0, 1 or 2 */
+    int32_t softmax;              /* 0 | 1 */
+    dctr_ifm_src_t src[2];
+    const float* mprime;          /* NULL, or [B, mprime_stride]: added to the sources' products; REQUIRED when n_src = 0 */
+    int64_t mprime_stride;        /* floats, >= F */
+    const dctr_ifm_lin_t* lin;    /* DEVICE array [n_lin], position order */
+    int32_t n_lin;                /* 0 or F */
+    int32_t n_add;                /* 0 .. 4 */
+    const float* add[4];          /* [B] each */
+    const float* global_bias;     /* NULL or a device scalar */
+    int32_t sigmoid_out;          /* 0 | 1 */
+    int32_t route;                /* DCTR_IFM_ROUTE_AUTO | DCTR_IFM_ROUTE_WORKSPACE (force the workspace route) */
+    float* out;                   /* [B] */
+    float* factor_out;            /* NULL, or [B, factor_stride]: m */
+    int64_t factor_stride;        /* floats, >= F */
+    int32_t* status;              /* optional device word, DCTR_STATUS_* bits are OR-ed in */
+    void* workspace;              /* NULL, or device scratch of dctr_ifm_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_ifm_args_t;
+/* Bytes dctr_ifm_fwd needs for these arguments (batch, n_fields, n_src, route are read): 0 on the LDS route and without sources;
+ * on the workspace route it is REQUIRED (DCTR_E_NULL without, before anything is launched). */
+size_t dctr_ifm_workspace_bytes(const dctr_ifm_args_t* args);
+/* The route dctr_ifm_fwd takes (DCTR_IFM_ROUTE_LDS / DCTR_IFM_ROUTE_WORKSPACE), or the DCTR_E_* its size checks answer.  Pointers are
+ * not looked at. */
+int dctr_ifm_route(const dctr_ifm_args_t* args);
+int dctr_ifm_fwd(const dctr_ifm_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
