@@ -1,10 +1,13 @@
 """Shared wiring for the in-scope model constructors."""
+import torch
+
 from .. import ops
 from ..engine import Model
 from ..feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
 from ..initializers import Zeros
 from ..inputs import create_embedding_matrix
 from ..layers.utils import Linear
+from .. import training as tops
 
 
 def linear_columns(feature_columns):
@@ -23,6 +26,43 @@ def linear_columns(feature_columns):
 
 class FeatureModel(Model):
     """linear part + embedding stage + DNN + head: the skeleton DeepFM / DCN / xDeepFM share."""
+
+    def __init__(self, *args, **kwargs):
+        super(FeatureModel, self).__init__(*args, **kwargs)
+        self._buf = {}              # batch size -> the model's own per-batch buffers (_per_batch)
+
+    def _per_batch(self, B, alloc):
+        """The buffers ``alloc()`` returns for launches of B rows: the same objects on every call while that size is held."""
+        bufs = self._buf.get(B)
+        if bufs is None:
+            if len(self._buf) >= 4:            # ragged remainder sizes (N % span) must not pile up per-B buffers
+                self._buf.clear()
+            bufs = self._buf[B] = alloc()
+        return bufs
+
+    def _one(self):
+        """ones[1]: the head weight of a launch whose only input column already is a logit."""
+        if getattr(self, "_one_t", None) is None:
+            self._one_t = torch.ones(1, dtype=torch.float32, device=self.device)
+        return self._one_t
+
+    # ---- the forward in differentiable torch ops (training.model_logits) ----------------------------------------------------------
+    def autograd_logits(self, staged, lo, hi, training=False):
+        """Pre-sigmoid logits [B] of rows [lo, hi): the stage, the model's own logit, then what every model adds to it."""
+        parts, extra, lin, fms = tops.stage_forward(self.stage_plan, staged, lo, hi)
+        return self._autograd_tail(self._autograd_logit(staged, lo, hi, parts, extra, training), lin, fms)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):
+        """The model's own logit [B] from the stage's outputs (``parts``: the columns of the DNN input, a None per slot of
+        ``extra`` for the model to fill).  Default: DNN over the whole DNN input, then dense/kernel."""
+        return (tops.dnn_forward(self.dnn, torch.cat(parts, dim=-1), training) @ self.dense.w("kernel")).reshape(-1)
+
+    def _autograd_tail(self, logit, lin, fms):
+        if lin is not None:
+            logit = logit + lin
+        for f in fms:
+            logit = logit + f
+        return logit + self.prediction.w("global_bias")
 
     def build_linear(self, linear_feature_columns, seed):
         lin_cols = linear_columns(linear_feature_columns)
@@ -162,7 +202,6 @@ class FusedForward(object):
 
     def _padded_dnn(self):
         """(kernels, biases, head_w, bn) at the padded widths: persistent buffers, refreshed in place from the current weights."""
-        import torch
         tgt = self._pad_spec
         ks, bs = self.dnn.kernels, self.dnn.biases
         bn = self.dnn.bn_params()
@@ -291,7 +330,6 @@ class FusedForward(object):
         """The two argument structs of the fused launch for rows [lo, hi) -> out.  Marshalling only, apart from the hash pre-pass of a
         hashed model (its output is an argument): the launches of _launch_extra are the caller's."""
         import ctypes
-        import torch
         from .. import _C
         sp, B = self.stage_plan, hi - lo
         padded = self._use_padded(B)
@@ -363,7 +401,6 @@ class FusedForward(object):
         g, m = type(g).from_buffer_copy(g), type(m).from_buffer_copy(m)     # private copies of the two argument structs
         fn, stream = _C.lib().dctr_embed_mlp_fwd, _C.stream_ptr()
         a, b = int(bool(sp.fm_group_names)), int(sp.has_linear)
-        import torch
         # its own hashed-id matrix and its own extra-logit vectors: prepared launches may run on several streams / in one multi-stream
         # graph (the per-B vectors of _extra_logit_buffers serve ONE stream)
         # (ids hashed at stage(): the struct already points into staged.hashed, nothing to launch)

@@ -4,6 +4,7 @@ AFMLayer (or FM) per embedding group named in ``fm_group``.  SURVEY §8(f) rank 
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..feature_column import DEFAULT_GROUP_NAME, DenseFeat
 from ..layers.base import name_scope
@@ -40,7 +41,6 @@ class _AFM(FeatureModel):
                     self.afm_layers.append(self._add(layer))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
         self.dnn = self.dense = None            # AFM has neither (afm.py:45-58); the HIP training step asks
-        self._buf = {}
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan
@@ -48,11 +48,7 @@ class _AFM(FeatureModel):
         B = hi - lo
         add = self._logits_to_add(ws)
         if self.use_attention:
-            bufs = self._buf.get(B)
-            if bufs is None:
-                if len(self._buf) >= 4:            # ragged remainder sizes (N % span) must not pile up per-B buffers
-                    self._buf.clear()
-                bufs = self._buf[B] = [torch.zeros(B, 1, dtype=torch.float32, device=self.device) for _ in self.groups]
+            bufs = self._per_batch(B, lambda: [torch.zeros(B, 1, dtype=torch.float32, device=self.device) for _ in self.groups])
             for g, layer, y in zip(self.groups, self.afm_layers, bufs):
                 first, n, dim = sp.group_slices[g]
                 ops.afm(ws["dnn_in"][:, first:], layer.w("attention_W"), layer.w("attention_b"), layer.w("projection_h"),
@@ -65,10 +61,17 @@ class _AFM(FeatureModel):
         ops.mlp(head_in, [], [], "linear", head_w=one, add=add + rest, global_bias=self.prediction.w('global_bias'),
                 sigmoid_out=self.task == "binary", in_dim=1, out=out)
 
-    def _one(self):
-        if getattr(self, "_one_t", None) is None:
-            self._one_t = torch.ones(1, dtype=torch.float32, device=self.device)
-        return self._one_t
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # afm.py:45-58: one AFMLayer per group (FM: the stage's)
+        logit = torch.zeros(hi - lo, device=self.device)
+        for g, layer in zip(self.groups, self.afm_layers):
+            embs = tops._group_embeddings(self.stage_plan, parts, g)
+            ii, jj = tops._pair_indices(len(embs))
+            bi = torch.stack([embs[i] for i in ii], dim=1) * torch.stack([embs[j] for j in jj], dim=1)     # [B,P,E]
+            att = torch.relu(bi @ layer.w("attention_W") + layer.w("attention_b"))
+            score = torch.softmax(att @ layer.w("projection_h"), dim=1)
+            att_out = tops._dropout((score * bi).sum(1), getattr(layer, "dropout_rate", 0), training)     # interaction.py:142-143
+            logit = logit + (att_out @ layer.w("projection_p")).reshape(-1)
+        return logit
 
 
 def AFM(linear_feature_columns, dnn_feature_columns, fm_group=DEFAULT_GROUP_NAME, use_attention=True, attention_factor=8,

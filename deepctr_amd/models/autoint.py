@@ -8,6 +8,7 @@ the remaining rows of dense/kernel as its head, adding the linear and attention 
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -59,15 +60,9 @@ class _AutoInt(FeatureModel):
                 last = dnn_hidden_units[-1]
             self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(self.att_out_dim + last))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
 
     def _att_weights(self):
         return [layer.weights_qkvr for layer in self.att_layers]
-
-    def _one(self):
-        if getattr(self, "_one_t", None) is None:
-            self._one_t = torch.ones(1, dtype=torch.float32, device=self.device)
-        return self._one_t
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan
@@ -77,11 +72,7 @@ class _AutoInt(FeatureModel):
         kernel = self.dense.w('kernel')
         att = None
         if self.att_layers:
-            att = self._buf.get(B)
-            if att is None:
-                if len(self._buf) >= 4:            # ragged remainder sizes (N % span) must not pile up per-B buffers
-                    self._buf.clear()
-                att = self._buf[B] = torch.zeros(B, dtype=torch.float32, device=self.device)
+            att = self._per_batch(B, lambda: torch.zeros(B, dtype=torch.float32, device=self.device))
             ops.interacting(ws["dnn_in"], self._att_weights(), self.att_embedding_size, self.att_head_num, self.att_res, False,
                             fields=self.n_fields, dim=self.emb_dim, head_w=kernel[:self.att_out_dim], logit=att)
         if self.dnn is not None:
@@ -91,6 +82,17 @@ class _AutoInt(FeatureModel):
         else:
             ops.mlp(att.reshape(-1, 1), [], [], "linear", head_w=self._one(), add=add, global_bias=self.prediction.w('global_bias'),
                     sigmoid_out=self.task == "binary", in_dim=1, out=out)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # autoint.py:55-79
+        outs = []
+        if self.att_layers:
+            h = torch.stack(parts[:self.n_fields], dim=1)          # [B,F,E]
+            for layer in self.att_layers:
+                h = tops._interacting(layer, h)
+            outs.append(h.reshape(h.shape[0], -1))
+        if self.dnn is not None:
+            outs.append(tops.dnn_forward(self.dnn, torch.cat(parts, dim=-1), training))
+        return (torch.cat(outs, dim=-1) @ self.dense.w("kernel")).reshape(-1)
 
 
 def AutoInt(linear_feature_columns, dnn_feature_columns, att_layer_num=3, att_embedding_size=8, att_head_num=2, att_res=True,

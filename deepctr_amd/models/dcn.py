@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -266,6 +267,25 @@ class _DCN(FusedForward, FeatureModel):
             xl, xl_stride = nxt, nxt_stride
         if logit is not None:
             ops.mlp(xl, [], [], "linear", head_w=head_w, in_dim=d, out=logit)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # dcn.py:45-64: Dense(1) over [cross_out, deep_out]
+        x = torch.cat(parts, dim=-1)
+        outs = []
+        if self.cross is not None:
+            outs.append(self._autograd_cross(x))
+        if self.dnn is not None:
+            outs.append(tops.dnn_forward(self.dnn, x, training))
+        return (torch.cat(outs, dim=-1) @ self.dense.w("kernel")).reshape(-1)
+
+    def _autograd_cross(self, x0):
+        xl = x0
+        for i in range(self.cross.layer_num):
+            w, b = self.cross.w("kernel%d" % i), self.cross.w("bias%d" % i).reshape(-1)
+            if self.cross.parameterization == "vector":
+                xl = x0 * (xl @ w) + b + xl
+            else:
+                xl = x0 * (xl @ w.t() + b) + xl
+        return xl
 
 
 def DCN(linear_feature_columns, dnn_feature_columns, cross_num=2, cross_parameterization='vector',

@@ -1,6 +1,8 @@
 """DCNMix — same signature as ``deepctr.models.dcnmix.DCNMix`` (reference deepctr/models/dcnmix.py:22-78): DCN with the
 cross part replaced by ``CrossNetMix`` (mixture of low-rank experts).  SURVEY §8(f) rank 4 sibling: DCN's launches with
 ``dctr_crossnet_mix_fwd`` in place of ``dctr_crossnet_fwd``."""
+import torch
+
 from .. import ops
 from ..layers.interaction import CrossNetMix
 from .dcn import _DCN
@@ -21,6 +23,19 @@ class _DCNMix(_DCN):
 
     def _run_cross(self, dnn_in, B, d, stack):
         ops.crossnet_mix(dnn_in, *self._cross_packed, dim=d, out=stack)
+
+    def _autograd_cross(self, x0):                  # CrossNetMix (interaction.py:511-549)
+        cr = self.cross
+        xl = x0
+        for i in range(cr.layer_num):
+            U, V, C, b = cr.w("U_list%d" % i), cr.w("V_list%d" % i), cr.w("C_list%d" % i), cr.w("bias%d" % i).reshape(-1)
+            gate = torch.softmax(torch.cat([xl @ g.w("kernel") for g in cr.gating], dim=-1), dim=-1)       # [B,experts]
+            moe = torch.zeros_like(xl)
+            for e in range(cr.num_experts):
+                v = torch.tanh(torch.tanh(xl @ V[e]) @ C[e].t())
+                moe = moe + gate[:, e:e + 1] * (x0 * (v @ U[e].t() + b))
+            xl = moe + xl
+        return xl
 
 
 def DCNMix(linear_feature_columns, dnn_feature_columns, cross_num=2, dnn_hidden_units=(256, 128, 64), l2_reg_linear=1e-5,

@@ -9,6 +9,7 @@ adding that logit, the bias and the sigmoid."""
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..feature_column import DEFAULT_GROUP_NAME
 from ..layers.base import name_scope
@@ -62,23 +63,15 @@ class _DeepFEFM(FeatureModel):
             # logit is used: the weight exists under dense/kernel)
             self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(last))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
-
-    def _one(self):
-        if getattr(self, "_one_t", None) is None:
-            self._one_t = torch.ones(1, dtype=torch.float32, device=self.device)
-        return self._one_t
 
     def _buffers(self, B):
-        bufs = self._buf.get(B)
-        if bufs is None:
-            if len(self._buf) >= 4:                # ragged remainder sizes (N % span) must not pile up per-B buffers
-                self._buf.clear()
-            bufs = self._buf[B] = {"logit": torch.zeros(B, dtype=torch.float32, device=self.device)}
+        def alloc():
+            bufs = {"logit": torch.zeros(B, dtype=torch.float32, device=self.device)}
             if self.pairs_in_dnn and self.exclude_embed:
                 # (zeros: the row padding to a multiple of 4 floats is never written, and the DNN kernels may read it)
                 bufs["pairs"] = torch.zeros(B, (self.n_pairs + 3) // 4 * 4, dtype=torch.float32, device=self.device)
-        return bufs
+            return bufs
+        return self._per_batch(B, alloc)
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan
@@ -110,6 +103,24 @@ class _DeepFEFM(FeatureModel):
                 bufs["logit"].zero_()
                 rest = [bufs["logit"]]
             ops.mlp(rest[0].reshape(-1, 1), [], [], "linear", head_w=self._one(), add=rest[1:], in_dim=1, **kw)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # deepfefm.py:62-99: the ablation switches
+        pairs = tops._fefm(self.fefm, torch.stack(tops._group_embeddings(self.stage_plan, parts, DEFAULT_GROUP_NAME), dim=1))
+        logit = torch.zeros(hi - lo, device=self.device)
+        if self.dnn is not None:
+            if not self.pairs_in_dnn:
+                h = torch.cat(parts, dim=-1)
+            elif self.exclude_embed:
+                h = pairs
+            else:
+                h = torch.cat(parts + [pairs], dim=-1)
+            logit = logit + (tops.dnn_forward(self.dnn, h, training) @ self.dense.w("kernel")).reshape(-1)
+        if self.use_fefm:
+            logit = logit + pairs.sum(-1)
+        return logit
+
+    def _autograd_tail(self, logit, lin, fms):
+        return super(_DeepFEFM, self)._autograd_tail(logit, lin if self.use_linear else None, fms)
 
 
 def DeepFEFM(linear_feature_columns, dnn_feature_columns, use_fefm=True, dnn_hidden_units=(256, 128, 64), l2_reg_linear=0.00001,

@@ -12,6 +12,7 @@ there, so the last bits change from run to run (DESIGN.md 4.12 has the figures)"
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..layers.base import name_scope
 from ..layers.core import Dense, PredictionLayer
 from ..layers.interaction import InteractingLayer
@@ -44,6 +45,10 @@ class _DIFM(InputAwareModel):
     def _more_buffers(self, B, bufs):
         bufs["att"] = torch.zeros(B, self.att_out_dim, dtype=torch.float32, device=self.device)
         bufs["m_vec"] = torch.zeros(B, self.n_fields, dtype=torch.float32, device=self.device)
+
+    def _autograd_factor(self, x, h):
+        att = tops._interacting(self.att, x)
+        return att.reshape(att.shape[0], -1) @ self.dense.w("kernel") + h @ self.dense_1.w("kernel")
 
     def _forward(self, staged, lo, hi, out):
         ws, bufs, add, desc = self._stage_run(staged, lo, hi)

@@ -7,6 +7,7 @@ head, adding the linear logit, the bias and the sigmoid."""
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -54,16 +55,10 @@ class _FiBiNET(FeatureModel):
                 last = dnn_hidden_units[-1]
             self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(last))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
 
     def _dnn_input(self, B):
-        buf = self._buf.get(B)
-        if buf is None:
-            if len(self._buf) >= 4:                # ragged remainder sizes (N % span) must not pile up per-B buffers
-                self._buf.clear()
-            # (zeros: the row padding to a multiple of 4 floats is never written, and the DNN kernels may read it)
-            buf = self._buf[B] = torch.zeros(B, (self.dnn_in_dim + 3) // 4 * 4, dtype=torch.float32, device=self.device)
-        return buf
+        # (zeros: the row padding to a multiple of 4 floats is never written, and the DNN kernels may read it)
+        return self._per_batch(B, lambda: torch.zeros(B, (self.dnn_in_dim + 3) // 4 * 4, dtype=torch.float32, device=self.device))
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan
@@ -78,6 +73,17 @@ class _FiBiNET(FeatureModel):
             ops.mlp(buf, self.dnn.kernels, self.dnn.biases, self.dnn.activation, dice=self.dnn.dice_params(), **kw)
         else:
             ops.mlp(buf, [], [], "linear", **kw)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # fibinet.py:50-63
+        F = self.n_fields
+        x = torch.stack(parts[:F], dim=1)                           # [B,F,E]
+        a2 = torch.relu(torch.relu(x.mean(-1) @ self.senet.w("W_1")) @ self.senet.w("W_2"))
+        # concat_func joins the two [B,P,E] outputs on the last axis (reference layers/utils.py:236), then Flatten
+        h = torch.cat([tops._bilinear(self.senet_bilinear, x * a2.unsqueeze(-1)), tops._bilinear(self.bilinear, x)], dim=-1)
+        h = torch.cat([h.reshape(x.shape[0], -1)] + parts[F:], dim=-1)
+        if self.dnn is not None:
+            h = tops.dnn_forward(self.dnn, h, training)
+        return (h @ self.dense.w("kernel")).reshape(-1)
 
 
 def FiBiNET(linear_feature_columns, dnn_feature_columns, bilinear_type='interaction', reduction_ratio=3,

@@ -7,6 +7,7 @@ the bias and the sigmoid."""
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..feature_column import DEFAULT_GROUP_NAME
 from ..layers.base import name_scope
@@ -52,23 +53,13 @@ class _FwFM(FeatureModel):
                                          device=self.device).build_for(sp.in_dim))
                 self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(dnn_hidden_units[-1]))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
-
-    def _one(self):
-        if getattr(self, "_one_t", None) is None:
-            self._one_t = torch.ones(1, dtype=torch.float32, device=self.device)
-        return self._one_t
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan
         ws = sp.run(staged, lo, hi)
         B = hi - lo
         add = self._logits_to_add(ws)
-        bufs = self._buf.get(B)
-        if bufs is None:
-            if len(self._buf) >= 4:                # ragged remainder sizes (N % span) must not pile up per-B buffers
-                self._buf.clear()
-            bufs = self._buf[B] = [torch.zeros(B, dtype=torch.float32, device=self.device) for _ in self.groups]
+        bufs = self._per_batch(B, lambda: [torch.zeros(B, dtype=torch.float32, device=self.device) for _ in self.groups])
         for k, (g, layer, y) in enumerate(zip(self.groups, self.fwfm_layers, bufs)):
             first, n, dim = sp.group_slices[g]
             ops.fieldpair(ws["dnn_in"], layer.field_strengths, kind="fwfm", fields=n, dim=dim, x_offset=first, logit=y,
@@ -80,6 +71,17 @@ class _FwFM(FeatureModel):
                     bn=self.dnn.bn_params(), head_w=self.dense.w('kernel'), add=rest, in_dim=sp.in_dim, **kw)
         else:
             ops.mlp(rest[0].reshape(-1, 1), [], [], "linear", head_w=self._one(), add=rest[1:], in_dim=1, **kw)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # fwfm.py:51-66
+        logit = torch.zeros(hi - lo, device=self.device)
+        for g, layer in zip(self.groups, self.fwfm_layers):
+            x = torch.stack(tops._group_embeddings(self.stage_plan, parts, g), dim=1)
+            gram = torch.einsum("bie,bje->bij", x, x)
+            logit = logit + (gram * torch.triu(layer.field_strengths, diagonal=1)).sum((1, 2))
+        if self.dnn is not None:
+            h = tops.dnn_forward(self.dnn, torch.cat(parts, dim=-1), training)
+            logit = logit + (h @ self.dense.w("kernel")).reshape(-1)
+        return logit
 
 
 def FwFM(linear_feature_columns, dnn_feature_columns, fm_group=(DEFAULT_GROUP_NAME,), dnn_hidden_units=(256, 128, 64),

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage, _column, _fit_int32, _ids_from_column, prehashed_on_host
 from ..feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
 from ..layers.base import name_scope
@@ -66,7 +67,6 @@ class InputAwareModel(FeatureModel):
         self.dnn = self._add(DNN(dnn_hidden_units, dnn_activation, 0, dnn_dropout, dnn_use_bn, seed=seed,
                                  device=self.device).build_for(sp.in_dim))
         self.hidden_dim = int(dnn_hidden_units[-1])
-        self._buf = {}
 
     # -- staging: the shared stage + the ids of the first-order terms, hashed once per feature ---------------------------------------
     def _hashes(self, fc):
@@ -108,15 +108,13 @@ class InputAwareModel(FeatureModel):
         return self.linear_tables[fc.embedding_name].embeddings
 
     def _buffers(self, B):
-        bufs = self._buf.get(B)
-        if bufs is None:
-            if len(self._buf) >= 4:                # ragged remainder sizes (N % span) must not pile up per-B buffers
-                self._buf.clear()
-            bufs = self._buf[B] = {"hidden": torch.zeros(B, self.hidden_dim, dtype=torch.float32, device=self.device),
-                                   "pooled": {fc.name: torch.zeros(B, 1, dtype=torch.float32, device=self.device)
-                                              for fc in self.lin_positions if isinstance(fc, VarLenSparseFeat)}}
+        def alloc():
+            bufs = {"hidden": torch.zeros(B, self.hidden_dim, dtype=torch.float32, device=self.device),
+                    "pooled": {fc.name: torch.zeros(B, 1, dtype=torch.float32, device=self.device)
+                               for fc in self.lin_positions if isinstance(fc, VarLenSparseFeat)}}
             self._more_buffers(B, bufs)
-        return bufs
+            return bufs
+        return self._per_batch(B, alloc)
 
     def _more_buffers(self, B, bufs):
         pass
@@ -139,23 +137,33 @@ class InputAwareModel(FeatureModel):
             desc = cache[key] = ops.make_ifm_lin(terms, hi - lo, self.device)
         return desc
 
-    def linear_terms(self, staged, lo, hi, pool):
-        """torch ops (training.model_logits): the [B, F_lin] first-order terms of rows [lo, hi) in position order, or None."""
+    def linear_terms(self, staged, lo, hi):
+        """torch ops (autograd_logits): the [B, F_lin] first-order terms of rows [lo, hi) in position order, or None."""
         if not self.lin_positions:
             return None
         ids = staged.extra["ifm_lin_ids"]
-        from ..training import _rows_for
         out = []
         for k, fc in enumerate(self.lin_positions):
             lt = self._lin_table(fc).reshape(-1)
             if isinstance(fc, VarLenSparseFeat):
-                rows = _rows_for(fc, staged.seq[fc.name][lo:hi], True)
+                rows = tops._rows_for(fc, staged.seq[fc.name][lo:hi], True)
                 length = staged.length[fc.length_name][lo:hi] if fc.length_name is not None else None
                 weight = staged.weight[fc.weight_name][lo:hi] if fc.weight_name is not None else None
-                out.append(pool(lt[rows].unsqueeze(-1), fc, rows != 0, length, weight).reshape(-1))
+                out.append(tops._pool(lt[rows].unsqueeze(-1), fc, rows != 0, length, weight).reshape(-1))
             else:
                 out.append(lt[ids[lo:hi, k].to(torch.int64)])
         return torch.stack(out, dim=1)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # ifm.py:55-72, difm.py:59-80
+        x = torch.stack(parts[:self.n_fields], dim=1)              # [B,F,d]
+        h = tops.dnn_forward(self.dnn, x.reshape(x.shape[0], -1), training)
+        m = self._autograd_factor(x, h)
+        r = x * m.unsqueeze(-1)
+        logit = 0.5 * (r.sum(1).pow(2) - (r * r).sum(1)).sum(-1)
+        terms = self.linear_terms(staged, lo, hi)                   # [B,F] in position order: paired with m by position
+        if terms is not None:
+            logit = logit + (terms * m).sum(-1)
+        return logit                                                # (the stage's linear part holds the DenseFeat only: not refined)
 
     def _stage_run(self, staged, lo, hi):
         """The stage's launches and the pooled first-order terms: (workspace, per-B buffers, add vectors, descriptors or None)."""
@@ -191,6 +199,9 @@ class _IFM(InputAwareModel):
                                dnn_dropout, seed)
             self.dense = self._add(Dense(self.n_fields, use_bias=False, seed=seed, device=self.device).build_for(self.hidden_dim))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
+
+    def _autograd_factor(self, x, h):
+        return x.shape[1] * torch.softmax(h @ self.dense.w("kernel"), dim=1)
 
     def _forward(self, staged, lo, hi, out):
         ws, bufs, add, desc = self._stage_run(staged, lo, hi)

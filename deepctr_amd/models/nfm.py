@@ -2,7 +2,10 @@
 [BiInteractionPooling(embeddings), dense values].  SURVEY §8(f) rank 4 sibling: the gather kernel produces the embeddings
 (+ linear logit), ``dctr_bi_interaction_fwd`` pools them into columns reserved in front of the dense values, and the DNN
 kernel reads that [E + n_dense] slice in place."""
+import torch
+
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -41,6 +44,11 @@ class _NFM(FeatureModel):
         ops.mlp(ws["dnn_in"][:, off:], self.dnn.kernels, self.dnn.biases, self.dnn.activation, dice=self.dnn.dice_params(), bn=self.dnn.bn_params(),
                 head_w=self.dense.w('kernel'), add=self._logits_to_add(ws), global_bias=self.prediction.w('global_bias'),
                 sigmoid_out=self.task == "binary", in_dim=self.dnn_in_dim, out=out)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # nfm.py:49-58: DNN over [BiInteractionPooling, dense]
+        x0 = torch.stack(parts[:self.n_emb], dim=1)
+        parts[extra["bi_interaction"]] = tops._dropout(0.5 * (x0.sum(1).pow(2) - (x0 * x0).sum(1)), self.bi_dropout, training)     # nfm.py:52-53
+        return super(_NFM, self)._autograd_logit(staged, lo, hi, parts[extra["bi_interaction"]:], extra, training)
 
 
 def NFM(linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 128, 64), l2_reg_embedding=1e-5,

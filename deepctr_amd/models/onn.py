@@ -22,6 +22,7 @@ from ..engine import EmbeddingStage, _column, _fit_int32, _ids_from_column, preh
 from ..feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
 from ..layers.base import Layer, name_scope
 from ..layers.core import DNN, BatchNormalization, Dense, PredictionLayer
+from .. import training as tops
 from ._common import FeatureModel
 
 
@@ -106,7 +107,6 @@ class _ONN(FeatureModel):
             self.dnn = self._add(DNN(units, 'relu', 0, dnn_dropout, False, seed=seed, device=self.device).build_for(self.dnn_in_dim))
             self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(units[-1] if units else self.dnn_in_dim))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
         self._scale = self._shift = None
 
     # -- staging: the shared stage (dense, linear part) + the deep part's ids, hashed once per feature ------------------------------
@@ -152,16 +152,11 @@ class _ONN(FeatureModel):
             self._scale, self._shift = self.bn.scale_shift()      # from the live tensors, in place
 
     def _buffers(self, B):
-        bufs = self._buf.get(B)
-        if bufs is None:
-            if len(self._buf) >= 4:
-                self._buf.clear()
-            R = (self.n_fields - 1) * self.emb_dim
-            # (zeros: the row padding to a multiple of 4 floats is never written, and the DNN kernels may read it)
-            bufs = self._buf[B] = {"dnn_in": torch.zeros(B, self.in_stride, dtype=torch.float32, device=self.device),
-                                   "pooled": {fc.name: torch.zeros(B, (R + 3) // 4 * 4, dtype=torch.float32, device=self.device)
-                                              for fc in self.deep_cols if isinstance(fc, VarLenSparseFeat)}}
-        return bufs
+        R = (self.n_fields - 1) * self.emb_dim
+        # (zeros: the row padding to a multiple of 4 floats is never written, and the DNN kernels may read it)
+        return self._per_batch(B, lambda: {"dnn_in": torch.zeros(B, self.in_stride, dtype=torch.float32, device=self.device),
+                                           "pooled": {fc.name: torch.zeros(B, (R + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+                                                      for fc in self.deep_cols if isinstance(fc, VarLenSparseFeat)}})
 
     def _linear_logits(self, staged, lo, hi):
         """The [B] vectors of the linear part: the stage's gather over no field (dense . linear_kernel) and its linear-only gather."""
@@ -196,8 +191,8 @@ class _ONN(FeatureModel):
             desc = cache[key] = ops.make_ffm_fields(fields, self.device)
         return desc
 
-    def field_aware_rows(self, staged, lo, hi, pool):
-        """torch ops (training.model_logits): embs[j][i] = feature j's embedding towards partner i for rows [lo, hi), gathered from the
+    def field_aware_rows(self, staged, lo, hi):
+        """torch ops (autograd_logits): embs[j][i] = feature j's embedding towards partner i for rows [lo, hi), gathered from the
         per-name views; sequences pooled with ONN's semantics (mask_zero on the post-hash id, no length / weight)."""
         ids = staged.extra["ffm_ids"]
         embs = []
@@ -213,9 +208,20 @@ class _ONN(FeatureModel):
                 if i == j:
                     continue
                 w = self.tables["%s_%s" % (fc_j.embedding_name, fc_i.embedding_name)].embeddings
-                row[i] = pool(w[rows], fc_j, mask, None, None) if isinstance(fc_j, VarLenSparseFeat) else w[rows]
+                row[i] = tops._pool(w[rows], fc_j, mask, None, None) if isinstance(fc_j, VarLenSparseFeat) else w[rows]
             embs.append(row)
         return embs
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # onn.py:59-105
+        embs = self.field_aware_rows(staged, lo, hi)
+        prods = []
+        for i, j in zip(*tops._pair_indices(self.n_fields)):
+            pr = embs[i][j] * embs[j][i]
+            prods.append(pr.sum(-1, keepdim=True) if self.reduce_sum else pr)
+        x = torch.cat(prods, dim=-1)
+        if self.bn is not None:
+            x = tops._batch_norm(self.bn, x, training)
+        return (tops.dnn_forward(self.dnn, torch.cat([x] + parts, dim=-1), training) @ self.dense.w("kernel")).reshape(-1)
 
     def _forward(self, staged, lo, hi, out):
         sp = self.stage_plan

@@ -2,7 +2,10 @@
 DNN input = [embeddings, flatten(InnerProductLayer(embeddings)), dense].  SURVEY §8(f) rank 4 sibling; the model-level
 consumer of §8 row a12: ``dctr_inner_product_fwd`` reads the embeddings in place from the gathered DNN-input buffer and
 writes the F(F-1)/2 products into the columns reserved between embeddings and dense values."""
+import torch
+
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -52,6 +55,13 @@ class _PNN(FeatureModel):
         ops.mlp(ws["dnn_in"], self.dnn.kernels, self.dnn.biases, self.dnn.activation, dice=self.dnn.dice_params(), bn=self.dnn.bn_params(),
                 head_w=self.dense.w('kernel'), global_bias=self.prediction.w('global_bias'),
                 sigmoid_out=self.task == "binary", in_dim=sp.in_dim, out=out)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # pnn.py:52-66, InnerProductLayer(reduce_sum) pair order
+        if self.use_inner:
+            ii, jj = tops._pair_indices(self.n_emb)
+            parts[extra["inner_product"]] = (torch.stack([parts[i] for i in ii], dim=1) *
+                                             torch.stack([parts[j] for j in jj], dim=1)).sum(-1)
+        return super(_PNN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
 
 def PNN(dnn_feature_columns, dnn_hidden_units=(256, 128, 64), l2_reg_embedding=0.00001, l2_reg_dnn=0, seed=1024,

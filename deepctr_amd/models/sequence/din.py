@@ -9,6 +9,7 @@ DIN has no linear term."""
 import torch
 
 from ... import ops
+from ... import training as tops
 from ...engine import EmbeddingStage, prehashed_on_host
 from ...feature_column import SparseFeat, VarLenSparseFeat
 from ...layers.base import name_scope
@@ -56,7 +57,6 @@ class _DIN(FeatureModel):
             last = dnn_hidden_units[-1] if len(dnn_hidden_units) else self.stage_plan.in_dim
             self.dense = self._add(Dense(1, use_bias=False, seed=seed, device=self.device).build_for(last))
             self.prediction = self._add(PredictionLayer(task, device=self.device).build_for())
-        self._buf = {}
         # query / key lookups folded into the attention kernels (dctr_din_attn_gather_fwd: the [B, T, E] keys never reach HBM);
         # False, or a shape outside those kernels: dctr_embed_lookup_multi + dctr_din_attn_pool_fwd
         self.fold_lookups = True
@@ -117,14 +117,10 @@ class _DIN(FeatureModel):
         lookups of the history features (``bufs['key_lookups']``: (feature, ids, hash_mode, first key column)) for the
         training step's scatter."""
         B = hi - lo
-        bufs = self._buf.get(B)
-        if bufs is None:
-            if len(self._buf) >= 4:            # ragged remainder sizes (N % span) must not pile up per-B buffers
-                self._buf.clear()
-            bufs = self._buf[B] = dict(
-                q=torch.zeros(B, self.query_dim, dtype=torch.float32, device=self.device),
-                k=torch.zeros(B, self.T, self.key_dim, dtype=torch.float32, device=self.device),
-                m=torch.ones(B, self.T, dtype=torch.uint8, device=self.device))
+        bufs = self._per_batch(B, lambda: dict(
+            q=torch.zeros(B, self.query_dim, dtype=torch.float32, device=self.device),
+            k=torch.zeros(B, self.T, self.key_dim, dtype=torch.float32, device=self.device),
+            m=torch.ones(B, self.T, dtype=torch.uint8, device=self.device)))
         st = ws["status"]
         # query features and behaviour sequences: ONE launch (dctr_embed_lookup_multi); the first mask_zero sequence's
         # lookup writes the attention mask = conjunction of all mask_zero sequences' (id != 0)
@@ -152,6 +148,29 @@ class _DIN(FeatureModel):
         for c0 in range(0, len(lookups), 8):            # eight lookups per launch
             ops.embed_lookup_multi(lookups[c0:c0 + 8], extra_mask_ids=extra, status=st)
         return bufs                         # bufs["m"]: all ones when no history feature masks zero (never written then)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # din.py:62-89: the attention output fills its slot
+        q = torch.cat([parts[i] for i in self._query_rows], dim=-1)
+        keys, km = [], None
+        for fc in self.history_cols:
+            emb = self.tables[fc.embedding_name]
+            rows = tops._rows_for(fc, staged.seq[fc.name][lo:hi], True)
+            keys.append(emb.embeddings[rows])
+            if emb.mask_zero:
+                km = (rows != 0) if km is None else (km & (rows != 0))
+        k = torch.cat(keys, dim=-1)
+        if km is None:
+            km = torch.ones(k.shape[:2], dtype=torch.bool, device=k.device)
+        la = self.attention.local_att
+        qq = q.unsqueeze(1).expand(-1, k.shape[1], -1)
+        att = tops.dnn_forward(la.dnn, torch.cat([qq, k, qq - k, qq * k], dim=-1), training)
+        score = (att @ la.w("kernel") + la.w("bias")).squeeze(-1)
+        if self.attention.weight_normalization:
+            score = torch.softmax(torch.where(km, score, torch.full_like(score, float(-2 ** 32 + 1))), dim=-1)
+        else:
+            score = torch.where(km, score, torch.zeros_like(score))
+        parts[extra["hist"]] = (score.unsqueeze(1) @ k).squeeze(1)
+        return super(_DIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
 
 def DIN(dnn_feature_columns, history_feature_list, dnn_use_bn=False, dnn_hidden_units=(256, 128, 64),

@@ -6,6 +6,7 @@ and ``dctr_embed_mlp_fwd`` (ids -> DNN -> head, + linear logit + the CIN logit).
 import torch
 
 from .. import ops
+from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer
@@ -133,6 +134,27 @@ class _xDeepFM(FusedForward, FeatureModel):
         ops.mlp(ws["dnn_in"], self.dnn.kernels, self.dnn.biases, self.dnn.activation, dice=self.dnn.dice_params(), bn=self.dnn.bn_params(),
                 head_w=self.dense.w('kernel'), add=add, global_bias=self.prediction.w('global_bias'),
                 sigmoid_out=self.task == "binary", in_dim=self.stage_plan.in_dim, out=out)
+
+    def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # xdeepfm.py:53-66: the DNN logit + Dense(1) over the CIN maps
+        logit = super(_xDeepFM, self)._autograd_logit(staged, lo, hi, parts, extra, training)
+        if self.cin is None:
+            return logit
+        x0 = torch.stack(parts[:len(self.stage_plan.fields)], dim=1)             # [B,F,D]
+        hidden, finals = x0, []
+        n = len(self.cin.layer_size)
+        for i, (w, b) in enumerate(zip(self.cin.filters, self.cin.biases)):
+            z = torch.einsum("bid,bjd->bdij", x0, hidden).reshape(x0.shape[0], x0.shape[2], -1)
+            cur = tops._act(self.cin.activation, z @ w[0] + b).transpose(1, 2)
+            H = cur.shape[1]
+            if self.cin.split_half:
+                if i != n - 1:
+                    hidden, direct = cur[:, :H // 2], cur[:, H // 2:]
+                else:
+                    hidden, direct = None, cur
+            else:
+                hidden, direct = cur, cur
+            finals.append(direct)
+        return logit + (torch.cat(finals, dim=1).sum(-1) @ self.dense_1.w("kernel")).reshape(-1)
 
 
 def xDeepFM(linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 128, 64), cin_layer_size=(128, 128,),

@@ -1,17 +1,19 @@
-"""``fit`` / ``train_on_batch`` — SURVEY.md §8(f) rank 1, "next" row; kept minimal in round 1.
+"""``fit`` / ``train_on_batch`` — SURVEY.md §8(f) rank 1.
 
-The forward path this repository is about is inference (``predict``) on hand-written HIP kernels.  Training
-needs gradients; until the HIP backward kernels exist (embedding-row scatter-add, FM/CIN/CrossNet grads) the
-training step uses PyTorch autograd over a differentiable restatement of the SAME forward, built from torch ops
-on the SAME device and the SAME weight tensors (so ``predict`` after ``fit`` runs the HIP kernels on the trained
-weights).  It exists so that the reference's ``compile → fit → predict`` workflow (tests/utils.py:356-381,
-examples/run_classification_criteo.py:44-50) works end to end; it is not a performance path and nothing in
-``predict`` ever routes through it.  Parity of this torch forward with the HIP forward is a GPU test
-(tests/test_gpu_fit.py).
+``fit_model`` picks one of two training steps.  The models ``training_hip.supported`` names train on the HIP step (``_fit_hip``:
+hand-written backward and optimizer kernels, no autograd).  Every other model or option trains on PyTorch autograd (``_fit_torch``)
+over a differentiable restatement of the SAME forward, built from torch ops on the SAME device and the SAME weight tensors, so
+``predict`` after ``fit`` runs the HIP kernels on the trained weights.  That restatement is ``model_logits``: the shared pieces
+(``stage_forward``, ``dnn_forward``, the layer restatements ``_interacting`` / ``_bilinear`` / ``_fefm``) live here, each model's
+own part in its model file (``FeatureModel.autograd_logits``).  It is also the oracle every HIP gradient test differentiates and the
+"torch ops" baseline of the scripts/bench_*.py; it is not a performance path and nothing in ``predict`` routes through it.  Parity of
+the torch forward with the HIP forward is a GPU test (tests/test_gpu_fit.py); the CPU suite pins it to the reference's outputs.
 
-Sequence features, hashing and DIN attention are covered; dropout / l2 regularisers of the reference
-constructors are not applied (documented gap).
+Sequence features, hashing, DIN attention, dropout, BatchNormalization / Dice in training mode and the l2 regularisers of the
+reference constructors are covered.
 """
+from itertools import combinations
+
 import numpy as np
 import torch
 
@@ -83,9 +85,7 @@ def stage_forward(sp, staged, lo, hi):
         embs.append(e)
     fms = []
     for g in sp.fm_group_names:
-        first, n, dim = sp.group_slices[g]
-        idx = [k for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim]
-        x = torch.stack([embs[k] for k in idx], dim=1)
+        x = torch.stack(_group_embeddings(sp, embs, g), dim=1)
         fms.append(0.5 * (x.sum(1).pow(2) - (x * x).sum(1)).sum(-1))
     parts = list(embs)
     extra = {}
@@ -245,6 +245,18 @@ def regularized_weights(model):
     return out
 
 
+def _pair_indices(n):
+    """(ii, jj): the pairs i < j of n fields in itertools.combinations order, as two index lists."""
+    pairs = list(combinations(range(n), 2))
+    return [i for i, _ in pairs], [j for _, j in pairs]
+
+
+def _group_embeddings(sp, embs, g):
+    """The [B, dim] embeddings of embedding group ``g`` of an EmbeddingStage, in field order (``embs``: one entry per field)."""
+    first, n, dim = sp.group_slices[g]
+    return [embs[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim]
+
+
 def _interacting(layer, x):
     """InteractingLayer.call (reference interaction.py:749-779) in torch ops: x [B,F,E] -> [B,F,d*H]."""
     d, H = layer.att_embedding_size, layer.head_num
@@ -266,8 +278,7 @@ def _bilinear(layer, x):
     """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
     itertools.combinations order."""
     F = x.shape[1]
-    ii = [i for i in range(F - 1) for _ in range(i + 1, F)]
-    jj = [j for i in range(F - 1) for j in range(i + 1, F)]
+    ii, jj = _pair_indices(F)
     if layer.bilinear_type == "all":
         vid = x[:, :F - 1] @ layer.w("bilinear_weight")
     elif layer.bilinear_type == "each":
@@ -280,222 +291,17 @@ def _bilinear(layer, x):
 def _fefm(layer, x):
     """FEFMLayer.call (reference interaction.py:1469-1488) in torch ops: x [B,F,E] -> [B,P], pairs i < j in itertools.combinations
     order, x_i^T (W + W^T) x_j."""
-    F = x.shape[1]
-    ii = [i for i in range(F - 1) for _ in range(i + 1, F)]
-    jj = [j for i in range(F - 1) for j in range(i + 1, F)]
+    ii, jj = _pair_indices(x.shape[1])
     w = torch.stack(layer.matrices)
     return (torch.einsum("bpe,ped->bpd", x[:, ii], w + w.transpose(1, 2)) * x[:, jj]).sum(-1)
 
 
 def model_logits(model, staged, lo, hi, training=False):
-    """Pre-sigmoid logits [B] of the four in-scope models and their siblings, torch ops only.  ``training`` switches Dice to
-    batch statistics (and updates its moving statistics), as tf.keras does inside fit(); the default is the inference form
-    the HIP forward implements and the gradient tests differentiate."""
-    sp = model.stage_plan
-    parts, extra, lin, fms = stage_forward(sp, staged, lo, hi)
-    name = model.name
-    if name == "DIN":
-        q = torch.cat([parts[i] for i in model._query_rows], dim=-1)
-        keys, km = [], None
-        for fc in model.history_cols:
-            emb = model.tables[fc.embedding_name]
-            rows = _rows_for(fc, staged.seq[fc.name][lo:hi], True)
-            keys.append(emb.embeddings[rows])
-            if emb.mask_zero:
-                km = (rows != 0) if km is None else (km & (rows != 0))
-        k = torch.cat(keys, dim=-1)
-        if km is None:
-            km = torch.ones(k.shape[:2], dtype=torch.bool, device=k.device)
-        la = model.attention.local_att
-        qq = q.unsqueeze(1).expand(-1, k.shape[1], -1)
-        att = dnn_forward(la.dnn, torch.cat([qq, k, qq - k, qq * k], dim=-1), training)
-        score = (att @ la.w("kernel") + la.w("bias")).squeeze(-1)
-        if model.attention.weight_normalization:
-            score = torch.softmax(torch.where(km, score, torch.full_like(score, float(-2 ** 32 + 1))), dim=-1)
-        else:
-            score = torch.where(km, score, torch.zeros_like(score))
-        parts[extra["hist"]] = (score.unsqueeze(1) @ k).squeeze(1)
-    if name == "AFM":                       # models/afm.py:45-58: linear logit + AFMLayer (or FM) per group
-        logit = torch.zeros(hi - lo, device=sp.device)
-        if model.use_attention:
-            for g, layer in zip(model.groups, model.afm_layers):
-                first, n, dim = sp.group_slices[g]
-                embs = [parts[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim]
-                ii = [i for i in range(n - 1) for _ in range(i + 1, n)]
-                jj = [j for i in range(n - 1) for j in range(i + 1, n)]
-                bi = torch.stack([embs[i] for i in ii], dim=1) * torch.stack([embs[j] for j in jj], dim=1)     # [B,P,E]
-                att = torch.relu(bi @ layer.w("attention_W") + layer.w("attention_b"))
-                score = torch.softmax(att @ layer.w("projection_h"), dim=1)
-                att_out = _dropout((score * bi).sum(1), getattr(layer, "dropout_rate", 0), training)     # interaction.py:142-143
-                logit = logit + (att_out @ layer.w("projection_p")).reshape(-1)
-        if lin is not None:
-            logit = logit + lin
-        for f in fms:
-            logit = logit + f
-        return logit + model.prediction.w("global_bias")
-    if name == "NFM":                       # models/nfm.py:49-58: DNN over [BiInteractionPooling(embeddings), dense]
-        x0 = torch.stack(parts[:len(sp.fields)], dim=1)
-        parts[extra["bi_interaction"]] = _dropout(0.5 * (x0.sum(1).pow(2) - (x0 * x0).sum(1)), getattr(model, "bi_dropout", 0),
-                                                  training)                                      # nfm.py:52-53
-        parts = parts[extra["bi_interaction"]:]
-    if name == "PNN" and "inner_product" in extra:      # models/pnn.py:52-66, InnerProductLayer(reduce_sum) pair order
-        n = len(sp.fields)
-        ii = [i for i in range(n - 1) for _ in range(i + 1, n)]
-        jj = [j for i in range(n - 1) for j in range(i + 1, n)]
-        parts[extra["inner_product"]] = (torch.stack([parts[i] for i in ii], dim=1) *
-                                         torch.stack([parts[j] for j in jj], dim=1)).sum(-1)
-    if name == "AutoInt":                   # models/autoint.py:55-79: Dense(1) over [Flatten(InteractingLayer stack), DNN]
-        outs = []
-        if model.att_layers:
-            h = torch.stack(parts[:len(sp.fields)], dim=1)          # [B,F,E]
-            for layer in model.att_layers:
-                h = _interacting(layer, h)
-            outs.append(h.reshape(h.shape[0], -1))
-        if model.dnn is not None:
-            outs.append(dnn_forward(model.dnn, torch.cat(parts, dim=-1), training))
-        logit = (torch.cat(outs, dim=-1) @ model.dense.w("kernel")).reshape(-1)
-        if lin is not None:
-            logit = logit + lin
-        for f in fms:
-            logit = logit + f
-        return logit + model.prediction.w("global_bias")
-    if name == "ONN":                       # models/onn.py:59-105: field-aware pair products (+ BN) and the dense values -> DNN -> Dense(1)
-        embs = model.field_aware_rows(staged, lo, hi, _pool)
-        F = model.n_fields
-        prods = []
-        for i in range(F - 1):
-            for j in range(i + 1, F):
-                pr = embs[i][j] * embs[j][i]
-                prods.append(pr.sum(-1, keepdim=True) if model.reduce_sum else pr)
-        x = torch.cat(prods, dim=-1)
-        if model.bn is not None:
-            x = _batch_norm(model.bn, x, training)
-        x = torch.cat([x] + parts, dim=-1)
-        h = dnn_forward(model.dnn, x, training)
-        logit = (h @ model.dense.w("kernel")).reshape(-1)
-        if lin is not None:
-            logit = logit + lin
-        return logit + model.prediction.w("global_bias")
-    if name in ("IFM", "DIFM"):             # models/ifm.py:55-72, difm.py:59-80: input-aware factor -> refined FM + refined linear terms
-        x = torch.stack(parts[:len(sp.fields)], dim=1)              # [B,F,d]
-        h = dnn_forward(model.dnn, x.reshape(x.shape[0], -1), training)
-        if name == "IFM":
-            m = x.shape[1] * torch.softmax(h @ model.dense.w("kernel"), dim=1)
-        else:
-            att = _interacting(model.att, x)
-            m = att.reshape(att.shape[0], -1) @ model.dense.w("kernel") + h @ model.dense_1.w("kernel")
-        r = x * m.unsqueeze(-1)
-        logit = 0.5 * (r.sum(1).pow(2) - (r * r).sum(1)).sum(-1)
-        terms = model.linear_terms(staged, lo, hi, _pool)           # [B,F] in position order: paired with m by position
-        if terms is not None:
-            logit = logit + (terms * m).sum(-1)
-        if lin is not None:                                         # (the stage's linear part holds the DenseFeat only: not refined)
-            logit = logit + lin
-        return logit + model.prediction.w("global_bias")
-    if name == "FwFM":                      # models/fwfm.py:51-66: linear + FwFMLayer per group (+ DNN over the plain DNN input)
-        logit = torch.zeros(hi - lo, device=sp.device)
-        for g, layer in zip(model.groups, model.fwfm_layers):
-            first, n, dim = sp.group_slices[g]
-            x = torch.stack([parts[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim], dim=1)
-            gram = torch.einsum("bie,bje->bij", x, x)
-            logit = logit + (gram * torch.triu(layer.field_strengths, diagonal=1)).sum((1, 2))
-        if model.dnn is not None:
-            h = dnn_forward(model.dnn, torch.cat(parts, dim=-1), training)
-            logit = logit + (h @ model.dense.w("kernel")).reshape(-1)
-        if lin is not None:
-            logit = logit + lin
-        return logit + model.prediction.w("global_bias")
-    if name == "DeepFEFM":                  # models/deepfefm.py:62-99: FEFM over the default group, the ablation switches
-        first, n, dim = model.group_first, model.n_fields, model.emb_dim
-        x = torch.stack([parts[k] for k, f in enumerate(sp.fields) if first <= f.out_offset < first + n * dim], dim=1)
-        pairs = _fefm(model.fefm, x)
-        logit = torch.zeros(hi - lo, device=sp.device)
-        if model.dnn is not None:
-            if not model.pairs_in_dnn:
-                h = torch.cat(parts, dim=-1)
-            elif model.exclude_embed:
-                h = pairs
-            else:
-                h = torch.cat(parts + [pairs], dim=-1)
-            logit = logit + (dnn_forward(model.dnn, h, training) @ model.dense.w("kernel")).reshape(-1)
-        if model.use_fefm:
-            logit = logit + pairs.sum(-1)
-        if model.use_linear and lin is not None:
-            logit = logit + lin
-        return logit + model.prediction.w("global_bias")
-    if name == "FiBiNET":                   # models/fibinet.py:50-63: DNN over [Flatten(bilinear(SENET(x)), bilinear(x)), dense]
-        F = len(sp.fields)
-        x = torch.stack(parts[:F], dim=1)                           # [B,F,E]
-        B = x.shape[0]
-        a2 = torch.relu(torch.relu(x.mean(-1) @ model.senet.w("W_1")) @ model.senet.w("W_2"))
-        # concat_func joins the two [B,P,E] outputs on the last axis (reference layers/utils.py:236), then Flatten
-        h = torch.cat([_bilinear(model.senet_bilinear, x * a2.unsqueeze(-1)), _bilinear(model.bilinear, x)], dim=-1)
-        h = torch.cat([h.reshape(B, -1)] + parts[F:], dim=-1)
-        if model.dnn is not None:
-            h = dnn_forward(model.dnn, h, training)
-        logit = (h @ model.dense.w("kernel")).reshape(-1)
-        if lin is not None:
-            logit = logit + lin
-        for f in fms:
-            logit = logit + f
-        return logit + model.prediction.w("global_bias")
-    x = torch.cat(parts, dim=-1)
-    if name == "DCNMix":                    # models/dcnmix.py:53-68 with CrossNetMix (interaction.py:511-549)
-        outs = []
-        if model.cross is not None:
-            cr = model.cross
-            x0 = xl = x
-            for i in range(cr.layer_num):
-                U, V, C, b = cr.w("U_list%d" % i), cr.w("V_list%d" % i), cr.w("C_list%d" % i), cr.w("bias%d" % i).reshape(-1)
-                gate = torch.softmax(torch.cat([xl @ g.w("kernel") for g in cr.gating], dim=-1), dim=-1)       # [B,experts]
-                moe = torch.zeros_like(xl)
-                for e in range(cr.num_experts):
-                    v = torch.tanh(torch.tanh(xl @ V[e]) @ C[e].t())
-                    moe = moe + gate[:, e:e + 1] * (x0 * (v @ U[e].t() + b))
-                xl = moe + xl
-            outs.append(xl)
-        if model.dnn is not None:
-            outs.append(dnn_forward(model.dnn, x, training))
-        logit = (torch.cat(outs, dim=-1) @ model.dense.w("kernel")).reshape(-1)
-    elif name == "DCN":
-        outs = []
-        if model.cross is not None:
-            x0 = x
-            xl = x
-            for i in range(model.cross.layer_num):
-                w, b = model.cross.w("kernel%d" % i), model.cross.w("bias%d" % i).reshape(-1)
-                if model.cross.parameterization == "vector":
-                    xl = x0 * (xl @ w) + b + xl
-                else:
-                    xl = x0 * (xl @ w.t() + b) + xl
-            outs.append(xl)
-        if model.dnn is not None:
-            outs.append(dnn_forward(model.dnn, x, training))
-        logit = (torch.cat(outs, dim=-1) @ model.dense.w("kernel")).reshape(-1)
-    else:
-        logit = (dnn_forward(model.dnn, x, training) @ model.dense.w("kernel")).reshape(-1)
-    if name == "xDeepFM" and model.cin is not None:
-        x0 = torch.stack(parts[:len(sp.fields)], dim=1)             # [B,F,D]
-        hidden, finals = x0, []
-        n = len(model.cin.layer_size)
-        for i, (w, b) in enumerate(zip(model.cin.filters, model.cin.biases)):
-            z = torch.einsum("bid,bjd->bdij", x0, hidden).reshape(x0.shape[0], x0.shape[2], -1)
-            cur = _act(model.cin.activation, z @ w[0] + b).transpose(1, 2)
-            H = cur.shape[1]
-            if model.cin.split_half:
-                if i != n - 1:
-                    hidden, direct = cur[:, :H // 2], cur[:, H // 2:]
-                else:
-                    hidden, direct = None, cur
-            else:
-                hidden, direct = cur, cur
-            finals.append(direct)
-        logit = logit + (torch.cat(finals, dim=1).sum(-1) @ model.dense_1.w("kernel")).reshape(-1)
-    if lin is not None:
-        logit = logit + lin
-    for f in fms:
-        logit = logit + f
-    return logit + model.prediction.w("global_bias")
+    """Pre-sigmoid logits [B] of rows [lo, hi) of any model, torch ops only: the model's own ``autograd_logits``
+    (models/_common.py:FeatureModel; every model file overrides its part of it).  ``training`` switches Dice and BatchNormalization
+    to batch statistics (and updates their moving statistics) and applies dropout, as tf.keras does inside fit(); the default is
+    the inference form the HIP forward implements and the gradient tests differentiate."""
+    return model.autograd_logits(staged, lo, hi, training)
 
 
 class KerasAdam(torch.optim.Optimizer):

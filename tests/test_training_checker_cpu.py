@@ -36,6 +36,29 @@ def test_torch_restatement_matches_reference_outputs(name):
     np.testing.assert_allclose(p[rows], g["y"].reshape(-1)[rows], rtol=1e-4, atol=1e-6)
 
 
+def test_restatement_follows_the_class_not_the_display_name():
+    """``model.name`` is a free display string (_DeepFM(..., name="WDL")): the graph model_logits differentiates is the class's, so a
+    renamed model keeps its cross net / CIN / bilinear part, bit for bit."""
+    from deepctr_amd import engine, training
+    from tests.test_fibinet_cpu import build_fibinet
+    from tests.test_gpu_models import build_model
+    for name in ("model_dcn_matrix", "model_xdeepfm", "model_fibinet_interaction"):
+        g = load_golden(name)
+        meta = golden_meta(g)
+        model = (build_fibinet if "fibinet" in name else build_model)(meta, torch.device("cpu"))
+        model.set_weights_by_name({k[2:]: v for k, v in g.items() if k.startswith("w/")})
+        feed = {k[5:]: v for k, v in g.items() if k.startswith("feed/")}
+        n = g["y"].shape[0]
+        staged = engine.Staged(n)
+        model._stage_inputs(feed, staged)
+        model._begin()
+        with torch.no_grad():
+            a = training.model_logits(model, staged, 0, n)
+            model.name = "renamed"
+            b = training.model_logits(model, staged, 0, n)
+        assert torch.equal(a, b), name
+
+
 def test_restatement_is_differentiable_on_cpu():
     """One autograd pass on CPU: every trainable weight of a DeepFM with sequence features receives a finite gradient."""
     from deepctr_amd import engine, training
