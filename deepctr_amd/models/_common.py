@@ -64,6 +64,50 @@ class FeatureModel(Model):
             logit = logit + f
         return logit + self.prediction.w("global_bias")
 
+    # ---- the HIP training step (training_hip.HipTrainer ``tr``): a model that trains on it overrides these beside _autograd_logit ----
+    def _hip_supported(self):
+        """Can this model train on the HIP step?  Default: no — fit() takes the torch-autograd step."""
+        return False
+
+    def _hip_params(self, tr):
+        """Registers the model's private parameters through ``tr.param()`` and keeps the handles in ``tr.own`` (per trainer)."""
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        """Forward from the stage's outputs ``ws`` to ``buf["pred"]``, ``tr._loss_grad``, backward to ``buf["dx"]`` (d of the stage's
+        DNN input) and the ``g`` of the parameters behind the stage; the model's own per-batch buffers are created in ``buf``."""
+        raise NotImplementedError("%s has no HIP training step" % type(self).__name__)
+
+    def _hip_batch_statistics(self):
+        """True when the model's own part of the step normalises with the statistics of the batch (HipTrainer.batch_statistics)."""
+        return False
+
+    def _hip_family_ok(self, extra_fm=False, extra_cols=False, need_dnn=True):
+        """The rules of _hip_supported several models share.  ``extra_fm``: FM groups beyond the gather's own are the model's (their
+        logits ride the head's four ``add`` slots beside the linear logit); ``extra_cols``: the model fills the columns it reserved
+        in the DNN input (``extra_offsets``); ``need_dnn``: the head sits on a non-empty DNN."""
+        sp, dnn = self.stage_plan, getattr(self, "dnn", None)
+        if len(sp.fm_group_names) > 1 and (not extra_fm or int(bool(sp.has_linear)) + len(sp.fm_group_names) > 4):
+            return False
+        if (sp.extra_offsets and not extra_cols) or (need_dnn and dnn is None):
+            return False
+        if dnn is None:
+            return True
+        if not dnn.kernels or getattr(dnn, "output_activation", None) not in (None, dnn.activation):
+            return False
+        # dnn_dropout / dnn_use_bn and dnn_activation="dice" (layers/activation.py:37-64 under training=True) run layer by layer
+        # (HipTrainer._dnn_forward), but not together
+        if dnn.activation in ("dice", "Dice"):
+            return not (getattr(dnn, "dropout_rate", 0) or getattr(dnn, "bn_layers", None) or dnn.dice_params() is None)
+        return dnn.activation in ("relu", "linear", "sigmoid", "tanh")
+
+    def _hip_add(self, ws):
+        """The logits the step's head adds: linear (the linear-only features' already summed into it), FM, further FM groups."""
+        sp = self.stage_plan
+        add = [ws["lin"]] if sp.has_linear else []
+        if sp.fm_group_names:
+            add += [ws["fm"]] + list(ws["fm_extra"])    # fm_group=(...): FM over further embedding groups (models/deepfm.py:53-54)
+        return add
+
     def build_linear(self, linear_feature_columns, seed):
         lin_cols = linear_columns(linear_feature_columns)
         self.linear_tables = create_embedding_matrix(lin_cols, 0, seed, prefix="linear0", device=self.device)

@@ -73,6 +73,36 @@ class _AFM(FeatureModel):
             logit = logit + (att_out @ layer.w("projection_p")).reshape(-1)
         return logit
 
+    # ---- the HIP training step (training_hip.HipTrainer): no DNN — linear logit + AFMLayer per group (or the gather's FM groups) ------
+    def _hip_supported(self):
+        return self._hip_family_ok(extra_fm=True, need_dnn=False) and not any(getattr(l, "dropout_rate", 0) for l in self.afm_layers)
+
+    def _hip_params(self, tr):          # l2_reg_att applies to attention_W only (interaction.py:100)
+        tr.own["afm"] = [(tr.param(l.w("attention_W"), getattr(l, "l2_reg_w", 0.0)), tr.param(l.w("attention_b")),
+                          tr.param(l.w("projection_h")), tr.param(l.w("projection_p"))) for l in self.afm_layers]
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        sp = self.stage_plan
+        add = self._hip_add(ws)
+        if "afm_out" not in buf:
+            buf["afm_out"] = [torch.zeros(hi - lo, 1, dtype=torch.float32, device=self.device) for _ in self.afm_layers]
+        outs = buf["afm_out"]
+        for g, layer, o in zip(self.groups, self.afm_layers, outs):
+            first, n, dim = sp.group_slices[g]
+            ops.afm(ws["dnn_in"][:, first:], layer.w("attention_W"), layer.w("attention_b"), layer.w("projection_h"),
+                    layer.w("projection_p"), fields=n, dim=dim, out=o)
+        head_in = outs[0] if outs else add[0].reshape(-1, 1)
+        rest = [o.reshape(-1) for o in outs[1:]] if outs else add[1:]
+        ops.mlp(head_in, [], [], "linear", head_w=self._one(), add=(add + rest) if outs else rest,
+                global_bias=None if tr.p_gbias is None else tr.p_gbias.w, sigmoid_out=binary, in_dim=1, out=buf["pred"])
+        tr._loss_grad(buf, y, binary)
+        dx = buf["dx"]
+        dx.zero_()                                   # groups outside fm_group contribute nothing to the logit
+        for g, layer, ps in zip(self.groups, self.afm_layers, tr.own["afm"]):
+            first, n, dim = sp.group_slices[g]
+            ops.afm_bwd(ws["dnn_in"][:, first:], n, dim, layer.w("attention_W"), layer.w("attention_b"), layer.w("projection_h"),
+                        layer.w("projection_p"), buf["dlogit"], dx[:, first:], ps[0].g, ps[1].g, ps[2].g, ps[3].g)
+
 
 def AFM(linear_feature_columns, dnn_feature_columns, fm_group=DEFAULT_GROUP_NAME, use_attention=True, attention_factor=8,
         l2_reg_linear=1e-5, l2_reg_embedding=1e-5, l2_reg_att=1e-5, afm_dropout=0, seed=1024, task='binary', device=None):

@@ -6,7 +6,7 @@ import ctypes
 
 import torch
 
-from .. import ops
+from .. import _C, ops
 from .. import training as tops
 from ..engine import EmbeddingStage
 from ..layers.base import name_scope
@@ -90,7 +90,6 @@ class _DCN(FusedForward, FeatureModel):
         return self.dense.w('kernel')[d:]
 
     def _cross_operands(self):
-        import torch
         if not self._fold_ok():
             return None                     # (matrix CrossNet on the one-launch DNN: the cross logit arrives through the head's add)
         ks, bs = self.cross.packed()
@@ -129,7 +128,6 @@ class _DCN(FusedForward, FeatureModel):
     fuse_matrix = True
 
     def _matrix_gather_ok(self, staged, B):
-        import torch
         if not (self.fuse_matrix and self.fuse_head and self.fused and self.cross is not None and self.dnn is not None and
                 getattr(self.cross, "parameterization", None) == "matrix" and not getattr(self, "_matrix_failed", False)):
             return False
@@ -139,7 +137,6 @@ class _DCN(FusedForward, FeatureModel):
         # which launches dctr_crossnet_gather_head_fwd takes (rows per CU, widths) is the library's answer, asked once per launch size
         ok = self._matrix_lib_ok.get(B)
         if ok is None:
-            from .. import _C
             a = _C.CrossnetArgs(batch=B, x_stride=sp.in_dim, dim=sp.in_dim, layers=int(self.cross.layer_num), mode=_C.CROSS_MATRIX, y_stride=sp.in_dim)
             g = _C.GatherFmArgs(batch=B, n_fields=len(sp.fields), ids_stride_b=1, max_dim=sp.max_dim, all_dim4=int(sp.all_dim4), any_hash=0,
                                 uniform_dim=int(sp.uniform_dim), any_identity=int(bool(sp.pooled_fields)), any_pitch=0,
@@ -157,7 +154,6 @@ class _DCN(FusedForward, FeatureModel):
         """The matrix CrossNet's share of Dense(1), a [B] logit the fused head adds."""
         if self.cross is None or getattr(self.cross, "parameterization", None) != "matrix":
             return []
-        import torch
         cl = self._cross_logit.get(B) if getattr(self, "_cross_logit", None) is not None else None
         if cl is None:
             if getattr(self, "_cross_logit", None) is None or len(self._cross_logit) > 8:
@@ -195,9 +191,7 @@ class _DCN(FusedForward, FeatureModel):
                     head_w=hw[d:], add=self._logits_to_add(ws) + [cl], global_bias=self.prediction.w('global_bias'),
                     sigmoid_out=self.task == "binary", in_dim=d, out=out)
             return
-        stack = self._stack.get(B)
-        if stack is None:
-            stack = self._stack[B] = torch.zeros(B, (self.width + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+        stack = self._stack_for(B)
         col = 0
         if self.cross is not None:          # stack_out = Concatenate()([cross_out, deep_out])  (dcn.py:61)
             self._run_cross(ws["dnn_in"], B, d, stack)
@@ -208,10 +202,15 @@ class _DCN(FusedForward, FeatureModel):
         ops.mlp(stack, [], [], "linear", head_w=self.dense.w('kernel'), add=self._logits_to_add(ws),
                 global_bias=self.prediction.w('global_bias'), sigmoid_out=self.task == "binary", in_dim=self.width, out=out)
 
+    def _stack_for(self, B):
+        """The [B, width padded to 4] buffer of Concatenate([cross_out, deep_out]), zeroed once: the padding columns are read."""
+        stack = self._stack.get(B)
+        if stack is None:
+            stack = self._stack[B] = torch.zeros(B, (self.width + 3) // 4 * 4, dtype=torch.float32, device=self.device)
+        return stack
+
     def _run_cross(self, dnn_in, B, d, stack, head_w=None, logit=None, gather=None):
         ks, bs = self._cross_packed
-        import ctypes
-        from .. import _C
         mode = _C.CROSS_VECTOR if self.cross.parameterization == "vector" else _C.CROSS_MATRIX
         need = int(_C.lib().dctr_crossnet_workspace_bytes(d, self.cross.layer_num, mode, ctypes.c_void_p(ks.data_ptr())))
         ready = 1 if getattr(self, "_cross_ws_fresh", False) else 0
@@ -240,8 +239,6 @@ class _DCN(FusedForward, FeatureModel):
         """The matrix CrossNet of an input wider than the on-chip kernels hold (their x_0 / x_l / x_{l+1} tiles live in LDS: ~800 columns):
         layer by layer, u = x_l W_l^T on the library's MFMA GEMM (dctr_sgemm), the elementwise half by dctr_crossnet_matrix_step
         (interaction.py:416-420); x_L goes to ``stack`` and / or its share of Dense(1) to ``logit``."""
-        import ctypes
-        from .. import _C
         ks, bs = self._cross_packed                       # [L, d, d] (W_l: [out n, in k]), [L, d]
         L = self.cross.layer_num
         bufs = self._wide_bufs.get(B) if getattr(self, "_wide_bufs", None) else None
@@ -286,6 +283,109 @@ class _DCN(FusedForward, FeatureModel):
             else:
                 xl = x0 * (xl @ w.t() + b) + xl
         return xl
+
+    # ---- the HIP training step (training_hip.HipTrainer): [CrossNet(dnn_in), DNN(dnn_in)] -> Dense(1) + linear logit -----------------
+    def _hip_supported(self):
+        # a vector CrossNet past the register file — 8192 columns — runs the closed form of the recurrence, up to 8 layers; a matrix
+        # one takes any width (_hip_cross_fwd), as the backward does (layer by layer past 2048 columns / 48 L d bytes of LDS)
+        if (getattr(self.cross, "parameterization", None) == "vector" and self.stage_plan.in_dim > 8192
+                and int(getattr(self.cross, "layer_num", 0)) > 8):
+            return False
+        return self._hip_family_ok(need_dnn=False)
+
+    def _hip_params(self, tr):
+        if self.cross is not None:
+            # the layer's Keras-named per-layer weights become views of packed parameter tensors (the layout the C ABI takes): one
+            # parameter segment covers each, no torch.stack launches per step (_begin: _trainer_owns_cross)
+            tr.own["cross"] = self._hip_pack_cross(tr, getattr(self, "regularizers", {}).get("cross", 0.0))
+            tr.own["bind_views"] = lambda: self._bind_cross_views(*[p.w for p in tr.own["cross"]])
+            tr.bind_cross_views()
+
+    def _hip_pack_cross(self, tr, l2):
+        ks, bs = self.cross.packed()
+        return [tr.param(ks.clone(), l2), tr.param(bs.clone())]
+
+    def _bind_cross_views(self, ks, bs):
+        cr = self.cross
+        for i in range(cr.layer_num):
+            cr._weights['kernel%d' % i] = ks[i].view(cr.dim, -1)
+            cr._weights['bias%d' % i] = bs[i].view(cr.dim, 1)
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        d = self.stage_plan.in_dim
+        stack = self._stack_for(hi - lo)
+        if "dstack" not in buf:
+            buf["dstack"] = torch.empty_like(stack)
+        dstack = buf["dstack"]
+        col = 0
+        if self.cross is not None:
+            self._hip_cross_fwd(tr, ws["dnn_in"], d, stack, buf)
+            col = d
+        if self.dnn is not None:
+            tr._dnn_forward(ws["dnn_in"], d, buf, stack[:, col:], head=False)
+        ops.mlp(stack, [], [], "linear", head_w=tr.p_head.w, add=self._hip_add(ws),
+                global_bias=None if tr.p_gbias is None else tr.p_gbias.w, sigmoid_out=binary, in_dim=self.width, out=buf["pred"])
+        tr._loss_grad(buf, y, binary)
+        ops.dense1_bwd(stack, self.width, tr.p_head.w, buf["dlogit"], dstack, tr.p_head.g)
+        if self.dnn is not None:
+            tr._dnn_backward(ws["dnn_in"], d, buf, buf["dx"], d_out=dstack[:, col:])
+        if self.cross is not None:
+            self._hip_cross_bwd(tr, ws["dnn_in"], d, dstack, buf, accumulate=self.dnn is not None)
+
+    def _hip_cross_bwd(self, tr, dnn_in, d, dstack, buf, accumulate):
+        (ks, bs), par = tr.own["cross"], self.cross.parameterization
+        ops.crossnet_bwd(dnn_in, d, ks.w, bs.w, par, dstack, ks.g, bs.g, buf["dx"], accumulate=accumulate,
+                         saved_u=buf.get("cross_u") if par == "matrix" else None, saved_x=buf.get("cross_x") if par == "matrix" else None)
+
+    def _hip_cross_fwd(self, tr, dnn_in, d, stack, buf):
+        par = self.cross.parameterization
+        mode = _C.CROSS_VECTOR if par == "vector" else _C.CROSS_MATRIX
+        ks, bs = (p.w for p in tr.own["cross"])
+        need = int(_C.lib().dctr_crossnet_workspace_bytes(d, ks.shape[0], mode, ctypes.c_void_p(ks.data_ptr())))
+        cws = tr.own.get("cross_ws")
+        if need and (cws is None or cws.numel() * 4 < need):
+            cws = tr.own["cross_ws"] = torch.empty(need // 4, dtype=torch.float32, device=ks.device)
+        su = sx = None
+        if par == "matrix" and ks.shape[0] >= 1:
+            # the forward kernel writes u_l = W_l x_l and x_1 .. x_{L-1} for the backward (dctr_crossnet_bwd_args_t.saved_u / saved_x:
+            # no recompute GEMM + elementwise launch per layer there)
+            L, B = ks.shape[0], dnn_in.shape[0]
+            if "cross_u" not in buf:
+                buf["cross_u"] = torch.empty(L, B, d, dtype=torch.float32, device=ks.device)
+                buf["cross_x"] = torch.empty(max(L - 1, 1), B, d, dtype=torch.float32, device=ks.device)
+            su, sx = buf["cross_u"], buf["cross_x"]
+        a = _C.CrossnetArgs(x=dnn_in.data_ptr(), batch=dnn_in.shape[0], x_stride=dnn_in.stride(0), dim=d, layers=ks.shape[0], mode=mode,
+                            workspace_ready=0, kernels=ks.data_ptr(), bias=bs.data_ptr(), y=stack.data_ptr(), y_stride=stack.stride(0),
+                            workspace=cws.data_ptr() if need else None, workspace_bytes=need,
+                            save_u=None if su is None else su.data_ptr(), save_x=None if sx is None else sx.data_ptr())
+        if su is not None:
+            # the one-kernel form keeps [16, dim] tiles of x_0 / x_l / x_{l+1} in LDS (~832 columns, i.e. Criteo at embedding_dim 32):
+            # whether it takes this width is the library's answer (dctr_crossnet_fwd_supported, asked once per shape)
+            key, one_kernel = (dnn_in.shape[0], d, ks.shape[0]), tr.own.setdefault("cross_one_kernel", {})
+            ok = one_kernel.get(key)
+            if ok is None:
+                if len(one_kernel) > 64:            # (ragged batch sizes must not pile up)
+                    one_kernel.clear()
+                ok = one_kernel[key] = bool(_C.lib().dctr_crossnet_fwd_supported(ctypes.byref(a), None))
+            if not ok:
+                return self._hip_cross_fwd_layered(dnn_in, d, stack, ks, bs, su, sx)
+        _C.check(_C.lib().dctr_crossnet_head_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_crossnet_head_fwd")
+
+    def _hip_cross_fwd_layered(self, dnn_in, d, stack, ks, bs, su, sx):
+        """Matrix CrossNet (interaction.py:416-420) of any width, layer by layer, writing what dctr_crossnet_bwd reads: u_l = x_l W_l^T
+        (the library's f32-MFMA GEMM, dctr_sgemm) -> saved_u[l]; x_{l+1} = x_0 * (u_l + b_l) + x_l (dctr_crossnet_matrix_step) ->
+        saved_x[l] (x_1 .. x_{L-1}) and, for the last layer, the cross half of the stack.  ks: [L, d, d] (W_l: [out n, in k]), bs: [L, d]."""
+        L, B, st = ks.shape[0], dnn_in.shape[0], _C.stream_ptr()
+        xl, xl_stride = dnn_in, ops.row_stride(dnn_in)
+        for l in range(L):
+            u = su[l]
+            # column-major BLAS view: u^T (d x B) = W^T-view (k x n)^T . x_l^T (k x B)
+            _C.check(_C.lib().dctr_sgemm(1, 0, d, B, d, ks[l].data_ptr(), d, 0, xl.data_ptr(), int(xl_stride), 0, 0.0, u.data_ptr(), d, 0, 1, st),
+                     "dctr_sgemm")
+            nxt, nxt_stride = (stack, ops.row_stride(stack)) if l == L - 1 else (sx[l], d)
+            _C.check(_C.lib().dctr_crossnet_matrix_step(dnn_in.data_ptr(), ops.row_stride(dnn_in), xl.data_ptr(), int(xl_stride), u.data_ptr(),
+                                                        bs[l].data_ptr(), B, d, nxt.data_ptr(), int(nxt_stride), st), "dctr_crossnet_matrix_step")
+            xl, xl_stride = nxt, nxt_stride
 
 
 def DCN(linear_feature_columns, dnn_feature_columns, cross_num=2, cross_parameterization='vector',

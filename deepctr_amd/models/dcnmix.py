@@ -37,6 +37,28 @@ class _DCNMix(_DCN):
             xl = moe + xl
         return xl
 
+    # ---- the HIP training step: _DCN's, on CrossNetMix's five packed parameter tensors and dctr_crossnet_mix_fwd / _bwd ---------------
+    def _hip_pack_cross(self, tr, l2):
+        # U / V / C stacked over layers, the experts' gating kernels, the biases, in the C ABI's layout.  l2 on U / V / C only (the
+        # reference regularises U_list / V_list / C_list, interaction.py:481-500)
+        U, V, C, G, Bb = self.cross.packed()
+        return [tr.param(U.clone(), l2), tr.param(V.clone(), l2), tr.param(C.clone(), l2), tr.param(G.clone()), tr.param(Bb.clone())]
+
+    def _bind_cross_views(self, U, V, C, G, Bb):
+        cr = self.cross
+        for i in range(cr.layer_num):
+            cr._weights['U_list%d' % i], cr._weights['V_list%d' % i], cr._weights['C_list%d' % i] = U[i], V[i], C[i]
+            cr._weights['bias%d' % i] = Bb[i].view(cr.dim, 1)
+        for e, dense in enumerate(cr.gating):
+            dense._weights['kernel'] = G[e].view(cr.dim, 1)
+
+    def _hip_cross_fwd(self, tr, dnn_in, d, stack, buf):
+        ops.crossnet_mix(dnn_in, *[p.w for p in tr.own["cross"]], dim=d, out=stack)
+
+    def _hip_cross_bwd(self, tr, dnn_in, d, dstack, buf, accumulate):
+        ps = tr.own["cross"]
+        ops.crossnet_mix_bwd(dnn_in, d, [p.w for p in ps], dstack, [p.g for p in ps], buf["dx"], accumulate=accumulate)
+
 
 def DCNMix(linear_feature_columns, dnn_feature_columns, cross_num=2, dnn_hidden_units=(256, 128, 64), l2_reg_linear=1e-5,
            l2_reg_embedding=1e-5, low_rank=32, num_experts=4, l2_reg_cross=1e-5, l2_reg_dnn=0, seed=1024, dnn_dropout=0,

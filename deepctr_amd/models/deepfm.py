@@ -68,6 +68,13 @@ class _DeepFM(FusedForward, FeatureModel):
                     head_w=self.dense.w('kernel'), add=add, global_bias=self.prediction.w('global_bias'),
                     sigmoid_out=self.task == "binary", in_dim=self.stage_plan.in_dim, out=out[a - lo:b - lo], tile_rows=self.tile_rows)
 
+    # ---- the HIP training step (training_hip.HipTrainer; WDL and FNN are this class) ----------------------------
+    def _hip_supported(self):
+        return self._hip_family_ok(extra_fm=True)
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        tr._dnn_step(ws["dnn_in"], self.stage_plan.in_dim, buf, y, binary, add=self._hip_add(ws))
+
 
 def DeepFM(linear_feature_columns, dnn_feature_columns, fm_group=(DEFAULT_GROUP_NAME,), dnn_hidden_units=(256, 128, 64),
            l2_reg_linear=0.00001, l2_reg_embedding=0.00001, l2_reg_dnn=0, seed=1024, dnn_dropout=0,
@@ -77,7 +84,7 @@ def DeepFM(linear_feature_columns, dnn_feature_columns, fm_group=(DEFAULT_GROUP_
     Arguments are those of the reference constructor; the l2_* regularisers only matter to training losses."""
     m = _DeepFM(linear_feature_columns, dnn_feature_columns, fm_group, dnn_hidden_units, seed, dnn_dropout,
                 dnn_activation, dnn_use_bn, task, device)
-    # l2 regularisers of the reference constructor (feature_column.py:171-210, inputs.py:22, core.py:168): applied by
-    # the HIP training step (training_hip.py) as 2*l2*w added to the gradients
+    # l2 regularisers of the reference constructor (feature_column.py:171-210, inputs.py:22, core.py:168): HipTrainer registers
+    # each parameter with its l2 (training_hip.py: __init__ / param) and apply_update adds 2*l2*w to the gradients
     m.regularizers = {"embedding": float(l2_reg_embedding), "linear": float(l2_reg_linear), "dnn": float(l2_reg_dnn)}
     return m

@@ -50,6 +50,27 @@ class _NFM(FeatureModel):
         parts[extra["bi_interaction"]] = tops._dropout(0.5 * (x0.sum(1).pow(2) - (x0 * x0).sum(1)), self.bi_dropout, training)     # nfm.py:52-53
         return super(_NFM, self)._autograd_logit(staged, lo, hi, parts[extra["bi_interaction"]:], extra, training)
 
+    # ---- the HIP training step (training_hip.HipTrainer): BiInteractionPooling (+ Dropout(bi_dropout)) around the DNN step ------------
+    def _hip_supported(self):
+        return self._hip_family_ok(extra_cols=True)
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        off, E = self.stage_plan.extra_offsets["bi_interaction"], self.emb_dim
+        x, dx = ws["dnn_in"][:, off:], buf["dx"]
+        bi_rate = float(self.bi_dropout or 0)
+        ops.bi_interaction(ws["dnn_in"], fields=self.n_emb, dim=E, out=x)
+        if bi_rate > 0:                 # nfm.py:52-53: Dropout on the pooled vector, in place (layer slot 100 of the step's mask seeds)
+            xe = x[:, :E]
+            ops.dnn_train_layer(xe, "linear", h=xe, dropout_rate=bi_rate, dropout_seed=tr.dropout_seed(100))
+        tr._dnn_step(x, self.dnn_in_dim, buf, y, binary, add=self._hip_add(ws), dx=dx[:, off:])
+        dy = dx[:, off:]
+        if bi_rate > 0:
+            if "bi_dz" not in buf:
+                buf["bi_dz"] = torch.empty(x.shape[0], E, dtype=torch.float32, device=self.device)
+            dy = ops.dnn_train_layer(x[:, :E], "linear", dropout_rate=bi_rate, dropout_seed=tr.dropout_seed(100), dh=dx[:, off:off + E],
+                                     dz=buf["bi_dz"])
+        ops.bi_interaction_bwd(ws["dnn_in"], self.n_emb, E, dy, dx)
+
 
 def NFM(linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 128, 64), l2_reg_embedding=1e-5,
         l2_reg_linear=1e-5, l2_reg_dnn=0, seed=1024, bi_dropout=0, dnn_dropout=0, dnn_activation='relu', task='binary',

@@ -63,6 +63,19 @@ class _PNN(FeatureModel):
                                              torch.stack([parts[j] for j in jj], dim=1)).sum(-1)
         return super(_PNN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
+    # ---- the HIP training step (training_hip.HipTrainer): the pair inner products around the DNN step ---------------------------------
+    def _hip_supported(self):
+        return self._hip_family_ok(extra_cols=True)
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        sp = self.stage_plan
+        if self.use_inner:
+            off = sp.extra_offsets["inner_product"]
+            ops.inner_product(ws["dnn_in"], True, fields=self.n_emb, dim=self.emb_dim, out=ws["dnn_in"][:, off:])
+        tr._dnn_step(ws["dnn_in"], sp.in_dim, buf, y, binary)
+        if self.use_inner:
+            ops.inner_product_bwd(ws["dnn_in"], self.n_emb, self.emb_dim, buf["dx"][:, off:], buf["dx"], accumulate=True)
+
 
 def PNN(dnn_feature_columns, dnn_hidden_units=(256, 128, 64), l2_reg_embedding=0.00001, l2_reg_dnn=0, seed=1024,
         dnn_dropout=0, dnn_activation='relu', use_inner=True, use_outter=False, kernel_type='mat', task='binary',

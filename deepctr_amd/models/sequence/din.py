@@ -172,6 +172,92 @@ class _DIN(FeatureModel):
         parts[extra["hist"]] = (score.unsqueeze(1) @ k).squeeze(1)
         return super(_DIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
+    # ---- the HIP training step (training_hip.HipTrainer) ----------------------------------------------------------------------------
+    def _hip_supported(self):
+        # attention unit: Dice, sigmoid / relu / tanh / linear, no dropout or BatchNormalization; any key width (the unit trains on the
+        # materialised [B * T, 4 E'] input, dctr_embed_lookup_bwd scatters any width)
+        dnn = self.attention.local_att.dnn
+        if dnn.activation not in ("dice", "Dice", "sigmoid", "relu", "tanh", "linear"):
+            return False
+        if not dnn.kernels or getattr(dnn, "dropout_rate", 0) or getattr(dnn, "use_bn", False):
+            return False
+        return self._hip_family_ok(extra_cols=True)
+
+    def _hip_batch_statistics(self):
+        # Dice as tf.keras runs it under fit(): BatchNormalization in training mode — this batch's statistics, gradients through them,
+        # stored statistics moved; hip_dice_stored_statistics = True keeps the stored ones (tests of the inference-form backward)
+        return self.attention.local_att.dnn.activation in ("dice", "Dice") and not getattr(self, "hip_dice_stored_statistics", False)
+
+    def _hip_params(self, tr):
+        la, sp = self.attention.local_att, self.stage_plan
+        dice = la.dnn.dice_params()
+        # no regulariser on the attention unit (AttentionSequencePoolingLayer builds it with l2_reg=0, sequence.py:243-245)
+        tr.own["att"] = dict(kernels=[tr.param(k) for k in la.dnn.kernels], biases=[tr.param(b) for b in la.dnn.biases],
+                             alphas=[tr.param(d[0]) for d in dice] if dice else None, out_w=tr.param(la.w("kernel")),
+                             out_b=tr.param(la.w("bias")))
+        # history tables (the query tables under another name) receive the key gradients through dctr_embed_lookup_bwd
+        l2e = getattr(self, "regularizers", {}).get("embedding", 0.0)
+        tr.own["hist"] = [tr.param(self.tables[fc.embedding_name].embeddings, l2e).track_rows() for fc in self.history_cols]
+        # columns of the query embeddings inside the DNN input (dq is added there; the gather backward scatters it)
+        qcol = []
+        for fc in self.query_cols:
+            f = next(f for f in sp.fields if f.kind == "sparse" and f.fc.name == fc.name)
+            qcol.extend(range(f.out_offset, f.out_offset + f.dim))
+        tr.own["qcol"] = torch.as_tensor(qcol, dtype=torch.int32, device=self.device)
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        """din.py:62-96: LocalActivationUnit over [q, k, q-k, q*k] per history position -> masked weighted sum of the keys -> DNN
+        over [embeddings | attention output | dense] -> Dense(1).  The unit's MLP runs on the materialised [B*T, 4E'] input through
+        dctr_mlp_fwd / dctr_mlp_bwd (activations saved)."""
+        sp, la, pa = self.stage_plan, self.attention.local_att, tr.own["att"]
+        B, T, E, dev = hi - lo, self.T, self.key_dim, self.device
+        bufs = self._attention_inputs(staged, lo, hi, ws)
+        q, k, m = bufs["q"], bufs["k"], bufs["m"]
+        if "att_in" not in buf:
+            units = [kk.shape[1] for kk in la.dnn.kernels]
+            buf.update(att_in=torch.empty(B * T, 4 * E, dtype=torch.float32, device=dev),
+                       d_att_in=torch.empty(B * T, 4 * E, dtype=torch.float32, device=dev),
+                       att_acts=[torch.empty(B * T, n, dtype=torch.float32, device=dev) for n in units],
+                       score=torch.empty(B * T, dtype=torch.float32, device=dev),
+                       d_score=torch.empty(B * T, dtype=torch.float32, device=dev),
+                       dk=torch.empty(B, T, E, dtype=torch.float32, device=dev))
+        act, dice = la.dnn.activation, la.dnn.dice_params()
+        ops.din_att_in(q, k, buf["att_in"])
+        dice_batch = None
+        if self._hip_batch_statistics():            # training-mode Dice: layer by layer over ALL B*T rows, head last
+            if "att_z" not in buf:
+                buf["att_z"] = [torch.empty_like(t) for t in buf["att_acts"]]
+            dice_batch, xin, kin = tr._dice_forward(buf["att_in"], 4 * E, la.dnn, buf["att_z"], buf["att_acts"])
+            ops.mlp(xin, [], [], "linear", head_w=pa["out_w"].w, global_bias=pa["out_b"].w, in_dim=kin, out=buf["score"])
+        else:
+            ops.mlp(buf["att_in"], la.dnn.kernels, la.dnn.biases, act, dice=dice, head_w=pa["out_w"].w, global_bias=pa["out_b"].w,
+                    in_dim=4 * E, out=buf["score"], save_acts=buf["att_acts"])
+        hist_off = sp.extra_offsets["hist"]
+        softmax = bool(self.attention.weight_normalization)
+        if softmax:                     # att_weight_normalization=True: masked softmax over the positions, then the sum over ALL of them
+            if "att_p" not in buf:
+                buf.update(att_p=torch.empty(B * T, dtype=torch.float32, device=dev), ones=torch.ones(B, T, dtype=torch.uint8, device=dev))
+            ops.din_softmax(buf["score"], m, buf["att_p"])
+            ops.din_wsum(buf["att_p"], buf["ones"], k, ws["dnn_in"][:, hist_off:])
+        else:
+            ops.din_wsum(buf["score"], m, k, ws["dnn_in"][:, hist_off:])
+        tr._dnn_step(ws["dnn_in"], sp.in_dim, buf, y, binary)
+        dx = buf["dx"]
+        if softmax:
+            ops.din_wsum_bwd(dx[:, hist_off:], buf["att_p"], buf["ones"], k, buf["d_score"], buf["dk"])
+            ops.din_softmax_bwd(buf["att_p"], m, buf["d_score"], buf["d_score"], d_bias=pa["out_b"].g)
+        else:
+            ops.din_wsum_bwd(dx[:, hist_off:], buf["score"], m, k, buf["d_score"], buf["dk"], d_bias=pa["out_b"].g)
+        ops.mlp_bwd(buf["att_in"], 4 * E, la.dnn.kernels, buf["att_acts"], act, pa["out_w"].w, buf["d_score"],
+                    [p.g for p in pa["kernels"]], [p.g for p in pa["biases"]], pa["out_w"].g, dx=buf["d_att_in"],
+                    biases=la.dnn.biases, dice=dice, d_dice_alpha=[p.g for p in pa["alphas"]] if pa["alphas"] else None,
+                    dice_batch=dice_batch, saved_z=buf["att_z"] if dice_batch is not None else None,
+                    workspace=buf.setdefault("mlp_bwd_ws_att", {}))
+        ops.din_att_in_bwd(buf["d_att_in"], q, k, buf["dk"], dx, tr.own["qcol"])
+        for (fc, idx, hm, col), pt in zip(bufs["key_lookups"], tr.own["hist"]):
+            if pt.g is not None:                                   # frozen history table: no scatter
+                ops.embed_lookup_bwd(idx, tuple(pt.w.shape), hm, buf["dk"][:, :, col:], pt.g, touched=pt.touched)
+
 
 def DIN(dnn_feature_columns, history_feature_list, dnn_use_bn=False, dnn_hidden_units=(256, 128, 64),
         dnn_activation='relu', att_hidden_size=(80, 40), att_activation="dice", att_weight_normalization=False,

@@ -156,6 +156,45 @@ class _xDeepFM(FusedForward, FeatureModel):
             finals.append(direct)
         return logit + (torch.cat(finals, dim=1).sum(-1) @ self.dense_1.w("kernel")).reshape(-1)
 
+    # ---- the HIP training step (training_hip.HipTrainer): the DNN step with the CIN in front and dctr_cin_bwd behind -------------------
+    def _hip_supported(self):
+        sp, cin = self.stage_plan, self.cin
+        # (the library's answer — dctr_cin_fwd_supported: any embedding width, in slices of d past 128)
+        if cin is not None and (not ops.cin_supported(len(sp.fields), self.cin_dim, list(cin.layer_size), cin.split_half, cin.activation)
+                                or cin.activation not in ("relu", "linear", "sigmoid", "tanh")):
+            return False
+        return self._hip_family_ok()
+
+    def _hip_params(self, tr):
+        if self.cin is not None:
+            tr.own.update(cin_f=[tr.param(f, getattr(self, "regularizers", {}).get("cin", 0.0)) for f in self.cin.filters],
+                          cin_b=[tr.param(b) for b in self.cin.biases], head1=tr.param(self.dense_1.w("kernel")))
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        sp, cin, own = self.stage_plan, self.cin, tr.own
+        add = self._hip_add(ws)
+        if cin is not None:             # xdeepfm.py:52-66: CIN over the embeddings -> Dense(1) -> extra logit
+            B, nf, dim, dev = hi - lo, len(sp.fields), self.cin_dim, self.device
+            if "maps" not in buf:
+                buf.update(maps=torch.empty(B, self.cin_out_dim, dtype=torch.float32, device=dev),
+                           dmaps=torch.empty(B, self.cin_out_dim, dtype=torch.float32, device=dev),
+                           cin_logit=torch.empty(B, dtype=torch.float32, device=dev),
+                           # layer activations written by the forward CIN kernel for dctr_cin_bwd; None beyond the 2-GiB buffer-descriptor
+                           # range dctr_cin_fwd takes for save_y: dctr_cin_bwd then re-runs the forward into its own workspace
+                           cin_y=[torch.empty(B * dim, h, dtype=torch.float32, device=dev) for h in cin.layer_size]
+                           if B * dim * max(cin.layer_size) * 4 < 2 ** 31 else None)
+            filt = [f.reshape(-1, f.shape[-1]) for f in cin.filters]
+            ops.cin(ws["dnn_in"], filt, cin.biases, list(cin.layer_size), cin.split_half, cin.activation, fields=nf, dim=dim,
+                    out=buf["maps"], save_y=buf["cin_y"])
+            ops.mlp(buf["maps"], [], [], "linear", head_w=own["head1"].w, in_dim=self.cin_out_dim, out=buf["cin_logit"])
+            add.append(buf["cin_logit"])
+        tr._dnn_step(ws["dnn_in"], sp.in_dim, buf, y, binary, add=add)
+        if cin is not None:
+            ops.dense1_bwd(buf["maps"], self.cin_out_dim, own["head1"].w, buf["dlogit"], buf["dmaps"], own["head1"].g)
+            ops.cin_bwd(ws["dnn_in"], filt, cin.biases, list(cin.layer_size), cin.split_half, cin.activation, buf["dmaps"],
+                        [p.g.reshape(-1, p.g.shape[-1]) for p in own["cin_f"]], [p.g for p in own["cin_b"]], dx=buf["dx"],
+                        accumulate=True, fields=nf, dim=dim, saved_y=buf["cin_y"])
+
 
 def xDeepFM(linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 128, 64), cin_layer_size=(128, 128,),
             cin_split_half=True, cin_activation='relu', l2_reg_linear=0.00001, l2_reg_embedding=0.00001, l2_reg_dnn=0,

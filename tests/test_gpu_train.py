@@ -203,8 +203,7 @@ def test_hip_training_with_a_dice_dnn_matches_torch_autograd(device, kind):
     for t in params:
         t.requires_grad_(True)
     try:
-        if tr.is_dcn:
-            tr.bind_cross_views()        # the per-layer views must descend from the grad-tracking packed tensors
+        tr.bind_cross_views()            # the per-layer views must descend from the grad-tracking packed tensors
         model._begin()
         logit = training.model_logits(model, staged, 0, n, training=True)
         ref_loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, yt)
@@ -212,8 +211,7 @@ def test_hip_training_with_a_dice_dnn_matches_torch_autograd(device, kind):
     finally:
         for t in params:
             t.requires_grad_(False)
-        if tr.is_dcn:
-            tr.bind_cross_views()
+        tr.bind_cross_views()
     assert_close(loss.cpu().numpy(), [float(ref_loss.detach())], rtol=1e-4, atol=1e-6, what="loss")
     for (m1, v1), d_ in zip(moved, model.dnn.dice_params()):
         assert_close(m1.cpu().numpy(), d_[1].cpu().numpy(), rtol=1e-4, atol=1e-6, what="moved mean")
@@ -884,3 +882,51 @@ def test_own_sgemm_matches_float64(device, m, n, k):
     refb = ab.astype(np.float64) @ bb.astype(np.float64)
     magb = np.abs(ab).astype(np.float64) @ np.abs(bb).astype(np.float64)
     assert (np.abs(gotb.cpu().numpy() - refb) <= 2e-6 * magb + 1e-30).all()
+
+
+@pytest.mark.parametrize("kind", ["DCN", "DIN"])
+def test_a_subclass_under_another_name_trains_on_the_hip_step_as_its_base(device, kind):
+    """Which step fit() takes is the model class's answer (FeatureModel._hip_supported), not its name: a renamed subclass of _DCN
+    (matrix CrossNet) / _DIN trains on the HIP step and ends where its base class ends from the same weights (SGD, no shuffle; not
+    bit for bit: the scatter kernels add with float atomics)."""
+    from deepctr_amd.feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
+    from deepctr_amd.models.dcn import _DCN
+    from deepctr_amd.models.sequence.din import _DIN
+    from tests.test_gpu_models import _randomise
+    rng = np.random.RandomState(41)
+    n, E, T = 211, 8, 5
+    if kind == "DCN":
+        class Renamed(_DCN):
+            pass
+        cols = [SparseFeat("a", 40, E), SparseFeat("b", 7, E), SparseFeat("c", 300, E, use_hash=True), SparseFeat("e", 19, E), DenseFeat("d", 2)]
+        make = lambda cls: cls(cols, cols, 2, "matrix", (24, 12), 1024, 0, False, "relu", "binary", device)      # noqa: E731
+        feed = {"a": rng.randint(0, 40, n).astype(np.int32), "b": rng.randint(0, 7, n).astype(np.int32),
+                "c": rng.randint(0, 2 ** 31 - 1, n).astype(np.int32), "e": rng.randint(0, 19, n).astype(np.int32)}
+        reg = {"embedding": 1e-5, "linear": 1e-5, "dnn": 0.0, "cross": 1e-5}
+    else:
+        class Renamed(_DIN):
+            pass
+        cols = [SparseFeat("user", 40, E), SparseFeat("item_id", 31, E), SparseFeat("cate_id", 11, E), DenseFeat("d", 2),
+                VarLenSparseFeat(SparseFeat("hist_item_id", 31, E, embedding_name="item_id"), maxlen=T)]
+        make = lambda cls: cls(cols, ["item_id"], False, (24, 12), "relu", (12, 6), "dice", False, 0, 1024, "binary", device)      # noqa: E731
+        hist = rng.randint(1, 31, (n, T)).astype(np.int32)
+        hist[np.arange(T)[None, :] >= rng.randint(0, T + 1, n)[:, None]] = 0
+        feed = {"user": rng.randint(0, 40, n).astype(np.int32), "item_id": rng.randint(1, 31, n).astype(np.int32),
+                "cate_id": rng.randint(0, 11, n).astype(np.int32), "hist_item_id": hist}
+        reg = {"embedding": 1e-6, "linear": 0.0, "dnn": 0.0}
+    feed["d"] = rng.rand(n, 2).astype(np.float32)
+    y = (rng.rand(n) > 0.5).astype(np.float32)
+    base, sub = make(Renamed.__bases__[0]), make(Renamed)
+    start = _randomise(base, rng)
+    sub.set_weights_by_name(start)
+    hist_, ends = [], []
+    for m in (base, sub):
+        m.regularizers = dict(reg)
+        m.compile("sgd", "binary_crossentropy")
+        hist_.append(m.fit(feed, y, batch_size=64, epochs=1, verbose=0, shuffle=False).history["loss"])
+        assert getattr(m, "_hip_trainer", None) is not None, "fit() did not take the HIP training step for %s" % type(m).__name__
+        ends.append(m.get_weights_by_name())
+    assert_close(np.array(hist_[1]), np.array(hist_[0]), rtol=2e-4, atol=1e-5, what="epoch loss")
+    assert any(not np.array_equal(ends[0][k], start[k]) for k in start)
+    for k in ends[0]:
+        assert_close(ends[1][k], ends[0][k], rtol=1e-3, atol=2e-5, what=k)

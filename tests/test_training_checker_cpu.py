@@ -431,3 +431,61 @@ def test_keras_adam_is_the_tf_keras_update():
     first = w0 - 1e-3 * np.sqrt(0.001) / 0.1 * (0.1 * grads[0]) / (np.sqrt(0.001 * grads[0] ** 2) + 1e-7)
     tiny = np.abs(grads[0]) < 1e-6
     assert tiny.any() and np.abs((q.detach().numpy() - w0)[tiny]).max() > 1.5 * np.abs((first - w0)[tiny]).max()
+
+
+def _small_columns():
+    from deepctr_amd.feature_column import DenseFeat, SparseFeat
+    return [SparseFeat("a", 20, 4), SparseFeat("b", 9, 4), SparseFeat("c", 5, 4), DenseFeat("d", 2)]
+
+
+@pytest.mark.parametrize("kind", ["DeepFM", "DCN", "DCNMix", "NFM", "AFM"])
+def test_a_subclass_under_another_name_is_on_the_hip_step(kind):
+    """Whether a model trains on the HIP step is its class's answer (_hip_supported), so a subclass under any name gets what its base
+    gets: supported(), and a HipTrainer with the same parameters."""
+    from deepctr_amd import models, training_hip
+    cpu = torch.device("cpu")
+    cols = _small_columns()
+    kw = dict(dnn_hidden_units=(8, 4))
+    base = {"DeepFM": lambda: models.DeepFM(cols, cols, device=cpu, **kw),
+            "DCN": lambda: models.DCN(cols, cols, cross_num=2, cross_parameterization="matrix", device=cpu, **kw),
+            "DCNMix": lambda: models.DCNMix(cols, cols, cross_num=2, low_rank=3, num_experts=2, device=cpu, **kw),
+            "NFM": lambda: models.NFM(cols, cols, device=cpu, **kw),
+            "AFM": lambda: models.AFM(cols, cols[:3], device=cpu)}[kind]
+    model, renamed = base(), base()
+    renamed.__class__ = type("My" + kind, (type(model),), {})
+    assert type(renamed).__name__ != type(model).__name__ and isinstance(renamed, type(model))
+    assert training_hip.supported(model) and training_hip.supported(renamed)
+
+    def shapes(m):
+        tr = training_hip.HipTrainer(m)
+        return sorted((tuple(p.w.shape), p.l2, p.touched is not None) for p in tr.params), len(tr.field_params)
+    assert shapes(renamed) == shapes(model)
+
+
+def test_models_without_the_hooks_are_declined():
+    """FeatureModel's default is "no HIP step": a subclass that defines none of the hooks, and the seven models that have none yet,
+    are declined by supported() and refused by HipTrainer — fit() takes the torch-autograd step for them."""
+    from deepctr_amd import models, training_hip
+    from deepctr_amd.models._common import FeatureModel
+    cpu = torch.device("cpu")
+    cols = _small_columns()
+    sparse = cols[:3]
+
+    class Bare(models.deepfm._DeepFM):
+        _hip_supported = FeatureModel._hip_supported
+        _hip_params = FeatureModel._hip_params
+        _hip_forward_backward = FeatureModel._hip_forward_backward
+
+    declined = [Bare(cols, cols, ("default_group",), (8, 4), 1024, 0, "relu", False, "binary", cpu),
+                models.AutoInt(cols, cols, dnn_hidden_units=(8, 4), device=cpu),
+                models.FiBiNET(cols, cols, dnn_hidden_units=(8, 4), device=cpu),
+                models.FwFM(cols, sparse, dnn_hidden_units=(8, 4), device=cpu),
+                models.DeepFEFM(cols, cols, dnn_hidden_units=(8, 4), device=cpu),
+                models.ONN(cols, sparse, dnn_hidden_units=(8, 4), device=cpu),
+                models.IFM(cols, sparse, dnn_hidden_units=(8, 4), device=cpu),
+                models.DIFM(cols, sparse, dnn_hidden_units=(8, 4), device=cpu)]
+    assert [type(m).__name__ for m in declined] == ["Bare", "_AutoInt", "_FiBiNET", "_FwFM", "_DeepFEFM", "_ONN", "_IFM", "_DIFM"]
+    for m in declined:
+        assert m.stage_plan is not None and training_hip.supported(m) is False, type(m).__name__
+        with pytest.raises(ValueError, match="outside the HIP training step"):
+            training_hip.HipTrainer(m)
