@@ -9,7 +9,7 @@ scripts (``examples/run_classification_criteo.py``, ``run_din.py`` ...) run unmo
 
 Differences from the reference package, on purpose: importing it performs no HTTP version check
 (reference ``deepctr/__init__.py:1-4`` -> ``utils.check_version`` starts a thread that queries PyPI), and only the §8
-scope exists: the other 14 model constructors, the Estimator API and ``deepctr.contrib`` raise ``ImportError`` /
+scope exists: the other 11 model constructors, the Estimator API and ``deepctr.contrib`` raise ``ImportError`` /
 ``AttributeError`` by absence.
 """
 import importlib
@@ -21,7 +21,7 @@ _ALIASES = (
     "feature_column", "inputs",
     "layers", "layers.activation", "layers.core", "layers.interaction", "layers.sequence", "layers.utils",
     "models", "models.afm", "models.autoint", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.fibinet",
-    "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
+    "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
     "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.din",
 )
 for _name in _ALIASES:

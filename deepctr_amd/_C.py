@@ -197,6 +197,27 @@ ifm.Args = type("Args", (ctypes.Structure,), {"_fields_": [
     ("factor_stride", c_i64), ("status", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
 
 
+class fieldwise(object):
+    """dctr_fieldwise_group_t / dctr_fieldwise_args_t / dctr_fieldwise_bwd_args_t, one level down for the same reason as
+    interacting.Args (tests/test_flen_cpu.py checks the layout)."""
+    ROUTE_AUTO, ROUTE_ON_CHIP, ROUTE_REREAD = 0, 1, 2
+
+    class Group(ctypes.Structure):
+        _fields_ = [("first", c_i64), ("n_fields", c_i32), ("reserved", c_i32)]
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_offset", c_i64), ("groups", c_vp), ("groups_host", c_vp),
+                    ("n_groups", c_i32), ("dim", c_i32), ("kernel_mf", c_vp), ("kernel_fm", c_vp), ("bias_mf", c_vp), ("bias_fm", c_vp),
+                    ("y", c_vp), ("y_stride", c_i64), ("y_offset", c_i64), ("head_w", c_vp), ("add", c_vp), ("logit", c_vp),
+                    ("route", c_i32), ("max_blocks", c_i32)]
+
+
+fieldwise.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", fieldwise.Args), ("dy", c_vp), ("dy_stride", c_i64), ("dlogit", c_vp), ("dx", c_vp), ("dx_stride", c_i64),
+    ("dx_offset", c_i64), ("accumulate", c_i32), ("reserved", c_i32), ("d_kernel_mf", c_vp), ("d_kernel_fm", c_vp),
+    ("d_bias_mf", c_vp), ("d_bias_fm", c_vp), ("d_head_w", c_vp)]})
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -291,6 +312,10 @@ SYMBOLS = {
     "dctr_ifm_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_route": (ctypes.c_int, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_fwd": (ctypes.c_int, [ctypes.POINTER(ifm.Args), c_vp]),
+    "dctr_fieldwise_route": (ctypes.c_int, [ctypes.POINTER(fieldwise.Args)]),
+    "dctr_fieldwise_fwd": (ctypes.c_int, [ctypes.POINTER(fieldwise.Args), c_vp]),
+    "dctr_fieldwise_bwd_supported": (ctypes.c_int, [ctypes.POINTER(fieldwise.BwdArgs)]),
+    "dctr_fieldwise_bwd": (ctypes.c_int, [ctypes.POINTER(fieldwise.BwdArgs), c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

@@ -52,6 +52,7 @@ SOURCES = [
     "fieldpair_kernels.hip",
     "ffm_kernels.hip",
     "ifm_kernels.hip",
+    "fieldwise_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

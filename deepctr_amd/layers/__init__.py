@@ -3,8 +3,8 @@
 siblings need — SURVEY.md §8a)."""
 from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer
-from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FEFMLayer, FM, FwFMLayer,
-                          InnerProductLayer, InteractingLayer, SENETLayer)
+from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
+                          FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
 from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
@@ -23,6 +23,7 @@ custom_objects = {
     'BilinearInteraction': BilinearInteraction,
     'FwFMLayer': FwFMLayer,
     'FEFMLayer': FEFMLayer,
+    'FieldWiseBiInteraction': FieldWiseBiInteraction,
     'LocalActivationUnit': LocalActivationUnit,
     'Dice': Dice,
     'SequencePoolingLayer': SequencePoolingLayer,

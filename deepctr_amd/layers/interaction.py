@@ -1,7 +1,7 @@
 """Host mirror of the ten in-scope layers of the reference's ``deepctr/layers/interaction.py``:
 ``AFMLayer`` (:39-160), ``CIN`` (:209-341), ``CrossNet`` (:344-435), ``FM`` (:563-607),
 ``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790), ``SENETLayer`` (:1067-1139), ``BilinearInteraction`` (:1142-1221),
-``FwFMLayer`` (:1351-1425), ``FEFMLayer`` (:1428-1499).
+``FwFMLayer`` (:1351-1425), ``FEFMLayer`` (:1428-1499), and ``FieldWiseBiInteraction`` (:1224-1348, fieldwise_kernels.hip).
 Same constructor kwargs, ``get_config`` and weight names/shapes; ``call`` launches the HIP kernels
 (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip,
 fieldpair_kernels.hip).  The other six interaction layers of the reference are out of scope."""
@@ -10,7 +10,7 @@ import itertools
 import torch
 
 from .. import ops
-from ..initializers import GlorotNormal, GlorotUniform, TruncatedNormal, Zeros
+from ..initializers import GlorotNormal, GlorotUniform, Ones, TruncatedNormal, Zeros
 from .base import Layer
 
 
@@ -278,6 +278,65 @@ class BilinearInteraction(Layer):
     def get_config(self):
         config = {'bilinear_type': self.bilinear_type, 'seed': self.seed}
         base = super(BilinearInteraction, self).get_config()
+        base.update(config)
+        return base
+
+
+class FieldWiseBiInteraction(Layer):
+    """FLEN's field-wise bi-interaction (reference interaction.py:1224-1348): a list of G >= 2 tensors [B, n_g, E], one per field
+    group -> [B, E].  With s_g / q_g the sum / the sum of squares of group g's embeddings:
+    (sum_{i<j} kernel_mf[p(i,j)] s_i s_j + bias_mf) + (sum_g kernel_fm[g] (s_g^2 - q_g) + bias_fm), pairs in
+    itertools.combinations order.  One ``dctr_fieldwise_fwd`` launch."""
+
+    def __init__(self, use_bias=True, seed=1024, **kwargs):
+        self.use_bias = use_bias
+        self.seed = seed
+        super(FieldWiseBiInteraction, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if not isinstance(input_shape, list) or len(input_shape) < 2:
+            raise ValueError('A `Field-Wise Bi-Interaction` layer should be called on a list of at least 2 inputs')
+        return self.build_for(len(input_shape), int(input_shape[0][-1]))
+
+    def build_for(self, num_fields, embedding_size):
+        if self.built:
+            return self
+        if int(num_fields) < 2:
+            raise ValueError('A `Field-Wise Bi-Interaction` layer should be called on a list of at least 2 inputs')
+        self.num_fields = int(num_fields)           # (the reference's name for the number of field GROUPS)
+        self.add_weight('kernel_mf', (self.num_fields * (self.num_fields - 1) // 2, 1), Ones())
+        self.add_weight('kernel_fm', (self.num_fields, 1), lambda shape: torch.full(shape, 0.5))
+        if self.use_bias:
+            self.add_weight('bias_mf', (int(embedding_size),), Zeros())
+            self.add_weight('bias_fm', (int(embedding_size),), Zeros())
+        self.built = True
+        return self
+
+    @property
+    def biases(self):
+        return (self.w('bias_mf'), self.w('bias_fm')) if self.use_bias else (None, None)
+
+    def call(self, inputs, **kwargs):
+        if inputs[0].dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs[0].dim()))
+        if len(inputs) != self.num_fields:
+            raise ValueError("FieldWiseBiInteraction was built for %d field groups, got %d" % (self.num_fields, len(inputs)))
+        B, dim = inputs[0].shape[0], inputs[0].shape[2]
+        x = torch.cat([t.reshape(B, -1) for t in inputs], dim=1)
+        groups, first = [], 0
+        for t in inputs:
+            groups.append((first, t.shape[1]))
+            first += t.shape[1] * dim
+        bias_mf, bias_fm = self.biases
+        y, _ = ops.fieldwise(x, groups, dim, self.w('kernel_mf'), self.w('kernel_fm'), bias_mf, bias_fm)
+        return y
+
+    def compute_output_shape(self, input_shape):
+        return (None, input_shape[0][-1])
+
+    def get_config(self):
+        config = {'use_bias': self.use_bias, 'seed': self.seed}
+        base = super(FieldWiseBiInteraction, self).get_config()
         base.update(config)
         return base
 

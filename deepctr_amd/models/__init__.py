@@ -2,7 +2,8 @@
 BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN, AFM, PNN, NFM and DCNMix
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
 SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel,
-IFM and DIFM the input-aware FM kernel)."""
+IFM and DIFM the input-aware FM kernel, FLEN the field-wise bi-interaction kernel and its backward: the first of these to train on
+the HIP step)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -11,6 +12,7 @@ from .deepfefm import DeepFEFM
 from .deepfm import DeepFM
 from .difm import DIFM
 from .fibinet import FiBiNET
+from .flen import FLEN
 from .fnn import FNN
 from .fwfm import FwFM
 from .ifm import IFM

@@ -1098,6 +1098,177 @@ def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), 
     return out
 
 
+_FIELDWISE_ROUTES = {None: _C.fieldwise.ROUTE_AUTO, "auto": _C.fieldwise.ROUTE_AUTO, "reread": _C.fieldwise.ROUTE_REREAD}
+_FIELDWISE_TABLES = {}
+
+
+def fieldwise_groups(groups, device):
+    """The group table [(first column, n fields)] as dctr_fieldwise_group_t arrays: (device tensor, host array), cached per table
+    and device (a model passes the same table on every call)."""
+    key = (str(device), tuple((int(a), int(n)) for a, n in groups))
+    hit = _FIELDWISE_TABLES.get(key)
+    if hit is None:
+        host = (_C.fieldwise.Group * max(1, len(key[1])))()
+        for i, (a, n) in enumerate(key[1]):
+            host[i].first, host[i].n_fields = a, n
+        raw = np.frombuffer(host, dtype=np.uint8).copy()
+        if len(_FIELDWISE_TABLES) >= 64:
+            _FIELDWISE_TABLES.clear()
+        hit = _FIELDWISE_TABLES[key] = (torch.from_numpy(raw).to(device), host)
+    return hit
+
+
+def _fieldwise_args(x, groups, dim, x_offset, route, device=None):
+    if route not in _FIELDWISE_ROUTES:
+        raise ValueError("fieldwise: route %r: expected None, 'auto' or 'reread'" % (route,))
+    groups = list(groups)
+    a = _C.fieldwise.Args(n_groups=len(groups), dim=int(dim), x_offset=int(x_offset), route=_FIELDWISE_ROUTES[route])
+    dev_t, host = fieldwise_groups(groups, device) if device is not None else (None, fieldwise_groups(groups, "cpu")[1])
+    a.groups_host = ctypes.addressof(host)
+    keep = [host, dev_t]
+    if dev_t is not None:
+        a.groups = dev_t.data_ptr()
+    if x is not None:
+        a.batch, a.x, a.x_stride = x.shape[0], x.data_ptr(), x.stride(0)
+    else:
+        a.x_stride = int(x_offset) + max([f + n * int(dim) for f, n in groups] + [0])
+    return a, keep
+
+
+def fieldwise_route(groups, dim, route=None):
+    """The route dctr_fieldwise_fwd takes for these shapes: 'on_chip' (the group sums wait in LDS) or 'reread' (read from the library)."""
+    a, _keep = _fieldwise_args(None, groups, dim, 0, route)
+    rc = int(_C.lib().dctr_fieldwise_route(ctypes.byref(a)))
+    _C.check(min(rc, 0), "dctr_fieldwise_route")
+    return {_C.fieldwise.ROUTE_ON_CHIP: "on_chip", _C.fieldwise.ROUTE_REREAD: "reread"}[rc]
+
+
+def fieldwise_bwd_supported(groups, dim):
+    """Does dctr_fieldwise_bwd take these shapes (its group sums and accumulators fit the LDS)?"""
+    b = _C.fieldwise.BwdArgs()
+    b.fwd, _keep = _fieldwise_args(None, groups, dim, 0, None)
+    return bool(_C.lib().dctr_fieldwise_bwd_supported(ctypes.byref(b)))
+
+
+def _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm):
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+        raise ValueError("fieldwise: x must be a float32 [B, stride] buffer with unit column stride")
+    G = len(groups)
+    if G < 2:
+        raise ValueError("A `Field-Wise Bi-Interaction` layer should be called on a list of at least 2 inputs")
+    kernel_mf, kernel_fm = _f32c(kernel_mf, "kernel_mf"), _f32c(kernel_fm, "kernel_fm")
+    if kernel_mf.numel() != G * (G - 1) // 2 or kernel_fm.numel() != G:
+        raise ValueError("fieldwise: %d groups take kernel_mf [%d, 1] and kernel_fm [%d, 1]" % (G, G * (G - 1) // 2, G))
+    if (bias_mf is None) != (bias_fm is None):
+        raise ValueError("fieldwise: bias_mf and bias_fm come together (use_bias)")
+    if bias_mf is not None:
+        bias_mf, bias_fm = _f32c(bias_mf, "bias_mf"), _f32c(bias_fm, "bias_fm")
+        if bias_mf.numel() != dim or bias_fm.numel() != dim:
+            raise ValueError("fieldwise: the biases hold dim = %d elements" % dim)
+    return kernel_mf, kernel_fm, bias_mf, bias_fm
+
+
+def fieldwise(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, x_offset=0, y=None, y_offset=0, head_w=None,
+              add=None, logit=None, route=None):
+    """FieldWiseBiInteraction.call (reference interaction.py:1283-1339), one launch.  x: a float32 [B, stride] buffer read in place;
+    ``groups``: [(first column, n fields)] counted from column ``x_offset``, every field ``dim`` wide (EmbeddingStage.group_slices).
+    The weights are the live tensors.  ``y``: True (a new [B, dim] tensor) or a float32 2-D view whose rows receive the dim values
+    from column ``y_offset``; ``logit``: True or a float32 [B] tensor = y . head_w (+ ``add`` [B]).  Default: y.  Returns (y, logit)."""
+    dim = int(dim)
+    groups = [(int(a), int(n)) for a, n in groups]
+    kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm)
+    B = x.shape[0]
+    if y is None and logit is None:
+        y = True
+    if y is True:
+        y, y_offset = torch.empty(B, dim, dtype=torch.float32, device=x.device), 0
+    if logit is True:
+        logit = torch.empty(B, dtype=torch.float32, device=x.device)
+    if y is not None and (y.dim() != 2 or y.stride(1) != 1 or y.dtype != torch.float32 or y.shape[0] != B or y_offset < 0
+                          or y.shape[1] < y_offset + dim):
+        raise ValueError("fieldwise: y must be a float32 [%d, >= %d] view with unit column stride" % (B, y_offset + dim))
+    if logit is not None:
+        if logit.dtype != torch.float32 or not logit.is_contiguous() or logit.numel() != B:
+            raise ValueError("fieldwise: logit must be a contiguous float32 tensor of %d elements" % B)
+        if head_w is None:
+            raise ValueError("fieldwise: a logit needs head_w [dim]")
+        head_w = _f32c(head_w, "head_w")
+        if head_w.numel() != dim:
+            raise ValueError("fieldwise: head_w must hold dim = %d elements" % dim)
+    if add is not None:
+        if logit is None:
+            raise ValueError("fieldwise: add needs a logit output")
+        add = _f32c(add, "add")
+        if add.numel() != B:
+            raise ValueError("fieldwise: add must hold %d elements" % B)
+    _dev_check(x, kernel_mf, kernel_fm, bias_mf, bias_fm, y, head_w, add, logit)
+    a, _keep = _fieldwise_args(x, groups, dim, x_offset, route, x.device)
+    if any(x_offset + f + n * dim > x.shape[1] or f < 0 for f, n in groups) or x_offset < 0:
+        raise ValueError("fieldwise: a group's columns are not inside x [%d, %d]" % (B, x.shape[1]))
+    a.kernel_mf, a.kernel_fm = kernel_mf.data_ptr(), kernel_fm.data_ptr()
+    if bias_mf is not None:
+        a.bias_mf, a.bias_fm = bias_mf.data_ptr(), bias_fm.data_ptr()
+    if y is not None:
+        a.y, a.y_stride, a.y_offset = y.data_ptr(), y.stride(0), int(y_offset)
+    if logit is not None:
+        a.logit, a.head_w = logit.data_ptr(), head_w.data_ptr()
+    if add is not None:
+        a.add = add.data_ptr()
+    _C.check(_C.lib().dctr_fieldwise_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_fieldwise_fwd")
+    return y, logit
+
+
+def fieldwise_bwd(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, x_offset=0, dy=None, dlogit=None, head_w=None,
+                  dx=None, dx_offset=0, accumulate=False, d_kernel_mf=None, d_kernel_fm=None, d_bias_mf=None, d_bias_fm=None,
+                  d_head_w=None, max_blocks=0):
+    """Backward of fieldwise() (include/dctr.h: dctr_fieldwise_bwd).  Upstream gradient: ``dy`` [B, >= dim], or ``dlogit`` [B] with
+    ``head_w`` [dim].  ``dx`` [B, stride]: the groups' columns from ``dx_offset`` are written, or added to with ``accumulate``.  The
+    weight gradients (shapes of the weights; ``d_head_w`` with dlogit only) are ACCUMULATED; any may be None."""
+    dim = int(dim)
+    groups = [(int(a), int(n)) for a, n in groups]
+    kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm)
+    B = x.shape[0]
+    if (dy is None) == (dlogit is None):
+        raise ValueError("fieldwise_bwd: exactly one of dy / dlogit")
+    if dy is not None and (dy.dim() != 2 or dy.stride(1) != 1 or dy.dtype != torch.float32 or dy.shape[0] != B or dy.shape[1] < dim):
+        raise ValueError("fieldwise_bwd: dy must be a float32 [%d, >= %d] view with unit column stride" % (B, dim))
+    if dlogit is not None:
+        if dlogit.dtype != torch.float32 or not dlogit.is_contiguous() or dlogit.numel() != B:
+            raise ValueError("fieldwise_bwd: dlogit must be a contiguous float32 tensor of %d elements" % B)
+        if head_w is None or head_w.dtype != torch.float32 or not head_w.is_contiguous() or head_w.numel() != dim:
+            raise ValueError("fieldwise_bwd: dlogit needs a contiguous float32 head_w of dim = %d elements" % dim)
+    elif d_head_w is not None:
+        raise ValueError("fieldwise_bwd: d_head_w needs the dlogit form")
+    if dx is not None and (dx.dim() != 2 or dx.stride(1) != 1 or dx.dtype != torch.float32 or dx.shape[0] != B or dx_offset < 0
+                           or any(dx_offset + f + n * dim > dx.shape[1] for f, n in groups)):
+        raise ValueError("fieldwise_bwd: dx must be a float32 [%d, stride] view that holds every group's columns" % B)
+    G = len(groups)
+    for t, n, name in ((d_kernel_mf, G * (G - 1) // 2, "d_kernel_mf"), (d_kernel_fm, G, "d_kernel_fm"), (d_bias_mf, dim, "d_bias_mf"),
+                       (d_bias_fm, dim, "d_bias_fm"), (d_head_w, dim, "d_head_w")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise ValueError("fieldwise_bwd: %s must be a contiguous float32 tensor of %d elements" % (name, n))
+    if any(x_offset + f + n * dim > x.shape[1] or f < 0 for f, n in groups) or x_offset < 0:
+        raise ValueError("fieldwise_bwd: a group's columns are not inside x [%d, %d]" % (B, x.shape[1]))
+    _dev_check(x, kernel_mf, kernel_fm, bias_mf, bias_fm, dy, dlogit, head_w, dx, d_kernel_mf, d_kernel_fm, d_bias_mf, d_bias_fm, d_head_w)
+    b = _C.fieldwise.BwdArgs()
+    b.fwd, _keep = _fieldwise_args(x, groups, dim, x_offset, None, x.device)
+    f = b.fwd
+    f.kernel_mf, f.kernel_fm, f.max_blocks = kernel_mf.data_ptr(), kernel_fm.data_ptr(), int(max_blocks)
+    if bias_mf is not None:
+        f.bias_mf, f.bias_fm = bias_mf.data_ptr(), bias_fm.data_ptr()
+    if dy is not None:
+        b.dy, b.dy_stride = dy.data_ptr(), dy.stride(0)
+    else:
+        b.dlogit, f.head_w = dlogit.data_ptr(), head_w.data_ptr()
+    if dx is not None:
+        b.dx, b.dx_stride, b.dx_offset, b.accumulate = dx.data_ptr(), dx.stride(0), int(dx_offset), int(bool(accumulate))
+    for name, t in (("d_kernel_mf", d_kernel_mf), ("d_kernel_fm", d_kernel_fm), ("d_bias_mf", d_bias_mf), ("d_bias_fm", d_bias_fm),
+                    ("d_head_w", d_head_w)):
+        if t is not None:
+            setattr(b, name, t.data_ptr())
+    _C.check(_C.lib().dctr_fieldwise_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_fieldwise_bwd")
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -10,7 +10,7 @@ What lies between the stage and the loss is the model class's, beside its forwar
 of ``models/_common.py:FeatureModel``): ``_hip_supported`` says whether an instance trains here, ``_hip_params`` registers its
 private parameters through ``HipTrainer.param``, ``_hip_forward_backward`` is its part of the step.  DeepFM / WDL / FNN
 (models/deepfm.py), NFM and PNN (interaction kernel in front of the DNN), AFM (AFMLayer instead of the DNN), DCN and DCNMix
-(``dctr_crossnet_bwd`` / ``dctr_crossnet_mix_bwd``), xDeepFM (``dctr_cin_bwd``) and DIN (attention input / weighted sum / lookup scatter
+(``dctr_crossnet_bwd`` / ``dctr_crossnet_mix_bwd``), xDeepFM (``dctr_cin_bwd``), FLEN (``dctr_fieldwise_bwd``) and DIN (attention input / weighted sum / lookup scatter
 kernels, Dice as tf.keras runs it under fit()) bring one; a model without, ``afm_dropout`` and a PReLU DNN keep ``training.py``'s step.
 
 Semantics follow tf.keras as the reference uses it (``model.compile("adam", "binary_crossentropy")``,
@@ -61,6 +61,15 @@ class _Frozen(object):
 
     def track_rows(self):
         return self
+
+
+class _ParamRows(object):
+    """Rows [lo, hi) of a registered parameter as a handle of their own: ``w`` and ``g`` are views into the parameter's, which
+    keeps its one optimizer segment (FLEN: the DNN's head is the rows of dense/kernel behind the field-wise vector's)."""
+    __slots__ = ("w", "g", "l2", "touched")
+
+    def __init__(self, p, lo, hi):
+        self.w, self.g, self.l2, self.touched = p.w[lo:hi], None if p.g is None else p.g[lo:hi], p.l2, None
 
 
 # tf.keras defaults of the optimizers model.compile() takes by name (optimizer_v2/*.py)
@@ -153,6 +162,11 @@ class HipTrainer(object):
                 self._by_ptr[key] = _Param(t, l2)
                 self.params.append(self._by_ptr[key])
         return self._by_ptr[key]
+
+    def param_rows(self, p, lo, hi):
+        """A handle on rows [lo, hi) of the registered parameter ``p`` (HipTrainer.param): what ``p_head`` may be set to by a model
+        whose Dense(1) kernel meets more than its DNN (FeatureModel._hip_params)."""
+        return _ParamRows(p, lo, hi)
 
     def _buffers(self, B):
         b = self._buf.get(B)

@@ -617,6 +617,79 @@ int dctr_ifm_route(const dctr_ifm_args_t* args);
 int dctr_ifm_fwd(const dctr_ifm_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FieldWiseBiInteraction.call (FLEN) — deepctr/layers/interaction.py:1224-1348, one launch
+ *     x [B, x_stride] read in place from column x_offset; G >= 2 embedding groups, group g = n_fields fields of width dim from column
+ *     first (relative to x_offset; groups need not be adjacent, ordered or equal in size).  Per sample, elementwise over the dim columns:
+ *       s_g = sum_f x_f,  q_g = sum_f x_f^2
+ *       y   = (sum_{i<j} kernel_mf[p(i,j)] s_i s_j + bias_mf) + (sum_g kernel_fm[g] (s_g^2 - q_g) + bias_fm)   (no factor 1/2)
+ *     p(i,j): itertools.combinations order.  Outputs, either or both: y [B, dim] at y_stride / y_offset; logit[b] = y[b,:] . head_w
+ *     (+ add[b]).  The weights are read from the given pointers on every call.  A thread owns one sample and 4 (16-B loads: dim % 4 == 0
+ *     and every column offset / stride / pointer a multiple of 16 B) or 1 adjacent columns, walks the groups once and keeps the s_g
+ *     in LDS; the lanes of a sample meet in shuffles for the logit.  No atomics: the same bits on every call.  Routes: ON_CHIP, or —
+ *     more groups than the LDS holds (G * 256 B per thread column over 128 KiB), or route = DCTR_FIELDWISE_ROUTE_REREAD — the s_i of
+ *     the earlier groups are summed again from x where the MF part needs them: the same additions in the same order, the same bits,
+ *     no workspace.  No shape is refused for its size (any dim, any number of fields) up to G < 2^20.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_FIELDWISE_ROUTE_AUTO = 0, DCTR_FIELDWISE_ROUTE_ON_CHIP = 1, DCTR_FIELDWISE_ROUTE_REREAD = 2 };
+typedef struct {
+    int64_t first;                /* first column of the group, relative to x_offset */
+    int32_t n_fields;             /* >= 1 */
+    int32_t reserved;             /* 0 */
+} dctr_fieldwise_group_t;
+typedef struct {
+    int64_t batch;
+    const float* x;               /* [B, x_stride] fp32 */
+    int64_t x_stride;             /* floats between rows */
+    int64_t x_offset;             /* first column the groups count from */
+    const dctr_fieldwise_group_t* groups;        /* DEVICE array [n_groups] */
+    const dctr_fieldwise_group_t* groups_host;   /* the same table in host memory (checked against x_stride before the launch) */
+    int32_t n_groups;             /* G >= 2 */
+    int32_t dim;                  /* d >= 1 */
+    const float* kernel_mf;       /* [G(G-1)/2] */
+    const float* kernel_fm;       /* [G] */
+    const float* bias_mf;         /* NULL or [d] */
+    const float* bias_fm;         /* NULL or [d] */
+    float* y;                     /* NULL, or [B, y_stride]: columns [y_offset, y_offset + d) written */
+    int64_t y_stride;
+    int64_t y_offset;
+    const float* head_w;          /* [d]; REQUIRED with logit */
+    const float* add;             /* NULL or [B] */
+    float* logit;                 /* NULL or [B] */
+    int32_t route;                /* DCTR_FIELDWISE_ROUTE_AUTO | DCTR_FIELDWISE_ROUTE_REREAD (force) */
+    int32_t max_blocks;           /* backward only: 0 = 4 per compute unit, else the most workgroups to launch (each walks its tiles) */
+} dctr_fieldwise_args_t;
+/* The route dctr_fieldwise_fwd takes (DCTR_FIELDWISE_ROUTE_ON_CHIP / _REREAD), or the DCTR_E_* its size checks answer. */
+int dctr_fieldwise_route(const dctr_fieldwise_args_t* args);
+int dctr_fieldwise_fwd(const dctr_fieldwise_args_t* args, void* stream);
+
+/* Backward of dctr_fieldwise_fwd; nothing is saved by the forward.  The upstream gradient is dy [B, dy_stride] (the layer), or
+ * dlogit [B] with fwd.head_w (the model: dy[b,e] = dlogit[b] * head_w[e]).  dx [B, dx_stride]: the groups' columns from dx_offset
+ * are written (accumulate = 0) or added to (1);
+ *     ds_g = dy (sum_{j != g} w_gj s_j + 2 k_g s_g),   dx_f = ds_g - 2 k_g dy x_f   for f in g.
+ * ACCUMULATED (each may be NULL): d_kernel_mf[p] += sum_{b,e} dy s_i s_j, d_kernel_fm[g] += sum_{b,e} dy (s_g^2 - q_g),
+ * d_bias_mf[e] and d_bias_fm[e] += sum_b dy[b,e], and with dlogit d_head_w[e] += sum_b dlogit[b] y[b,e] (y recomputed).  Partial sums
+ * meet per wave in shuffles and per workgroup in LDS: one atomic per workgroup and destination.  fwd.y / logit / add are ignored.
+ * Shapes whose s_g and accumulators do not fit 128 KiB of LDS answer DCTR_E_UNSUPPORTED (dctr_fieldwise_bwd_supported: 1 / 0). */
+typedef struct {
+    dctr_fieldwise_args_t fwd;
+    const float* dy;              /* NULL or [B, dy_stride] */
+    int64_t dy_stride;
+    const float* dlogit;          /* NULL or [B]; exactly one of dy / dlogit */
+    float* dx;                    /* NULL or [B, dx_stride] */
+    int64_t dx_stride;
+    int64_t dx_offset;
+    int32_t accumulate;           /* 0 | 1 */
+    int32_t reserved;             /* 0 */
+    float* d_kernel_mf;
+    float* d_kernel_fm;
+    float* d_bias_mf;
+    float* d_bias_fm;
+    float* d_head_w;              /* dlogit form only */
+} dctr_fieldwise_bwd_args_t;
+int dctr_fieldwise_bwd_supported(const dctr_fieldwise_bwd_args_t* args);
+int dctr_fieldwise_bwd(const dctr_fieldwise_bwd_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
