@@ -65,6 +65,77 @@ def _i32_array(vals):
     return arr
 
 
+def row_stride(t):
+    """Elements between consecutive rows of a 2-D tensor with unit column stride.  torch leaves the stride of a size-1 dimension
+    arbitrary (a [1, n] result of ``.t().contiguous()`` reports stride(0) = 1): a single row gets its width."""
+    return int(t.stride(0)) if t.shape[0] != 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+# The operand checks of the interaction ops' wrappers.  They raise before anything is launched and never touch the device (the one
+# _dev_check per call stays with the wrapper).
+def _rows2d(op, name, t, rows, cols, offset=0, at_least_rows=False):
+    """``t`` is a float32 2-D view with unit column stride that holds ``rows`` rows (or more, with ``at_least_rows``) and the columns
+    [offset, offset + cols).  A single column may have any column stride (torch keeps (1, n) for the [n, 1] transpose of a [1, n]
+    row).  Returns the row pitch in elements (row_stride): what the op's args struct takes as the operand's stride."""
+    shape = t.shape         # (each of these is a call into torch: one of each per operand, the wrappers are latency-bound)
+    if len(shape) == 2 and t.dtype == torch.float32 and offset >= 0:
+        (r, c), (pitch, step) = shape, t.stride()
+        if (step == 1 or c <= 1) and c >= offset + cols and (r >= rows if at_least_rows else r == rows):
+            return pitch if r != 1 else max(pitch, c)       # = row_stride(t)
+    raise ValueError("%s: %s must be a float32 [%s%d, >= %d] view with unit column stride"
+                     % (op, name, ">= " if at_least_rows else "", rows, offset + cols))
+
+
+def _vec(op, name, t, n):
+    """``t`` is a contiguous float32 tensor of ``n`` elements (any shape)."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError("%s: %s must be a contiguous float32 tensor of %d elements" % (op, name, n))
+
+
+def _x_in_place(op, x, fields, dim, x_offset=0):
+    """The input of an interaction layer: a [B,F,E] tensor (made contiguous float32), or with ``fields`` / ``dim`` the F*E columns from
+    ``x_offset`` of a float32 [B, stride] buffer read in place.  Returns (x, B, F, E, x_stride, x_offset)."""
+    if fields is None:
+        if x.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+        x = _f32c(x, "x")
+        B, F, E = x.shape
+        return x, B, F, E, F * E, 0
+    B, F, E = x.shape[0], int(fields), int(dim)
+    return x, B, F, E, _rows2d(op, "x (with fields / dim)", x, B, F * E, x_offset), int(x_offset)
+
+
+def _workspace(op, a, need, workspace, device):
+    """Hand the args struct ``a`` the ``need`` bytes the library asked for: the caller's tensor if it is large enough, else the
+    per-stream scratch.  Returns the tensor (None when nothing is needed)."""
+    if not need:
+        return None
+    if workspace is None:
+        workspace = _scratch(device, need)   # rewritten by every call: stream order keeps calls apart
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
+        raise ValueError("%s: workspace must be a contiguous float32 tensor of >= %d bytes" % (op, need))
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+    return workspace
+
+
+def _route_name(op, rc, names):
+    """The reply of a dctr_*_route call: a negative error code, or the index of the route in ``names``."""
+    rc = int(rc)
+    if rc < 0:
+        _C.check(rc, op)
+    return names[rc]
+
+
+def _upload(arr, device):
+    """A ctypes array of descriptors as a uint8 device tensor (kept alive by the caller)."""
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def _id_stride(ids):
+    """Elements between consecutive ids of a 1-D view (the stride of a single element is arbitrary)."""
+    return int(ids.stride(0)) if ids.shape[0] != 1 else 1
+
+
 # ---------------------------------------------------------------------------------------------
 # a2 Hash
 # ---------------------------------------------------------------------------------------------
@@ -275,13 +346,7 @@ def make_field_descriptors(fields, device):
         arr[j].hash_mode = int(f.get("hash_mode", 0))
         arr[j].identity = int(bool(f.get("identity", False)))
         arr[j].row_pitch = int(f.get("row_pitch", 0))
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-
-
-def row_stride(t):
-    """Elements between consecutive rows of a 2-D tensor with unit column stride.  torch leaves the stride of a size-1 dimension
-    arbitrary (a [1, n] result of ``.t().contiguous()`` reports stride(0) = 1): a single row gets its width."""
-    return int(t.stride(0)) if t.shape[0] != 1 else max(int(t.stride(0)), int(t.shape[1]))
+    return _upload(arr, device)
 
 
 def make_gather_args(desc, n_fields, ids, ids_stride_f, ids_stride_b, batch, max_dim, all_dim4, any_hash,
@@ -323,7 +388,7 @@ def make_pool_seqs(seqs, device):
     for i, (ids, length, combiner) in enumerate(seqs):
         arr[i].idx, arr[i].length = ids.data_ptr(), (None if length is None else length.data_ptr())
         arr[i].idx_stride, arr[i].maxlen, arr[i].combiner = ids.stride(0), ids.shape[1], _C.POOL_CODES[combiner]
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return _upload(arr, device)
 
 
 def embed_gather_fm(*args, **kwargs):
@@ -427,14 +492,7 @@ def cin(x, filters, biases, layer_size, split_half=True, activation="relu", fiel
     float32 tensor of ``cin_workspace_bytes`` for the fold (default: the per-stream scratch, rewritten by every call);
     ``workspace_ready``: it still holds an earlier call's fold of the same filter values (no fold launch)."""
     _dev_check(x, *filters, *biases)
-    if fields is None:
-        if x.dim() != 3:
-            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
-        x = _f32c(x, "x")
-        B, F0, D = x.shape
-        x_stride = F0 * D
-    else:
-        B, F0, D, x_stride = x.shape[0], fields, dim, x.stride(0)
+    x, B, F0, D, x_stride, _ = _x_in_place("cin", x, fields, dim)
     n = len(layer_size)
     filters = [_f32c(f, "filter").reshape(-1, h) for f, h in zip(filters, layer_size)]
     biases = [_f32c(b, "bias") for b in biases]
@@ -568,24 +626,12 @@ def interacting(x, weights, att_embedding_size, head_num, use_res, scaling, fiel
     possibly strided view; allocated when neither ``out`` nor ``head_w`` is given) and / or, with ``head_w`` [F*d*H(, 1)], the Dense(1)
     over it to ``logit`` [B].  ``workspace``: a float32 tensor of >= interacting_workspace_bytes (default: the per-stream scratch).
     Returns ``out`` (or ``logit`` when only the head is asked for)."""
-    if fields is None:
-        if x.dim() != 3:
-            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        x_stride = F * E
-    else:
-        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
-            raise ValueError("interacting: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
-        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
+    x, B, F, E, x_stride, _ = _x_in_place("interacting", x, fields, dim)
     weights = [[None if w is None else _f32c(w, "weight") for w in layer] for layer in weights]
     _dev_check(x, out, logit, head_w, *[w for layer in weights for w in layer])
     dH = int(att_embedding_size) * int(head_num)
     if head_w is None and out is None:
         out = torch.empty(B, F * dH, dtype=torch.float32, device=x.device)
-    if out is not None and (out.dim() != 2 or out.stride(1) != 1 or out.dtype != torch.float32 or out.shape[0] != B
-                            or out.shape[1] < F * dH):
-        raise ValueError("interacting: out must be a float32 [%d, >= %d] view with unit column stride" % (B, F * dH))
     if head_w is not None:
         head_w = _f32c(head_w, "head_w").reshape(-1)
         if head_w.numel() != F * dH:
@@ -595,18 +641,10 @@ def interacting(x, weights, att_embedding_size, head_num, use_res, scaling, fiel
     a, keep = _interacting_args(B, F, E, x_stride, weights, att_embedding_size, head_num, use_res, scaling)
     a.x = x.data_ptr()
     if out is not None:
-        a.out, a.out_stride = out.data_ptr(), out.stride(0)
+        a.out, a.out_stride = out.data_ptr(), _rows2d("interacting", "out", out, B, F * dH)
     if head_w is not None:
         a.head_w, a.logit = head_w.data_ptr(), logit.data_ptr()
-    need = int(_C.lib().dctr_interacting_workspace_bytes(ctypes.byref(a)))
-    if need:
-        if workspace is not None:
-            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
-                raise ValueError("interacting: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
-            ws = workspace
-        else:
-            ws = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _workspace("interacting", a, int(_C.lib().dctr_interacting_workspace_bytes(ctypes.byref(a))), workspace, x.device)
     _C.check(_C.lib().dctr_interacting_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_interacting_fwd")
     del keep
     return out if out is not None else logit
@@ -665,16 +703,7 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
       * ``bilinear_w`` alone: out [B, >= P*E] = the bilinear interaction over x.
     ``out`` is a 2-D (possibly strided) view, allocated when not given; ``workspace``: a float32 tensor of
     >= senet_bilinear_workspace_bytes (default: the per-stream scratch).  Returns ``out``."""
-    if fields is None:
-        if x.dim() != 3:
-            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        x_stride = F * E
-    else:
-        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
-            raise ValueError("senet_bilinear: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
-        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
+    x, B, F, E, x_stride, _ = _x_in_place("senet_bilinear", x, fields, dim)
     if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
         mode = _C.bilinear.MODE_MODEL
     elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
@@ -708,9 +737,7 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
     width = senet_bilinear_width(F, E, mode, dense_cols)
     if out is None:
         out = torch.empty(B, width, dtype=torch.float32, device=x.device)
-    if out.dim() != 2 or out.stride(1) != 1 or out.dtype != torch.float32 or out.shape[0] != B or out.shape[1] < width:
-        raise ValueError("senet_bilinear: out must be a float32 [%d, >= %d] view with unit column stride" % (B, width))
-    a = _bilinear_args(B, F, E, x_stride, bilinear_type, mode, max(r, 1), dense_cols, out.stride(0))
+    a = _bilinear_args(B, F, E, x_stride, bilinear_type, mode, max(r, 1), dense_cols, _rows2d("senet_bilinear", "out", out, B, width))
     a.x, a.out = x.data_ptr(), out.data_ptr()
     if senet_w is not None:
         a.senet_w1, a.senet_w2 = w1.data_ptr(), w2.data_ptr()
@@ -718,15 +745,7 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
         a.senet_bilinear_w = tables[0].data_ptr()
     if tables[1] is not None:
         a.bilinear_w = tables[1].data_ptr()
-    need = int(_C.lib().dctr_bilinear_workspace_bytes(ctypes.byref(a)))
-    if need:
-        if workspace is not None:
-            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
-                raise ValueError("senet_bilinear: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
-            ws_t = workspace
-        else:
-            ws_t = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
-        a.workspace, a.workspace_bytes = ws_t.data_ptr(), ws_t.numel() * 4
+    _workspace("senet_bilinear", a, int(_C.lib().dctr_bilinear_workspace_bytes(ctypes.byref(a))), workspace, x.device)
     _C.check(_C.lib().dctr_bilinear_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_bilinear_fwd")
     return out
 
@@ -759,18 +778,7 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
     the per-stream scratch).  Returns (pairs, logit), None for an output not asked for."""
     if kind not in _FIELDPAIR_KINDS:
         raise ValueError("fieldpair: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
-    if fields is None:
-        if x.dim() != 3:
-            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        x_stride, x_offset = F * E, 0
-    else:
-        if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
-            raise ValueError("fieldpair: with fields / dim, x must be a float32 [B, stride] buffer with unit column stride")
-        B, F, E, x_stride = x.shape[0], int(fields), int(dim), x.stride(0)
-        if x_offset < 0 or x_offset + F * E > x.shape[1]:
-            raise ValueError("fieldpair: columns [%d, %d) are not inside x [%d, %d]" % (x_offset, x_offset + F * E, B, x.shape[1]))
+    x, B, F, E, x_stride, x_offset = _x_in_place("fieldpair", x, fields, dim, x_offset)
     if F < 2:
         raise ValueError("fieldpair: %d field(s): a field pair needs at least 2" % F)
     P = F * (F - 1) // 2
@@ -797,11 +805,9 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
         pairs, pairs_offset = torch.empty(B, P, dtype=torch.float32, device=x.device), 0
     if logit is True:
         logit = torch.empty(B, dtype=torch.float32, device=x.device)
-    if pairs is not None and (pairs.dim() != 2 or pairs.stride(1) != 1 or pairs.dtype != torch.float32 or pairs.shape[0] != B
-                              or pairs_offset < 0 or pairs.shape[1] < pairs_offset + P):
-        raise ValueError("fieldpair: pairs must be a float32 [%d, >= %d] view with unit column stride" % (B, pairs_offset + P))
-    if logit is not None and (logit.dtype != torch.float32 or not logit.is_contiguous() or logit.numel() != B):
-        raise ValueError("fieldpair: logit must be a contiguous float32 tensor of %d elements" % B)
+    pairs_stride = 0 if pairs is None else _rows2d("fieldpair", "pairs", pairs, B, P, pairs_offset)
+    if logit is not None:
+        _vec("fieldpair", "logit", logit, B)
     if add is not None:
         if logit is None:
             raise ValueError("fieldpair: add needs a logit output")
@@ -812,20 +818,12 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
     a = _fieldpair_args(_FIELDPAIR_KINDS[kind], B, F, E, x_stride, x_offset)
     a.x, a.weights = x.data_ptr(), wptr.data_ptr()
     if pairs is not None:
-        a.pairs_out, a.pairs_stride, a.pairs_offset = pairs.data_ptr(), pairs.stride(0), int(pairs_offset)
+        a.pairs_out, a.pairs_stride, a.pairs_offset = pairs.data_ptr(), pairs_stride, int(pairs_offset)
     if logit is not None:
         a.logit_out = logit.data_ptr()
     if add is not None:
         a.add = add.data_ptr()
-    need = int(_C.lib().dctr_fieldpair_workspace_bytes(ctypes.byref(a)))
-    if need:
-        if workspace is not None:
-            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
-                raise ValueError("fieldpair: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
-            ws_t = workspace
-        else:
-            ws_t = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
-        a.workspace, a.workspace_bytes = ws_t.data_ptr(), ws_t.numel() * 4
+    _workspace("fieldpair", a, int(_C.lib().dctr_fieldpair_workspace_bytes(ctypes.byref(a))), workspace, x.device)
     _C.check(_C.lib().dctr_fieldpair_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_fieldpair_fwd")
     return pairs, logit
 
@@ -854,10 +852,7 @@ def ffm_workspace_bytes(batch, fields, dim, reduce_sum=False, route=None):
 def ffm_route(batch, fields, dim, reduce_sum=False, route=None):
     """'lds' or 'direct': the route dctr_ffm_fwd takes for these shapes (the library's answer, dctr_ffm_route)."""
     a = _ffm_args(batch, fields, dim, reduce_sum, route=route)
-    rc = int(_C.lib().dctr_ffm_route(ctypes.byref(a)))
-    if rc < 0:
-        _C.check(rc, "dctr_ffm_route")
-    return {_C.ffm.ROUTE_LDS: "lds", _C.ffm.ROUTE_DIRECT: "direct"}[rc]
+    return _route_name("dctr_ffm_route", _C.lib().dctr_ffm_route(ctypes.byref(a)), {_C.ffm.ROUTE_LDS: "lds", _C.ffm.ROUTE_DIRECT: "direct"})
 
 
 def make_ffm_fields(fields, device):
@@ -873,9 +868,9 @@ def make_ffm_fields(fields, device):
             arr[j].identity = 1
         else:
             arr[j].ids = ids.data_ptr()
-            arr[j].ids_stride = int(ids.stride(0)) if ids.shape[0] != 1 else 1
+            arr[j].ids_stride = _id_stride(ids)
             arr[j].ids_is_i64 = int(ids.dtype == torch.int64)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return _upload(arr, device)
 
 
 def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None, reduce_sum=False, out=None, out_offset=0,
@@ -925,12 +920,8 @@ def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None
     P = F * (F - 1) // 2
     W = P if reduce_sum else P * dim
     if dense is not None:
-        # (a single column's stride is arbitrary: torch keeps (1, n) for the [n, 1] transpose of a staged [1, n] row)
-        if dense.dim() != 2 or dense.dtype != torch.float32 or (dense.shape[1] > 1 and dense.stride(1) != 1) or dense.shape[0] < B:
-            raise ValueError("ffm: dense must be a float32 [B, n] matrix with unit column stride")
-        n_dense = int(dense.shape[1]) if n_dense is None else int(n_dense)
-        if n_dense > dense.shape[1]:
-            raise ValueError("ffm: n_dense %d > %d dense columns" % (n_dense, dense.shape[1]))
+        n_dense = int(dense.shape[-1] if n_dense is None else n_dense)
+        dense_stride = _rows2d("ffm", "dense", dense, B, n_dense, at_least_rows=True)
     else:
         n_dense = 0
     if (scale is None) != (shift is None):
@@ -942,16 +933,14 @@ def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None
     width = W + n_dense
     if out is None:
         out = torch.empty(B, (out_offset + width + 3) // 4 * 4, dtype=torch.float32, device=desc.device)
-    if (out.dim() != 2 or out.dtype != torch.float32 or out.stride(1) != 1 or out.shape[0] < B or out_offset < 0
-            or out.shape[1] < out_offset + width):
-        raise ValueError("ffm: out must be a float32 [%d, >= %d] view with unit column stride" % (B, out_offset + width))
+    out_stride = _rows2d("ffm", "out", out, B, width, out_offset, at_least_rows=True)
     _dev_check(desc, scale, shift, dense, out, status)
-    a = _ffm_args(B, F, dim, reduce_sum, n_dense, route, out_stride=row_stride(out), out_offset=out_offset)
+    a = _ffm_args(B, F, dim, reduce_sum, n_dense, route, out_stride=out_stride, out_offset=out_offset)
     a.fields, a.out = desc.data_ptr(), out.data_ptr()
     if scale is not None:
         a.scale, a.shift = scale.data_ptr(), shift.data_ptr()
     if n_dense:
-        a.dense, a.dense_stride = dense.data_ptr(), row_stride(dense)
+        a.dense, a.dense_stride = dense.data_ptr(), dense_stride
     if status is not None:
         a.status = status.data_ptr()
     _C.check(_C.lib().dctr_ffm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_ffm_fwd")
@@ -985,10 +974,7 @@ def ifm_workspace_bytes(batch, fields, dim, n_src=1, route=None):
 def ifm_route(batch, fields, dim, n_src=1, route=None):
     """'lds' or 'workspace': the route dctr_ifm_fwd takes for these shapes (the library's answer, dctr_ifm_route)."""
     a = _ifm_args(batch, fields, dim, n_src, route)
-    rc = int(_C.lib().dctr_ifm_route(ctypes.byref(a)))
-    if rc < 0:
-        _C.check(rc, "dctr_ifm_route")
-    return {_C.ifm.ROUTE_LDS: "lds", _C.ifm.ROUTE_WORKSPACE: "workspace"}[rc]
+    return _route_name("dctr_ifm_route", _C.lib().dctr_ifm_route(ctypes.byref(a)), {_C.ifm.ROUTE_LDS: "lds", _C.ifm.ROUTE_WORKSPACE: "workspace"})
 
 
 def make_ifm_lin(terms, batch, device):
@@ -1006,14 +992,14 @@ def make_ifm_lin(terms, batch, device):
             _dev_check(table, ids)
             arr[k].table, arr[k].vocab = table.data_ptr(), int(table.shape[0])
             arr[k].ids, arr[k].ids_is_i64 = ids.data_ptr(), int(ids.dtype == torch.int64)
-            arr[k].ids_stride = int(ids.stride(0)) if ids.shape[0] != 1 else 1
+            arr[k].ids_stride = _id_stride(ids)
         else:
             if t.dtype != torch.float32 or t.numel() != t.shape[0] or t.shape[0] < batch:
                 raise ValueError("ifm: linear term %d: a pre-pooled term must be a float32 [B] or [B, 1] tensor of >= %d rows" % (k, batch))
             _dev_check(t)
             arr[k].vec = t.data_ptr()
             arr[k].vec_stride = int(t.stride(0)) if t.shape[0] != 1 else 1
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return _upload(arr, device)
 
 
 def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), global_bias=None, sigmoid_out=False, out=None,
@@ -1027,29 +1013,24 @@ def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), 
     through a sigmoid with ``sigmoid_out``.  ``factor_out`` [B, >= fields]: receives m.  ``route='workspace'`` forces the route whose
     m' goes through HBM; ``workspace``: a float32 tensor of >= ifm_workspace_bytes (default: the per-stream scratch)."""
     F, d = int(fields), int(dim)
-    if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1) or x.shape[1] < F * d:
-        raise ValueError("ifm: x must be a float32 [B, >= %d] buffer with unit column stride" % (F * d))
     B = int(x.shape[0])
+    x_stride = _rows2d("ifm", "x", x, B, F * d)
     sources = list(sources)
     a = _ifm_args(B, F, d, len(sources), route)
-    a.x, a.x_stride = x.data_ptr(), row_stride(x)
+    a.x, a.x_stride = x.data_ptr(), x_stride
     keep = []
     for s, (act, kernel) in enumerate(sources):
-        if act.dim() != 2 or act.dtype != torch.float32 or (act.shape[1] > 1 and act.stride(1) != 1) or act.shape[0] != B:
-            raise ValueError("ifm: source %d: act must be a float32 [%d, K] matrix with unit column stride" % (s, B))
+        act_stride = _rows2d("ifm", "a source's act", act, B, 1)
         K = int(act.shape[1])
-        if K < 1 or kernel.dtype != torch.float32 or tuple(kernel.shape) != (K, F):
+        if kernel.dtype != torch.float32 or tuple(kernel.shape) != (K, F):
             raise ValueError("ifm: source %d: kernel must be float32 [%d, %d], got %s" % (s, K, F, tuple(kernel.shape)))
         kernel = _f32c(kernel, "kernel")
         keep.append(kernel)
-        a.src[s].act, a.src[s].act_stride, a.src[s].K, a.src[s].kernel = act.data_ptr(), row_stride(act), K, kernel.data_ptr()
+        a.src[s].act, a.src[s].act_stride, a.src[s].K, a.src[s].kernel = act.data_ptr(), act_stride, K, kernel.data_ptr()
     if mprime is None and not sources:
         raise ValueError("ifm: neither a factor source nor mprime")
     if mprime is not None:
-        if mprime.dim() != 2 or mprime.dtype != torch.float32 or (mprime.shape[1] > 1 and mprime.stride(1) != 1) \
-                or mprime.shape[0] != B or mprime.shape[1] < F:
-            raise ValueError("ifm: mprime must be a float32 [%d, >= %d] matrix with unit column stride" % (B, F))
-        a.mprime, a.mprime_stride = mprime.data_ptr(), row_stride(mprime)
+        a.mprime, a.mprime_stride = mprime.data_ptr(), _rows2d("ifm", "mprime", mprime, B, F)
     n_lin = len(lin)
     if n_lin not in (0, F):
         raise ValueError("ifm: %d linear terms for %d fields: the factor refines them by position, 0 or one per field" % (n_lin, F))
@@ -1061,8 +1042,7 @@ def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), 
     if len(add) > 4:
         raise ValueError("ifm: %d add vectors: at most 4" % len(add))
     for i, t in enumerate(add):
-        if t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous():
-            raise ValueError("ifm: add[%d] must be a contiguous float32 vector of %d elements" % (i, B))
+        _vec("ifm", "an add vector", t, B)
         a.add[i] = t.data_ptr()
     a.n_add = len(add)
     if global_bias is not None:
@@ -1071,28 +1051,16 @@ def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), 
         a.global_bias = global_bias.data_ptr()
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=x.device)
-    if out.dtype != torch.float32 or out.numel() != B or not out.is_contiguous():
-        raise ValueError("ifm: out must be a contiguous float32 vector of %d elements" % B)
+    _vec("ifm", "out", out, B)
     if factor_out is not None:
-        if factor_out.dim() != 2 or factor_out.dtype != torch.float32 or (factor_out.shape[1] > 1 and factor_out.stride(1) != 1) \
-                or factor_out.shape[0] != B or factor_out.shape[1] < F:
-            raise ValueError("ifm: factor_out must be a float32 [%d, >= %d] matrix with unit column stride" % (B, F))
-        a.factor_out, a.factor_stride = factor_out.data_ptr(), row_stride(factor_out)
+        a.factor_out, a.factor_stride = factor_out.data_ptr(), _rows2d("ifm", "factor_out", factor_out, B, F)
     if status is not None:
         if status.dtype != torch.int32:
             raise ValueError("ifm: status must be an int32 tensor")
         a.status = status.data_ptr()
     _dev_check(x, mprime, lin_desc, global_bias, out, factor_out, status, workspace, *(add + keep + [s_[0] for s_ in sources]))
     a.softmax, a.sigmoid_out, a.out = int(bool(softmax)), int(bool(sigmoid_out)), out.data_ptr()
-    need = int(_C.lib().dctr_ifm_workspace_bytes(ctypes.byref(a)))
-    if need:
-        if workspace is not None:
-            if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < need:
-                raise ValueError("ifm: workspace must be a contiguous float32 tensor of >= %d bytes" % need)
-            ws = workspace
-        else:
-            ws = _scratch(x.device, need)   # rewritten by every call: stream order keeps calls apart
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    _workspace("ifm", a, int(_C.lib().dctr_ifm_workspace_bytes(ctypes.byref(a))), workspace, x.device)
     _C.check(_C.lib().dctr_ifm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_ifm_fwd")
     del keep
     return out
@@ -1118,7 +1086,7 @@ def fieldwise_groups(groups, device):
     return hit
 
 
-def _fieldwise_args(x, groups, dim, x_offset, route, device=None):
+def _fieldwise_args(x, groups, dim, x_offset, route, device=None, x_stride=0):
     if route not in _FIELDWISE_ROUTES:
         raise ValueError("fieldwise: route %r: expected None, 'auto' or 'reread'" % (route,))
     groups = list(groups)
@@ -1129,7 +1097,7 @@ def _fieldwise_args(x, groups, dim, x_offset, route, device=None):
     if dev_t is not None:
         a.groups = dev_t.data_ptr()
     if x is not None:
-        a.batch, a.x, a.x_stride = x.shape[0], x.data_ptr(), x.stride(0)
+        a.batch, a.x, a.x_stride = x.shape[0], x.data_ptr(), x_stride
     else:
         a.x_stride = int(x_offset) + max([f + n * int(dim) for f, n in groups] + [0])
     return a, keep
@@ -1138,9 +1106,8 @@ def _fieldwise_args(x, groups, dim, x_offset, route, device=None):
 def fieldwise_route(groups, dim, route=None):
     """The route dctr_fieldwise_fwd takes for these shapes: 'on_chip' (the group sums wait in LDS) or 'reread' (read from the library)."""
     a, _keep = _fieldwise_args(None, groups, dim, 0, route)
-    rc = int(_C.lib().dctr_fieldwise_route(ctypes.byref(a)))
-    _C.check(min(rc, 0), "dctr_fieldwise_route")
-    return {_C.fieldwise.ROUTE_ON_CHIP: "on_chip", _C.fieldwise.ROUTE_REREAD: "reread"}[rc]
+    return _route_name("dctr_fieldwise_route", _C.lib().dctr_fieldwise_route(ctypes.byref(a)),
+                       {_C.fieldwise.ROUTE_ON_CHIP: "on_chip", _C.fieldwise.ROUTE_REREAD: "reread"})
 
 
 def fieldwise_bwd_supported(groups, dim):
@@ -1150,12 +1117,15 @@ def fieldwise_bwd_supported(groups, dim):
     return bool(_C.lib().dctr_fieldwise_bwd_supported(ctypes.byref(b)))
 
 
-def _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm):
-    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
-        raise ValueError("fieldwise: x must be a float32 [B, stride] buffer with unit column stride")
+def _fieldwise_operands(op, x, x_offset, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm):
+    """The checks fieldwise() and fieldwise_bwd() share: (x's row pitch, the columns the groups span, the weights made contiguous)."""
     G = len(groups)
     if G < 2:
         raise ValueError("A `Field-Wise Bi-Interaction` layer should be called on a list of at least 2 inputs")
+    if min(f for f, _ in groups) < 0:
+        raise ValueError("%s: a group starts before column 0" % op)
+    span = max(f + n * dim for f, n in groups)
+    x_stride = _rows2d(op, "x", x, x.shape[0], span, x_offset)
     kernel_mf, kernel_fm = _f32c(kernel_mf, "kernel_mf"), _f32c(kernel_fm, "kernel_fm")
     if kernel_mf.numel() != G * (G - 1) // 2 or kernel_fm.numel() != G:
         raise ValueError("fieldwise: %d groups take kernel_mf [%d, 1] and kernel_fm [%d, 1]" % (G, G * (G - 1) // 2, G))
@@ -1165,7 +1135,7 @@ def _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm):
         bias_mf, bias_fm = _f32c(bias_mf, "bias_mf"), _f32c(bias_fm, "bias_fm")
         if bias_mf.numel() != dim or bias_fm.numel() != dim:
             raise ValueError("fieldwise: the biases hold dim = %d elements" % dim)
-    return kernel_mf, kernel_fm, bias_mf, bias_fm
+    return x_stride, span, kernel_mf, kernel_fm, bias_mf, bias_fm
 
 
 def fieldwise(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, x_offset=0, y=None, y_offset=0, head_w=None,
@@ -1176,7 +1146,8 @@ def fieldwise(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, 
     from column ``y_offset``; ``logit``: True or a float32 [B] tensor = y . head_w (+ ``add`` [B]).  Default: y.  Returns (y, logit)."""
     dim = int(dim)
     groups = [(int(a), int(n)) for a, n in groups]
-    kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm)
+    x_stride, _, kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands("fieldwise", x, x_offset, groups, dim, kernel_mf, kernel_fm,
+                                                                              bias_mf, bias_fm)
     B = x.shape[0]
     if y is None and logit is None:
         y = True
@@ -1184,12 +1155,9 @@ def fieldwise(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, 
         y, y_offset = torch.empty(B, dim, dtype=torch.float32, device=x.device), 0
     if logit is True:
         logit = torch.empty(B, dtype=torch.float32, device=x.device)
-    if y is not None and (y.dim() != 2 or y.stride(1) != 1 or y.dtype != torch.float32 or y.shape[0] != B or y_offset < 0
-                          or y.shape[1] < y_offset + dim):
-        raise ValueError("fieldwise: y must be a float32 [%d, >= %d] view with unit column stride" % (B, y_offset + dim))
+    y_stride = 0 if y is None else _rows2d("fieldwise", "y", y, B, dim, y_offset)
     if logit is not None:
-        if logit.dtype != torch.float32 or not logit.is_contiguous() or logit.numel() != B:
-            raise ValueError("fieldwise: logit must be a contiguous float32 tensor of %d elements" % B)
+        _vec("fieldwise", "logit", logit, B)
         if head_w is None:
             raise ValueError("fieldwise: a logit needs head_w [dim]")
         head_w = _f32c(head_w, "head_w")
@@ -1202,14 +1170,12 @@ def fieldwise(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=None, 
         if add.numel() != B:
             raise ValueError("fieldwise: add must hold %d elements" % B)
     _dev_check(x, kernel_mf, kernel_fm, bias_mf, bias_fm, y, head_w, add, logit)
-    a, _keep = _fieldwise_args(x, groups, dim, x_offset, route, x.device)
-    if any(x_offset + f + n * dim > x.shape[1] or f < 0 for f, n in groups) or x_offset < 0:
-        raise ValueError("fieldwise: a group's columns are not inside x [%d, %d]" % (B, x.shape[1]))
+    a, _keep = _fieldwise_args(x, groups, dim, x_offset, route, x.device, x_stride)
     a.kernel_mf, a.kernel_fm = kernel_mf.data_ptr(), kernel_fm.data_ptr()
     if bias_mf is not None:
         a.bias_mf, a.bias_fm = bias_mf.data_ptr(), bias_fm.data_ptr()
     if y is not None:
-        a.y, a.y_stride, a.y_offset = y.data_ptr(), y.stride(0), int(y_offset)
+        a.y, a.y_stride, a.y_offset = y.data_ptr(), y_stride, int(y_offset)
     if logit is not None:
         a.logit, a.head_w = logit.data_ptr(), head_w.data_ptr()
     if add is not None:
@@ -1226,42 +1192,39 @@ def fieldwise_bwd(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=No
     weight gradients (shapes of the weights; ``d_head_w`` with dlogit only) are ACCUMULATED; any may be None."""
     dim = int(dim)
     groups = [(int(a), int(n)) for a, n in groups]
-    kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands(x, groups, dim, kernel_mf, kernel_fm, bias_mf, bias_fm)
+    x_stride, span, kernel_mf, kernel_fm, bias_mf, bias_fm = _fieldwise_operands("fieldwise_bwd", x, x_offset, groups, dim, kernel_mf,
+                                                                                 kernel_fm, bias_mf, bias_fm)
     B = x.shape[0]
     if (dy is None) == (dlogit is None):
         raise ValueError("fieldwise_bwd: exactly one of dy / dlogit")
-    if dy is not None and (dy.dim() != 2 or dy.stride(1) != 1 or dy.dtype != torch.float32 or dy.shape[0] != B or dy.shape[1] < dim):
-        raise ValueError("fieldwise_bwd: dy must be a float32 [%d, >= %d] view with unit column stride" % (B, dim))
-    if dlogit is not None:
-        if dlogit.dtype != torch.float32 or not dlogit.is_contiguous() or dlogit.numel() != B:
-            raise ValueError("fieldwise_bwd: dlogit must be a contiguous float32 tensor of %d elements" % B)
-        if head_w is None or head_w.dtype != torch.float32 or not head_w.is_contiguous() or head_w.numel() != dim:
-            raise ValueError("fieldwise_bwd: dlogit needs a contiguous float32 head_w of dim = %d elements" % dim)
-    elif d_head_w is not None:
-        raise ValueError("fieldwise_bwd: d_head_w needs the dlogit form")
-    if dx is not None and (dx.dim() != 2 or dx.stride(1) != 1 or dx.dtype != torch.float32 or dx.shape[0] != B or dx_offset < 0
-                           or any(dx_offset + f + n * dim > dx.shape[1] for f, n in groups)):
-        raise ValueError("fieldwise_bwd: dx must be a float32 [%d, stride] view that holds every group's columns" % B)
+    if dy is not None:
+        dy_stride = _rows2d("fieldwise_bwd", "dy", dy, B, dim)
+        if d_head_w is not None:
+            raise ValueError("fieldwise_bwd: d_head_w needs the dlogit form")
+    else:
+        _vec("fieldwise_bwd", "dlogit", dlogit, B)
+        if head_w is None:
+            raise ValueError("fieldwise_bwd: dlogit needs head_w [dim]")
+        _vec("fieldwise_bwd", "head_w", head_w, dim)
+    dx_stride = 0 if dx is None else _rows2d("fieldwise_bwd", "dx", dx, B, span, dx_offset)
     G = len(groups)
     for t, n, name in ((d_kernel_mf, G * (G - 1) // 2, "d_kernel_mf"), (d_kernel_fm, G, "d_kernel_fm"), (d_bias_mf, dim, "d_bias_mf"),
                        (d_bias_fm, dim, "d_bias_fm"), (d_head_w, dim, "d_head_w")):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
-            raise ValueError("fieldwise_bwd: %s must be a contiguous float32 tensor of %d elements" % (name, n))
-    if any(x_offset + f + n * dim > x.shape[1] or f < 0 for f, n in groups) or x_offset < 0:
-        raise ValueError("fieldwise_bwd: a group's columns are not inside x [%d, %d]" % (B, x.shape[1]))
+        if t is not None:
+            _vec("fieldwise_bwd", name, t, n)
     _dev_check(x, kernel_mf, kernel_fm, bias_mf, bias_fm, dy, dlogit, head_w, dx, d_kernel_mf, d_kernel_fm, d_bias_mf, d_bias_fm, d_head_w)
     b = _C.fieldwise.BwdArgs()
-    b.fwd, _keep = _fieldwise_args(x, groups, dim, x_offset, None, x.device)
+    b.fwd, _keep = _fieldwise_args(x, groups, dim, x_offset, None, x.device, x_stride)
     f = b.fwd
     f.kernel_mf, f.kernel_fm, f.max_blocks = kernel_mf.data_ptr(), kernel_fm.data_ptr(), int(max_blocks)
     if bias_mf is not None:
         f.bias_mf, f.bias_fm = bias_mf.data_ptr(), bias_fm.data_ptr()
     if dy is not None:
-        b.dy, b.dy_stride = dy.data_ptr(), dy.stride(0)
+        b.dy, b.dy_stride = dy.data_ptr(), dy_stride
     else:
         b.dlogit, f.head_w = dlogit.data_ptr(), head_w.data_ptr()
     if dx is not None:
-        b.dx, b.dx_stride, b.dx_offset, b.accumulate = dx.data_ptr(), dx.stride(0), int(dx_offset), int(bool(accumulate))
+        b.dx, b.dx_stride, b.dx_offset, b.accumulate = dx.data_ptr(), dx_stride, int(dx_offset), int(bool(accumulate))
     for name, t in (("d_kernel_mf", d_kernel_mf), ("d_kernel_fm", d_kernel_fm), ("d_bias_mf", d_bias_mf), ("d_bias_fm", d_bias_fm),
                     ("d_head_w", d_head_w)):
         if t is not None:
@@ -1273,12 +1236,7 @@ def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, di
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""
     _dev_check(x, attention_W, attention_b, projection_h, projection_p)
-    if fields is None:
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        stride = F * E
-    else:
-        B, F, E, stride = x.shape[0], int(fields), int(dim), x.stride(0)
+    x, B, F, E, stride, _ = _x_in_place("afm", x, fields, dim)
     A = attention_W.shape[1]
     y = torch.empty(B, 1, dtype=torch.float32, device=x.device) if out is None else out
     _C.check(_C.lib().dctr_afm_fwd(_ptr(x), B, stride, F, E, _ptr(_f32c(attention_W, "W")), _ptr(_f32c(attention_b, "b")),
@@ -1329,14 +1287,7 @@ def bi_interaction(x, fields=None, dim=None, out=None):
     """BiInteractionPooling.call (reference interaction.py:190-203): x [B,F,E] -> [B,1,E]; with ``fields``/``dim`` x is a
     2-D buffer read in place and ``out`` a 2-D (strided) view to write [B,E] into."""
     _dev_check(x)
-    if fields is None:
-        if x.dim() != 3:
-            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        xs = F * E
-    else:
-        B, F, E, xs = x.shape[0], int(fields), int(dim), x.stride(0)
+    x, B, F, E, xs, _ = _x_in_place("bi_interaction", x, fields, dim)
     if out is None:
         y = torch.empty(B, 1, E, dtype=torch.float32, device=x.device)
         ys = E
@@ -1350,12 +1301,7 @@ def inner_product(x, reduce_sum=True, fields=None, dim=None, out=None):
     """InnerProductLayer.call (reference interaction.py:655-678): x [B,F,E] -> [B,P,1] or [B,P,E].
     With ``fields``/``dim`` x is a 2-D buffer read in place; ``out`` may be a 2-D (strided) view to write into."""
     _dev_check(x)
-    if fields is None:
-        x = _f32c(x, "x")
-        B, F, E = x.shape
-        xs = F * E
-    else:
-        B, F, E, xs = x.shape[0], int(fields), int(dim), x.stride(0)
+    x, B, F, E, xs, _ = _x_in_place("inner_product", x, fields, dim)
     P = F * (F - 1) // 2
     if out is None:
         y = torch.empty(B, P, 1 if reduce_sum else E, dtype=torch.float32, device=x.device)
@@ -1890,7 +1836,7 @@ def make_adam_segments(params, device):
                 raise ValueError("touched: uint8 [n / 4] beside a parameter of n %% 4 == 0 elements")
             arr[i].touched = tch.data_ptr()
         mx = max(mx, w.numel())
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), len(params), mx
+    return _upload(arr, device), len(params), mx
 
 
 def adam_multi(segs, n_segs, max_n, alpha, beta1=0.9, beta2=0.999, eps=1e-7, zero_grad=True):
@@ -1972,12 +1918,7 @@ def cin_bwd(x, filters, biases, layer_size, split_half, activation, d_out, d_fil
     """Backward of dctr_cin_fwd: x as in ``cin`` (3-D, or the leading F0*D columns of a 2-D buffer with fields/dim);
     d_out [B, featuremap_num]; d_filters / d_biases are ACCUMULATED; dx (2-D, same layout as x) written or added to."""
     _dev_check(x, d_out, *filters)
-    if fields is None:
-        x = _f32c(x, "x")
-        B, F0, D = x.shape
-        x_stride = F0 * D
-    else:
-        B, F0, D, x_stride = x.shape[0], fields, dim, x.stride(0)
+    x, B, F0, D, x_stride, _ = _x_in_place("cin_bwd", x, fields, dim)
     n = len(layer_size)
     filters = [_f32c(f, "filter").reshape(-1, h) for f, h in zip(filters, layer_size)]
     biases = [_f32c(b, "bias") for b in biases]
