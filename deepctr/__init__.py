@@ -20,7 +20,7 @@ __version__ = "0.9.4"           # API level of the reference this build mirrors 
 _ALIASES = (
     "feature_column", "inputs",
     "layers", "layers.activation", "layers.core", "layers.interaction", "layers.sequence", "layers.utils",
-    "models", "models.afm", "models.autoint", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.fibinet",
+    "models", "models.afm", "models.autoint", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.edcn", "models.fibinet",
     "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
     "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.din",
 )

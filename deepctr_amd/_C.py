@@ -218,6 +218,22 @@ fieldwise.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
     ("d_bias_mf", c_vp), ("d_bias_fm", c_vp), ("d_head_w", c_vp)]})
 
 
+class edcn(object):
+    """dctr_edcn_args_t, one level down for the same reason as interacting.Args (tests/test_edcn_cpu.py checks the layout)."""
+    BRIDGE_ADD, BRIDGE_HADAMARD, BRIDGE_CONCAT, BRIDGE_ATTENTION = 0, 1, 2, 3
+    BRIDGES = {"pointwise_addition": BRIDGE_ADD, "hadamard_product": BRIDGE_HADAMARD, "concatenation": BRIDGE_CONCAT,
+               "attention_pooling": BRIDGE_ATTENTION}
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_LAYERED = 0, 1, 2
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_offset", c_i64), ("fields", c_i32), ("dim", c_i32),
+                    ("cross_num", c_i32), ("mode", c_i32), ("bridge", c_i32), ("activation", c_i32), ("bridge_activation", c_i32),
+                    ("inv_tau", c_f32), ("gates", c_vp), ("cross_w", c_vp), ("cross_b", c_vp), ("dnn_w", c_vp), ("dnn_b", c_vp),
+                    ("bn_scale", c_vp), ("bn_shift", c_vp), ("bridge_w", c_vp), ("bridge_b", c_vp), ("head_w", c_vp), ("add", c_vp * 4),
+                    ("global_bias", c_vp), ("sigmoid_out", c_i32), ("route", c_i32), ("logit", c_vp), ("out", c_vp), ("out_stride", c_i64),
+                    ("out_offset", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -316,6 +332,11 @@ SYMBOLS = {
     "dctr_fieldwise_fwd": (ctypes.c_int, [ctypes.POINTER(fieldwise.Args), c_vp]),
     "dctr_fieldwise_bwd_supported": (ctypes.c_int, [ctypes.POINTER(fieldwise.BwdArgs)]),
     "dctr_fieldwise_bwd": (ctypes.c_int, [ctypes.POINTER(fieldwise.BwdArgs), c_vp]),
+    "dctr_edcn_workspace_bytes": (c_sz, [ctypes.POINTER(edcn.Args)]),
+    "dctr_edcn_route": (ctypes.c_int, [ctypes.POINTER(edcn.Args)]),
+    "dctr_edcn_fwd": (ctypes.c_int, [ctypes.POINTER(edcn.Args), c_vp]),
+    "dctr_edcn_regulate": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "dctr_edcn_bridge": (ctypes.c_int, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "dctr_host_pack_columns": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32]),
     "dctr_crossnet_mix_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

@@ -53,6 +53,7 @@ SOURCES = [
     "ffm_kernels.hip",
     "ifm_kernels.hip",
     "fieldwise_kernels.hip",
+    "edcn_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -2,8 +2,8 @@
 ``custom_objects`` registry; the subset below is what DeepFM / DCN / xDeepFM / DIN and the AFM / PNN
 siblings need — SURVEY.md §8a)."""
 from .activation import Dice
-from .core import DNN, Dense, LocalActivationUnit, PredictionLayer
-from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
+from .core import DNN, Dense, LocalActivationUnit, PredictionLayer, RegulationModule
+from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, BridgeModule, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
                           FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
 from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
@@ -24,6 +24,8 @@ custom_objects = {
     'FwFMLayer': FwFMLayer,
     'FEFMLayer': FEFMLayer,
     'FieldWiseBiInteraction': FieldWiseBiInteraction,
+    'BridgeModule': BridgeModule,
+    'RegulationModule': RegulationModule,
     'LocalActivationUnit': LocalActivationUnit,
     'Dice': Dice,
     'SequencePoolingLayer': SequencePoolingLayer,

@@ -1,5 +1,5 @@
 """Host mirror of the reference's ``deepctr/layers/core.py``: ``LocalActivationUnit`` (:28-120), ``DNN``
-(:123-223), ``PredictionLayer`` (:226-267).  Forward = the fused f32-MFMA MLP kernel (``dctr_mlp_fwd``):
+(:123-223), ``PredictionLayer`` (:226-267), ``RegulationModule`` (:270-321).  Forward = the fused f32-MFMA MLP kernel (``dctr_mlp_fwd``):
 all layers, bias, activation/Dice in one launch; models additionally fuse the Dense(1) head, the extra
 logits and the PredictionLayer into the same launch."""
 import torch
@@ -300,3 +300,44 @@ class PredictionLayer(Layer):
         config = {'task': self.task, 'use_bias': self.use_bias}
         base = super(PredictionLayer, self).get_config()
         return dict(list(base.items()) + list(config.items()))
+
+
+class RegulationModule(Layer):
+    """Regulation module of EDCN (reference core.py:270-321): a field-wise gate, softmax over the fields of the F weights ``g`` / tau,
+    scales every embedding; [B, F, E] -> [B, F * E].  One ``dctr_edcn_regulate`` launch."""
+
+    def __init__(self, tau=1.0, **kwargs):
+        if tau == 0:
+            raise ValueError("RegulationModule tau can not be zero.")
+        self.tau = 1.0 / tau                    # (as the reference keeps it: the reciprocal)
+        self._tau = tau
+        super(RegulationModule, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        self.build_for(int(input_shape[1]), int(input_shape[2]))
+
+    def build_for(self, field_size, embedding_size):
+        if not self.built:
+            self.field_size, self.embedding_size = int(field_size), int(embedding_size)
+            self.add_weight(self.name + '_field_weight', (1, self.field_size, 1), Ones())
+            self.built = True
+        return self
+
+    @property
+    def g(self):
+        return self.w(self.name + '_field_weight')
+
+    def call(self, inputs, **kwargs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        return ops.edcn_regulate(inputs, self.g, tau=self._tau)[0]
+
+    def compute_output_shape(self, input_shape):
+        return (None, self.field_size * self.embedding_size)
+
+    def get_config(self):
+        base = super(RegulationModule, self).get_config()
+        base.update({'tau': self.tau})
+        return base

@@ -648,3 +648,71 @@ class InnerProductLayer(Layer):
         base = super(InnerProductLayer, self).get_config()
         base.update(config)
         return base
+
+
+class BridgeModule(Layer):
+    """Bridge module of EDCN (reference interaction.py:1502-1565): [x, h], two [B, D] tensors -> [B, D] by 'pointwise_addition',
+    'hadamard_product', 'concatenation' (a Dense(D, activation) over [x, h]) or 'attention_pooling' (softmax-DNN(x) * x +
+    softmax-DNN(h) * h, two DNN([D, D], activation, output_activation='softmax')).  As in the reference an unknown ``bridge_type``
+    builds no weights; here it is refused when the layer is called (the reference returns None)."""
+    TYPES = ("pointwise_addition", "hadamard_product", "concatenation", "attention_pooling")
+
+    def __init__(self, bridge_type='hadamard_product', activation='relu', **kwargs):
+        self.bridge_type = bridge_type
+        self.activation = activation
+        super(BridgeModule, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if not isinstance(input_shape, list) or len(input_shape) < 2:
+            raise ValueError('A `BridgeModule` layer should be called on a list of 2 inputs')
+        self.build_for(int(input_shape[0][-1]))
+
+    def build_for(self, dnn_dim):
+        if self.built:
+            return self
+        from .core import DNN, Dense
+        self.dnn_dim = D = int(dnn_dim)
+        self.dense = self.dense_x = self.dense_h = None
+        if self.bridge_type == "concatenation":
+            if self.activation not in ("relu", "sigmoid", "tanh", "linear", None):
+                raise ValueError("BridgeModule: the Dense of 'concatenation' takes relu / sigmoid / tanh / linear, got %r" % (self.activation,))
+            self.dense = Dense(D, device=self.device).build_for(2 * D)
+            self._sublayers.append(self.dense)
+        elif self.bridge_type == "attention_pooling":
+            # (the softmax of the last layer is the bridge kernel's: the DNNs end linear here and keep the reference's names)
+            self.dense_x = DNN([D, D], self.activation, device=self.device).build_for(D)
+            self.dense_h = DNN([D, D], self.activation, device=self.device).build_for(D)
+            self._sublayers += [self.dense_x, self.dense_h]
+        self.built = True
+        return self
+
+    def weights_for_op(self):
+        """This round's ``bridge_weights`` entry of ops.edcn (None for the weightless bridges)."""
+        if self.bridge_type == "concatenation":
+            return (self.dense.w('kernel'), self.dense.w('bias'))
+        if self.bridge_type == "attention_pooling":
+            return tuple((dn.w('kernel0'), dn.w('bias0'), dn.w('kernel1'), dn.w('bias1')) for dn in (self.dense_x, self.dense_h))
+        return None
+
+    def call(self, inputs, **kwargs):
+        x, h = inputs
+        if self.bridge_type not in self.TYPES:
+            raise ValueError("BridgeModule: unknown bridge_type %r" % (self.bridge_type,))
+        if self.bridge_type == "concatenation":
+            return ops.mlp(torch.cat([x, h], dim=-1), [self.dense.w('kernel')], [self.dense.w('bias')], self.activation or "linear")
+        if self.bridge_type == "attention_pooling":
+            ax, ah = (self._scores(dn, t) for dn, t in ((self.dense_x, x), (self.dense_h, h)))
+            return ops.edcn_bridge(x.contiguous(), h.contiguous(), self.bridge_type, ax=ax, ah=ah)
+        return ops.edcn_bridge(x.contiguous(), h.contiguous(), self.bridge_type)
+
+    def _scores(self, dn, t):
+        hid = ops.mlp(t, [dn.w('kernel0')], [dn.w('bias0')], dn.activation, dice=None if not dn.dice_layers else [dn.dice_layers[0].params()])
+        return ops.mlp(hid, [dn.w('kernel1')], [dn.w('bias1')], "linear")
+
+    def compute_output_shape(self, input_shape):
+        return (None, self.dnn_dim)
+
+    def get_config(self):
+        base = super(BridgeModule, self).get_config()
+        base.update({'bridge_type': self.bridge_type, 'activation': self.activation})
+        return base

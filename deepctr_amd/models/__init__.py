@@ -3,7 +3,7 @@ BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN,
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
 SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel,
 IFM and DIFM the input-aware FM kernel, FLEN the field-wise bi-interaction kernel and its backward: the first of these to train on
-the HIP step)."""
+the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modules)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -11,6 +11,7 @@ from .dcnmix import DCNMix
 from .deepfefm import DeepFEFM
 from .deepfm import DeepFM
 from .difm import DIFM
+from .edcn import EDCN
 from .fibinet import FiBiNET
 from .flen import FLEN
 from .fnn import FNN

@@ -1232,6 +1232,255 @@ def fieldwise_bwd(x, groups, dim, kernel_mf, kernel_fm, bias_mf=None, bias_fm=No
     _C.check(_C.lib().dctr_fieldwise_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_fieldwise_bwd")
 
 
+_EDCN_ROUTES = {None: _C.edcn.ROUTE_AUTO, "auto": _C.edcn.ROUTE_AUTO, "layered": _C.edcn.ROUTE_LAYERED}
+_EDCN_ROUTE_NAMES = {_C.edcn.ROUTE_FUSED: "fused", _C.edcn.ROUTE_LAYERED: "layered"}
+_EDCN_GEMM_K = 768              # reduction length of one dctr_sgemm call of the layered route's wide matrix cross (_edcn_cross)
+
+
+def _edcn_args(batch, fields, dim, cross_num, bridge_type, parameterization, tau, activation, bridge_activation, route, x_stride=None,
+               x_offset=0):
+    if bridge_type not in _C.edcn.BRIDGES:
+        raise ValueError("edcn: bridge_type %r: expected one of %s" % (bridge_type, sorted(_C.edcn.BRIDGES)))
+    if parameterization not in ("vector", "matrix"):
+        raise ValueError("parameterization should be 'vector' or 'matrix'")
+    if route not in _EDCN_ROUTES:
+        raise ValueError("edcn: route %r: expected None, 'auto' or 'layered'" % (route,))
+    if tau == 0:
+        raise ValueError("RegulationModule tau can not be zero.")
+    if cross_num < 1:
+        raise ValueError("Cross layer num must > 0")
+    if activation not in _C.ACT_CODES or bridge_activation not in _C.ACT_CODES:
+        raise ValueError("edcn: unknown activation %r / %r" % (activation, bridge_activation))
+    D = int(fields) * int(dim)
+    return _C.edcn.Args(batch=int(batch), x_stride=int(x_offset) + D if x_stride is None else int(x_stride), x_offset=int(x_offset),
+                        fields=int(fields), dim=int(dim), cross_num=int(cross_num),
+                        mode=_C.CROSS_VECTOR if parameterization == "vector" else _C.CROSS_MATRIX, bridge=_C.edcn.BRIDGES[bridge_type],
+                        activation=_C.ACT_CODES[activation], bridge_activation=_C.ACT_CODES[bridge_activation], inv_tau=1.0 / tau,
+                        route=_EDCN_ROUTES[route])
+
+
+def edcn_route(fields, dim, cross_num=1, bridge_type="hadamard_product", parameterization="vector", activation="relu",
+               bridge_activation="relu", route=None):
+    """The route ops.edcn takes for these shapes and options: 'fused' (one dctr_edcn_fwd launch, the tiles in LDS) or 'layered' (read
+    from the library: it knows what its LDS holds)."""
+    a = _edcn_args(0, fields, dim, cross_num, bridge_type, parameterization, 1.0, activation, bridge_activation, route)
+    return _route_name("dctr_edcn_route", _C.lib().dctr_edcn_route(ctypes.byref(a)), _EDCN_ROUTE_NAMES)
+
+
+def edcn_regulate(x, g_deep, g_cross=None, tau=1.0, fields=None, dim=None, x_offset=0, deep=None, cross=None):
+    """RegulationModule.call (reference core.py:304-312) over one read of x, for one or two gates: x [B,F,E], or with ``fields`` /
+    ``dim`` the F*E columns from ``x_offset`` of a 2-D buffer; g_* hold F live weights.  ``deep`` / ``cross``: float32 2-D views to write
+    [B, F*E] into (default: new tensors).  Returns (deep, cross); cross is None without g_cross."""
+    if tau == 0:
+        raise ValueError("RegulationModule tau can not be zero.")
+    x, B, F, E, x_stride, x_offset = _x_in_place("edcn_regulate", x, fields, dim, x_offset)
+    D = F * E
+    _vec("edcn_regulate", "g_deep", g_deep, F)
+    if g_cross is not None:
+        _vec("edcn_regulate", "g_cross", g_cross, F)
+    elif cross is not None:
+        raise ValueError("edcn_regulate: a cross output needs g_cross")
+    if deep is None:
+        deep = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    if cross is None and g_cross is not None:
+        cross = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    deep_stride = _rows2d("edcn_regulate", "deep", deep, B, D)
+    cross_stride = 0 if cross is None else _rows2d("edcn_regulate", "cross", cross, B, D)
+    _dev_check(x, g_deep, g_cross, deep, cross)
+    _C.check(_C.lib().dctr_edcn_regulate(x.data_ptr() + 4 * x_offset, x_stride, B, F, E, _ptr(g_deep), _ptr(g_cross), 1.0 / tau, _ptr(deep),
+                                         deep_stride, _ptr(cross), cross_stride, _C.stream_ptr()), "dctr_edcn_regulate")
+    return deep, cross
+
+
+def edcn_bridge(c, h, bridge_type, ax=None, ah=None, out=None):
+    """BridgeModule.call's elementwise forms (reference interaction.py:1542-1553) on float32 2-D views [B, D]: 'pointwise_addition',
+    'hadamard_product', or 'attention_pooling' = softmax(ax) * c + softmax(ah) * h with ``ax`` / ``ah`` the scores before the softmax
+    over the row.  ('concatenation' is a Dense: ops.mlp.)"""
+    if bridge_type not in ("pointwise_addition", "hadamard_product", "attention_pooling"):
+        raise ValueError("edcn_bridge: bridge_type %r is no elementwise bridge" % (bridge_type,))
+    if c.dim() != 2:
+        raise ValueError("edcn_bridge: c must be a float32 [B, D] view with unit column stride")
+    B, D = c.shape
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=c.device)
+    strides = [_rows2d("edcn_bridge", n, t, B, D) for n, t in (("c", c), ("h", h), ("out", out))]
+    att = [0, 0]
+    if bridge_type == "attention_pooling":
+        if ax is None or ah is None:
+            raise ValueError("edcn_bridge: attention_pooling needs the scores ax and ah")
+        att = [_rows2d("edcn_bridge", n, t, B, D) for n, t in (("ax", ax), ("ah", ah))]
+    else:
+        ax = ah = None
+    _dev_check(c, h, ax, ah, out)
+    _C.check(_C.lib().dctr_edcn_bridge(_C.edcn.BRIDGES[bridge_type], _ptr(c), strides[0], _ptr(h), strides[1], _ptr(ax), att[0], _ptr(ah),
+                                       att[1], B, D, _ptr(out), strides[2], _C.stream_ptr()), "dctr_edcn_bridge")
+    return out
+
+
+def _edcn_cross(xc, w, b, mode, y):
+    """One CrossNet layer whose x_0 is its input: dctr_crossnet_head_fwd with layers = 1, or — a matrix wider than its tiles hold —
+    dctr_sgemm + dctr_crossnet_matrix_step.  xc [B, D] contiguous; y: a [B, D] view."""
+    B, D = xc.shape
+    st = _C.stream_ptr()
+    need = int(_C.lib().dctr_crossnet_workspace_bytes(D, 1, mode, _ptr(w)))
+    ws = _scratch(xc.device, need) if need else None
+    a = _C.CrossnetArgs(x=xc.data_ptr(), batch=B, x_stride=D, dim=D, layers=1, mode=mode, workspace_ready=0, kernels=w.data_ptr(),
+                        bias=b.data_ptr(), y=y.data_ptr(), y_stride=row_stride(y), workspace=_ptr(ws), workspace_bytes=need)
+    rc = _C.lib().dctr_crossnet_head_fwd(ctypes.byref(a), st)
+    if rc == _C.E_UNSUPPORTED and mode == _C.CROSS_MATRIX:
+        u = torch.empty(B, D, dtype=torch.float32, device=xc.device)
+        # column-major BLAS view: u^T (D x B) = W^T-view (k x n)^T . xc^T (k x B).  dctr_sgemm cuts a reduction of >= 1024 over
+        # workgroups that add with float atomics when the output has few tiles: slices of k below that, accumulated call after call
+        # (beta = 1), keep the forward free of atomics — the same bits on every call
+        for k0 in range(0, D, _EDCN_GEMM_K):
+            _C.check(_C.lib().dctr_sgemm(1, 0, D, B, min(_EDCN_GEMM_K, D - k0), w.data_ptr() + 4 * k0, D, 0, xc.data_ptr() + 4 * k0, D, 0,
+                                         0.0 if k0 == 0 else 1.0, u.data_ptr(), D, 0, 1, st), "dctr_sgemm")
+        rc = _C.lib().dctr_crossnet_matrix_step(xc.data_ptr(), D, xc.data_ptr(), D, u.data_ptr(), b.data_ptr(), B, D, y.data_ptr(),
+                                                row_stride(y), st)
+        _C.check(rc, "dctr_crossnet_matrix_step")
+        return
+    _C.check(rc, "dctr_crossnet_head_fwd")
+
+
+def _edcn_layered(x, B, F, E, x_offset, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, bridge_type, mode, tau, activation,
+                  bn, dice, bridge_weights, bridge_activation, head_w, add, global_bias, sigmoid_out, logit, out, out_offset):
+    """The tower layer by layer on the existing entry points: per round one regulate launch, the CrossNet layer, the DNN, the bridge."""
+    D, L, dev = F * E, len(dnn_kernels), x.device
+    stack = torch.empty(B, 3 * D, dtype=torch.float32, device=dev) if out is None else out[:, out_offset:out_offset + 3 * D]
+    c, h, br = stack[:, :D], stack[:, D:2 * D], stack[:, 2 * D:]
+    deep = torch.empty(B, D, dtype=torch.float32, device=dev)
+    cross = torch.empty(B, D, dtype=torch.float32, device=dev)
+    att = bridge_type == "attention_pooling"
+    if att:
+        ax, ah = (torch.empty(B, D, dtype=torch.float32, device=dev) for _ in range(2))
+    src, src_off = x, x_offset
+    for i in range(L):
+        edcn_regulate(src, gates[2 * i], gates[2 * i + 1], tau, fields=F, dim=E, x_offset=src_off, deep=deep, cross=cross)
+        _edcn_cross(cross, cross_kernels[i], cross_biases[i], mode, c)
+        mlp(deep, [dnn_kernels[i]], [dnn_biases[i]], activation, dice=None if dice is None else [dice[i]],
+            bn=None if bn is None else [bn[i]], in_dim=D, out=h)
+        if bridge_type == "concatenation":
+            wb, bb = bridge_weights[i]
+            mlp(stack, [wb], [bb], bridge_activation, in_dim=2 * D, out=br)
+        elif att:
+            for src_t, (k0, b0, k1, b1), dst in ((c, bridge_weights[i][0], ax), (h, bridge_weights[i][1], ah)):
+                hid = mlp(src_t, [k0], [b0], bridge_activation, in_dim=D)
+                mlp(hid, [k1], [b1], "linear", in_dim=D, out=dst)
+            edcn_bridge(c, h, bridge_type, ax=ax, ah=ah, out=br)
+        else:
+            edcn_bridge(c, h, bridge_type, out=br)
+        src, src_off = br, 0
+    if logit is not None:
+        mlp(stack, [], [], "linear", head_w=head_w, add=add, global_bias=global_bias, sigmoid_out=sigmoid_out, in_dim=3 * D, out=logit)
+
+
+def edcn(x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, bridge_type="hadamard_product",
+         parameterization="vector", tau=1.0, activation="relu", bn=None, dice=None, bridge_weights=None, bridge_activation="relu",
+         x_offset=0, head_w=None, add=(), global_bias=None, sigmoid_out=False, logit=None, out=None, out_offset=0, route=None,
+         workspace=None):
+    """EDCN's tower (reference models/edcn.py:66-87; include/dctr.h: dctr_edcn_fwd).  x: a float32 [B, stride] buffer whose ``fields``
+    * ``dim`` columns from ``x_offset`` are read in place.  Per round i (cross_num = len(dnn_kernels)): ``gates[2i]`` / ``gates[2i+1]``
+    the F field weights of the deep / cross RegulationModule, ``cross_kernels[i]`` [D, 1] or [D, D] with ``cross_biases[i]`` [D, 1],
+    ``dnn_kernels[i]`` [D, D] with ``dnn_biases[i]`` [D], ``bn[i]`` None or (scale, shift), ``dice[i]`` (alpha, mean, variance) with
+    activation 'dice', ``bridge_weights[i]``: (kernel [2D, D], bias [D]) for 'concatenation', ((k0, b0, k1, b1) of the DNN over c,
+    the same over h) for 'attention_pooling'.  All weights are the live tensors.
+    Outputs: ``logit`` (True or a float32 [B] tensor) = [c, h, br] . head_w + sum(add) + global_bias (sigmoid with sigmoid_out);
+    ``out`` (True or a float32 2-D view) receives c, h, br of the last round in columns [out_offset, out_offset + 3D).  Default: the
+    logit with head_w, else out.  One launch where ops.edcn_route says 'fused', else layer by layer.  Returns (logit, out)."""
+    x, B, F, E, x_stride, x_offset = _x_in_place("edcn", x, int(fields), int(dim), x_offset)
+    D, L = F * E, len(dnn_kernels)
+    a = _edcn_args(B, F, E, L, bridge_type, parameterization, tau, activation, bridge_activation, route, x_stride, x_offset)
+    if not (len(gates) == 2 * L and len(cross_kernels) == len(cross_biases) == len(dnn_biases) == L):
+        raise ValueError("edcn: %d rounds take %d gates and %d of every other weight" % (L, 2 * L, L))
+    for k, g in enumerate(gates):
+        _vec("edcn", "gates[%d]" % k, g, F)
+    for i in range(L):
+        _vec("edcn", "cross_kernels[%d]" % i, cross_kernels[i], D if parameterization == "vector" else D * D)
+        _vec("edcn", "cross_biases[%d]" % i, cross_biases[i], D)
+        _vec("edcn", "dnn_kernels[%d]" % i, dnn_kernels[i], D * D)
+        _vec("edcn", "dnn_biases[%d]" % i, dnn_biases[i], D)
+    flat = list(gates) + list(cross_kernels) + list(cross_biases) + list(dnn_kernels) + list(dnn_biases)
+    if bn is not None:
+        if len(bn) != L:
+            raise ValueError("edcn: bn holds one entry (None or (scale, shift)) per round")
+        for i, sb in enumerate(bn):
+            if sb is not None:
+                _vec("edcn", "bn[%d] scale" % i, sb[0], D)
+                _vec("edcn", "bn[%d] shift" % i, sb[1], D)
+                flat += list(sb)
+        if all(sb is None for sb in bn):
+            bn = None
+    if activation in ("dice", "Dice"):
+        if dice is None or len(dice) != L:
+            raise ValueError("edcn: activation 'dice' takes dice = [(alpha, moving_mean, moving_variance)] per round")
+        for i, dp in enumerate(dice):
+            for t in dp:
+                _vec("edcn", "dice[%d]" % i, t, D)
+            flat += list(dp)
+    else:
+        dice = None
+    if bridge_type in ("concatenation", "attention_pooling"):
+        if bridge_weights is None or len(bridge_weights) != L:
+            raise ValueError("edcn: bridge_type %r takes bridge_weights per round" % bridge_type)
+        for i, bw in enumerate(bridge_weights):
+            if bridge_type == "concatenation":
+                _vec("edcn", "bridge_weights[%d] kernel" % i, bw[0], 2 * D * D)
+                _vec("edcn", "bridge_weights[%d] bias" % i, bw[1], D)
+                flat += list(bw)
+            else:
+                for half in bw:
+                    for j, t in enumerate(half):
+                        _vec("edcn", "bridge_weights[%d]" % i, t, D if j % 2 else D * D)
+                    flat += list(half)
+    if logit is None and out is None:
+        logit, out = (True, None) if head_w is not None else (None, True)
+    if logit is True:
+        logit = torch.empty(B, dtype=torch.float32, device=x.device)
+    if out is True:
+        out, out_offset = torch.empty(B, 3 * D, dtype=torch.float32, device=x.device), 0
+    add = [t for t in add if t is not None]
+    if logit is not None:
+        _vec("edcn", "logit", logit, B)
+        if head_w is None:
+            raise ValueError("edcn: a logit needs head_w [3 * fields * dim]")
+        _vec("edcn", "head_w", head_w, 3 * D)
+        if len(add) > 4:
+            raise ValueError("edcn: at most four logits to add")
+        for t in add:
+            _vec("edcn", "add", t, B)
+        if global_bias is not None:
+            _vec("edcn", "global_bias", global_bias, 1)
+    elif add or global_bias is not None or sigmoid_out:
+        raise ValueError("edcn: add / global_bias / sigmoid_out need a logit output")
+    out_stride = 0 if out is None else _rows2d("edcn", "out", out, B, 3 * D, out_offset)
+    _dev_check(x, head_w, global_bias, logit, out, *(flat + add))
+    lib = _C.lib()
+    if _route_name("dctr_edcn_route", lib.dctr_edcn_route(ctypes.byref(a)), _EDCN_ROUTE_NAMES) == "layered":
+        _edcn_layered(x, B, F, E, x_offset, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, bridge_type, a.mode, tau, activation,
+                      bn, dice, bridge_weights, bridge_activation, head_w, add, global_bias, sigmoid_out, logit, out, out_offset)
+        return logit, out
+    keep = [_ptr_array(ts) for ts in (gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases)]
+    a.x = x.data_ptr()
+    a.gates, a.cross_w, a.cross_b, a.dnn_w, a.dnn_b = (ctypes.cast(p, ctypes.c_void_p) for p in keep)
+    if bn is not None:
+        keep += [_ptr_array([None if sb is None else sb[j] for sb in bn]) for j in range(2)]
+        a.bn_scale, a.bn_shift = (ctypes.cast(p, ctypes.c_void_p) for p in keep[-2:])
+    if bridge_type == "concatenation":
+        keep += [_ptr_array([bw[j] for bw in bridge_weights]) for j in range(2)]
+        a.bridge_w, a.bridge_b = (ctypes.cast(p, ctypes.c_void_p) for p in keep[-2:])
+    if logit is not None:
+        a.logit, a.head_w, a.sigmoid_out = logit.data_ptr(), head_w.data_ptr(), int(bool(sigmoid_out))
+        for i, t in enumerate(add):
+            a.add[i] = t.data_ptr()
+        if global_bias is not None:
+            a.global_bias = global_bias.data_ptr()
+    if out is not None:
+        a.out, a.out_stride, a.out_offset = out.data_ptr(), out_stride, int(out_offset)
+    _keep_ws = _workspace("edcn", a, int(lib.dctr_edcn_workspace_bytes(ctypes.byref(a))), workspace, x.device)
+    _C.check(lib.dctr_edcn_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_edcn_fwd")
+    return logit, out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -225,8 +225,13 @@ def regularized_weights(model):
     if dnn is not None:
         for k in dnn.kernels:
             add(k, reg.get("dnn", 0.0))
-    cross = getattr(model, "cross", None)
-    if cross is not None:
+    for dnn in getattr(model, "dnn_layers", None) or []:          # EDCN: one DNN and one CrossNet per round (edcn.py:75-78)
+        for k in dnn.kernels:
+            add(k, reg.get("dnn", 0.0))
+    crosses = list(getattr(model, "cross_layers", None) or [])
+    if getattr(model, "cross", None) is not None:
+        crosses.append(model.cross)
+    for cross in crosses:
         for name, t in cross._weights.items():
             if name.startswith(("kernel", "U_list", "V_list", "C_list")):
                 add(t, reg.get("cross", 0.0))

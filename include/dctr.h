@@ -690,6 +690,79 @@ int dctr_fieldwise_bwd_supported(const dctr_fieldwise_bwd_args_t* args);
 int dctr_fieldwise_bwd(const dctr_fieldwise_bwd_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * EDCN's tower — deepctr/models/edcn.py:66-87 with RegulationModule (layers/core.py:270-321) and BridgeModule
+ * (layers/interaction.py:1502-1565), one launch
+ *     x [B, x_stride] read in place from column x_offset: F fields of width dim, D = F * dim.  deep = cross = x, then per round
+ *     i < cross_num:
+ *       deep  *= softmax_f(gates[2i] * inv_tau)[field of the column];  cross *= softmax_f(gates[2i+1] * inv_tau)[field of the column]
+ *       c  = cross * (cross . w_i) + b_i + cross  (DCTR_CROSS_VECTOR)  |  cross * (W_i cross + b_i) + cross  (DCTR_CROSS_MATRIX, W [out, in])
+ *       h  = act((deep Wd_i + bd_i) [* bn_scale_i + bn_shift_i])        (Wd: Keras layout [in, out])
+ *       br = c + h | c * h | bridge_act([c, h] Wb_i + bb_i)             (Wb [2D, D], Keras layout)
+ *       deep = cross = br
+ *     Outputs, either or both: logit[b] = [c, h, br] . head_w + sum(add) + global_bias (sigmoid with sigmoid_out); out [B, out_stride]:
+ *     c, h, br of the LAST round in columns [out_offset, out_offset + 3D).
+ *     The gates are computed inside the launch from the F weights the pointers show on every call; c / h / br live in LDS; the
+ *     products are exact fp32 on v_mfma_f32_16x16x4_f32.  No atomics: the same bits on every call.  More than 32 rounds are chained
+ *     launches through a workspace of dctr_edcn_workspace_bytes() that carries br (0 bytes up to 32 rounds).
+ *     The FUSED route takes the bridges ADD / HADAMARD / CONCAT with activation and bridge_activation in {LINEAR, RELU} while four
+ *     [16, pad16(D) + 4] tiles and the gates fit 160 KiB of LDS (D <= 624 at dim 16).  Everything else — wider rows, attention pooling,
+ *     other activations, route = DCTR_EDCN_ROUTE_LAYERED — answers DCTR_E_UNSUPPORTED here and DCTR_EDCN_ROUTE_LAYERED from
+ *     dctr_edcn_route: the host then runs the tower layer by layer (dctr_mlp_fwd, dctr_crossnet_head_fwd or dctr_sgemm +
+ *     dctr_crossnet_matrix_step, dctr_edcn_regulate, dctr_edcn_bridge).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_EDCN_BRIDGE_ADD = 0, DCTR_EDCN_BRIDGE_HADAMARD = 1, DCTR_EDCN_BRIDGE_CONCAT = 2, DCTR_EDCN_BRIDGE_ATTENTION = 3 };
+enum { DCTR_EDCN_ROUTE_AUTO = 0, DCTR_EDCN_ROUTE_FUSED = 1, DCTR_EDCN_ROUTE_LAYERED = 2 };
+typedef struct {
+    int64_t batch;
+    const float* x;               /* [B, x_stride] fp32 */
+    int64_t x_stride;             /* floats between rows */
+    int64_t x_offset;             /* first column of the F * dim the tower reads */
+    int32_t fields;               /* F >= 1 */
+    int32_t dim;                  /* d >= 1 */
+    int32_t cross_num;            /* rounds >= 1 */
+    int32_t mode;                 /* DCTR_CROSS_VECTOR | DCTR_CROSS_MATRIX */
+    int32_t bridge;               /* DCTR_EDCN_BRIDGE_* */
+    int32_t activation;           /* the DNNs': DCTR_ACT_* (fused: LINEAR | RELU) */
+    int32_t bridge_activation;    /* the concatenation bridge's Dense: DCTR_ACT_* (fused: LINEAR | RELU) */
+    float inv_tau;                /* 1 / tau, finite */
+    const float* const* gates;    /* HOST array [2 * cross_num] of DEVICE pointers to F floats: the deep and the cross gate of round i */
+    const float* const* cross_w;  /* HOST array [cross_num] of DEVICE pointers: [D] (vector) or [D, D] (matrix) */
+    const float* const* cross_b;  /* [cross_num] -> [D] */
+    const float* const* dnn_w;    /* [cross_num] -> [D, D] */
+    const float* const* dnn_b;    /* [cross_num] -> [D] */
+    const float* const* bn_scale; /* NULL, or [cross_num] -> [D] (entries may be NULL): inference BatchNormalization as an affine */
+    const float* const* bn_shift;
+    const float* const* bridge_w; /* DCTR_EDCN_BRIDGE_CONCAT: [cross_num] -> [2D, D] */
+    const float* const* bridge_b; /* DCTR_EDCN_BRIDGE_CONCAT: [cross_num] -> [D] */
+    const float* head_w;          /* [3D]; REQUIRED with logit */
+    const float* add[4];          /* NULL or [B] each */
+    const float* global_bias;     /* NULL or a device scalar */
+    int32_t sigmoid_out;          /* 0 | 1 */
+    int32_t route;                /* DCTR_EDCN_ROUTE_AUTO | DCTR_EDCN_ROUTE_LAYERED (the query answers LAYERED, dctr_edcn_fwd declines) */
+    float* logit;                 /* NULL or [B] */
+    float* out;                   /* NULL, or [B, out_stride]: columns [out_offset, out_offset + 3D) written */
+    int64_t out_stride;
+    int64_t out_offset;
+    void* workspace;              /* NULL, or device scratch of dctr_edcn_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_edcn_args_t;
+/* Bytes dctr_edcn_fwd needs (batch, fields, dim, cross_num and what decides the route are read): 0 up to 32 rounds. */
+size_t dctr_edcn_workspace_bytes(const dctr_edcn_args_t* args);
+/* The route these arguments take (DCTR_EDCN_ROUTE_FUSED / _LAYERED), or the DCTR_E_* the size checks answer.  Pointers are not
+ * looked at. */
+int dctr_edcn_route(const dctr_edcn_args_t* args);
+int dctr_edcn_fwd(const dctr_edcn_args_t* args, void* stream);
+/* RegulationModule over one read of x [B, x_stride] (F fields of width dim): deep = x * softmax_f(g_deep * inv_tau)[field],
+ * cross = x * softmax_f(g_cross * inv_tau)[field].  Either output (with its weights) may be NULL. */
+int dctr_edcn_regulate(const float* x, int64_t x_stride, int64_t batch, int32_t fields, int32_t dim, const float* g_deep,
+                       const float* g_cross, float inv_tau, float* deep, int64_t deep_stride, float* cross, int64_t cross_stride,
+                       void* stream);
+/* BridgeModule's elementwise forms over rows of dim columns: DCTR_EDCN_BRIDGE_ADD c + h, _HADAMARD c * h, _ATTENTION
+ * softmax(ax) * c + softmax(ah) * h with the softmaxes over the dim columns of a row (ax / ah: the scores BEFORE the softmax). */
+int dctr_edcn_bridge(int32_t kind, const float* c, int64_t c_stride, const float* h, int64_t h_stride, const float* ax, int64_t ax_stride,
+                     const float* ah, int64_t ah_stride, int64_t batch, int32_t dim, float* out, int64_t out_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
