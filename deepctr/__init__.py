@@ -23,6 +23,7 @@ _ALIASES = (
     "models", "models.afm", "models.autoint", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.edcn", "models.fibinet",
     "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
     "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.din",
+    "models.multitask", "models.multitask.esmm", "models.multitask.mmoe", "models.multitask.ple", "models.multitask.sharedbottom",
 )
 for _name in _ALIASES:
     _mod = importlib.import_module("deepctr_amd." + _name)

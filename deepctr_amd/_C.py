@@ -234,6 +234,27 @@ class edcn(object):
                     ("out_offset", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class mtl(object):
+    """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
+    layout)."""
+    LEVEL, TOWERS = 0, 1
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_LAYERED = 0, 1, 2
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_offsets", c_vp), ("n_slots", c_i32), ("in_dim", c_i32),
+                    ("n_experts", c_i32), ("n_layers", c_i32), ("units", c_vp), ("expert_src", c_vp), ("expert_w", c_vp), ("expert_b", c_vp),
+                    ("expert_bn_scale", c_vp), ("expert_bn_shift", c_vp), ("activation", c_i32), ("route", c_i32), ("n_gates", c_i32),
+                    ("n_gate_layers", c_i32), ("gate_units", c_vp), ("gate_src", c_vp), ("gate_n", c_vp), ("members", c_vp), ("gate_w", c_vp),
+                    ("gate_b", c_vp), ("gate_bn_scale", c_vp), ("gate_bn_shift", c_vp), ("gate_kernel", c_vp), ("out", c_vp),
+                    ("out_stride", c_i64), ("out_offset", c_i64), ("head_w", c_vp), ("global_bias", c_vp), ("binary", c_vp), ("esmm", c_i32),
+                    ("tile_rows", c_i32), ("probs", c_vp), ("probs_stride", c_i64)]
+
+    class MixArgs(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("h", c_vp), ("h_stride", c_i64), ("n_experts", c_i32), ("width", c_i32), ("n_gates", c_i32),
+                    ("z_dim", c_i32), ("z", c_vp), ("z_stride", c_vp), ("gate_kernel", c_vp), ("gate_n", c_vp), ("members", c_vp),
+                    ("members_dev", c_vp), ("out", c_vp), ("out_stride", c_i64), ("out_offset", c_i64)]
+
+
 class CinBwdArgs(ctypes.Structure):
     _fields_ = [("fwd", ctypes.POINTER(CinArgs)), ("d_out", c_vp), ("out_dim", c_i32), ("dx_accumulate", c_i32),
                 ("d_filters", c_vp), ("d_bias", c_vp), ("dx", c_vp), ("dx_stride", c_i64), ("workspace", c_vp),
@@ -335,6 +356,10 @@ SYMBOLS = {
     "dctr_edcn_workspace_bytes": (c_sz, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_route": (ctypes.c_int, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_fwd": (ctypes.c_int, [ctypes.POINTER(edcn.Args), c_vp]),
+    "dctr_mtl_route": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_i32]),
+    "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),
+    "dctr_mtl_towers_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),
+    "dctr_mtl_mix": (ctypes.c_int, [ctypes.POINTER(mtl.MixArgs), c_vp]),
     "dctr_edcn_regulate": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "dctr_edcn_bridge": (ctypes.c_int, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),

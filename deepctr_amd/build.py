@@ -54,6 +54,7 @@ SOURCES = [
     "ifm_kernels.hip",
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",
+    "mtl_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -3,7 +3,8 @@ BASELINE north_star scopes this build to DeepFM, DCN, xDeepFM and DIN; WDL, FNN,
 are SURVEY §8(f) rank-4 siblings on the same kernels; AutoInt adds the fused self-attention kernel, FiBiNET the fused
 SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ONN the field-aware gather + pair-product kernel,
 IFM and DIFM the input-aware FM kernel, FLEN the field-wise bi-interaction kernel and its backward: the first of these to train on
-the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modules)."""
+the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modules;
+SharedBottom, ESMM, MMOE and PLE — deepctr.models.multitask — the fused expert / gate level and tower kernels)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -17,6 +18,7 @@ from .flen import FLEN
 from .fnn import FNN
 from .fwfm import FwFM
 from .ifm import IFM
+from .multitask import ESMM, MMOE, PLE, SharedBottom
 from .nfm import NFM
 from .onn import ONN
 from .pnn import PNN

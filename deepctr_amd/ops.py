@@ -1481,6 +1481,294 @@ def edcn(x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_bi
     return logit, out
 
 
+_MTL_ROUTES = {None: _C.mtl.ROUTE_AUTO, "auto": _C.mtl.ROUTE_AUTO, "layered": _C.mtl.ROUTE_LAYERED}
+_MTL_ROUTE_NAMES = {_C.mtl.ROUTE_FUSED: "fused", _C.mtl.ROUTE_LAYERED: "layered"}
+_MTL_MEMBERS = {}               # (device, members) -> int32 device copy of a gate-member list (dctr_mtl_mix reads it on the device)
+
+
+def _i64_array(vals):
+    arr = (ctypes.c_int64 * max(1, len(vals)))()
+    for i, v in enumerate(vals):
+        arr[i] = int(v)
+    return arr
+
+
+def _mtl_options(op, activation, route):
+    if route not in _MTL_ROUTES:
+        raise ValueError("%s: route %r: expected None, 'auto' or 'layered'" % (op, route))
+    if activation not in _C.ACT_CODES:
+        raise ValueError("%s: unknown activation %r" % (op, activation))
+
+
+def _mtl_args(op, kind, batch, x_stride, x_offsets, in_dim, units, expert_src, activation, route, gate_units=(), gate_src=(), members=(),
+              esmm=False, tile_rows=0):
+    """The host side of dctr_mtl_args_t (sizes, slots, member lists): what dctr_mtl_route reads.  Returns (args, keep-alive)."""
+    _mtl_options(op, activation, route)
+    members = [[int(m) for m in ms] for ms in members]
+    keep = [_i64_array(x_offsets), _i32_array(units), _i32_array(expert_src), _i32_array(gate_units), _i32_array(gate_src),
+            _i32_array([len(ms) for ms in members]), _i32_array([m for ms in members for m in ms])]
+    cast = lambda p: ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    a = _C.mtl.Args(batch=int(batch), x_stride=int(x_stride), x_offsets=cast(keep[0]), n_slots=len(x_offsets), in_dim=int(in_dim),
+                    n_experts=len(expert_src), n_layers=len(units), units=cast(keep[1]), expert_src=cast(keep[2]),
+                    activation=_C.ACT_CODES[activation], route=_MTL_ROUTES[route], n_gates=len(members), n_gate_layers=len(gate_units),
+                    gate_units=cast(keep[3]), gate_src=cast(keep[4]), gate_n=cast(keep[5]), members=cast(keep[6]), esmm=int(bool(esmm)),
+                    tile_rows=int(tile_rows))
+    return a, keep
+
+
+def mtl_route(in_dim, units, n_experts, members=None, gate_units=(), n_slots=1, expert_src=None, gate_src=None, activation="relu",
+              towers=False, esmm=False, route=None):
+    """The route ops.mtl_level (``towers=False``: ``members`` = the gates' expert lists) or ops.mtl_towers (``towers=True``: n_experts
+    towers) takes for these shapes: 'fused' (one launch, everything in LDS) or 'layered' — the library's answer (dctr_mtl_route)."""
+    expert_src = [0] * int(n_experts) if expert_src is None else list(expert_src)
+    members = [] if towers else list(members)
+    gate_src = [0] * len(members) if gate_src is None else list(gate_src)
+    a, _keep = _mtl_args("mtl_route", _C.mtl.TOWERS if towers else _C.mtl.LEVEL, 0, int(in_dim), [0] * int(n_slots), in_dim, list(units),
+                         expert_src, activation, route, list(gate_units), gate_src, members, esmm)
+    return _route_name("dctr_mtl_route", _C.lib().dctr_mtl_route(ctypes.byref(a), _C.mtl.TOWERS if towers else _C.mtl.LEVEL),
+                       _MTL_ROUTE_NAMES)
+
+
+def _mtl_dnns(op, what, kernels, biases, bn, dice, activation, in_dim, units, flat):
+    """Checks n DNNs of the same ``units`` over ``in_dim`` columns; returns (bn, dice) with None for 'absent everywhere'."""
+    n, L = len(kernels), len(units)
+    if len(biases) != n or (bn is not None and len(bn) != n):
+        raise ValueError("%s: %s: one list of kernels, biases (and bn) per DNN" % (op, what))
+    for i in range(n):
+        if len(kernels[i]) != L or len(biases[i]) != L:
+            raise ValueError("%s: %s %d: %d layers expected" % (op, what, i, L))
+        k = in_dim
+        for l in range(L):
+            _vec(op, "%s %d kernel%d" % (what, i, l), kernels[i][l], k * units[l])
+            _vec(op, "%s %d bias%d" % (what, i, l), biases[i][l], units[l])
+            k = units[l]
+        flat += list(kernels[i]) + list(biases[i])
+        if bn is not None and bn[i] is not None:
+            if len(bn[i]) != L:
+                raise ValueError("%s: %s %d: bn holds one entry (None or (scale, shift)) per layer" % (op, what, i))
+            for l, sb in enumerate(bn[i]):
+                if sb is not None:
+                    _vec(op, "%s %d bn scale%d" % (what, i, l), sb[0], units[l])
+                    _vec(op, "%s %d bn shift%d" % (what, i, l), sb[1], units[l])
+                    flat += list(sb)
+    if bn is not None and all(b is None or all(sb is None for sb in b) for b in bn):
+        bn = None
+    if activation in ("dice", "Dice") and L:
+        if dice is None or len(dice) != n or any(len(d) != L for d in dice):
+            raise ValueError("%s: %s: activation 'dice' takes [(alpha, moving_mean, moving_variance)] per layer and DNN" % (op, what))
+        for d in dice:
+            for dp in d:
+                flat += list(dp)
+    else:
+        dice = None
+    return bn, dice
+
+
+def _mtl_dnn_ptrs(kernels, biases, bn):
+    """HOST arrays [n * L] of the device pointers (w, b, bn_scale, bn_shift; the last two None without bn)."""
+    w = _ptr_array([k for ks in kernels for k in ks])
+    b = _ptr_array([t for bs in biases for t in bs])
+    if bn is None:
+        return w, b, None, None
+    per_layer = [None if bl is None else bl[l] for ks, bl in zip(kernels, bn) for l in range(len(ks))]
+    return (w, b, _ptr_array([None if sb is None else sb[0] for sb in per_layer]),
+            _ptr_array([None if sb is None else sb[1] for sb in per_layer]))
+
+
+def mtl_mix(h, n_experts, width, z, gate_kernels, members, out=None, out_offset=0):
+    """The gated mixtures of the layered route (dctr_mtl_mix).  h: float32 [B, >= n_experts * width] view, expert e in columns
+    [e * width, + width); z: per gate a float32 [B, >= dz] view (the gate's input rows); gate_kernels[g] [dz, n_g]; members[g]: the n_g
+    expert indices the gate mixes.  out: float32 2-D view, columns [out_offset + g * width, + width) written (default: new [B, G * width]).
+    One launch for up to eight gates; any shape."""
+    op = "mtl_mix"
+    E, H, G = int(n_experts), int(width), len(gate_kernels)
+    if h.dim() != 2:
+        raise ValueError("mtl_mix: h must be a float32 [B, >= n_experts * width] view with unit column stride")
+    B = h.shape[0]
+    h_stride = _rows2d(op, "h", h, B, E * H)
+    if not (G >= 1 and len(z) == G and len(members) == G):
+        raise ValueError("mtl_mix: one input, kernel and member list per gate")
+    dz = int(gate_kernels[0].shape[0])
+    members = [[int(m) for m in ms] for ms in members]
+    z_strides = []
+    for g in range(G):
+        if not members[g]:
+            raise ValueError("mtl_mix: gate %d mixes no expert" % g)
+        if any(m < 0 or m >= E for m in members[g]):
+            raise ValueError("mtl_mix: gate %d: members %s with %d experts" % (g, members[g], E))
+        if gate_kernels[g].dim() != 2 or gate_kernels[g].shape[0] != dz:
+            raise ValueError("mtl_mix: gate_kernels[%d] must be [%d, n_g]" % (g, dz))
+        _vec(op, "gate_kernels[%d]" % g, gate_kernels[g], dz * len(members[g]))
+        z_strides.append(_rows2d(op, "z[%d]" % g, z[g], B, dz))
+    if out is None:
+        out, out_offset = torch.empty(B, G * H, dtype=torch.float32, device=h.device), 0
+    out_stride = _rows2d(op, "out", out, B, G * H, out_offset)
+    _dev_check(h, out, *(list(z) + list(gate_kernels)))
+    key = (h.device, tuple(tuple(ms) for ms in members))
+    mdev = _MTL_MEMBERS.get(key)
+    if mdev is None:
+        if len(_MTL_MEMBERS) >= 64:
+            _MTL_MEMBERS.clear()
+        mdev = _MTL_MEMBERS[key] = torch.tensor([m for ms in members for m in ms], dtype=torch.int32).to(h.device)
+    keep = [_ptr_array(list(z)), _i64_array(z_strides), _ptr_array(list(gate_kernels)), _i32_array([len(ms) for ms in members]),
+            _i32_array([m for ms in members for m in ms])]
+    cast = lambda p: ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    a = _C.mtl.MixArgs(batch=B, h=h.data_ptr(), h_stride=h_stride, n_experts=E, width=H, n_gates=G, z_dim=dz, z=cast(keep[0]),
+                       z_stride=cast(keep[1]), gate_kernel=cast(keep[2]), gate_n=cast(keep[3]), members=cast(keep[4]),
+                       members_dev=mdev.data_ptr(), out=out.data_ptr(), out_stride=out_stride, out_offset=int(out_offset))
+    _C.check(_C.lib().dctr_mtl_mix(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_mix")
+    return out
+
+
+def mtl_level(x, in_dim, x_offsets, expert_kernels, expert_biases, gate_kernels, members, expert_src=None, gate_src=None,
+              activation="relu", expert_bn=None, expert_dice=None, gate_dnn_kernels=None, gate_dnn_biases=None, gate_bn=None, gate_dice=None,
+              out=None, out_offset=0, route=None, tile_rows=0):
+    """One expert / gate level of MMOE or PLE (reference mmoe.py:63-84, ple.py:65-133; include/dctr.h: dctr_mtl_level_fwd).
+    x: a float32 [B, stride] buffer; slot s = the ``in_dim`` columns from ``x_offsets[s]``, read in place.  ``expert_kernels[e]`` /
+    ``expert_biases[e]``: the L layers of expert e (the same units for every expert) over slot ``expert_src[e]`` (default 0);
+    ``gate_kernels[g]`` [dz, n_g] over the gate's input — slot ``gate_src[g]``, or the output of the gate's DNN
+    (``gate_dnn_kernels[g]`` / ``gate_dnn_biases[g]``, the same units for every gate); ``members[g]``: the n_g experts gate g mixes.
+    ``*_bn[i][l]``: None or (scale, shift); ``*_dice[i][l]``: (alpha, moving_mean, moving_variance) with activation 'dice'.  All weights
+    are the live tensors.  Returns out: columns [out_offset + g * H, + H) of a float32 2-D view (default: a new [B, G * H]) hold
+    sum_j softmax(z_g Wg_g)[j] * h_{members[g][j]}.  One launch where ops.mtl_route says 'fused', else layer by layer."""
+    op = "mtl_level"
+    _mtl_options(op, activation, route)
+    in_dim, x_offsets = int(in_dim), [int(o) for o in x_offsets]
+    E, G = len(expert_kernels), len(gate_kernels)
+    if E < 1 or G < 1 or not x_offsets or not expert_kernels[0]:
+        raise ValueError("mtl_level: at least one slot, one expert of one layer and one gate")
+    if x.dim() != 2:
+        raise ValueError("mtl_level: x must be a float32 [B, stride] view with unit column stride")
+    B = x.shape[0]
+    if min(x_offsets) < 0:
+        raise ValueError("mtl_level: negative slot offset")
+    x_stride = _rows2d(op, "x", x, B, max(x_offsets) + in_dim)
+    units = [int(k.shape[1]) for k in expert_kernels[0]]
+    expert_src = [0] * E if expert_src is None else [int(s) for s in expert_src]
+    gate_src = [0] * G if gate_src is None else [int(s) for s in gate_src]
+    if len(expert_src) != E or len(gate_src) != G or len(members) != G:
+        raise ValueError("mtl_level: one source slot per expert and gate, one member list per gate")
+    if any(s < 0 or s >= len(x_offsets) for s in expert_src + gate_src):
+        raise ValueError("mtl_level: source slots %s / %s with %d slots" % (expert_src, gate_src, len(x_offsets)))
+    members = [[int(m) for m in ms] for ms in members]
+    for g, ms in enumerate(members):
+        if not ms:
+            raise ValueError("mtl_level: gate %d mixes no expert" % g)
+        if any(m < 0 or m >= E for m in ms):
+            raise ValueError("mtl_level: gate %d: members %s with %d experts" % (g, ms, E))
+    flat = []
+    expert_bn, expert_dice = _mtl_dnns(op, "expert", expert_kernels, expert_biases, expert_bn, expert_dice, activation, in_dim, units, flat)
+    gate_units = []
+    if gate_dnn_kernels is not None and len(gate_dnn_kernels) and len(gate_dnn_kernels[0]):
+        if len(gate_dnn_kernels) != G:
+            raise ValueError("mtl_level: one gate DNN per gate")
+        gate_units = [int(k.shape[1]) for k in gate_dnn_kernels[0]]
+        gate_bn, gate_dice = _mtl_dnns(op, "gate DNN", gate_dnn_kernels, gate_dnn_biases, gate_bn, gate_dice, activation, in_dim, gate_units,
+                                       flat)
+    else:
+        gate_dnn_kernels = gate_dnn_biases = gate_bn = gate_dice = None
+    dz, H = (gate_units[-1] if gate_units else in_dim), units[-1]
+    for g in range(G):
+        _vec(op, "gate_kernels[%d]" % g, gate_kernels[g], dz * len(members[g]))
+    if out is None:
+        out, out_offset = torch.empty(B, G * H, dtype=torch.float32, device=x.device), 0
+    out_stride = _rows2d(op, "out", out, B, G * H, out_offset)
+    _dev_check(x, out, *(flat + list(gate_kernels)))
+    a, keep = _mtl_args(op, _C.mtl.LEVEL, B, x_stride, x_offsets, in_dim, units, expert_src, activation, route, gate_units, gate_src, members,
+                        tile_rows=tile_rows)
+    lib = _C.lib()
+    if _route_name("dctr_mtl_route", lib.dctr_mtl_route(ctypes.byref(a), _C.mtl.LEVEL), _MTL_ROUTE_NAMES) == "layered":
+        slot = lambda s: x[:, x_offsets[s]:x_offsets[s] + in_dim]      # noqa: E731
+        hbuf = torch.empty(B, E * H, dtype=torch.float32, device=x.device)
+        for e in range(E):
+            mlp(slot(expert_src[e]), list(expert_kernels[e]), list(expert_biases[e]), activation, dice=None if expert_dice is None else expert_dice[e],
+                bn=None if expert_bn is None else expert_bn[e], in_dim=in_dim, out=hbuf[:, e * H:(e + 1) * H])
+        zs = []
+        for g in range(G):
+            if gate_units:
+                zs.append(mlp(slot(gate_src[g]), list(gate_dnn_kernels[g]), list(gate_dnn_biases[g]), activation,
+                              dice=None if gate_dice is None else gate_dice[g], bn=None if gate_bn is None else gate_bn[g], in_dim=in_dim))
+            else:
+                zs.append(slot(gate_src[g]))
+        return mtl_mix(hbuf, E, H, zs, gate_kernels, members, out=out, out_offset=out_offset)
+    cast = lambda p: None if p is None else ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    ptrs = list(_mtl_dnn_ptrs(expert_kernels, expert_biases, expert_bn))
+    a.x = x.data_ptr()
+    a.expert_w, a.expert_b, a.expert_bn_scale, a.expert_bn_shift = (cast(p) for p in ptrs)
+    if gate_units:
+        gp = list(_mtl_dnn_ptrs(gate_dnn_kernels, gate_dnn_biases, gate_bn))
+        a.gate_w, a.gate_b, a.gate_bn_scale, a.gate_bn_shift = (cast(p) for p in gp)
+        ptrs += gp
+    gk = _ptr_array(list(gate_kernels))
+    a.gate_kernel = cast(gk)
+    a.out, a.out_stride, a.out_offset = out.data_ptr(), out_stride, int(out_offset)
+    _C.check(lib.dctr_mtl_level_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_level_fwd")
+    del keep, ptrs, gk
+    return out
+
+
+def mtl_towers(x, in_dim, x_offsets, kernels, biases, head_ws, global_biases=None, binary=None, activation="relu", bn=None, dice=None,
+               esmm=False, out=None, route=None, tile_rows=0):
+    """All task towers (reference mmoe.py:86-94, esmm.py:52-63; include/dctr.h: dctr_mtl_towers_fwd).  Tower t reads the ``in_dim``
+    columns from ``x_offsets[t]`` of the float32 [B, stride] buffer x in place: DNN ``kernels[t]`` / ``biases[t]`` (possibly no layer,
+    the same units for every tower), . ``head_ws[t]``, + ``global_biases[t]``, the sigmoid where ``binary[t]``.  ``esmm``: two binary
+    towers, out[1] = sigmoid(l_0) * sigmoid(l_1).  Returns out, float32 [T, B] (contiguous rows).  One launch where ops.mtl_route says
+    'fused', else one ops.mlp call per tower."""
+    op = "mtl_towers"
+    _mtl_options(op, activation, route)
+    in_dim, x_offsets = int(in_dim), [int(o) for o in x_offsets]
+    T = len(head_ws)
+    if T < 1 or len(x_offsets) != T or len(kernels) != T:
+        raise ValueError("mtl_towers: one slot offset, DNN and head per tower")
+    if x.dim() != 2:
+        raise ValueError("mtl_towers: x must be a float32 [B, stride] view with unit column stride")
+    B = x.shape[0]
+    if min(x_offsets) < 0:
+        raise ValueError("mtl_towers: negative slot offset")
+    x_stride = _rows2d(op, "x", x, B, max(x_offsets) + in_dim)
+    units = [int(k.shape[1]) for k in kernels[0]]
+    binary = [True] * T if binary is None else [bool(b) for b in binary]
+    if len(binary) != T or (global_biases is not None and len(global_biases) != T):
+        raise ValueError("mtl_towers: one task type (and bias) per tower")
+    if esmm and not (T == 2 and all(binary)):
+        raise ValueError("mtl_towers: esmm takes two binary towers")
+    flat = []
+    bn, dice = _mtl_dnns(op, "tower", kernels, biases, bn, dice, activation, in_dim, units, flat)
+    last = units[-1] if units else in_dim
+    for t in range(T):
+        _vec(op, "head_ws[%d]" % t, head_ws[t], last)
+        if global_biases is not None and global_biases[t] is not None:
+            _vec(op, "global_biases[%d]" % t, global_biases[t], 1)
+    if out is None:
+        out = torch.empty(T, B, dtype=torch.float32, device=x.device)
+    if out.dim() != 2 or out.shape[0] != T or out.shape[1] != B or out.dtype != torch.float32 or (B > 1 and out.stride(1) != 1):
+        raise ValueError("mtl_towers: out must be a float32 [%d, %d] tensor with unit column stride" % (T, B))
+    _dev_check(x, out, *(flat + list(head_ws) + [g for g in (global_biases or []) if g is not None]))
+    a, keep = _mtl_args(op, _C.mtl.TOWERS, B, x_stride, x_offsets, in_dim, units, list(range(T)), activation, route, esmm=esmm,
+                        tile_rows=tile_rows)
+    lib = _C.lib()
+    gb = [None] * T if global_biases is None else list(global_biases)
+    if _route_name("dctr_mtl_route", lib.dctr_mtl_route(ctypes.byref(a), _C.mtl.TOWERS), _MTL_ROUTE_NAMES) == "layered":
+        cvr = torch.empty(B, dtype=torch.float32, device=x.device) if esmm else None
+        for t in range(T):
+            mlp(x[:, x_offsets[t]:x_offsets[t] + in_dim], list(kernels[t]), list(biases[t]), activation if units else "linear",
+                dice=None if dice is None else dice[t], bn=None if bn is None else bn[t], head_w=head_ws[t], global_bias=gb[t],
+                sigmoid_out=binary[t], in_dim=in_dim, out=cvr if (esmm and t == 1) else out[t])
+        if esmm:
+            edcn_bridge(out[0].reshape(B, 1), cvr.reshape(B, 1), "hadamard_product", out=out[1].reshape(B, 1))
+        return out
+    cast = lambda p: None if p is None else ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    ptrs = list(_mtl_dnn_ptrs(kernels, biases, bn))
+    a.x = x.data_ptr()
+    a.expert_w, a.expert_b, a.expert_bn_scale, a.expert_bn_shift = (cast(p) for p in ptrs)
+    ptrs += [_ptr_array(list(head_ws)), _ptr_array(gb), _i32_array([int(b) for b in binary])]
+    a.head_w, a.global_bias, a.binary = (cast(p) for p in ptrs[-3:])
+    a.probs, a.probs_stride = out.data_ptr(), (int(out.stride(0)) if T > 1 else max(int(out.stride(0)), B))
+    _C.check(lib.dctr_mtl_towers_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_towers_fwd")
+    del keep, ptrs
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

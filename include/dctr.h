@@ -763,6 +763,95 @@ int dctr_edcn_bridge(int32_t kind, const float* c, int64_t c_stride, const float
                      const float* ah, int64_t ah_stride, int64_t batch, int32_t dim, float* out, int64_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The multi-task models' expert / gate / tower stack — deepctr/models/multitask/{mmoe,ple,sharedbottom,esmm}.py
+ *   One LEVEL (DCTR_MTL_LEVEL: MMOE once, PLE's cgc_net num_levels times) over n_slots input slots, slot s = the in_dim columns from
+ *   x_offsets[s] of x [B, x_stride], read in place:
+ *       expert e : h_e = DNN_e(X_expert_src[e])           n_layers layers of units[l] for every expert, weights expert_w[e * n_layers + l]
+ *                                                         (Keras layout [in, out]), bias, optional BatchNormalization affine, activation
+ *       gate g   : z_g = GateDNN_g(X_gate_src[g])         (n_gate_layers may be 0: z_g = the slot);  p_g = softmax(z_g gate_kernel[g]),
+ *                                                         gate_kernel[g] [dz, gate_n[g]], no bias
+ *                  O_g = sum_j p_g[j] * h_{members[g][j]}  -> out columns [out_offset + g * H, + H),  H = units[n_layers - 1]
+ *       members: the gates' index lists into the experts, concatenated (gate g's start = sum of gate_n before it).
+ *   The TOWERS (DCTR_MTL_TOWERS): tower t < n_experts = DNN_t (n_layers may be 0) over slot expert_src[t], then . head_w[t],
+ *       + global_bias[t][0], sigmoid where binary[t] -> probs[t * probs_stride + b];  esmm = 1 (two towers, both binary):
+ *       probs[1] = sigmoid(l_0) * sigmoid(l_1) (esmm.py:60-63).
+ *   dctr_mtl_level_fwd / dctr_mtl_towers_fwd are the FUSED route: one launch, slots, layer outputs, every expert's output and the gate
+ *   weights in LDS, exact fp32 on v_mfma_f32_16x16x4_f32, no atomics (the same bits on every call).  It takes activations LINEAR | RELU |
+ *   SIGMOID | TANH, <= 8 slots, <= 16 experts (8 towers) of <= 4 layers and <= 32 layers together, <= 8 gates of <= 4 layers and <= 16
+ *   together, <= 64 members in all, while a tile of 16 rows fits 160 KiB of LDS.  Everything else answers DCTR_E_UNSUPPORTED there and
+ *   DCTR_MTL_ROUTE_LAYERED from dctr_mtl_route: the host then runs the DNNs through dctr_mlp_fwd and the mixtures through dctr_mtl_mix.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_MTL_LEVEL = 0, DCTR_MTL_TOWERS = 1 };
+enum { DCTR_MTL_ROUTE_AUTO = 0, DCTR_MTL_ROUTE_FUSED = 1, DCTR_MTL_ROUTE_LAYERED = 2 };
+typedef struct {
+    int64_t batch;
+    const float* x;                       /* [B, x_stride] fp32 */
+    int64_t x_stride;
+    const int64_t* x_offsets;             /* HOST [n_slots]: first column of every slot */
+    int32_t n_slots;
+    int32_t in_dim;                       /* width of every slot */
+    int32_t n_experts;                    /* E (towers: T) */
+    int32_t n_layers;                     /* level: >= 1; towers: >= 0 */
+    const int32_t* units;                 /* HOST [n_layers] */
+    const int32_t* expert_src;            /* HOST [E]: slot of every expert / tower */
+    const float* const* expert_w;         /* HOST [E * n_layers] of DEVICE pointers */
+    const float* const* expert_b;
+    const float* const* expert_bn_scale;  /* NULL, or [E * n_layers] (entries may be NULL) */
+    const float* const* expert_bn_shift;
+    int32_t activation;                   /* DCTR_ACT_* (fused: not DICE) */
+    int32_t route;                        /* DCTR_MTL_ROUTE_AUTO | _LAYERED (the query answers LAYERED, the launch declines) */
+    int32_t n_gates;                      /* level: G >= 1 */
+    int32_t n_gate_layers;                /* >= 0 */
+    const int32_t* gate_units;            /* HOST [n_gate_layers] */
+    const int32_t* gate_src;              /* HOST [G] */
+    const int32_t* gate_n;                /* HOST [G]: members per gate, >= 1 */
+    const int32_t* members;               /* HOST [sum gate_n]: expert indices */
+    const float* const* gate_w;           /* HOST [G * n_gate_layers] */
+    const float* const* gate_b;
+    const float* const* gate_bn_scale;
+    const float* const* gate_bn_shift;
+    const float* const* gate_kernel;      /* HOST [G] -> [dz, gate_n[g]] */
+    float* out;                           /* level: [B, out_stride] */
+    int64_t out_stride;
+    int64_t out_offset;
+    const float* const* head_w;           /* towers: HOST [T] -> [units[last] or in_dim] */
+    const float* const* global_bias;      /* towers: NULL, or HOST [T] of device scalars (entries may be NULL) */
+    const int32_t* binary;                /* towers: HOST [T], 1 = sigmoid */
+    int32_t esmm;                         /* towers: 0 | 1 */
+    int32_t tile_rows;                    /* 0 = the library's choice, or 16 | 32 | 64: at most this many rows per workgroup */
+    float* probs;                         /* towers: [T, probs_stride] */
+    int64_t probs_stride;                 /* >= batch */
+} dctr_mtl_args_t;
+/* The route these arguments take for kind = DCTR_MTL_LEVEL | DCTR_MTL_TOWERS (DCTR_MTL_ROUTE_FUSED / _LAYERED), or the DCTR_E_* the size
+ * and index checks answer.  Host arrays are read, device pointers are not looked at. */
+int dctr_mtl_route(const dctr_mtl_args_t* args, int32_t kind);
+int dctr_mtl_level_fwd(const dctr_mtl_args_t* args, void* stream);
+int dctr_mtl_towers_fwd(const dctr_mtl_args_t* args, void* stream);
+/* The layered route's mixture: expert outputs h [B, h_stride] (expert e in columns [e * width, + width)), per gate its input rows
+ * z[g] [B, z_stride[g]] of z_dim columns and its kernel [z_dim, gate_n[g]]:  out columns [out_offset + g * width, + width) =
+ * sum_j softmax(z_g kernel_g)[j] * h_{members[g][j]}.  members: HOST array (checked) and the same values on the device (members_dev).
+ * Any shape; gates go out eight per launch; no atomics. */
+typedef struct {
+    int64_t batch;
+    const float* h;
+    int64_t h_stride;
+    int32_t n_experts;
+    int32_t width;
+    int32_t n_gates;
+    int32_t z_dim;
+    const float* const* z;                /* HOST [G] of DEVICE pointers */
+    const int64_t* z_stride;              /* HOST [G] */
+    const float* const* gate_kernel;      /* HOST [G] */
+    const int32_t* gate_n;                /* HOST [G] */
+    const int32_t* members;               /* HOST [sum gate_n] */
+    const int32_t* members_dev;           /* DEVICE copy of members */
+    float* out;
+    int64_t out_stride;
+    int64_t out_offset;
+} dctr_mtl_mix_args_t;
+int dctr_mtl_mix(const dctr_mtl_mix_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
