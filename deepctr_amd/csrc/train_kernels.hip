@@ -291,26 +291,29 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(dctr_pool_args_t a, const
     bool ltaken = false;
     for (int t = 0; t < T; ++t) {
         const int64_t r = row_of(t);
-        if ((uint64_t)r >= (uint64_t)a.vocab) continue;
+        const bool ok = (uint64_t)r < (uint64_t)a.vocab;
+        if (!ok && !is_max) continue;
         const bool m = mask_of(t, r);
         const float wt = weight_of(t, m);
         if (is_max) {
+            // (an out-of-range id entered the forward maximum as a zero row: where it is the first position that attains the
+            // maximum it takes the gradient with it — there is no row to add to — instead of passing it on to a later tie)
             const float pen = m ? 0.f : 1e9f;
             float v[VEC];
 #pragma unroll
             for (int c = 0; c < VEC; ++c) v[c] = 0.f;
-            if (colok) load_vec<VEC>(a.table + r * a.dim + q * VEC, v);
+            if (ok && colok) load_vec<VEC>(a.table + r * a.dim + q * VEC, v);
             if (colok && g_table != nullptr) {
 #pragma unroll
                 for (int c = 0; c < VEC; ++c)
                     if (!taken[c] && v[c] * wt - pen == mx[c]) {
                         taken[c] = true;
-                        unsafeAtomicAdd(g_table + r * a.dim + q * VEC + c, dv[c] * wt);
+                        if (ok) unsafeAtomicAdd(g_table + r * a.dim + q * VEC + c, dv[c] * wt);
                     }
             }
-            if (q == 0 && g_lin_table != nullptr && a.lin_table != nullptr && !ltaken && a.lin_table[r] * wt - pen == lmx) {
+            if (q == 0 && g_lin_table != nullptr && a.lin_table != nullptr && !ltaken && (ok ? a.lin_table[r] : 0.f) * wt - pen == lmx) {
                 ltaken = true;
-                unsafeAtomicAdd(g_lin_table + r, dl * wt);
+                if (ok) unsafeAtomicAdd(g_lin_table + r, dl * wt);
             }
         } else {
             const float f = wt * (m ? 1.f : 0.f) / denom;
