@@ -234,6 +234,23 @@ class edcn(object):
                     ("out_offset", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class transformer(object):
+    """dctr_transformer_args_t, one level down for the same reason as interacting.Args (tests/test_bst_cpu.py checks the layout)."""
+    OUT_NONE, OUT_MEAN, OUT_SUM = 0, 1, 2
+    OUTPUTS = {None: OUT_NONE, "mean": OUT_MEAN, "sum": OUT_SUM}
+    ROUTE_AUTO, ROUTE_FUSED, ROUTE_GENERAL = 0, 1, 2
+    LAYER_PTRS = 9      # query, key, value, fw1, fw2, ln_gamma, ln_beta, pe_q, pe_k
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("queries", c_vp), ("q_stride", c_i64), ("q_row_stride", c_i64), ("keys", c_vp), ("k_stride", c_i64),
+                    ("k_row_stride", c_i64), ("seq_len", c_i32), ("dim", c_i32), ("att_embedding_size", c_i32), ("head_num", c_i32),
+                    ("n_layers", c_i32), ("use_positional_encoding", c_i32), ("use_res", c_i32), ("use_feed_forward", c_i32),
+                    ("use_layer_norm", c_i32), ("blinding", c_i32), ("output_type", c_i32), ("route", c_i32), ("ln_eps", c_f32),
+                    ("reserved", c_i32), ("layers", c_vp), ("query_lengths", c_vp), ("key_lengths", c_vp), ("query_mask", c_vp),
+                    ("key_mask", c_vp), ("out", c_vp), ("out_stride", c_i64), ("out_row_stride", c_i64), ("key_mask_out", c_vp),
+                    ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class mtl(object):
     """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
     layout)."""
@@ -356,6 +373,10 @@ SYMBOLS = {
     "dctr_edcn_workspace_bytes": (c_sz, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_route": (ctypes.c_int, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_fwd": (ctypes.c_int, [ctypes.POINTER(edcn.Args), c_vp]),
+    "dctr_transformer_workspace_bytes": (c_sz, [ctypes.POINTER(transformer.Args)]),
+    "dctr_transformer_route": (ctypes.c_int, [ctypes.POINTER(transformer.Args)]),
+    "dctr_transformer_fwd": (ctypes.c_int, [ctypes.POINTER(transformer.Args), c_vp]),
+    "dctr_layer_norm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "dctr_mtl_route": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_i32]),
     "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),
     "dctr_mtl_towers_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),

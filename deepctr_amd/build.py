@@ -55,6 +55,7 @@ SOURCES = [
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",
     "mtl_kernels.hip",
+    "transformer_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

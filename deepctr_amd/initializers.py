@@ -35,6 +35,15 @@ class Ones(Initializer):
         return torch.ones(tuple(shape), dtype=dtype)
 
 
+class Constant(Initializer):
+    def __init__(self, value=0):
+        self.value = value
+
+    def __call__(self, shape, dtype=torch.float32):
+        import numpy as np
+        return torch.from_numpy(np.broadcast_to(np.asarray(self.value, dtype=np.float64), tuple(shape)).copy()).to(dtype)
+
+
 class RandomNormal(Initializer):
     def __init__(self, mean=0.0, stddev=0.05, seed=None):
         self.mean, self.stddev, self.seed = mean, stddev, seed

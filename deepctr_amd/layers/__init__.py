@@ -5,7 +5,8 @@ from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer, RegulationModule
 from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, BridgeModule, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
                           FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
-from .sequence import AttentionSequencePoolingLayer, SequencePoolingLayer, WeightedSequenceLayer
+from .normalization import LayerNormalization
+from .sequence import AttentionSequencePoolingLayer, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
 custom_objects = {
@@ -31,6 +32,9 @@ custom_objects = {
     'SequencePoolingLayer': SequencePoolingLayer,
     'WeightedSequenceLayer': WeightedSequenceLayer,
     'AttentionSequencePoolingLayer': AttentionSequencePoolingLayer,
+    'Transformer': Transformer,
+    'PositionEncoding': PositionEncoding,
+    'LayerNormalization': LayerNormalization,
     'Hash': Hash,
     'Linear': Linear,
     'Concat': Concat,

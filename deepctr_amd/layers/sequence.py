@@ -1,14 +1,17 @@
-"""Host mirror of the three in-scope layers of the reference's ``deepctr/layers/sequence.py``:
+"""Host mirror of the in-scope layers of the reference's ``deepctr/layers/sequence.py``:
 ``SequencePoolingLayer`` (:41-120), ``WeightedSequenceLayer`` (:123-197), ``AttentionSequencePoolingLayer``
-(:200-315).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
+(:200-315), ``Transformer`` (:431-651) and ``PositionEncoding`` (:654-703).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
 pooled vector, the [B,T,E] tensor never exists); these classes are the stand-alone layer API over an
 already gathered [B,T,E] tensor.  Stand-alone pooling of a materialised tensor is pure data movement, done
 here with the same kernel by treating the sequence tensor as its own table."""
+import numpy as np
 import torch
 
 from .. import ops
+from ..initializers import Constant, GlorotUniform, TruncatedNormal
 from .base import Layer
 from .core import LocalActivationUnit
+from .normalization import LayerNormalization
 
 
 def _pool_materialised(seq, mode, mask=None, lengths=None, weight=None, weight_norm=True):
@@ -166,4 +169,165 @@ class AttentionSequencePoolingLayer(Layer):
                   'weight_normalization': self.weight_normalization, 'return_score': self.return_score,
                   'supports_masking': self.supports_masking}
         base = super(AttentionSequencePoolingLayer, self).get_config()
+        return dict(list(base.items()) + list(config.items()))
+
+
+class Transformer(Layer):
+    """Multi-head self-attention block with positional encodings, residual, LayerNormalization and feed-forward (reference
+    sequence.py:431-651): every flag, both input forms, ``attention_type='scaled_dot_product'``.  One launch of
+    ``dctr_transformer_fwd``; BST stacks its layers into a single launch through ``operands``."""
+
+    def __init__(self, att_embedding_size=1, head_num=8, dropout_rate=0.0, use_positional_encoding=True, use_res=True,
+                 use_feed_forward=True, use_layer_norm=False, blinding=True, seed=1024, supports_masking=False,
+                 attention_type="scaled_dot_product", output_type="mean", **kwargs):
+        if head_num <= 0:
+            raise ValueError('head_num must be a int > 0')
+        if attention_type in ("cos", "ln", "additive"):
+            raise NotImplementedError("Transformer attention_type=%r is outside this build: only 'scaled_dot_product' has a kernel"
+                                      % (attention_type,))
+        if attention_type != "scaled_dot_product":
+            raise ValueError("attention_type must be [scaled_dot_product,cos,ln,additive]")
+        self.att_embedding_size = att_embedding_size
+        self.head_num = head_num
+        self.num_units = att_embedding_size * head_num
+        self.use_res = use_res
+        self.use_feed_forward = use_feed_forward
+        self.seed = seed
+        self.use_positional_encoding = use_positional_encoding
+        self.dropout_rate = dropout_rate
+        self.use_layer_norm = use_layer_norm
+        self.blinding = blinding
+        self.attention_type = attention_type
+        self.output_type = output_type
+        super(Transformer, self).__init__(**kwargs)
+        self.supports_masking = supports_masking
+
+    def build(self, input_shape):
+        return self.build_for(int(input_shape[0][-2]), int(input_shape[0][-1]))
+
+    def build_for(self, seq_len_max, embedding_size):
+        if self.built:
+            return self
+        if self.num_units != embedding_size:
+            raise ValueError("att_embedding_size * head_num must equal the last dimension size of inputs,got %d * %d != %d" % (
+                self.att_embedding_size, self.head_num, embedding_size))
+        self.seq_len_max = int(seq_len_max)
+        shape = (embedding_size, self.num_units)
+        self.add_weight('query', shape, TruncatedNormal(seed=self.seed))
+        self.add_weight('key', shape, TruncatedNormal(seed=self.seed + 1))
+        self.add_weight('value', shape, TruncatedNormal(seed=self.seed + 2))
+        if self.use_feed_forward:
+            self.add_weight('fw1', (self.num_units, 4 * self.num_units), GlorotUniform(seed=self.seed))
+            self.add_weight('fw2', (4 * self.num_units, self.num_units), GlorotUniform(seed=self.seed))
+        # one LayerNormalization serves both applications (sequence.py:516, :619, :628); keras builds it at its first call
+        self.ln = LayerNormalization(device=self.device)
+        if self.use_layer_norm:
+            self.ln.build_for(self.num_units)
+        self._sublayers.append(self.ln)
+        if self.use_positional_encoding:
+            self.query_pe = PositionEncoding(device=self.device).build_for(self.seq_len_max, embedding_size)
+            self.key_pe = PositionEncoding(device=self.device).build_for(self.seq_len_max, embedding_size)
+            self._sublayers += [self.query_pe, self.key_pe]
+        self.built = True
+        return self
+
+    def operands(self):
+        """The layer's weights as ops.transformer takes them; the positional tables are folded with float32(sqrt(E)) from the live
+        tables on every call (one multiply each, the rounding of sequence.py:687-688)."""
+        w = {k: self.w(k) for k in ("query", "key", "value")}
+        if self.use_feed_forward:
+            w["fw1"], w["fw2"] = self.w("fw1"), self.w("fw2")
+        if self.use_layer_norm:
+            w["ln_gamma"], w["ln_beta"] = self.ln.w("gamma"), self.ln.w("beta")
+        if self.use_positional_encoding:
+            w["pe_q"], w["pe_k"] = self.query_pe.scaled_table(), self.key_pe.scaled_table()
+        return w
+
+    def flags(self):
+        return dict(use_positional_encoding=self.use_positional_encoding, use_res=self.use_res, use_feed_forward=self.use_feed_forward,
+                    use_layer_norm=self.use_layer_norm, blinding=self.blinding, ln_eps=self.ln.eps)
+
+    def run(self, queries, keys=None, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None, out=None,
+            key_mask_out=None):
+        return ops.transformer(queries, [self.operands()], self.head_num, keys=keys, query_lengths=query_lengths,
+                               key_lengths=key_lengths, query_mask=query_mask, key_mask=key_mask, output_type=self.output_type, out=out,
+                               key_mask_out=key_mask_out, **self.flags())
+
+    def call(self, inputs, mask=None, training=None, **kwargs):
+        if self.supports_masking:
+            queries, keys = inputs
+            if mask is None:
+                raise ValueError("When supports_masking=True,input must support masking")
+            query_masks, key_masks = mask
+            kw = dict(query_mask=query_masks.reshape(queries.shape[0], -1) != 0, key_mask=key_masks.reshape(keys.shape[0], -1) != 0)
+        else:
+            queries, keys, query_masks, key_masks = inputs
+            kw = dict(query_lengths=query_masks.reshape(-1).to(torch.int32), key_lengths=key_masks.reshape(-1).to(torch.int32))
+        if queries.dim() != 3 or keys.shape != queries.shape:
+            raise ValueError("Transformer takes queries and keys of one shape (batch_size, timesteps, input_dim), got %s and %s"
+                             % (tuple(queries.shape), tuple(keys.shape)))
+        q = queries if queries.dtype == torch.float32 and queries.stride(-1) == 1 else queries.to(torch.float32).contiguous()
+        k = None if keys is queries else (keys if keys.dtype == torch.float32 and keys.stride(-1) == 1 else keys.to(torch.float32).contiguous())
+        y = self.run(q, k, **kw)
+        return y if self.output_type is None else y.reshape(y.shape[0], 1, y.shape[1])
+
+    def compute_output_shape(self, input_shape):
+        return (None, 1, self.att_embedding_size * self.head_num)
+
+    def compute_mask(self, inputs, mask=None):
+        return None
+
+    def get_config(self):
+        config = {'att_embedding_size': self.att_embedding_size, 'head_num': self.head_num, 'dropout_rate': self.dropout_rate,
+                  'use_res': self.use_res, 'use_positional_encoding': self.use_positional_encoding,
+                  'use_feed_forward': self.use_feed_forward, 'use_layer_norm': self.use_layer_norm, 'seed': self.seed,
+                  'supports_masking': self.supports_masking, 'blinding': self.blinding, 'attention_type': self.attention_type,
+                  'output_type': self.output_type}
+        base = super(Transformer, self).get_config()
+        return dict(list(base.items()) + list(config.items()))
+
+
+class PositionEncoding(Layer):
+    """Trainable sinusoid positional table added to the inputs, scaled by sqrt(width) (reference sequence.py:654-703).  Inside
+    Transformer the addition is fused into ``dctr_transformer_fwd``; stand-alone it is one elementwise addition."""
+
+    def __init__(self, pos_embedding_trainable=True, zero_pad=False, scale=True, **kwargs):
+        self.pos_embedding_trainable = pos_embedding_trainable
+        self.zero_pad = zero_pad
+        self.scale = scale
+        super(PositionEncoding, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        return self.build_for(int(input_shape[-2]), int(input_shape[-1]))
+
+    def build_for(self, T, num_units):
+        if self.built:
+            return self
+        # pe[t, i] = sin(t / 10000^(2 floor(i / 2) / width)) for even i, cos of the same angle for odd i
+        column = np.arange(int(num_units))
+        angle = np.arange(int(T), dtype=np.float64)[:, None] / 10000.0 ** (2.0 * (column // 2) / num_units)[None, :]
+        table = np.where(column[None, :] % 2 == 0, np.sin(angle), np.cos(angle))
+        if self.zero_pad:
+            table[0] = 0.0
+        self.add_weight("lookup_table", (T, num_units), Constant(table), trainable=self.pos_embedding_trainable)
+        self.built = True
+        return self
+
+    def scaled_table(self):
+        """lookup_table * float32(sqrt(width)) (sequence.py:687-688), from the live table."""
+        t = self.w("lookup_table")
+        return t * float(np.float32(t.shape[1] ** 0.5)) if self.scale else t
+
+    def call(self, inputs, mask=None, **kwargs):
+        return self.scaled_table() + inputs
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+    def compute_mask(self, inputs, mask=None):
+        return mask
+
+    def get_config(self):
+        config = {'pos_embedding_trainable': self.pos_embedding_trainable, 'zero_pad': self.zero_pad, 'scale': self.scale}
+        base = super(PositionEncoding, self).get_config()
         return dict(list(base.items()) + list(config.items()))

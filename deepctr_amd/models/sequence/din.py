@@ -19,9 +19,16 @@ from .._common import FeatureModel
 
 
 class _DIN(FeatureModel):
+    model_name = "DIN"
+    key_hash_mode = 2            # the query / key lookups hash with mask_zero=True (din.py:66-69)
+    key_mask_from_ids = True     # the key lookups write the (id != 0) attention mask; False: the subclass fills bufs["m"] itself
+
+    def _build_sequence_block(self, seed, dnn_dropout):
+        """Layers between the key lookups and the attention pooling (none in DIN; BST's Transformers)."""
+
     def __init__(self, dnn_feature_columns, history_feature_list, dnn_use_bn, dnn_hidden_units, dnn_activation,
                  att_hidden_size, att_activation, att_weight_normalization, dnn_dropout, seed, task, device):
-        super(_DIN, self).__init__("DIN", list(dnn_feature_columns), device, task)
+        super(_DIN, self).__init__(self.model_name, list(dnn_feature_columns), device, task)
         self.history_feature_list = list(history_feature_list)
         hist_names = ["hist_" + n for n in self.history_feature_list]
         sparse = [fc for fc in dnn_feature_columns if isinstance(fc, SparseFeat)]
@@ -47,6 +54,7 @@ class _DIN(FeatureModel):
                                              mask_feat_list=tuple(self.history_feature_list),
                                              extra_dims=(("hist", self.key_dim),),
                                              skip_varlen=tuple(hist_names), device=self.device)
+            self._build_sequence_block(seed, dnn_dropout)
             self.attention = AttentionSequencePoolingLayer(att_hidden_size, att_activation,
                                                            weight_normalization=att_weight_normalization,
                                                            supports_masking=True, device=self.device)
@@ -127,15 +135,15 @@ class _DIN(FeatureModel):
         lookups, col = [], 0
         for fc, row in zip(self.query_cols, self._query_rows):
             table = self.tables[fc.embedding_name].embeddings
-            hm = 2 if (fc.use_hash and not prehashed_on_host(fc)) else 0
+            hm = self.key_hash_mode if (fc.use_hash and not prehashed_on_host(fc)) else 0
             lookups.append(dict(idx=staged.ids[row, lo:hi], table=table, hash_mode=hm, out=bufs["q"][:, col:]))
             col += fc.embedding_dim
         col = 0
-        masked = [fc for fc in self.history_cols if self.tables[fc.embedding_name].mask_zero]
+        masked = [fc for fc in self.history_cols if self.tables[fc.embedding_name].mask_zero] if self.key_mask_from_ids else []
         bufs["key_lookups"] = []
         for fc in self.history_cols:
             emb = self.tables[fc.embedding_name]
-            hm = 2 if (fc.use_hash and not prehashed_on_host(fc)) else 0
+            hm = self.key_hash_mode if (fc.use_hash and not prehashed_on_host(fc)) else 0
             lk = dict(idx=staged.seq[fc.name][lo:hi], table=emb.embeddings, hash_mode=hm, out=bufs["k"][:, :, col:])
             bufs["key_lookups"].append((fc, lk["idx"], hm, col))
             if masked and fc is masked[0]:

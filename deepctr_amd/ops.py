@@ -1769,6 +1769,163 @@ def mtl_towers(x, in_dim, x_offsets, kernels, biases, head_ws, global_biases=Non
     return out
 
 
+_TRANSFORMER_ROUTES = {None: _C.transformer.ROUTE_AUTO, "auto": _C.transformer.ROUTE_AUTO, "fused": _C.transformer.ROUTE_FUSED,
+                       "general": _C.transformer.ROUTE_GENERAL}
+TRANSFORMER_WEIGHTS = ("query", "key", "value", "fw1", "fw2", "ln_gamma", "ln_beta", "pe_q", "pe_k")
+
+
+def transformer_flops(T, E, n_layers=1, use_feed_forward=True):
+    """FLOP per sample of the Transformer stack: 6 T E^2 projections + 4 T^2 E attention + 16 T E^2 feed-forward per layer."""
+    return int(n_layers) * (6 * T * E * E + 4 * T * T * E + (16 * T * E * E if use_feed_forward else 0))
+
+
+def _seq3d(op, name, t, B, T, E):
+    """``t`` is a float32 [B, T, E] view with unit stride on the last axis; returns its (sample, position) strides in elements (the
+    stride torch reports for a size-1 axis is arbitrary: such an axis gets the extent of what it holds)."""
+    if t.dim() != 3 or t.dtype != torch.float32 or tuple(t.shape) != (B, T, E) or (E > 1 and t.stride(2) != 1):
+        raise ValueError("%s: %s must be a float32 [%d, %d, %d] view with unit stride on the last axis" % (op, name, B, T, E))
+    row = int(t.stride(1)) if T != 1 else max(int(t.stride(1)), E)
+    sample = int(t.stride(0)) if B > 1 else max(int(t.stride(0)), (T - 1) * row + E)
+    return sample, row
+
+
+def _transformer_args(B, T, E, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding,
+                      output_type, route, ln_eps=1e-9):
+    if output_type not in _C.transformer.OUTPUTS:
+        raise ValueError("transformer: output_type must be None, 'mean' or 'sum', got %r" % (output_type,))
+    if route not in _TRANSFORMER_ROUTES:
+        raise ValueError("transformer: route must be None, 'fused' or 'general', got %r" % (route,))
+    H = int(head_num)
+    if H <= 0:
+        raise ValueError("head_num must be a int > 0")
+    if E % H:
+        raise ValueError("att_embedding_size * head_num must equal the last dimension size of inputs,got %d * %d != %d" % (E // H, H, E))
+    return _C.transformer.Args(batch=int(B), q_stride=int(T) * int(E), q_row_stride=int(E), k_stride=int(T) * int(E), k_row_stride=int(E),
+                               seq_len=int(T), dim=int(E), att_embedding_size=E // H, head_num=H, n_layers=int(n_layers),
+                               use_positional_encoding=int(bool(use_positional_encoding)), use_res=int(bool(use_res)),
+                               use_feed_forward=int(bool(use_feed_forward)), use_layer_norm=int(bool(use_layer_norm)),
+                               blinding=int(bool(blinding)), output_type=_C.transformer.OUTPUTS[output_type],
+                               route=_TRANSFORMER_ROUTES[route], ln_eps=float(ln_eps), out_stride=int(T) * int(E), out_row_stride=int(E))
+
+
+def transformer_workspace_bytes(batch, seq_len, dim, head_num, n_layers=1, use_positional_encoding=True, use_res=True,
+                                use_feed_forward=True, use_layer_norm=False, blinding=True, output_type=None, route=None):
+    """Bytes of the workspace dctr_transformer_fwd needs for these shapes (0 on the fused route; read from the library)."""
+    a = _transformer_args(batch, seq_len, dim, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm,
+                          blinding, output_type, route)
+    return int(_C.lib().dctr_transformer_workspace_bytes(ctypes.byref(a)))
+
+
+def transformer_route(seq_len, dim, head_num, n_layers=1, use_positional_encoding=True, use_res=True, use_feed_forward=True,
+                      use_layer_norm=False, blinding=True, output_type=None, route=None):
+    """'fused' or 'general': the route dctr_transformer_fwd takes for these shapes (dctr_transformer_route)."""
+    a = _transformer_args(1, seq_len, dim, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm,
+                          blinding, output_type, route)
+    return _route_name("dctr_transformer_route", _C.lib().dctr_transformer_route(ctypes.byref(a)), (None, "fused", "general"))
+
+
+def _transformer_mask(op, name, lengths, mask, B, T):
+    """One side's mask operands: int32 lengths [B] or a uint8 / bool [B, T] mask, at most one of them."""
+    if lengths is not None and mask is not None:
+        raise ValueError("%s: give %s_lengths or %s_mask, not both" % (op, name, name))
+    if lengths is not None:
+        if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+            raise ValueError("%s: %s_lengths must be a contiguous int32 tensor of %d elements" % (op, name, B))
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, T) or not mask.is_contiguous():
+            raise ValueError("%s: %s_mask must be a contiguous uint8 or bool [%d, %d] tensor" % (op, name, B, T))
+    return lengths, mask
+
+
+def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None,
+                use_positional_encoding=True, use_res=True, use_feed_forward=True, use_layer_norm=False, blinding=True,
+                output_type=None, out=None, key_mask_out=None, route=None, workspace=None, ln_eps=1e-9):
+    """Transformer.call (reference sequence.py:523-635) stacked over len(layers) layers (bst.py:84-92), one launch.
+
+    ``queries`` [B, T, E] float32 view (any sample / position strides, unit stride on the last axis); ``keys`` the same shape or None
+    (the queries).  ``layers``: per layer a dict (or a sequence in this order) of query, key, value [E, E], fw1 [E, 4E], fw2 [4E, E],
+    ln_gamma, ln_beta [E], pe_q, pe_k [T, E] — the positional tables ALREADY multiplied by float32(sqrt(E)); weights a flag switches
+    off may be None.  Masks: int32 lengths [B] or a uint8 / bool [B, T] mask per side, None = every position counts.
+    ``out``: a [B, T, E] view (``output_type`` None; may be ``queries`` itself: in place) or [B, E] ('mean' / 'sum'), allocated when
+    None.  ``key_mask_out``: a uint8 [B, T] tensor that receives the key mask.  Returns ``out``."""
+    op = "transformer"
+    if queries.dim() != 3:
+        raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % queries.dim())
+    B, T, E = (int(v) for v in queries.shape)
+    a = _transformer_args(B, T, E, head_num, len(layers), use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding,
+                          output_type, route, ln_eps)
+    a.q_stride, a.q_row_stride = _seq3d(op, "queries", queries, B, T, E)
+    if keys is not None:
+        a.k_stride, a.k_row_stride = _seq3d(op, "keys", keys, B, T, E)
+    if not layers:
+        raise ValueError("transformer: at least one layer")
+    shapes = {"query": (E, E), "key": (E, E), "value": (E, E), "fw1": (E, 4 * E), "fw2": (4 * E, E), "ln_gamma": (1, E), "ln_beta": (1, E),
+              "pe_q": (T, E), "pe_k": (T, E)}
+    needed = {"query": True, "key": True, "value": True, "fw1": bool(use_feed_forward and use_res), "fw2": bool(use_feed_forward and use_res),
+              "ln_gamma": bool(use_layer_norm), "ln_beta": bool(use_layer_norm), "pe_q": bool(use_positional_encoding),
+              "pe_k": bool(use_positional_encoding)}
+    flat = []
+    for li, layer in enumerate(layers):
+        if not isinstance(layer, dict):
+            layer = dict(zip(TRANSFORMER_WEIGHTS, layer))
+        for name in TRANSFORMER_WEIGHTS:
+            w = layer.get(name)
+            if w is None or not needed[name]:
+                if needed[name]:
+                    raise ValueError("transformer: layer %d: %s is missing" % (li, name))
+                flat.append(None)
+                continue
+            rows, cols = shapes[name]
+            if name.startswith("ln_"):
+                _vec(op, "layer %d %s" % (li, name), w, cols)
+            elif _rows2d(op, "layer %d %s" % (li, name), w, rows, cols) != cols and rows > 1:
+                raise ValueError("transformer: layer %d: %s must be contiguous" % (li, name))
+            flat.append(w)
+    query_lengths, query_mask = _transformer_mask(op, "query", query_lengths, query_mask, B, T)
+    key_lengths, key_mask = _transformer_mask(op, "key", key_lengths, key_mask, B, T)
+    if out is None:
+        out = torch.empty((B, T, E) if output_type is None else (B, E), dtype=torch.float32, device=queries.device)
+    if output_type is None:
+        a.out_stride, a.out_row_stride = _seq3d(op, "out", out, B, T, E)
+    else:
+        a.out_stride = _rows2d(op, "out", out, B, E)
+    if key_mask_out is not None and (key_mask_out.dtype != torch.uint8 or tuple(key_mask_out.shape) != (B, T) or not key_mask_out.is_contiguous()):
+        raise ValueError("transformer: key_mask_out must be a contiguous uint8 [%d, %d] tensor" % (B, T))
+    _dev_check(queries, keys, out, query_lengths, key_lengths, query_mask, key_mask, key_mask_out, *flat)
+    lp = _ptr_array(flat)
+    a.layers = ctypes.cast(lp, ctypes.c_void_p)
+    a.queries = queries.data_ptr()
+    a.keys = None if keys is None else keys.data_ptr()
+    a.query_lengths, a.key_lengths = _ptr(query_lengths), _ptr(key_lengths)
+    a.query_mask, a.key_mask = _ptr(query_mask), _ptr(key_mask)
+    a.out = out.data_ptr()
+    a.key_mask_out = _ptr(key_mask_out)
+    _workspace(op, a, int(_C.lib().dctr_transformer_workspace_bytes(ctypes.byref(a))), workspace, queries.device)
+    _C.check(_C.lib().dctr_transformer_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_transformer_fwd")
+    del lp
+    return out
+
+
+def layer_norm(x, gamma=None, beta=None, eps=1e-9, out=None):
+    """LayerNormalization.call (reference layers/normalization.py:34-43) over the last axis of a contiguous float32 tensor; gamma / beta
+    None = scale / center off."""
+    x = _f32c(x, "x")
+    dim = int(x.shape[-1])
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None:
+            _vec("layer_norm", name, t, dim)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape:
+        raise ValueError("layer_norm: out must be a contiguous float32 tensor of x's shape")
+    _dev_check(x, gamma, beta, out)
+    _C.check(_C.lib().dctr_layer_norm_fwd(_ptr(x), x.numel() // dim, dim, dim, _ptr(gamma), _ptr(beta), float(eps), _ptr(out), dim,
+                                          _C.stream_ptr()), "dctr_layer_norm_fwd")
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

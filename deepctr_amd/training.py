@@ -279,6 +279,56 @@ def _interacting(layer, x):
     return torch.relu(o)
 
 
+def _layer_norm(ln, x):
+    """LayerNormalization.call (reference layers/normalization.py:34-43) in torch ops."""
+    mean = x.mean(dim=-1, keepdim=True)
+    var = ((x - mean) ** 2).mean(dim=-1, keepdim=True)
+    y = (x - mean) / torch.sqrt(var + ln.eps)
+    if ln.scale:
+        y = y * ln.w("gamma")
+    if ln.center:
+        y = y + ln.w("beta")
+    return y
+
+
+def _transformer(layer, queries, keys, query_mask, key_mask, training=False):
+    """Transformer.call (reference sequence.py:523-635) in torch ops: queries, keys [B,T,E], bool masks [B,T] -> [B,T,E], or [B,1,E]
+    with output_type 'mean' / 'sum'.  Dropout on the attention weights and the feed-forward hidden layer (:609, :623)."""
+    B, T, E = queries.shape
+    H, d = layer.head_num, layer.att_embedding_size
+    if layer.use_positional_encoding:
+        scale = float(np.float32(E ** 0.5))
+        queries = queries + layer.query_pe.w("lookup_table") * scale
+        keys = keys + layer.key_pe.w("lookup_table") * scale
+
+    def heads(x, w):
+        return (x @ w).reshape(B, T, H, d).permute(0, 2, 1, 3)                 # [B,H,T,d]
+    q, k, v = heads(queries, layer.w("query")), heads(keys, layer.w("key")), heads(keys, layer.w("value"))
+    s = q @ k.transpose(-1, -2) / d ** 0.5
+    neg = torch.full_like(s, float(-2 ** 32 + 1))
+    s = torch.where(key_mask[:, None, None, :], s, neg)
+    if layer.blinding:
+        s = torch.where(torch.eye(T, dtype=torch.bool, device=s.device)[None, None], neg, s)
+    p = torch.softmax(s - s.max(dim=-1, keepdim=True).values, dim=-1) * query_mask[:, None, :, None].to(s.dtype)
+    p = _dropout(p, layer.dropout_rate, training)
+    r = (p @ v).permute(0, 2, 1, 3).reshape(B, T, E)
+    if layer.use_res:
+        r = r + queries
+    if layer.use_layer_norm:
+        r = _layer_norm(layer.ln, r)
+    if layer.use_feed_forward:
+        f = _dropout(torch.relu(r @ layer.w("fw1")), layer.dropout_rate, training) @ layer.w("fw2")
+        if layer.use_res:
+            r = r + f
+        if layer.use_layer_norm:
+            r = _layer_norm(layer.ln, r)
+    if layer.output_type == "mean":
+        return r.mean(dim=1, keepdim=True)
+    if layer.output_type == "sum":
+        return r.sum(dim=1, keepdim=True)
+    return r
+
+
 def _bilinear(layer, x):
     """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
     itertools.combinations order."""

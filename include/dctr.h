@@ -852,6 +852,79 @@ typedef struct {
 int dctr_mtl_mix(const dctr_mtl_mix_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Transformer.call x n_layers — deepctr/layers/sequence.py:523-635 with PositionEncoding (:683-689) and LayerNormalization
+ * (layers/normalization.py:34-43), stacked as deepctr/models/sequence/bst.py:84-92 stacks it, one launch
+ *     queries [B, T, E] (sample stride q_stride, position stride q_row_stride, elements); keys the same shape (NULL: the queries).
+ *     Per layer, with the layer's nine pointers query, key, value [E, E], fw1 [E, 4E], fw2 [4E, E] (Keras layout), ln_gamma, ln_beta
+ *     [E], pe_q, pe_k [T, E] (the lookup tables ALREADY multiplied by float32(sqrt(E)), sequence.py:687-688):
+ *       Xq = x + pe_q, Xk = keys + pe_k                               (use_positional_encoding; sequence.py:540-542)
+ *       Q = Xq query, K = Xk key, V = Xk value, split into H heads of width d = E / H          (:544-552)
+ *       s = Q_h K_h^T / float32(sqrt(d)); s = -2^32 + 1 where the key is masked, and on the diagonal with blinding   (:556-598)
+ *       p = softmax(s - max s) * query mask;  r = concat_h(p V_h) (+ Xq with use_res)            (:600-617)
+ *       r = LN(r)                                                       (use_layer_norm; :618-619)
+ *       r = r + relu(r fw1) fw2 (use_feed_forward and use_res), then LN(r) again (use_feed_forward and use_layer_norm)   (:621-628)
+ *       LN(x) = (x - mean) / sqrt(var + ln_eps) * ln_gamma + ln_beta, var the biased variance of the row (normalization.py:35-43)
+ *     The next layer's queries and keys are r.  Masks: int32 lengths [B] (position t counts while t < length: tf.sequence_mask,
+ *     :533-536) or uint8 [B, T]; at most one form per side, neither = every position counts.  A sample whose keys are all masked
+ *     has a uniform softmax; with a zero query mask its attention output is 0 (no NaN).
+ *     out: output_type NONE [B, T, E] at out_stride / out_row_stride (may alias queries: in place), MEAN / SUM [B, E] at out_stride
+ *     over ALL T rows (:630-633).  key_mask_out: NULL, or uint8 [B, T] that receives the key mask of the first layer.
+ *     Exact fp32 on v_mfma_f32_16x16x4_f32, no atomics: the same bits on every call.  FUSED route: the activations of a tile of samples
+ *     stay in LDS (<= 160 KiB for one sample); larger samples take the GENERAL route through a workspace of
+ *     dctr_transformer_workspace_bytes() (room for <= 256 workgroups), which is then REQUIRED (DCTR_E_NULL without, before anything is
+ *     launched).  route = FUSED for a sample that does not fit answers DCTR_E_UNSUPPORTED.  No shape is refused for its size.
+ *     Argument errors (nothing launched): NULL queries / layers / out or a NULL weight a flag needs (DCTR_E_NULL), seq_len or dim < 1,
+ *     att_embedding_size * head_num != dim, strides smaller than the block (DCTR_E_DIM), both mask forms on one side, flags not 0 / 1,
+ *     unknown output_type / route (DCTR_E_ENUM).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_TRANSFORMER_OUT_NONE = 0, DCTR_TRANSFORMER_OUT_MEAN = 1, DCTR_TRANSFORMER_OUT_SUM = 2 };
+enum { DCTR_TRANSFORMER_ROUTE_AUTO = 0, DCTR_TRANSFORMER_ROUTE_FUSED = 1, DCTR_TRANSFORMER_ROUTE_GENERAL = 2 };
+#define DCTR_TRANSFORMER_LAYER_PTRS 9
+typedef struct {
+    int64_t batch;
+    const float* queries;            /* [B, T, E] fp32 */
+    int64_t q_stride;                /* elements between samples */
+    int64_t q_row_stride;            /* elements between positions, >= dim */
+    const float* keys;               /* NULL (= queries), or [B, T, E] */
+    int64_t k_stride;
+    int64_t k_row_stride;
+    int32_t seq_len;                 /* T >= 1 (queries and keys share it: the reference's seq_len_max) */
+    int32_t dim;                     /* E >= 1 */
+    int32_t att_embedding_size;      /* d, d * head_num == dim */
+    int32_t head_num;                /* H */
+    int32_t n_layers;                /* >= 1 */
+    int32_t use_positional_encoding; /* 0 | 1 */
+    int32_t use_res;
+    int32_t use_feed_forward;
+    int32_t use_layer_norm;
+    int32_t blinding;
+    int32_t output_type;             /* DCTR_TRANSFORMER_OUT_* */
+    int32_t route;                   /* DCTR_TRANSFORMER_ROUTE_AUTO | _FUSED | _GENERAL */
+    float ln_eps;                    /* the reference's 1e-9 */
+    int32_t reserved;
+    const float* const* layers;      /* HOST array [n_layers * 9] of DEVICE pointers (unused ones may be NULL) */
+    const int32_t* query_lengths;    /* NULL or [B] */
+    const int32_t* key_lengths;
+    const uint8_t* query_mask;       /* NULL or [B, T] */
+    const uint8_t* key_mask;
+    float* out;
+    int64_t out_stride;
+    int64_t out_row_stride;          /* output_type NONE only */
+    uint8_t* key_mask_out;           /* NULL or [B, T] */
+    void* workspace;                 /* NULL, or device scratch of dctr_transformer_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_transformer_args_t;
+/* Bytes dctr_transformer_fwd needs (sizes, flags and route are read, pointers are not): 0 on the fused route up to 16 layers. */
+size_t dctr_transformer_workspace_bytes(const dctr_transformer_args_t* args);
+/* The route these arguments take (DCTR_TRANSFORMER_ROUTE_FUSED / _GENERAL), or the DCTR_E_* the checks answer. */
+int dctr_transformer_route(const dctr_transformer_args_t* args);
+int dctr_transformer_fwd(const dctr_transformer_args_t* args, void* stream);
+/* LayerNormalization.call alone (layers/normalization.py:34-43) over the rows of x [rows, dim]: (x - mean) / sqrt(var + eps) * gamma +
+ * beta with the biased variance; gamma / beta NULL = scale / center off.  out may be x. */
+int dctr_layer_norm_fwd(const float* x, int64_t rows, int32_t dim, int64_t x_stride, const float* gamma, const float* beta, float eps,
+                        float* out, int64_t out_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
