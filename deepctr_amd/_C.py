@@ -251,6 +251,21 @@ class transformer(object):
                     ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class gru(object):
+    """dctr_gru_args_t, one level down for the same reason as interacting.Args (tests/test_dien_cpu.py checks the layout)."""
+    CELL_GRU, CELL_AGRU, CELL_AUGRU = 0, 1, 2
+    CELLS = {"GRU": CELL_GRU, "AGRU": CELL_AGRU, "AUGRU": CELL_AUGRU}
+    ROUTE_AUTO, ROUTE_RESIDENT, ROUTE_STREAMED = 0, 1, 2
+    ROUTES = {None: ROUTE_AUTO, "resident": ROUTE_RESIDENT, "streamed": ROUTE_STREAMED}
+    LAYER_PTRS = 4      # gate kernel, gate bias, candidate kernel, candidate bias
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_row_stride", c_i64), ("lengths", c_vp), ("att_scores", c_vp),
+                    ("att_stride", c_i64), ("seq_len", c_i32), ("dim", c_i32), ("n_layers", c_i32), ("cell", c_i32), ("scale_input", c_i32),
+                    ("return_sequence", c_i32), ("route", c_i32), ("reserved", c_i32), ("layers", c_vp), ("out", c_vp),
+                    ("out_stride", c_i64), ("out_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class mtl(object):
     """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
     layout)."""
@@ -376,6 +391,9 @@ SYMBOLS = {
     "dctr_transformer_workspace_bytes": (c_sz, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_route": (ctypes.c_int, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_fwd": (ctypes.c_int, [ctypes.POINTER(transformer.Args), c_vp]),
+    "dctr_gru_workspace_bytes": (c_sz, [ctypes.POINTER(gru.Args)]),
+    "dctr_gru_route": (ctypes.c_int, [ctypes.POINTER(gru.Args)]),
+    "dctr_gru_fwd": (ctypes.c_int, [ctypes.POINTER(gru.Args), c_vp]),
     "dctr_layer_norm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "dctr_mtl_route": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_i32]),
     "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),

@@ -56,6 +56,7 @@ SOURCES = [
     "edcn_kernels.hip",
     "mtl_kernels.hip",
     "transformer_kernels.hip",
+    "gru_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -6,7 +6,7 @@ from .core import DNN, Dense, LocalActivationUnit, PredictionLayer, RegulationMo
 from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, BridgeModule, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
                           FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
 from .normalization import LayerNormalization
-from .sequence import AttentionSequencePoolingLayer, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
+from .sequence import AttentionSequencePoolingLayer, DynamicGRU, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
 custom_objects = {
@@ -34,6 +34,7 @@ custom_objects = {
     'AttentionSequencePoolingLayer': AttentionSequencePoolingLayer,
     'Transformer': Transformer,
     'PositionEncoding': PositionEncoding,
+    'DynamicGRU': DynamicGRU,
     'LayerNormalization': LayerNormalization,
     'Hash': Hash,
     'Linear': Linear,

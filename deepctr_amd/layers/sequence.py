@@ -1,6 +1,6 @@
 """Host mirror of the in-scope layers of the reference's ``deepctr/layers/sequence.py``:
 ``SequencePoolingLayer`` (:41-120), ``WeightedSequenceLayer`` (:123-197), ``AttentionSequencePoolingLayer``
-(:200-315), ``Transformer`` (:431-651) and ``PositionEncoding`` (:654-703).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
+(:200-315), ``Transformer`` (:431-651), ``PositionEncoding`` (:654-703) and ``DynamicGRU`` (:760-815).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
 pooled vector, the [B,T,E] tensor never exists); these classes are the stand-alone layer API over an
 already gathered [B,T,E] tensor.  Stand-alone pooling of a materialised tensor is pure data movement, done
 here with the same kernel by treating the sequence tensor as its own table."""
@@ -331,3 +331,73 @@ class PositionEncoding(Layer):
         config = {'pos_embedding_trainable': self.pos_embedding_trainable, 'zero_pad': self.zero_pad, 'scale': self.scale}
         base = super(PositionEncoding, self).get_config()
         return dict(list(base.items()) + list(config.items()))
+
+
+class DynamicGRU(Layer):
+    """GRU / AGRU / AUGRU over a [B, T, E] sequence under dynamic_rnn's sequence_length rule (reference sequence.py:760-815 with the
+    cells of contrib/utils.py): one launch of ``dctr_gru_fwd`` for the whole time loop; DIEN's plain stack gru1 -> gru2 goes out as
+    a single launch through ``operands``.  Weight names are TensorFlow's variable names below the layer's scope: tf's GRUCell opens a
+    ``gru_cell`` scope (``gru_cell/gates/kernel`` ...), the contrib cells override ``__call__`` and do not (``gates/kernel`` ...).
+    Initial values as there: gate bias 1, candidate bias 0, kernels from get_variable's default glorot_uniform."""
+
+    def __init__(self, num_units=None, gru_type='GRU', return_sequence=True, **kwargs):
+        self.num_units = num_units
+        self.return_sequence = return_sequence
+        self.gru_type = gru_type
+        super(DynamicGRU, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        return self.build_for(int(input_shape[0][-1]))
+
+    def build_for(self, embedding_size):
+        if self.built:
+            return self
+        if self.num_units is None:
+            self.num_units = int(embedding_size)
+        if self.num_units != int(embedding_size):
+            raise NotImplementedError("DynamicGRU(num_units=%d) over inputs of width %d is outside this build: the kernel takes inputs and "
+                                      "units of one width (the reference's models pass num_units=None)" % (self.num_units, embedding_size))
+        E = self.num_units
+        self._scope = "" if self.gru_type in ("AGRU", "AUGRU") else "gru_cell/"
+        self.add_weight(self._scope + "gates/kernel", (2 * E, 2 * E), GlorotUniform())
+        self.add_weight(self._scope + "gates/bias", (2 * E,), Constant(1.0))
+        self.add_weight(self._scope + "candidate/kernel", (2 * E, E), GlorotUniform())
+        self.add_weight(self._scope + "candidate/bias", (E,), Constant(0.0))
+        self.built = True
+        return self
+
+    @property
+    def cell(self):
+        """The kernel's cell kind: 'AGRU' / 'AUGRU', and 'GRU' for every other gru_type (the reference's else branch, :777-781)."""
+        return self.gru_type if self.gru_type in ("AGRU", "AUGRU") else "GRU"
+
+    def operands(self):
+        """(gate kernel, gate bias, candidate kernel, candidate bias) as ops.dynamic_gru and training._gru take a layer."""
+        s = self._scope
+        return (self.w(s + "gates/kernel"), self.w(s + "gates/bias"), self.w(s + "candidate/kernel"), self.w(s + "candidate/bias"))
+
+    def run(self, x, lengths, att_scores=None, scale_input=False, out=None, out_stride=None):
+        return ops.dynamic_gru(x, lengths, [self.operands()], cell=self.cell, att_scores=att_scores, scale_input=scale_input,
+                               return_sequence=self.return_sequence, out=out, out_stride=out_stride)
+
+    def call(self, input_list, **kwargs):
+        if self.cell == "GRU":
+            rnn_input, sequence_length = input_list
+            att_score = None
+        else:
+            rnn_input, sequence_length, att_score = input_list
+            att_score = att_score.to(torch.float32).contiguous()
+        x = rnn_input if rnn_input.dtype == torch.float32 and rnn_input.stride(-1) == 1 else rnn_input.to(torch.float32).contiguous()
+        y = self.run(x, sequence_length.reshape(-1).to(torch.int32).contiguous(), att_score)
+        return y if self.return_sequence else y.reshape(y.shape[0], 1, y.shape[1])
+
+    def compute_output_shape(self, input_shape):
+        rnn_input_shape = input_shape[0]
+        if self.return_sequence:
+            return rnn_input_shape
+        return (None, 1, rnn_input_shape[2])
+
+    def get_config(self):
+        config = {'num_units': self.num_units, 'gru_type': self.gru_type, 'return_sequence': self.return_sequence}
+        base_config = super(DynamicGRU, self).get_config()
+        return dict(list(base_config.items()) + list(config.items()))

@@ -5,7 +5,8 @@ SENET + bilinear-interaction kernel, FwFM and DeepFEFM the field-pair kernel, ON
 IFM and DIFM the input-aware FM kernel, FLEN the field-wise bi-interaction kernel and its backward: the first of these to train on
 the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modules;
 SharedBottom, ESMM, MMOE and PLE — deepctr.models.multitask — the fused expert / gate level and tower kernels;
-BST — deepctr.models.sequence.bst — DIN's wiring with the fused Transformer sequence-block kernel)."""
+BST — deepctr.models.sequence.bst — DIN's wiring with the fused Transformer sequence-block kernel;
+DIEN — deepctr.models.sequence.dien — DIN's wiring with the fused recurrent GRU / AGRU / AUGRU kernel)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -23,6 +24,6 @@ from .multitask import ESMM, MMOE, PLE, SharedBottom
 from .nfm import NFM
 from .onn import ONN
 from .pnn import PNN
-from .sequence import BST, DIN
+from .sequence import BST, DIEN, DIN
 from .wdl import WDL
 from .xdeepfm import xDeepFM

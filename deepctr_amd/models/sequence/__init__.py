@@ -1,2 +1,3 @@
 from .din import DIN
 from .bst import BST
+from .dien import DIEN

@@ -22,6 +22,7 @@ class _DIN(FeatureModel):
     model_name = "DIN"
     key_hash_mode = 2            # the query / key lookups hash with mask_zero=True (din.py:66-69)
     key_mask_from_ids = True     # the key lookups write the (id != 0) attention mask; False: the subclass fills bufs["m"] itself
+    skip_varlen_extra = ()       # further sequence columns the stage neither pools nor feeds to the DNN (DIEN's neg_hist_*)
 
     def _build_sequence_block(self, seed, dnn_dropout):
         """Layers between the key lookups and the attention pooling (none in DIN; BST's Transformers)."""
@@ -53,7 +54,7 @@ class _DIN(FeatureModel):
             self.stage_plan = EmbeddingStage(self.tables, {}, [], dnn_feature_columns,
                                              mask_feat_list=tuple(self.history_feature_list),
                                              extra_dims=(("hist", self.key_dim),),
-                                             skip_varlen=tuple(hist_names), device=self.device)
+                                             skip_varlen=tuple(hist_names) + tuple(self.skip_varlen_extra), device=self.device)
             self._build_sequence_block(seed, dnn_dropout)
             self.attention = AttentionSequencePoolingLayer(att_hidden_size, att_activation,
                                                            weight_normalization=att_weight_normalization,

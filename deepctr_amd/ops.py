@@ -1926,6 +1926,97 @@ def layer_norm(x, gamma=None, beta=None, eps=1e-9, out=None):
     return out
 
 
+GRU_WEIGHTS = ("gate_kernel", "gate_bias", "candidate_kernel", "candidate_bias")
+
+
+def gru_macs(T, E, n_layers=1):
+    """Multiply-adds per sample of the recurrence: T x 6 E^2 per layer (4 E^2 gates + 2 E^2 candidate)."""
+    return int(n_layers) * int(T) * 6 * int(E) * int(E)
+
+
+def _gru_args(B, T, E, n_layers, cell, scale_input, return_sequence, route):
+    if cell not in _C.gru.CELLS:
+        raise ValueError("dynamic_gru: cell must be 'GRU', 'AGRU' or 'AUGRU', got %r" % (cell,))
+    if route not in _C.gru.ROUTES:
+        raise ValueError("dynamic_gru: route must be None, 'resident' or 'streamed', got %r" % (route,))
+    return _C.gru.Args(batch=int(B), x_stride=int(T) * int(E), x_row_stride=int(E), att_stride=int(T), seq_len=int(T), dim=int(E),
+                       n_layers=int(n_layers), cell=_C.gru.CELLS[cell], scale_input=int(bool(scale_input)),
+                       return_sequence=int(bool(return_sequence)), route=_C.gru.ROUTES[route],
+                       out_stride=int(T) * int(E) if return_sequence else int(E), out_row_stride=int(E))
+
+
+def gru_workspace_bytes(batch, seq_len, dim, n_layers=1, cell="GRU", scale_input=False, return_sequence=True, route=None):
+    """Bytes of the workspace dctr_gru_fwd needs for these shapes (0 while a workgroup's tiles fit the LDS; read from the library)."""
+    a = _gru_args(batch, seq_len, dim, n_layers, cell, scale_input, return_sequence, route)
+    return int(_C.lib().dctr_gru_workspace_bytes(ctypes.byref(a)))
+
+
+def gru_route(seq_len, dim, n_layers=1, cell="GRU", scale_input=False, return_sequence=True, route=None):
+    """'resident' or 'streamed': the route dctr_gru_fwd takes for these shapes (dctr_gru_route)."""
+    a = _gru_args(1, seq_len, dim, n_layers, cell, scale_input, return_sequence, route)
+    return _route_name("dctr_gru_route", _C.lib().dctr_gru_route(ctypes.byref(a)), (None, "resident", "streamed"))
+
+
+def dynamic_gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, return_sequence=True, out=None, out_stride=None,
+                route=None, workspace=None):
+    """DynamicGRU.call (reference sequence.py:786-803) over one or two stacked layers, the whole time loop in one launch.
+
+    ``x`` [B, T, E] float32 view (any sample / step strides, unit stride on the last axis); ``lengths`` int32 [B] (dynamic_rnn's
+    sequence_length: state copied through and zero rows at t >= length).  ``layers``: per layer (gate kernel [2E, 2E], gate bias [2E],
+    candidate kernel [2E, E], candidate bias [E]), or a dict of GRU_WEIGHTS.  ``cell``: 'GRU', 'AGRU' or 'AUGRU' (the attention-gated
+    cells take one layer); ``att_scores`` [B, T] (or [B, T, 1] / [B, 1, T] contiguous) for them and for ``scale_input`` (x_t times its
+    score: AIGRU).  ``out``: ``return_sequence`` a [B, T, E] view, else a [B, >= E] view with ``out_stride`` elements between samples
+    (the final state, written in place into a wider buffer); allocated when None.  Returns ``out``."""
+    op = "dynamic_gru"
+    if x.dim() != 3:
+        raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+    B, T, E = (int(v) for v in x.shape)
+    if not layers:
+        raise ValueError("dynamic_gru: at least one layer")
+    a = _gru_args(B, T, E, len(layers), cell, scale_input, return_sequence, route)
+    a.x_stride, a.x_row_stride = _seq3d(op, "x", x, B, T, E)
+    if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("dynamic_gru: lengths must be a contiguous int32 tensor of %d elements" % B)
+    need_att = cell != "GRU" or bool(scale_input)
+    if need_att:
+        if att_scores is None:
+            raise ValueError("dynamic_gru: cell %r%s needs att_scores" % (cell, " with scale_input" if scale_input else ""))
+        _vec(op, "att_scores", att_scores, B * T)
+    else:
+        att_scores = None
+    shapes = {"gate_kernel": (2 * E, 2 * E), "gate_bias": (1, 2 * E), "candidate_kernel": (2 * E, E), "candidate_bias": (1, E)}
+    flat = []
+    for li, layer in enumerate(layers):
+        if isinstance(layer, dict):
+            layer = [layer.get(name) for name in GRU_WEIGHTS]
+        if len(layer) != len(GRU_WEIGHTS) or any(w is None for w in layer):
+            raise ValueError("dynamic_gru: layer %d: needs %s" % (li, ", ".join(GRU_WEIGHTS)))
+        for name, w in zip(GRU_WEIGHTS, layer):
+            rows, cols = shapes[name]
+            if name.endswith("bias"):
+                _vec(op, "layer %d %s" % (li, name), w, cols)
+            elif _rows2d(op, "layer %d %s" % (li, name), w, rows, cols) != cols and rows > 1:
+                raise ValueError("dynamic_gru: layer %d: %s must be contiguous" % (li, name))
+            flat.append(w)
+    if out is None:
+        out = torch.empty((B, T, E) if return_sequence else (B, E), dtype=torch.float32, device=x.device)
+    if return_sequence:
+        a.out_stride, a.out_row_stride = _seq3d(op, "out", out, B, T, E)
+    else:
+        pitch = _rows2d(op, "out", out, B, E, at_least_rows=False)
+        a.out_stride = int(out_stride) if out_stride is not None else pitch
+        if a.out_stride < E:
+            raise ValueError("dynamic_gru: out_stride %d < dim %d" % (a.out_stride, E))
+    _dev_check(x, lengths, att_scores, out, *flat)
+    lp = _ptr_array(flat)
+    a.layers = ctypes.cast(lp, ctypes.c_void_p)
+    a.x, a.lengths, a.att_scores, a.out = x.data_ptr(), lengths.data_ptr(), _ptr(att_scores), out.data_ptr()
+    _workspace(op, a, int(_C.lib().dctr_gru_workspace_bytes(ctypes.byref(a))), workspace, x.device)
+    _C.check(_C.lib().dctr_gru_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_gru_fwd")
+    del lp
+    return out
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

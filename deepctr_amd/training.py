@@ -329,6 +329,39 @@ def _transformer(layer, queries, keys, query_mask, key_mask, training=False):
     return r
 
 
+def _gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, return_sequence=True):
+    """DynamicGRU.call (reference sequence.py:786-803) in torch ops: tf's GRUCell / the AGRU and AUGRU cells of contrib/utils.py
+    (:208-261, :327-378) under dynamic_rnn's sequence_length rule (contrib/rnn_v2.py:1324-1401) — at t >= length the state is copied
+    through and the emitted row is zero.  x [B,T,E], lengths [B], layers [(gate kernel [2E,2E], gate bias [2E], candidate kernel
+    [2E,E], candidate bias [E])] stacked, att_scores [B,T] -> [B,T,E], or the final state [B,E]."""
+    B, T, E = x.shape
+    lengths = lengths.reshape(-1)
+    a = None if att_scores is None else att_scores.reshape(B, T)
+    if scale_input:
+        x = x * a.unsqueeze(-1)
+    live = torch.arange(T, device=x.device)[None, :] < lengths[:, None]            # [B,T]
+    for wg, bg, wc, bc in layers:
+        h = torch.zeros(B, E, dtype=x.dtype, device=x.device)
+        rows = []
+        for t in range(T):
+            xt = x[:, t]
+            ru = torch.sigmoid(torch.cat([xt, h], dim=-1) @ wg + bg)
+            r, u = ru[:, :E], ru[:, E:]
+            c = torch.tanh(torch.cat([xt, r * h], dim=-1) @ wc + bc)
+            if cell == "AGRU":
+                at = a[:, t:t + 1]
+                hn = (1.0 - at) * h + at * c
+            else:
+                if cell == "AUGRU":
+                    u = (1.0 - a[:, t:t + 1]) * u
+                hn = u * h + (1.0 - u) * c
+            m = live[:, t:t + 1]
+            h = torch.where(m, hn, h)
+            rows.append(torch.where(m, hn, torch.zeros_like(hn)))
+        x = torch.stack(rows, dim=1)
+    return x if return_sequence else h
+
+
 def _bilinear(layer, x):
     """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
     itertools.combinations order."""
@@ -862,6 +895,10 @@ def _fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end, wt=None,
                     shown = loss.detach()
                 loss = (loss if wt is None else loss * wt[lo:hi]).mean()      # Keras: sum_b w_b l_b / B
                 shown = (shown if wt is None else shown * wt[lo:hi]).mean()
+                added = model._autograd_added_loss() if hasattr(model, "_autograd_added_loss") else None
+                if added is not None:                               # keras Model.add_loss (DIEN's alpha * auxiliary loss, dien.py:212-213)
+                    loss = loss + added
+                    shown = shown + added.detach()
                 for t, l2 in regs:                                  # keras adds the regularisation losses to the loss
                     pen = l2 * (t * t).sum()
                     loss = loss + pen

@@ -925,6 +925,65 @@ int dctr_layer_norm_fwd(const float* x, int64_t rows, int32_t dim, int64_t x_str
                         float* out, int64_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DynamicGRU.call — deepctr/layers/sequence.py:760-815 over tf.nn.rnn_cell.GRUCell and the attention-gated cells of
+ * deepctr/contrib/utils.py (QAAttGRUCell :208-261 "AGRU", VecAttGRUCell :327-378 "AUGRU") under dynamic_rnn(sequence_length=...)
+ * (contrib/rnn_v2.py:1324-1401): the whole time loop in one launch, one or two stacked layers (DIEN's gru1 -> gru2)
+ *     x [B, T, E] (sample stride x_stride, step stride x_row_stride, elements); inputs and units share the width E.
+ *     Per layer its four pointers gate kernel [2E, 2E], gate bias [2E], candidate kernel [2E, E], candidate bias [E] (Keras layout):
+ *       [r | u] = sigmoid([x_t | h] gate_kernel + gate_bias)              (gate order r then u)
+ *       c = tanh([x_t | r * h] candidate_kernel + candidate_bias)
+ *       GRU:   h' = u h + (1 - u) c
+ *       AGRU:  h' = (1 - a) h + a c
+ *       AUGRU: u <- (1 - a) u, then the GRU form                            a = att_scores[b, t]
+ *     h_0 = 0.  lengths [B] int32: at steps t >= length the state is copied through and the emitted row is zero; the final state
+ *     is the state at min(length, T); lengths <= 0 give a zero final state and all-zero rows, lengths > T behave as T.
+ *     scale_input: x_t is multiplied by att_scores[b, t] first (AIGRU's multiply([rnn_outputs, scores]) folded in).
+ *     n_layers = 2 (cell GRU only): layer 2's step t consumes layer 1's h_t on chip; layer 1's [B, T, E] is never written.
+ *     out: return_sequence 1 -> [B, T, E] at out_stride / out_row_stride, 0 -> the final state [B, E] at out_stride (so that it can
+ *     be written straight into its columns of a wider buffer).
+ *     Exact-fp32 products on v_mfma_f32_16x16x4_f32, sigmoid / tanh on the hardware exp and rcp (they saturate to 0 / 1 / -1 without
+ *     NaN), no atomics: the same bits on every call.  RESIDENT route: the weights of every layer stay in LDS for all T steps
+ *     (6 E^2 floats per layer next to the tiles within 160 KiB: E <= 74 for one layer, E <= 51 for two); STREAMED route: the same
+ *     step code with the weights read from global / L2 each step, and from E = 497 (308 for two layers) the tiles of a workgroup in a workspace of
+ *     dctr_gru_workspace_bytes() (room for <= 256 workgroups), which is then REQUIRED (DCTR_E_NULL without, before anything is
+ *     launched).  route = RESIDENT for weights that do not fit answers DCTR_E_UNSUPPORTED.  No shape is refused for its size.
+ *     Argument errors (nothing launched): NULL x / lengths / layers / out / a layer's pointer, NULL att_scores with an attention-gated
+ *     cell or scale_input (DCTR_E_NULL), seq_len or dim < 1, n_layers outside 1..2, strides smaller than the block (DCTR_E_DIM),
+ *     unknown cell / route, flags not 0 / 1, two layers with an attention-gated cell (DCTR_E_ENUM).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_GRU_CELL_GRU = 0, DCTR_GRU_CELL_AGRU = 1, DCTR_GRU_CELL_AUGRU = 2 };
+enum { DCTR_GRU_ROUTE_AUTO = 0, DCTR_GRU_ROUTE_RESIDENT = 1, DCTR_GRU_ROUTE_STREAMED = 2 };
+#define DCTR_GRU_LAYER_PTRS 4
+typedef struct {
+    int64_t batch;
+    const float* x;                  /* [B, T, E] fp32 */
+    int64_t x_stride;                /* elements between samples */
+    int64_t x_row_stride;            /* elements between steps, >= dim */
+    const int32_t* lengths;          /* [B] */
+    const float* att_scores;         /* NULL, or [B, T] at att_stride (AGRU / AUGRU / scale_input) */
+    int64_t att_stride;              /* elements between samples, >= seq_len */
+    int32_t seq_len;                 /* T >= 1 */
+    int32_t dim;                     /* E >= 1 */
+    int32_t n_layers;                /* 1 | 2 */
+    int32_t cell;                    /* DCTR_GRU_CELL_* */
+    int32_t scale_input;             /* 0 | 1 */
+    int32_t return_sequence;         /* 0 | 1 */
+    int32_t route;                   /* DCTR_GRU_ROUTE_AUTO | _RESIDENT | _STREAMED */
+    int32_t reserved;
+    const float* const* layers;      /* HOST array [n_layers * 4] of DEVICE pointers */
+    float* out;
+    int64_t out_stride;
+    int64_t out_row_stride;          /* return_sequence only */
+    void* workspace;                 /* NULL, or device scratch of dctr_gru_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_gru_args_t;
+/* Bytes dctr_gru_fwd needs (sizes, flags and route are read, pointers are not): 0 while a workgroup's tiles fit the LDS. */
+size_t dctr_gru_workspace_bytes(const dctr_gru_args_t* args);
+/* The route these arguments take (DCTR_GRU_ROUTE_RESIDENT / _STREAMED), or the DCTR_E_* the checks answer. */
+int dctr_gru_route(const dctr_gru_args_t* args);
+int dctr_gru_fwd(const dctr_gru_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
