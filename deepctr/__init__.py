@@ -2,14 +2,14 @@
 
 BASELINE north_star: the path "drops in under ``deepctr.models.{DeepFM,DCN,xDeepFM,DIN}``"; SURVEY.md §8(b) names the module
 paths a user's code imports: ``deepctr.feature_column``, ``deepctr.inputs``, ``deepctr.models`` (and
-``deepctr.models.<name>``, ``deepctr.models.sequence.{din,bst,dien}``), ``deepctr.layers`` (and ``deepctr.layers.{core,interaction,
+``deepctr.models.<name>``, ``deepctr.models.sequence.{din,bst,dien,dsin}``), ``deepctr.layers`` (and ``deepctr.layers.{core,interaction,
 sequence,normalization,activation,utils}``).  Every one of those modules IS the ``deepctr_amd`` module of the same name (registered under
 both names in ``sys.modules``), so classes are identical objects whichever way they are imported and the reference's example
 scripts (``examples/run_classification_criteo.py``, ``run_din.py`` ...) run unmodified.
 
 Differences from the reference package, on purpose: importing it performs no HTTP version check
 (reference ``deepctr/__init__.py:1-4`` -> ``utils.check_version`` starts a thread that queries PyPI), and only the §8
-scope exists: the other 4 model constructors, the Estimator API and ``deepctr.contrib`` raise ``ImportError`` /
+scope exists: the other 3 model constructors, the Estimator API and ``deepctr.contrib`` raise ``ImportError`` /
 ``AttributeError`` by absence.
 """
 import importlib
@@ -22,7 +22,7 @@ _ALIASES = (
     "layers", "layers.activation", "layers.core", "layers.interaction", "layers.normalization", "layers.sequence", "layers.utils",
     "models", "models.afm", "models.autoint", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.edcn", "models.fibinet",
     "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
-    "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.bst", "models.sequence.dien", "models.sequence.din",
+    "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.bst", "models.sequence.dien", "models.sequence.din", "models.sequence.dsin",
     "models.multitask", "models.multitask.esmm", "models.multitask.mmoe", "models.multitask.ple", "models.multitask.sharedbottom",
 )
 for _name in _ALIASES:

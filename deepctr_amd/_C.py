@@ -266,6 +266,22 @@ class gru(object):
                     ("out_stride", c_i64), ("out_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class lstm(object):
+    """dctr_lstm_args_t, one level down for the same reason as interacting.Args (tests/test_dsin_cpu.py checks the layout)."""
+    MERGES = {"fw": 0, "bw": 1, "sum": 2, "mul": 3, "ave": 4, "concat": 5, None: 6}
+    ACTIVATIONS = {"sigmoid": 0, "hard_sigmoid": 1}
+    ROUTE_AUTO, ROUTE_RESIDENT, ROUTE_STREAMED, ROUTE_WORKSPACE = 0, 1, 2, 3
+    ROUTES = {None: ROUTE_AUTO, "resident": ROUTE_RESIDENT, "streamed": ROUTE_STREAMED, "workspace": ROUTE_WORKSPACE}
+    LAYER_PTRS = 6      # fw kernel, fw recurrent kernel, fw bias, bw kernel, bw recurrent kernel, bw bias
+    MAX_LAYERS = 8
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_row_stride", c_i64), ("seq_len", c_i32), ("in_dim", c_i32),
+                    ("units", c_i32), ("n_layers", c_i32), ("res_layers", c_i32), ("merge_mode", c_i32), ("recurrent_activation", c_i32),
+                    ("route", c_i32), ("layers", c_vp), ("out", c_vp), ("out_stride", c_i64), ("out_row_stride", c_i64), ("out_bw", c_vp),
+                    ("out_bw_stride", c_i64), ("out_bw_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
+
+
 class mtl(object):
     """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
     layout)."""
@@ -394,6 +410,10 @@ SYMBOLS = {
     "dctr_gru_workspace_bytes": (c_sz, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_route": (ctypes.c_int, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_fwd": (ctypes.c_int, [ctypes.POINTER(gru.Args), c_vp]),
+    "dctr_bilstm_workspace_bytes": (c_sz, [ctypes.POINTER(lstm.Args)]),
+    "dctr_bilstm_route": (ctypes.c_int, [ctypes.POINTER(lstm.Args)]),
+    "dctr_bilstm_fwd": (ctypes.c_int, [ctypes.POINTER(lstm.Args), c_vp]),
+    "dctr_bias_encoding_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "dctr_layer_norm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "dctr_mtl_route": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_i32]),
     "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),

@@ -57,6 +57,7 @@ SOURCES = [
     "mtl_kernels.hip",
     "transformer_kernels.hip",
     "gru_kernels.hip",
+    "lstm_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -103,5 +103,26 @@ class TruncatedNormal(Initializer):
         return t.to(dtype)
 
 
+class Orthogonal(Initializer):
+    """keras Orthogonal (the LSTM's recurrent_initializer): Q of the QR decomposition of a seeded normal matrix, its columns' signs
+    fixed by the diagonal of R, times ``gain``; a [rows, cols] weight with rows < cols is the transpose of the [cols, rows] draw."""
+
+    def __init__(self, gain=1.0, seed=None):
+        self.gain, self.seed = gain, seed
+
+    def __call__(self, shape, dtype=torch.float32):
+        shape = tuple(shape)
+        cols = shape[-1]
+        rows = 1
+        for s in shape[:-1]:
+            rows *= s
+        a = torch.randn((max(rows, cols), min(rows, cols)), generator=_gen(self.seed), dtype=torch.float64)
+        q, r = torch.linalg.qr(a)
+        q = q * torch.sign(torch.diagonal(r))
+        if rows < cols:
+            q = q.t()
+        return (self.gain * q).reshape(shape).to(dtype)
+
+
 glorot_normal = GlorotNormal
 glorot_uniform = GlorotUniform

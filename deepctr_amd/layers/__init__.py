@@ -6,7 +6,7 @@ from .core import DNN, Dense, LocalActivationUnit, PredictionLayer, RegulationMo
 from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, BridgeModule, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
                           FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
 from .normalization import LayerNormalization
-from .sequence import AttentionSequencePoolingLayer, DynamicGRU, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
+from .sequence import AttentionSequencePoolingLayer, BiLSTM, BiasEncoding, DynamicGRU, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
 custom_objects = {
@@ -35,6 +35,8 @@ custom_objects = {
     'Transformer': Transformer,
     'PositionEncoding': PositionEncoding,
     'DynamicGRU': DynamicGRU,
+    'BiLSTM': BiLSTM,
+    'BiasEncoding': BiasEncoding,
     'LayerNormalization': LayerNormalization,
     'Hash': Hash,
     'Linear': Linear,

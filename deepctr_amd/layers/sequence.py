@@ -1,6 +1,7 @@
 """Host mirror of the in-scope layers of the reference's ``deepctr/layers/sequence.py``:
 ``SequencePoolingLayer`` (:41-120), ``WeightedSequenceLayer`` (:123-197), ``AttentionSequencePoolingLayer``
-(:200-315), ``Transformer`` (:431-651), ``PositionEncoding`` (:654-703) and ``DynamicGRU`` (:760-815).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
+(:200-315), ``BiLSTM`` (:318-428), ``Transformer`` (:431-651), ``PositionEncoding`` (:654-703), ``BiasEncoding`` (:706-757) and
+``DynamicGRU`` (:760-815).  In the model path pooling is fused INTO the embedding gather (``dctr_embed_pool``: ids ->
 pooled vector, the [B,T,E] tensor never exists); these classes are the stand-alone layer API over an
 already gathered [B,T,E] tensor.  Stand-alone pooling of a materialised tensor is pure data movement, done
 here with the same kernel by treating the sequence tensor as its own table."""
@@ -8,8 +9,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..initializers import Constant, GlorotUniform, TruncatedNormal
-from .base import Layer
+from ..initializers import Constant, GlorotUniform, Orthogonal, TruncatedNormal
+from .base import Layer, next_auto_name
 from .core import LocalActivationUnit
 from .normalization import LayerNormalization
 
@@ -400,4 +401,138 @@ class DynamicGRU(Layer):
     def get_config(self):
         config = {'num_units': self.num_units, 'gru_type': self.gru_type, 'return_sequence': self.return_sequence}
         base_config = super(DynamicGRU, self).get_config()
+        return dict(list(base_config.items()) + list(config.items()))
+
+
+class _LSTMWeights(Layer):
+    """The weights of one tf.keras.layers.LSTM under keras' names: ``kernel`` [D, 4u], ``recurrent_kernel`` [u, 4u], ``bias`` [4u], gate
+    order i | f | c~ | o.  Initial values as BiLSTM builds them (reference sequence.py:365-370): kernel glorot_uniform, recurrent kernel
+    orthogonal, bias ones (``bias_initializer='ones'``; keras' unit_forget_bias then leaves every quarter at one)."""
+
+    def __init__(self, input_dim, units, **kwargs):
+        super(_LSTMWeights, self).__init__(name=next_auto_name("lstm"), **kwargs)
+        self.add_weight("kernel", (input_dim, 4 * units), GlorotUniform())
+        self.add_weight("recurrent_kernel", (units, 4 * units), Orthogonal())
+        self.add_weight("bias", (4 * units,), Constant(1.0))
+        self.built = True
+
+    def operands(self):
+        return (self.w("kernel"), self.w("recurrent_kernel"), self.w("bias"))
+
+
+class BiLSTM(Layer):
+    """A multiple layer bidirectional residual LSTM (reference sequence.py:318-428): one launch of ``dctr_bilstm_fwd`` for both stacks.
+    ``dropout_rate`` is the LSTMs' input dropout: inactive at inference, applied by the torch restatement under fit()
+    (training._bilstm).  keras' masked-step rule (a masked step copies the state through) is outside this build: a mask raises
+    NotImplementedError; in DSIN none reaches the layer (Transformer.compute_mask returns None)."""
+
+    def __init__(self, units, layers=2, res_layers=0, dropout_rate=0.2, merge_mode='ave', **kwargs):
+        if merge_mode not in ['fw', 'bw', 'sum', 'mul', 'ave', 'concat', None]:
+            raise ValueError('Invalid merge mode. '
+                             'Merge mode should be one of '
+                             '{"fw","bw","sum", "mul", "ave", "concat", None}')
+        self.units = units
+        self.layers = layers
+        self.res_layers = res_layers
+        self.dropout_rate = dropout_rate
+        self.merge_mode = merge_mode
+        self.recurrent_activation = "sigmoid"       # the TF 2.x default; 'hard_sigmoid' serves weights trained under TF 1.x
+        super(BiLSTM, self).__init__(**kwargs)
+        self.supports_masking = True
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        return self.build_for(int(input_shape[-1]))
+
+    def build_for(self, input_dim):
+        if self.built:
+            return self
+        if self.res_layers >= self.layers and int(input_dim) != int(self.units):
+            raise ValueError("BiLSTM: a residual over layer 0 needs inputs of the units' width, got %d and %d" % (input_dim, self.units))
+        self.fw_lstm, self.bw_lstm = [], []
+        for i in range(self.layers):
+            D = int(input_dim) if i == 0 else int(self.units)
+            self.fw_lstm.append(_LSTMWeights(D, int(self.units), device=self.device))
+            self.bw_lstm.append(_LSTMWeights(D, int(self.units), device=self.device))
+            self._sublayers += [self.fw_lstm[-1], self.bw_lstm[-1]]
+        self.built = True
+        return self
+
+    def operands(self):
+        """Per layer (fw kernel, fw recurrent kernel, fw bias, bw kernel, bw recurrent kernel, bw bias) as ops.bilstm and
+        training._bilstm take it."""
+        return [f.operands() + b.operands() for f, b in zip(self.fw_lstm, self.bw_lstm)]
+
+    def run(self, x, out=None):
+        return ops.bilstm(x, self.operands(), res_layers=self.res_layers, merge_mode=self.merge_mode,
+                          recurrent_activation=self.recurrent_activation, out=out)
+
+    def call(self, inputs, mask=None, **kwargs):
+        if mask is not None:
+            raise NotImplementedError("BiLSTM over masked inputs is outside this build: keras' masked-step rule has no kernel")
+        x = inputs if inputs.dtype == torch.float32 and inputs.stride(-1) == 1 else inputs.to(torch.float32).contiguous()
+        y = self.run(x)
+        return list(y) if self.merge_mode is None else y
+
+    def compute_output_shape(self, input_shape):
+        if self.merge_mode is None:
+            return [input_shape, input_shape]
+        elif self.merge_mode == 'concat':
+            return input_shape[:-1] + (input_shape[-1] * 2,)
+        return input_shape
+
+    def compute_mask(self, inputs, mask=None):
+        return mask
+
+    def get_config(self):
+        config = {'units': self.units, 'layers': self.layers, 'res_layers': self.res_layers, 'dropout_rate': self.dropout_rate,
+                  'merge_mode': self.merge_mode}
+        base_config = super(BiLSTM, self).get_config()
+        return dict(list(base_config.items()) + list(config.items()))
+
+
+class BiasEncoding(Layer):
+    """Session, position and item biases added to every session's [B, T, E] embeddings (reference sequence.py:706-757).  Inside DSIN
+    ``dctr_bias_encoding_fwd`` adds them in place over the [B, S, T, E] lookup buffer; stand-alone the layer takes the reference's
+    list of ``sess_max_count`` tensors (one tensor when ``sess_max_count`` is 1) and returns a list."""
+
+    def __init__(self, sess_max_count, seed=1024, **kwargs):
+        self.sess_max_count = sess_max_count
+        self.seed = seed
+        super(BiasEncoding, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        shape = input_shape if self.sess_max_count == 1 and not isinstance(input_shape, list) else input_shape[0]
+        return self.build_for(int(shape[1]), int(shape[2]))
+
+    def build_for(self, seq_len_max, embed_size):
+        if self.built:
+            return self
+        init = lambda: TruncatedNormal(mean=0.0, stddev=0.0001, seed=self.seed)    # noqa: E731
+        self.add_weight('sess_bias_embedding', (self.sess_max_count, 1, 1), init())
+        self.add_weight('seq_bias_embedding', (1, seq_len_max, 1), init())
+        self.add_weight('item_bias_embedding', (1, 1, embed_size), init())
+        self.built = True
+        return self
+
+    def run(self, x):
+        """In place over a float32 [B, S, T, E] view."""
+        return ops.bias_encoding(x, self.w('sess_bias_embedding'), self.w('seq_bias_embedding'), self.w('item_bias_embedding'))
+
+    def call(self, inputs, mask=None):
+        seqs = [inputs] if isinstance(inputs, torch.Tensor) else list(inputs)
+        x = torch.stack([t.to(torch.float32) for t in seqs[:self.sess_max_count]], dim=1).contiguous()
+        self.run(x)
+        return [x[:, i] for i in range(self.sess_max_count)]
+
+    def compute_output_shape(self, input_shape):
+        return input_shape
+
+    def compute_mask(self, inputs, mask=None):
+        return mask
+
+    def get_config(self):
+        config = {'sess_max_count': self.sess_max_count, 'seed': self.seed}
+        base_config = super(BiasEncoding, self).get_config()
         return dict(list(base_config.items()) + list(config.items()))

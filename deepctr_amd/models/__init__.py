@@ -6,7 +6,8 @@ IFM and DIFM the input-aware FM kernel, FLEN the field-wise bi-interaction kerne
 the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modules;
 SharedBottom, ESMM, MMOE and PLE — deepctr.models.multitask — the fused expert / gate level and tower kernels;
 BST — deepctr.models.sequence.bst — DIN's wiring with the fused Transformer sequence-block kernel;
-DIEN — deepctr.models.sequence.dien — DIN's wiring with the fused recurrent GRU / AGRU / AUGRU kernel)."""
+DIEN — deepctr.models.sequence.dien — DIN's wiring with the fused recurrent GRU / AGRU / AUGRU kernel;
+DSIN — deepctr.models.sequence.dsin — sessions through the Transformer kernel, then the fused bidirectional LSTM kernel)."""
 from .afm import AFM
 from .autoint import AutoInt
 from .dcn import DCN
@@ -24,6 +25,6 @@ from .multitask import ESMM, MMOE, PLE, SharedBottom
 from .nfm import NFM
 from .onn import ONN
 from .pnn import PNN
-from .sequence import BST, DIEN, DIN
+from .sequence import BST, DIEN, DIN, DSIN
 from .wdl import WDL
 from .xdeepfm import xDeepFM

@@ -2017,6 +2017,124 @@ def dynamic_gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=Fal
     return out
 
 
+LSTM_WEIGHTS = ("fw_kernel", "fw_recurrent_kernel", "fw_bias", "bw_kernel", "bw_recurrent_kernel", "bw_bias")
+
+
+def bilstm_macs(T, Din, u, n_layers=1):
+    """Multiply-adds per sample of both stacks: T x 2 x 4u (D + u) per layer, D = Din for layer 0 and u after it."""
+    T, Din, u = int(T), int(Din), int(u)
+    return T * 2 * 4 * u * ((Din + u) + (int(n_layers) - 1) * 2 * u)
+
+
+def _bilstm_args(B, T, Din, u, n_layers, res_layers, merge_mode, recurrent_activation, route):
+    if merge_mode not in _C.lstm.MERGES:
+        raise ValueError('Invalid merge mode. Merge mode should be one of {"fw","bw","sum", "mul", "ave", "concat", None}')
+    if recurrent_activation not in _C.lstm.ACTIVATIONS:
+        raise ValueError("bilstm: recurrent_activation must be 'sigmoid' or 'hard_sigmoid', got %r" % (recurrent_activation,))
+    if route not in _C.lstm.ROUTES:
+        raise ValueError("bilstm: route must be None, 'resident', 'streamed' or 'workspace', got %r" % (route,))
+    n_layers, res_layers = int(n_layers), int(res_layers)
+    if not 1 <= n_layers <= _C.lstm.MAX_LAYERS:
+        raise ValueError("bilstm: 1 to %d layers, got %d" % (_C.lstm.MAX_LAYERS, n_layers))
+    if res_layers >= n_layers and int(Din) != int(u):
+        raise ValueError("bilstm: a residual over layer 0 needs inputs of the units' width, got %d and %d" % (Din, u))
+    w = (2 if merge_mode == "concat" else 1) * int(u)
+    return _C.lstm.Args(batch=int(B), x_stride=int(T) * int(Din), x_row_stride=int(Din), seq_len=int(T), in_dim=int(Din), units=int(u),
+                        n_layers=n_layers, res_layers=max(res_layers, 0), merge_mode=_C.lstm.MERGES[merge_mode],
+                        recurrent_activation=_C.lstm.ACTIVATIONS[recurrent_activation], route=_C.lstm.ROUTES[route],
+                        out_stride=int(T) * w, out_row_stride=w, out_bw_stride=int(T) * int(u), out_bw_row_stride=int(u))
+
+
+def bilstm_workspace_bytes(batch, T, Din, u, n_layers, res_layers=0, merge_mode="ave", route=None):
+    """Bytes of the workspace dctr_bilstm_fwd needs for these shapes (0 while a workgroup's tiles fit the LDS; read from the library)."""
+    a = _bilstm_args(batch, T, Din, u, n_layers, res_layers, merge_mode, "sigmoid", route)
+    return int(_C.lib().dctr_bilstm_workspace_bytes(ctypes.byref(a)))
+
+
+def bilstm_route(T, Din, u, n_layers, res_layers=0, merge_mode="ave", route=None):
+    """'resident' or 'streamed': the route dctr_bilstm_fwd takes for these shapes (dctr_bilstm_route)."""
+    a = _bilstm_args(1, T, Din, u, n_layers, res_layers, merge_mode, "sigmoid", route)
+    return _route_name("dctr_bilstm_route", _C.lib().dctr_bilstm_route(ctypes.byref(a)), (None, "resident", "streamed"))
+
+
+def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", out=None, route=None, workspace=None):
+    """BiLSTM.call (reference sequence.py:375-409) over keras' LSTM: both stacks of len(layers) layers in one launch.
+
+    ``x`` [B, T, Din] float32 view (any sample / step strides, unit stride on the last axis).  ``layers``: per layer (fw kernel [D, 4u],
+    fw recurrent kernel [u, 4u], fw bias [4u], then the same three of the backward stack), or a dict of LSTM_WEIGHTS; D = Din for
+    layer 0 and u after it, gate order i | f | c~ | o.  The last ``res_layers`` layers add their input to their output.  ``merge_mode``:
+    'fw', 'bw', 'sum', 'mul', 'ave' -> [B, T, u], 'concat' -> [B, T, 2u], None -> the pair (fw, bw).  ``out``: a view of that shape (a
+    pair for None), allocated when None.  Returns ``out``."""
+    op = "bilstm"
+    if x.dim() != 3:
+        raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+    B, T, Din = (int(v) for v in x.shape)
+    if not layers:
+        raise ValueError("bilstm: at least one layer")
+    rows = []
+    for li, layer in enumerate(layers):
+        if isinstance(layer, dict):
+            layer = [layer.get(name) for name in LSTM_WEIGHTS]
+        if len(layer) != len(LSTM_WEIGHTS) or any(w is None for w in layer):
+            raise ValueError("bilstm: layer %d: needs %s" % (li, ", ".join(LSTM_WEIGHTS)))
+        rows.append(layer)
+    u = int(rows[0][1].shape[0])
+    a = _bilstm_args(B, T, Din, u, len(rows), res_layers, merge_mode, recurrent_activation, route)
+    a.x_stride, a.x_row_stride = _seq3d(op, "x", x, B, T, Din)
+    flat = []
+    for li, layer in enumerate(rows):
+        D = Din if li == 0 else u
+        shapes = {"kernel": (D, 4 * u), "recurrent_kernel": (u, 4 * u)}
+        for name, w in zip(LSTM_WEIGHTS, layer):
+            what = "layer %d %s" % (li, name)
+            if name.endswith("bias"):
+                _vec(op, what, w, 4 * u)
+            else:
+                r, c = shapes[name[3:]]
+                if _rows2d(op, what, w, r, c) != c and r > 1:
+                    raise ValueError("bilstm: %s must be contiguous" % what)
+            flat.append(w)
+    wout = 2 * u if merge_mode == "concat" else u
+    if merge_mode is None:
+        out_fw, out_bw = out if out is not None else (None, None)
+    else:
+        out_fw, out_bw = out, None
+    if out_fw is None:
+        out_fw = torch.empty((B, T, wout), dtype=torch.float32, device=x.device)
+    a.out_stride, a.out_row_stride = _seq3d(op, "out", out_fw, B, T, wout)
+    if merge_mode is None:
+        if out_bw is None:
+            out_bw = torch.empty((B, T, u), dtype=torch.float32, device=x.device)
+        a.out_bw_stride, a.out_bw_row_stride = _seq3d(op, "out (backward)", out_bw, B, T, u)
+    _dev_check(x, out_fw, out_bw, *flat)
+    lp = _ptr_array(flat)
+    a.layers = ctypes.cast(lp, ctypes.c_void_p)
+    a.x, a.out, a.out_bw = x.data_ptr(), out_fw.data_ptr(), _ptr(out_bw)
+    _workspace(op, a, int(_C.lib().dctr_bilstm_workspace_bytes(ctypes.byref(a))), workspace, x.device)
+    _C.check(_C.lib().dctr_bilstm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_bilstm_fwd")
+    del lp
+    return (out_fw, out_bw) if merge_mode is None else out_fw
+
+
+def bias_encoding(x, sess_bias, seq_bias, item_bias):
+    """BiasEncoding.call (reference sequence.py:735-744) in place: ``x`` a float32 [B, S, T, E] view with unit stride on the last axis,
+    x[b, s, t, e] += item_bias[e] + seq_bias[t] + sess_bias[s].  Returns ``x``."""
+    op = "bias_encoding"
+    if x.dim() != 4 or x.dtype != torch.float32 or (x.shape[3] > 1 and x.stride(3) != 1):
+        raise ValueError("bias_encoding: x must be a float32 [B, S, T, E] view with unit stride on the last axis")
+    B, S, T, E = (int(v) for v in x.shape)
+    _vec(op, "sess_bias", sess_bias, S)
+    _vec(op, "seq_bias", seq_bias, T)
+    _vec(op, "item_bias", item_bias, E)
+    row = int(x.stride(2)) if T != 1 else max(int(x.stride(2)), E)
+    sess = int(x.stride(1)) if S != 1 else max(int(x.stride(1)), (T - 1) * row + E)
+    sample = int(x.stride(0)) if B > 1 else max(int(x.stride(0)), (S - 1) * sess + (T - 1) * row + E)
+    _dev_check(x, sess_bias, seq_bias, item_bias)
+    _C.check(_C.lib().dctr_bias_encoding_fwd(_ptr(x), B, S, T, E, sample, sess, row, _ptr(sess_bias), _ptr(seq_bias), _ptr(item_bias),
+                                             _C.stream_ptr()), "dctr_bias_encoding_fwd")
+    return x
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

@@ -362,6 +362,55 @@ def _gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, ret
     return x if return_sequence else h
 
 
+def _bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", dropout_rate=0.0, training=False):
+    """BiLSTM.call (reference sequence.py:375-409) over keras' LSTM in torch ops.  x [B,T,Din]; layers [(fw kernel [D,4u], fw recurrent
+    kernel [u,4u], fw bias [4u], bw kernel, bw recurrent kernel, bw bias)], gate order i | f | c~ | o; every step runs (no mask).  The
+    backward stack walks t = T-1 .. 0 and its output is put back into time order before the next layer.  ``training``: the input
+    dropout of every LSTM, one mask [B,1,D] per LSTM and call shared over the steps (keras' implementation=2).  Returns [B,T,u]
+    ([B,T,2u] for 'concat', the pair (fw, bw) for None)."""
+    gate = torch.sigmoid if recurrent_activation == "sigmoid" else (lambda z: torch.clamp(0.2 * z + 0.5, 0.0, 1.0))
+
+    def lstm(seq, w, u_, b, backwards):
+        B, T, _ = seq.shape
+        n = u_.shape[0]
+        if training and dropout_rate:
+            seq = seq * _dropout(torch.ones_like(seq[:, :1]), dropout_rate, True)
+        zx = seq @ w + b
+        h = torch.zeros(B, n, dtype=seq.dtype, device=seq.device)
+        c = torch.zeros_like(h)
+        rows = [None] * T
+        for t in (range(T - 1, -1, -1) if backwards else range(T)):
+            z = zx[:, t] + h @ u_
+            i, f, o = gate(z[:, :n]), gate(z[:, n:2 * n]), gate(z[:, 3 * n:])
+            c = f * c + i * torch.tanh(z[:, 2 * n:3 * n])
+            h = o * torch.tanh(c)
+            rows[t] = h
+        return torch.stack(rows, dim=1)
+
+    fw = bw = x
+    L = len(layers)
+    for li, (wf, uf, bf, wb, ub, bb) in enumerate(layers):
+        of, ob = lstm(fw, wf, uf, bf, False), lstm(bw, wb, ub, bb, True)
+        if li >= L - res_layers:
+            of, ob = of + fw, ob + bw
+        fw, bw = of, ob
+    if merge_mode == "fw":
+        return fw
+    if merge_mode == "bw":
+        return bw
+    if merge_mode == "concat":
+        return torch.cat([fw, bw], dim=-1)
+    if merge_mode == "sum":
+        return fw + bw
+    if merge_mode == "ave":
+        return (fw + bw) / 2
+    if merge_mode == "mul":
+        return fw * bw
+    if merge_mode is None:
+        return fw, bw
+    raise ValueError('Invalid merge mode. Merge mode should be one of {"fw","bw","sum", "mul", "ave", "concat", None}')
+
+
 def _bilinear(layer, x):
     """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
     itertools.combinations order."""

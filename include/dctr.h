@@ -984,6 +984,68 @@ int dctr_gru_route(const dctr_gru_args_t* args);
 int dctr_gru_fwd(const dctr_gru_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * BiLSTM.call — deepctr/layers/sequence.py:318-428 over tf.keras.layers.LSTM as documented: two independent stacks of n_layers LSTMs,
+ * the whole of both in one launch (DSIN's session-interest interaction, models/sequence/dsin.py:121-122)
+ *     x [B, T, in_dim] (sample stride x_stride, step stride x_row_stride, elements).
+ *     Per layer its six pointers fw kernel [D, 4u], fw recurrent kernel [u, 4u], fw bias [4u], then the same three of the backward
+ *     stack (Keras layout; D = in_dim for layer 0, units after it), gate order i | f | c~ | o:
+ *       z = x_t W + h U + b;  i, f, o = sigma(z_i, z_f, z_o);  g = tanh(z_c);  c' = f c + i g;  h' = o tanh(c');  h_0 = c_0 = 0
+ *     The forward stack walks t = 0 .. T-1, the backward stack t = T-1 .. 0 with every layer's output back in time order before it
+ *     feeds the next.  No mask, no lengths: every step runs.  Layer l >= n_layers - res_layers adds its input to its output, in each
+ *     stack (res_layers > n_layers behaves as n_layers; a residual over layer 0 needs in_dim == units).
+ *     recurrent_activation: sigma = sigmoid (0, the TF 2.x default) or hard_sigmoid clip(0.2 z + 0.5, 0, 1) (1, the TF 1.x default).
+ *     merge_mode: out [B, T, u] = fw | bw | fw + bw | fw * bw | (fw + bw) / 2, CONCAT out [B, T, 2u] = [fw | bw], NONE fw -> out and
+ *     bw -> out_bw.  out at out_stride / out_row_stride: columns beside the written ones are left alone.
+ *     Exact-fp32 products on v_mfma_f32_16x16x4_f32, sigmoid / tanh on the hardware exp and rcp (they saturate without NaN), no
+ *     atomics: the same bits on every call.  RESIDENT route: the current layer's kernels of both directions stay in LDS for its T
+ *     steps (next to the tiles within 160 KiB); STREAMED route: the same step code with the kernels read from global / L2;
+ *     WORKSPACE: streamed, with a workgroup's tiles in a workspace of dctr_bilstm_workspace_bytes() (room for <= 256 workgroups) —
+ *     taken by AUTO when the tiles exceed the LDS — which is then REQUIRED (DCTR_E_NULL without, before anything is launched).
+ *     route = RESIDENT for kernels that do not fit answers DCTR_E_UNSUPPORTED.  No shape is refused for its size.
+ *     Argument errors (nothing launched): NULL x / layers / out / a layer's pointer, NULL out_bw with NONE (DCTR_E_NULL), sizes < 1,
+ *     n_layers outside 1..DCTR_LSTM_MAX_LAYERS, res_layers < 0, a residual over in_dim != units, strides smaller than the block
+ *     (DCTR_E_DIM), unknown merge_mode / recurrent_activation / route (DCTR_E_ENUM), on the RESIDENT route a kernel or recurrent
+ *     kernel that is not 16-byte aligned (DCTR_E_ALIGN: the copy into LDS reads them 16 bytes at a time).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_LSTM_MERGE_FW = 0, DCTR_LSTM_MERGE_BW = 1, DCTR_LSTM_MERGE_SUM = 2, DCTR_LSTM_MERGE_MUL = 3, DCTR_LSTM_MERGE_AVE = 4,
+       DCTR_LSTM_MERGE_CONCAT = 5, DCTR_LSTM_MERGE_NONE = 6 };
+enum { DCTR_LSTM_ROUTE_AUTO = 0, DCTR_LSTM_ROUTE_RESIDENT = 1, DCTR_LSTM_ROUTE_STREAMED = 2, DCTR_LSTM_ROUTE_WORKSPACE = 3 };
+#define DCTR_LSTM_LAYER_PTRS 6
+#define DCTR_LSTM_MAX_LAYERS 8
+typedef struct {
+    int64_t batch;
+    const float* x;                  /* [B, T, in_dim] fp32 */
+    int64_t x_stride;                /* elements between samples */
+    int64_t x_row_stride;            /* elements between steps, >= in_dim */
+    int32_t seq_len;                 /* T >= 1 */
+    int32_t in_dim;                  /* >= 1 */
+    int32_t units;                   /* u >= 1 */
+    int32_t n_layers;                /* 1 .. DCTR_LSTM_MAX_LAYERS */
+    int32_t res_layers;              /* >= 0 */
+    int32_t merge_mode;              /* DCTR_LSTM_MERGE_* */
+    int32_t recurrent_activation;    /* 0 sigmoid | 1 hard_sigmoid */
+    int32_t route;                   /* DCTR_LSTM_ROUTE_* */
+    const float* const* layers;      /* HOST array [n_layers * 6] of DEVICE pointers */
+    float* out;
+    int64_t out_stride;
+    int64_t out_row_stride;
+    float* out_bw;                   /* DCTR_LSTM_MERGE_NONE only */
+    int64_t out_bw_stride;
+    int64_t out_bw_row_stride;
+    void* workspace;                 /* NULL, or device scratch of dctr_bilstm_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_lstm_args_t;
+/* Bytes dctr_bilstm_fwd needs (sizes, flags and route are read, pointers are not): 0 while a workgroup's tiles fit the LDS. */
+size_t dctr_bilstm_workspace_bytes(const dctr_lstm_args_t* args);
+/* The route these arguments take (DCTR_LSTM_ROUTE_RESIDENT, or _STREAMED with or without a workspace), or the DCTR_E_* the checks answer. */
+int dctr_bilstm_route(const dctr_lstm_args_t* args);
+int dctr_bilstm_fwd(const dctr_lstm_args_t* args, void* stream);
+/* BiasEncoding.call — deepctr/layers/sequence.py:735-744, in place over a [B, S, T, E] view (sample / session / step strides in
+ * elements, unit stride on the last axis): x[b, s, t, e] += item_bias[e] + seq_bias[t] + sess_bias[s]. */
+int dctr_bias_encoding_fwd(float* x, int64_t batch, int32_t sess, int32_t seq_len, int32_t dim, int64_t x_stride, int64_t sess_stride,
+                           int64_t row_stride, const float* sess_bias, const float* seq_bias, const float* item_bias, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
