@@ -282,6 +282,22 @@ class lstm(object):
                     ("out_bw_stride", c_i64), ("out_bw_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class fieldconv(object):
+    """dctr_fieldconv_args_t, one level down for the same reason as interacting.Args (tests/test_ccpm_fgcnn_cpu.py checks the layout)."""
+    POOL_KMAX, POOL_MAX = 0, 1
+    POOLS = {"kmax": POOL_KMAX, "max": POOL_MAX}
+    ROUTE_AUTO, ROUTE_RESIDENT, ROUTE_STREAMED, ROUTE_WORKSPACE = 0, 1, 2, 3
+    ROUTES = {None: ROUTE_AUTO, "resident": ROUTE_RESIDENT, "streamed": ROUTE_STREAMED, "workspace": ROUTE_WORKSPACE}
+    MAX_STAGES = 8
+
+    class Args(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("x", c_vp), ("x_stride", c_i64), ("x_offset", c_i64), ("fields", c_i32), ("dim", c_i32),
+                    ("in_channels", c_i32), ("n_stages", c_i32), ("route", c_i32), ("reserved", c_i32), ("widths", c_vp),
+                    ("channels", c_vp), ("pool_kinds", c_vp), ("pool_args", c_vp), ("kernels", c_vp), ("biases", c_vp), ("out", c_vp),
+                    ("out_stride", c_i64), ("out_offset", c_i64), ("stage_outs", c_vp), ("stage_out_strides", c_vp), ("workspace", c_vp),
+                    ("workspace_bytes", c_sz)]
+
+
 class mtl(object):
     """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
     layout)."""
@@ -414,6 +430,10 @@ SYMBOLS = {
     "dctr_bilstm_route": (ctypes.c_int, [ctypes.POINTER(lstm.Args)]),
     "dctr_bilstm_fwd": (ctypes.c_int, [ctypes.POINTER(lstm.Args), c_vp]),
     "dctr_bias_encoding_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "dctr_fieldconv_workspace_bytes": (c_sz, [ctypes.POINTER(fieldconv.Args)]),
+    "dctr_fieldconv_route": (ctypes.c_int, [ctypes.POINTER(fieldconv.Args)]),
+    "dctr_fieldconv_fwd": (ctypes.c_int, [ctypes.POINTER(fieldconv.Args), c_vp]),
+    "dctr_kmax_pool_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "dctr_layer_norm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp]),
     "dctr_mtl_route": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_i32]),
     "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),

@@ -58,6 +58,7 @@ SOURCES = [
     "transformer_kernels.hip",
     "gru_kernels.hip",
     "lstm_kernels.hip",
+    "fieldconv_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",
     "gemm_kernels.hip",

@@ -4,9 +4,9 @@ siblings need — SURVEY.md §8a)."""
 from .activation import Dice
 from .core import DNN, Dense, LocalActivationUnit, PredictionLayer, RegulationModule
 from .interaction import (AFMLayer, BiInteractionPooling, BilinearInteraction, BridgeModule, CIN, CrossNet, CrossNetMix, FEFMLayer, FM,
-                          FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
+                          FGCNNLayer, FieldWiseBiInteraction, FwFMLayer, InnerProductLayer, InteractingLayer, SENETLayer)
 from .normalization import LayerNormalization
-from .sequence import AttentionSequencePoolingLayer, BiLSTM, BiasEncoding, DynamicGRU, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
+from .sequence import AttentionSequencePoolingLayer, BiLSTM, BiasEncoding, DynamicGRU, KMaxPooling, PositionEncoding, SequencePoolingLayer, Transformer, WeightedSequenceLayer
 from .utils import Concat, Hash, Linear, NoMask, add_func, combined_dnn_input, concat_func
 
 custom_objects = {
@@ -37,6 +37,8 @@ custom_objects = {
     'DynamicGRU': DynamicGRU,
     'BiLSTM': BiLSTM,
     'BiasEncoding': BiasEncoding,
+    'KMaxPooling': KMaxPooling,
+    'FGCNNLayer': FGCNNLayer,
     'LayerNormalization': LayerNormalization,
     'Hash': Hash,
     'Linear': Linear,

@@ -1,7 +1,8 @@
 """Host mirror of the ten in-scope layers of the reference's ``deepctr/layers/interaction.py``:
 ``AFMLayer`` (:39-160), ``CIN`` (:209-341), ``CrossNet`` (:344-435), ``FM`` (:563-607),
 ``InnerProductLayer`` (:610-694), ``InteractingLayer`` (:697-790), ``SENETLayer`` (:1067-1139), ``BilinearInteraction`` (:1142-1221),
-``FwFMLayer`` (:1351-1425), ``FEFMLayer`` (:1428-1499), and ``FieldWiseBiInteraction`` (:1224-1348, fieldwise_kernels.hip).
+``FwFMLayer`` (:1351-1425), ``FEFMLayer`` (:1428-1499), ``FieldWiseBiInteraction`` (:1224-1348, fieldwise_kernels.hip) and
+``FGCNNLayer`` (:937-1064, fieldconv_kernels.hip).
 Same constructor kwargs, ``get_config`` and weight names/shapes; ``call`` launches the HIP kernels
 (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip,
 fieldpair_kernels.hip).  The other six interaction layers of the reference are out of scope."""
@@ -11,7 +12,7 @@ import torch
 
 from .. import ops
 from ..initializers import GlorotNormal, GlorotUniform, Ones, TruncatedNormal, Zeros
-from .base import Layer
+from .base import Layer, next_auto_name
 
 
 def _stack_fields(inputs):
@@ -716,3 +717,120 @@ class BridgeModule(Layer):
         base = super(BridgeModule, self).get_config()
         base.update({'bridge_type': self.bridge_type, 'activation': self.activation})
         return base
+
+
+class _Conv2DWeights(Layer):
+    """The weights of one tf.keras.layers.Conv2D(filters, (width, 1)) under keras' names: ``kernel`` [width, 1, C_in, filters]
+    (glorot_uniform over fan_in = width C_in, fan_out = width filters) and ``bias`` [filters] (zeros)."""
+
+    def __init__(self, width, in_channels, filters, **kwargs):
+        super(_Conv2DWeights, self).__init__(name=next_auto_name("conv2d"), **kwargs)
+        self.add_weight("kernel", (int(width), 1, int(in_channels), int(filters)), GlorotUniform())
+        self.add_weight("bias", (int(filters),), Zeros())
+        self.built = True
+
+
+class FGCNNLayer(Layer):
+    """Feature Generation Layer used in FGCNN, including Convolution, MaxPooling and Recombination (reference interaction.py:937-1064):
+    [B, F, E] -> the new features [B, sum_i rows_i new_maps_i, E].  The conv / pool stack is ONE ``dctr_fieldconv_fwd`` launch that also
+    hands out every stage's pooled map; each stage's recombination Dense(rows E new_maps, tanh) reads its map in place through the DNN
+    kernel and writes its new fields straight into the output at their field offset (the reference's reshape of the flat row to
+    (rows new_maps, E) is a reinterpretation)."""
+
+    def __init__(self, filters=(14, 16,), kernel_width=(7, 7,), new_maps=(3, 3,), pooling_width=(2, 2), **kwargs):
+        if not (len(filters) == len(kernel_width) == len(new_maps) == len(pooling_width)):
+            raise ValueError("length of argument must be equal")
+        self.filters = filters
+        self.kernel_width = kernel_width
+        self.new_maps = new_maps
+        self.pooling_width = pooling_width
+        super(FGCNNLayer, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if len(input_shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(input_shape)))
+        return self.build_for(int(input_shape[1]), int(input_shape[2]))
+
+    def build_for(self, field_size, embedding_size):
+        if self.built:
+            return self
+        from .core import Dense
+        self.field_size, self.embedding_size = int(field_size), int(embedding_size)
+        self.conv_layers, self.dense_layers, self.rows = [], [], []
+        rows, cin = self.field_size, 1
+        for filters, width, new, pool in zip(self.filters, self.kernel_width, self.new_maps, self.pooling_width):
+            if int(pool) < 1 or rows // int(pool) < 1:
+                raise ValueError("FGCNNLayer: pooling width %d over %d rows leaves an empty feature map" % (pool, rows))
+            conv = _Conv2DWeights(width, cin, filters, device=self.device)
+            rows, cin = rows // int(pool), int(filters)
+            dense = Dense(rows * self.embedding_size * int(new), device=self.device).build_for(rows * self.embedding_size * cin)
+            self.conv_layers.append(conv)
+            self.dense_layers.append(dense)
+            self.rows.append(rows)
+            self._sublayers += [conv, dense]
+        self.new_features = sum(r * int(n) for r, n in zip(self.rows, self.new_maps))
+        self._maps = {}
+        self.built = True
+        return self
+
+    @property
+    def pools(self):
+        return [("max", int(p)) for p in self.pooling_width]
+
+    @property
+    def conv_kernels(self):
+        return [c.w("kernel") for c in self.conv_layers]
+
+    @property
+    def conv_biases(self):
+        return [c.w("bias") for c in self.conv_layers]
+
+    def _stage_maps(self, B, device):
+        """Per batch size, the buffers that receive the stages' pooled maps (rows padded to 4 floats with zeros: the DNN kernel may
+        read the padding)."""
+        key = (B, str(device))
+        bufs = self._maps.pop(key, None)
+        if bufs is None:
+            while len(self._maps) >= 4:                     # least recently used out
+                self._maps.pop(next(iter(self._maps)))
+            E = self.embedding_size
+            bufs = [torch.zeros(B, (r * E * int(c) + 3) // 4 * 4, dtype=torch.float32, device=device) for r, c in zip(self.rows, self.filters)]
+        self._maps[key] = bufs                              # (dicts keep insertion order: most recently used last)
+        return bufs
+
+    def run(self, x, out, out_offset=0, fields=None, dim=None, x_offset=0):
+        """x: [B, F, E], or with ``fields`` / ``dim`` a [B, stride] buffer read in place from ``x_offset``; the new features go to the
+        columns [out_offset, out_offset + new_features E) of the float32 [B, stride] buffer ``out``."""
+        B, E = int(x.shape[0]), self.embedding_size
+        maps = self._stage_maps(B, x.device)
+        ops.field_conv(x, self.conv_kernels, self.conv_biases, self.pools, fields=fields, dim=dim, x_offset=x_offset, out=maps[-1],
+                       stage_outs=maps[:-1] + [None])
+        off = int(out_offset)
+        for m, dense, r, c, new in zip(maps, self.dense_layers, self.rows, self.filters, self.new_maps):
+            n = r * E * int(new)
+            ops.mlp(m, [dense.w("kernel")], [dense.w("bias")], "tanh", in_dim=r * E * int(c), out=out[:, off:off + n])
+            off += n
+        return out
+
+    def call(self, inputs, **kwargs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        B, E = int(inputs.shape[0]), self.embedding_size
+        out = torch.empty(B, self.new_features * E, dtype=torch.float32, device=inputs.device)
+        return self.run(inputs, out).reshape(B, self.new_features, E)
+
+    def compute_output_shape(self, input_shape):
+        new_features_num = 0
+        features_num = input_shape[1]
+        for i in range(0, len(self.kernel_width)):
+            pooled_features_num = features_num // self.pooling_width[i]
+            new_features_num += self.new_maps[i] * pooled_features_num
+            features_num = pooled_features_num
+        return (None, new_features_num, input_shape[-1])
+
+    def get_config(self, ):
+        config = {'kernel_width': self.kernel_width, 'filters': self.filters, 'new_maps': self.new_maps,
+                  'pooling_width': self.pooling_width}
+        base_config = super(FGCNNLayer, self).get_config()
+        base_config.update(config)
+        return base_config

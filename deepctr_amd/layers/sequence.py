@@ -536,3 +536,34 @@ class BiasEncoding(Layer):
         config = {'sess_max_count': self.sess_max_count, 'seed': self.seed}
         base_config = super(BiasEncoding, self).get_config()
         return dict(list(base_config.items()) + list(config.items()))
+
+
+class KMaxPooling(Layer):
+    """K Max pooling that selects the k biggest value along the specific axis (reference sequence.py:818-874): nD tensor -> the same
+    tensor with ``k`` entries on ``axis``, in descending order of value (tf.nn.top_k(sorted=True)); one ``dctr_kmax_pool_fwd`` launch."""
+
+    def __init__(self, k=1, axis=-1, **kwargs):
+        self.k = k
+        self.axis = axis
+        super(KMaxPooling, self).__init__(**kwargs)
+
+    def build(self, input_shape):
+        if self.axis < 1 or self.axis > len(input_shape):
+            raise ValueError("axis must be 1~%d,now is %d" % (len(input_shape), self.axis))
+        if self.k < 1 or self.k > input_shape[self.axis]:
+            raise ValueError("k must be in 1 ~ %d,now k is %d" % (input_shape[self.axis], self.k))
+        self.dims = len(input_shape)
+        super(KMaxPooling, self).build(input_shape)
+
+    def call(self, inputs):
+        return ops.kmax_pool(inputs, self.k, self.axis)
+
+    def compute_output_shape(self, input_shape):
+        output_shape = list(input_shape)
+        output_shape[self.axis] = self.k
+        return tuple(output_shape)
+
+    def get_config(self, ):
+        config = {'k': self.k, 'axis': self.axis}
+        base_config = super(KMaxPooling, self).get_config()
+        return dict(list(base_config.items()) + list(config.items()))

@@ -2135,6 +2135,161 @@ def bias_encoding(x, sess_bias, seq_bias, item_bias):
     return x
 
 
+def _field_conv_stages(op, kernels, pools, fields, in_channels=None):
+    """The stages' geometry from the kernels' shapes [w, C_in, C_out] and ``pools`` = per stage ('kmax', k) or ('max', p).  Returns
+    (widths, channels, kinds, args, rows per stage's pooled map, C_0)."""
+    if len(kernels) == 0 or len(kernels) != len(pools):
+        raise ValueError("%s: one pooling per conv kernel and at least one stage, got %d and %d" % (op, len(kernels), len(pools)))
+    if len(kernels) > _C.fieldconv.MAX_STAGES:
+        raise ValueError("%s: at most %d stages, got %d" % (op, _C.fieldconv.MAX_STAGES, len(kernels)))
+    widths, channels, kinds, args, rows_out = [], [], [], [], []
+    rows, cin = int(fields), None
+    for s, (kern, pool) in enumerate(zip(kernels, pools)):
+        shape = tuple(int(v) for v in (kern.shape if hasattr(kern, "shape") else kern))
+        if len(shape) == 4 and shape[1] == 1:           # keras' Conv2D kernel [w, 1, C_in, C_out]
+            shape = (shape[0],) + shape[2:]
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError("%s: stage %d: the kernel must be [w, C_in, C_out], got %s" % (op, s, shape))
+        if cin is None:
+            cin = shape[1] if in_channels is None else int(in_channels)
+            c0 = cin
+        if shape[1] != cin:
+            raise ValueError("%s: stage %d: the kernel takes %d channels, its input has %d" % (op, s, shape[1], cin))
+        kind, arg = pool
+        if kind not in _C.fieldconv.POOLS:
+            raise ValueError("%s: stage %d: pooling must be ('kmax', k) or ('max', p), got %r" % (op, s, pool))
+        arg = int(arg)
+        if not 1 <= arg <= rows:
+            raise ValueError("%s: stage %d: %s %d outside 1..%d rows" % (op, s, "k" if kind == "kmax" else "pooling width", arg, rows))
+        widths.append(shape[0])
+        channels.append(shape[2])
+        kinds.append(_C.fieldconv.POOLS[kind])
+        args.append(arg)
+        rows = arg if kind == "kmax" else rows // arg
+        rows_out.append(rows)
+        cin = shape[2]
+    return widths, channels, kinds, args, rows_out, c0
+
+
+def _field_conv_args(op, batch, fields, dim, kernels, pools, route, in_channels=None):
+    if route not in _C.fieldconv.ROUTES:
+        raise ValueError("%s: route must be None, 'resident', 'streamed' or 'workspace', got %r" % (op, route))
+    widths, channels, kinds, pargs, rows_out, c0 = _field_conv_stages(op, kernels, pools, fields, in_channels)
+    if int(fields) < 1 or int(dim) < 1:
+        raise ValueError("%s: fields and dim must be >= 1, got %d and %d" % (op, fields, dim))
+    arrs = [_i32_array(v) for v in (widths, channels, kinds, pargs)]
+    a = _C.fieldconv.Args(batch=int(batch), x_stride=int(fields) * int(dim) * c0, x_offset=0, fields=int(fields), dim=int(dim), in_channels=c0,
+                          n_stages=len(widths), route=_C.fieldconv.ROUTES[route], out_stride=rows_out[-1] * int(dim) * channels[-1], out_offset=0)
+    a.widths, a.channels, a.pool_kinds, a.pool_args = (ctypes.cast(v, ctypes.c_void_p) for v in arrs)
+    return a, arrs, channels, rows_out
+
+
+def field_conv_macs(fields, dim, kernels, pools):
+    """Multiply-adds per sample of the conv stack: E x sum over the stages of rows w C_in C_out (``kernels``: tensors or shapes)."""
+    widths, channels, _, _, rows_out, c0 = _field_conv_stages("field_conv_macs", kernels, pools, fields)
+    total, rows, cin = 0, int(fields), c0
+    for w, c, ro in zip(widths, channels, rows_out):
+        total += rows * w * cin * c
+        rows, cin = ro, c
+    return total * int(dim)
+
+
+def field_conv_workspace_bytes(batch, fields, dim, kernels, pools, route=None):
+    """Bytes of the workspace dctr_fieldconv_fwd needs for these shapes (0 while a workgroup's maps fit the LDS; read from the library).
+    ``kernels``: tensors or shapes [w, C_in, C_out]."""
+    a, arrs, _, _ = _field_conv_args("field_conv", batch, fields, dim, kernels, pools, route)
+    return int(_C.lib().dctr_fieldconv_workspace_bytes(ctypes.byref(a)))
+
+
+def field_conv_route(fields, dim, kernels, pools, route=None):
+    """'resident' or 'streamed': the route dctr_fieldconv_fwd takes for these shapes (dctr_fieldconv_route)."""
+    a, arrs, _, _ = _field_conv_args("field_conv", 1, fields, dim, kernels, pools, route)
+    return _route_name("dctr_fieldconv_route", _C.lib().dctr_fieldconv_route(ctypes.byref(a)), (None, "resident", "streamed"))
+
+
+def field_conv(x, kernels, biases, pools, fields=None, dim=None, x_offset=0, out=None, out_offset=0, stage_outs=None, route=None,
+               workspace=None):
+    """The conv / pool stack of CCPM and FGCNNLayer along the field axis (dctr_fieldconv_fwd), one launch.
+
+    ``x`` [B, F, E] (or [B, F, E, C_0] channel-last); with ``fields`` / ``dim`` the F E C_0 columns from ``x_offset`` of a float32
+    [B, stride] buffer read in place.  ``kernels``: per stage [w, C_in, C_out] (or keras' [w, 1, C_in, C_out]), ``biases`` [C_out],
+    ``pools`` ('kmax', k) or ('max', p).  ``out``: a float32 [B, >= out_offset + rows E C] buffer that receives the last pooled map
+    channel-last from column ``out_offset`` (allocated [B, rows, E, C] when None).  ``stage_outs``: True for every stage's pooled map in
+    new [B, rows_s, E, C_s] tensors, or a list with per stage None or a float32 [B, >= rows_s E C_s] buffer.  Returns ``out``, or
+    (out, stage_outs) with ``stage_outs``."""
+    op = "field_conv"
+    if len(kernels) != len(biases):
+        raise ValueError("field_conv: one bias per kernel, got %d and %d" % (len(biases), len(kernels)))
+    if fields is None:
+        if x.dim() not in (3, 4):
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 or 4 dimensions" % x.dim())
+        x = _f32c(x, "x")
+        B, F, E = (int(v) for v in x.shape[:3])
+        c_in = int(x.shape[3]) if x.dim() == 4 else 1
+        a, arrs, channels, rows_out = _field_conv_args(op, B, F, E, kernels, pools, route, c_in)
+    else:
+        B, F, E = int(x.shape[0]), int(fields), int(dim)
+        a, arrs, channels, rows_out = _field_conv_args(op, B, F, E, kernels, pools, route)
+        a.x_stride, a.x_offset = _rows2d(op, "x (with fields / dim)", x, B, F * E * a.in_channels, x_offset), int(x_offset)
+    flat = []
+    for s, (kern, bias) in enumerate(zip(kernels, biases)):
+        if kern.dtype != torch.float32 or not kern.is_contiguous():
+            raise ValueError("field_conv: stage %d kernel must be a contiguous float32 tensor" % s)
+        _vec(op, "stage %d bias" % s, bias, channels[s])
+        flat += [kern, bias]
+    widths_out = [r * E * c for r, c in zip(rows_out, channels)]
+    ret = out
+    if out is None:
+        ret = torch.empty((B, rows_out[-1], E, channels[-1]), dtype=torch.float32, device=x.device)
+        out = ret.view(B, -1)
+    a.out_stride, a.out_offset = _rows2d(op, "out", out, B, widths_out[-1], out_offset), int(out_offset)
+    souts = None
+    if stage_outs is not None and stage_outs is not False:
+        if stage_outs is True:
+            souts = [torch.empty((B, r, E, c), dtype=torch.float32, device=x.device) for r, c in zip(rows_out, channels)]
+        else:
+            souts = list(stage_outs)
+            if len(souts) != len(kernels):
+                raise ValueError("field_conv: stage_outs needs one entry per stage, got %d for %d" % (len(souts), len(kernels)))
+        strides = []
+        for s, t in enumerate(souts):
+            if t is None:
+                strides.append(0)
+            elif t.dim() == 4 and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, rows_out[s], E, channels[s]):
+                strides.append(widths_out[s])
+            else:
+                strides.append(_rows2d(op, "stage_outs[%d]" % s, t, B, widths_out[s]))
+        sp, ss = _ptr_array(souts), _i64_array(strides)
+        a.stage_outs, a.stage_out_strides = ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(ss, ctypes.c_void_p)
+    _dev_check(x, out, *flat, *(souts or ()))
+    kp, bp = _ptr_array(flat[0::2]), _ptr_array(flat[1::2])
+    a.kernels, a.biases = ctypes.cast(kp, ctypes.c_void_p), ctypes.cast(bp, ctypes.c_void_p)
+    a.x, a.out = x.data_ptr(), out.data_ptr()
+    _workspace(op, a, int(_C.lib().dctr_fieldconv_workspace_bytes(ctypes.byref(a))), workspace, x.device)
+    _C.check(_C.lib().dctr_fieldconv_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_fieldconv_fwd")
+    del kp, bp, arrs
+    return ret if souts is None else (ret, souts)
+
+
+def kmax_pool(x, k, axis=-1):
+    """KMaxPooling.call (reference sequence.py:853-864): the ``k`` largest values along ``axis`` of a tensor of any rank, in descending
+    order of value (tf.nn.top_k(sorted=True)); the other axes keep their place."""
+    nd = x.dim()
+    if nd < 1 or not -nd <= int(axis) < nd:
+        raise ValueError("kmax_pool: axis %d outside a tensor of %d dimensions" % (axis, nd))
+    axis = int(axis) % nd
+    n, k = int(x.shape[axis]), int(k)
+    if not 1 <= k <= n:
+        raise ValueError("k must be in 1 ~ %d,now k is %d" % (n, k))
+    _dev_check(x)
+    x = _f32c(x, "x")
+    outer = int(np.prod(x.shape[:axis], dtype=np.int64))
+    inner = int(np.prod(x.shape[axis + 1:], dtype=np.int64))
+    y = torch.empty(tuple(x.shape[:axis]) + (k,) + tuple(x.shape[axis + 1:]), dtype=torch.float32, device=x.device)
+    _C.check(_C.lib().dctr_kmax_pool_fwd(_ptr(x), outer, n, inner, k, _ptr(y), _C.stream_ptr()), "dctr_kmax_pool_fwd")
+    return y
+
+
 def afm(x, attention_W, attention_b, projection_h, projection_p, fields=None, dim=None, out=None):
     """AFMLayer.call (reference interaction.py:116-146), inference: x [B,F,E] -> [B,1].
     With ``fields``/``dim`` x is a 2-D buffer [B, stride >= fields*dim] read in place (a slice of dnn_in)."""

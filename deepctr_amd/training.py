@@ -181,7 +181,7 @@ def frozen_weights(model):
     """data_ptr()s of the tables built from SparseFeat(trainable=False) (reference inputs.py:25: ``emb.trainable =
     feat.trainable``; docs FAQ "pretrained embeddings"): neither training path may touch them."""
     out = set()
-    for embs in (getattr(model, "tables", None) or {}, getattr(model, "linear_tables", None) or {}):
+    for embs in (getattr(model, "tables", None) or {}, getattr(model, "linear_tables", None) or {}, getattr(model, "fg_tables", None) or {}):
         for emb in embs.values():
             if not getattr(emb, "trainable", True):
                 out.add(emb.embeddings.data_ptr())
@@ -216,6 +216,8 @@ def regularized_weights(model):
             out.append((t, float(l2)))
 
     for emb in (getattr(model, "tables", None) or {}).values():
+        add(emb.embeddings, reg.get("embedding", 0.0))
+    for emb in (getattr(model, "fg_tables", None) or {}).values():         # FGCNN's second embedding set (fgcnn.py:64-65)
         add(emb.embeddings, reg.get("embedding", 0.0))
     for emb in (getattr(model, "linear_tables", None) or {}).values():
         add(emb.embeddings, reg.get("linear", 0.0))
@@ -431,6 +433,39 @@ def _fefm(layer, x):
     ii, jj = _pair_indices(x.shape[1])
     w = torch.stack(layer.matrices)
     return (torch.einsum("bpe,ped->bpd", x[:, ii], w + w.transpose(1, 2)) * x[:, jj]).sum(-1)
+
+
+def _field_conv(x, kernels, biases, pools):
+    """The conv / pool stack of CCPM and FGCNNLayer in torch ops.  x [B,F,E] (or [B,F,E,C_0]); per stage keras' Conv2D kernel
+    [w, 1, C_in, C_out] (or [w, C_in, C_out]) and bias [C_out]: a cross-correlation along the fields under 'same' padding, (w - 1) // 2
+    zero rows in front and the rest behind, tanh; then ('kmax', k): the k largest rows in descending order of value, or ('max', p):
+    windows of p rows at stride p, the trailing rows dropped.  Returns (last pooled map, every stage's), each channel-last [B,rows,E,C]."""
+    h = (x.unsqueeze(-1) if x.dim() == 3 else x).permute(0, 3, 1, 2)          # [B,C,rows,E]
+    maps = []
+    for kern, bias, (kind, arg) in zip(kernels, biases, pools):
+        if kern.dim() == 4:
+            kern = kern[:, 0]
+        w = kern.shape[0]
+        before = (w - 1) // 2
+        h = torch.nn.functional.pad(h, (0, 0, before, w - 1 - before))
+        h = torch.tanh(torch.nn.functional.conv2d(h, kern.permute(2, 1, 0).unsqueeze(-1), bias))
+        if kind == "kmax":
+            h = torch.topk(h, int(arg), dim=2, sorted=True).values
+        else:
+            p, n = int(arg), h.shape[2] // int(arg)
+            h = h[:, :, :n * p].reshape(h.shape[0], h.shape[1], n, p, h.shape[3]).amax(dim=3)
+        maps.append(h.permute(0, 2, 3, 1))
+    return maps[-1], maps
+
+
+def _fgcnn_layer(layer, x):
+    """FGCNNLayer.call (reference interaction.py:994-1020) in torch ops: x [B,F,E] -> the new features [B, new, E]."""
+    B, E = x.shape[0], x.shape[2]
+    _, maps = _field_conv(x, layer.conv_kernels, layer.conv_biases, layer.pools)
+    out = []
+    for m, dense in zip(maps, layer.dense_layers):
+        out.append(torch.tanh(m.reshape(B, -1) @ dense.w("kernel") + dense.w("bias")).reshape(B, -1, E))
+    return torch.cat(out, dim=1)
 
 
 def model_logits(model, staged, lo, hi, training=False):

@@ -1046,6 +1046,72 @@ int dctr_bias_encoding_fwd(float* x, int64_t batch, int32_t sess, int32_t seq_le
                            int64_t row_stride, const float* sess_bias, const float* seq_bias, const float* item_bias, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The field-axis convolution stack of CCPM (deepctr/models/ccpm.py:62-70) and FGCNNLayer (deepctr/layers/interaction.py:1022-1047):
+ * n_stages x [Conv2D(C_out, (w, 1), padding='same', activation='tanh', use_bias=True), then a pooling along the field axis], the
+ * whole stack in one launch.
+ *     x [B, F, E, C_0] channel-last (C_0 = in_channels, 1 for an embedding block), read in place: the F E C_0 columns from x_offset of a
+ *     [B, x_stride] buffer.  Stage s: kernel [w, C_in, C_out] (keras' [w, 1, C_in, C_out]), bias [C_out]; rows = F for stage 0.
+ *       y[b, r, e, co] = tanh(bias[co] + sum_{d, ci} xpad[b, r + d, e, ci] K[d, ci, co])
+ *     a cross-correlation (K is not flipped); 'same' puts (w - 1) / 2 zero rows before the first row and w - 1 - (w - 1) / 2 after
+ *     the last (w = 6: 2 and 3).  Pooling of a stage:
+ *       DCTR_FIELDCONV_POOL_KMAX, arg k: the k largest of the rows for every (b, e, channel) in DESCENDING order of value
+ *         (tf.nn.top_k(sorted=True), as KMaxPooling calls it; not the order-preserving variant), 1 <= k <= rows -> k rows
+ *       DCTR_FIELDCONV_POOL_MAX, arg p: max over windows of p rows at stride p, 'valid': rows / p rows, the trailing rows % p dropped,
+ *         1 <= p <= rows.
+ *     out: the last stage's pooled map [rows, E, C] (what Flatten sees) in the columns from out_offset of a [B, out_stride] buffer;
+ *     columns beside them are left alone.  stage_outs: NULL, or per stage NULL or a [B, stage_out_strides[s]] buffer that receives
+ *     that stage's pooled map [rows_s, E, C_s] from column 0 (FGCNN's recombination Dense reads each).
+ *     Exact-fp32 products on v_mfma_f32_16x16x4_f32 (M = 16 (sample, e) columns at one row, K over (d, ci), N a 16-wide slice of
+ *     C_out), tanh on the hardware exp and rcp (it saturates to +-1 without NaN), k-max by rank counting, no atomics: the same bits
+ *     on every call while the operands are finite.  RESIDENT route: a tile's maps and every stage's kernel stay in LDS; AUTO takes
+ *     it while both fit 64 KiB (two workgroups per CU), a forced RESIDENT holds up to 160 KiB.  STREAMED route: the same step code
+ *     with the kernels read from global / L2.  WORKSPACE: streamed, with a workgroup's maps in a workspace of
+ *     dctr_fieldconv_workspace_bytes() (room for <= 256 workgroups); AUTO takes it when 16 columns' maps exceed the LDS, and the
+ *     workspace is then REQUIRED (DCTR_E_NULL without, before anything is launched).  route = RESIDENT for shapes that do not fit
+ *     answers DCTR_E_UNSUPPORTED.  No shape is refused for its size below 2^20 per extent.
+ *     Argument errors (nothing launched): NULL x / out / arrays / a stage's kernel or bias (DCTR_E_NULL), sizes < 1, n_stages outside
+ *     1..DCTR_FIELDCONV_MAX_STAGES, k or p outside 1..rows, strides smaller than offset + block (DCTR_E_DIM), unknown pooling / route
+ *     (DCTR_E_ENUM).
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_FIELDCONV_POOL_KMAX = 0, DCTR_FIELDCONV_POOL_MAX = 1 };
+enum { DCTR_FIELDCONV_ROUTE_AUTO = 0, DCTR_FIELDCONV_ROUTE_RESIDENT = 1, DCTR_FIELDCONV_ROUTE_STREAMED = 2, DCTR_FIELDCONV_ROUTE_WORKSPACE = 3 };
+#define DCTR_FIELDCONV_MAX_STAGES 8
+typedef struct {
+    int64_t batch;
+    const float* x;                  /* [B, x_stride] fp32; the block is [F, E, in_channels] from x_offset */
+    int64_t x_stride;                /* elements between samples */
+    int64_t x_offset;
+    int32_t fields;                  /* F >= 1 */
+    int32_t dim;                     /* E >= 1 */
+    int32_t in_channels;             /* C_0 >= 1 */
+    int32_t n_stages;                /* 1 .. DCTR_FIELDCONV_MAX_STAGES */
+    int32_t route;                   /* DCTR_FIELDCONV_ROUTE_* */
+    int32_t reserved;
+    const int32_t* widths;           /* HOST [n_stages] */
+    const int32_t* channels;         /* HOST [n_stages]: C_out */
+    const int32_t* pool_kinds;       /* HOST [n_stages]: DCTR_FIELDCONV_POOL_* */
+    const int32_t* pool_args;        /* HOST [n_stages]: k or p */
+    const float* const* kernels;     /* HOST array [n_stages] of DEVICE pointers, [w, C_in, C_out] */
+    const float* const* biases;      /* HOST array [n_stages] of DEVICE pointers, [C_out] */
+    float* out;
+    int64_t out_stride;
+    int64_t out_offset;
+    float* const* stage_outs;        /* NULL, or HOST array [n_stages] of DEVICE pointers (entries may be NULL) */
+    const int64_t* stage_out_strides; /* HOST [n_stages], read where stage_outs[s] is set */
+    void* workspace;                 /* NULL, or device scratch of dctr_fieldconv_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_fieldconv_args_t;
+/* Bytes dctr_fieldconv_fwd needs (sizes and route are read, device pointers are not): 0 while a workgroup's maps fit the LDS. */
+size_t dctr_fieldconv_workspace_bytes(const dctr_fieldconv_args_t* args);
+/* The route these arguments take (DCTR_FIELDCONV_ROUTE_RESIDENT, or _STREAMED with or without a workspace), or the DCTR_E_* the checks
+ * answer. */
+int dctr_fieldconv_route(const dctr_fieldconv_args_t* args);
+int dctr_fieldconv_fwd(const dctr_fieldconv_args_t* args, void* stream);
+/* KMaxPooling.call — deepctr/layers/sequence.py:853-864 over a contiguous [outer, n, inner] view: y [outer, k, inner] holds the k
+ * largest along the middle axis in descending order of value, 1 <= k <= n (DCTR_E_DIM otherwise). */
+int dctr_kmax_pool_fwd(const float* x, int64_t outer, int32_t n, int64_t inner, int32_t k, float* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a11 AFMLayer.call — deepctr/layers/interaction.py:116-146 (inference: dropout inactive)
  *     x [B,F,E] (sample stride x_stride); W [E,A]; b [A]; h [A]; p [E]  ->  y [B]
  * ------------------------------------------------------------------------------------------------ */
