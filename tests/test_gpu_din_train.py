@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.ref_dice import dice_dnn, scaled_close as _scaled
 from tests.util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -11,11 +12,6 @@ pytestmark = pytest.mark.gpu
 
 def dev(a, device):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-
-
-def _scaled(got, ref, what, rtol=2e-4, atol=2e-6):
-    scale = max(float(ref.abs().max()), 1e-4)
-    assert_close(got.cpu().numpy() / scale, ref.cpu().numpy() / scale, rtol=rtol, atol=atol, what=what)
 
 
 @pytest.mark.parametrize("B,T,E", [(1, 1, 4), (37, 6, 8), (130, 50, 16)])
@@ -110,11 +106,7 @@ def test_mlp_bwd_dice_matches_autograd(device, n_layers, head):
     leaves = [t.clone().requires_grad_(True) for t in [x] + Ws + bs + al + [hw]]
     xa, Wa, ba, aa, ha = leaves[0], leaves[1:1 + n_layers], leaves[1 + n_layers:1 + 2 * n_layers], \
         leaves[1 + 2 * n_layers:1 + 3 * n_layers], leaves[-1]
-    h = xa[:, :K]
-    for i in range(n_layers):
-        z = h @ Wa[i] + ba[i]
-        p = torch.sigmoid((z - mu[i]) / torch.sqrt(va[i] + 1e-9))
-        h = aa[i] * (1 - p) * z + p * z
+    h, _ = dice_dnn(xa[:, :K], Wa, ba, aa, mu, va, eps=1e-9)
     dice = list(zip(al, mu, va))
     acts = [torch.empty(B, n, device=device) for n in units]
     if head:
@@ -162,14 +154,7 @@ def test_dice_training_mode_forward_and_backward_match_autograd(device, n_layers
     leaves = [t.clone().requires_grad_(True) for t in [x] + Ws + bs + al + [hw]]
     xa, Wa, ba, aa, ha = leaves[0], leaves[1:1 + n_layers], leaves[1 + n_layers:1 + 2 * n_layers], \
         leaves[1 + 2 * n_layers:1 + 3 * n_layers], leaves[-1]
-    h = xa[:, :K]
-    ref_stats = []
-    for i in range(n_layers):
-        z = h @ Wa[i] + ba[i]
-        bm, bv = z.mean(dim=0), z.var(dim=0, unbiased=False)
-        ref_stats.append((bm.detach(), bv.detach()))
-        p = torch.sigmoid((z - bm) / torch.sqrt(bv + 1e-9))
-        h = aa[i] * (1 - p) * z + p * z
+    h, ref_stats = dice_dnn(xa[:, :K], Wa, ba, aa, eps=1e-9)
     # forward, layer by layer as the trainer does
     acts, zs, stats = [torch.empty(R, n, device=device) for n in units], [torch.empty(R, n, device=device) for n in units], []
     mm2, mv2 = [t.clone() for t in mm], [t.clone() for t in mv]

@@ -116,7 +116,8 @@ def test_adam_step_matches_torch_adam(device):
 def test_mlp_bwd_matches_autograd(device, act):
     from deepctr_amd import ops
     rng = np.random.RandomState(3)
-    # (10000 rows: from 8192 on dW runs as a strided batch of row slices + a sum)
+    # (all four shapes take the chained form — no layer is wider than 1216; 10000 rows: 32-row chain tiles and 32 dW row slices.
+    #  The layered form, both forms' operand variants and the accumulation are covered by tests/test_gpu_mlp_bwd.py)
     for B, dims in ((37, [13, 8, 5]), (300, [429, 256, 128, 64]), (65, [20, 7]), (10000, [21, 12, 8])):
         x = rng.standard_normal((B, dims[0] + 3)).astype(np.float32)      # row stride > in_dim
         ks = [(rng.standard_normal((dims[i], dims[i + 1])) / np.sqrt(dims[i])).astype(np.float32) for i in range(len(dims) - 1)]
@@ -857,7 +858,7 @@ def test_xdeepfm_hip_training_gradients_match_torch_autograd(device, split, cin_
 
 @pytest.mark.parametrize("m,n,k", [(1, 1, 1), (429, 256, 4096), (4096, 429, 256), (77, 33, 5), (128, 128, 16), (130, 257, 1000), (64, 8, 300)])
 def test_own_sgemm_matches_float64(device, m, n, k):
-    """dctr_sgemm (csrc/gemm_kernels.hip: the training step's contractions on the library's own f32 MFMA kernel; rocBLAS until round 3):
+    """dctr_sgemm (deepctr_amd/csrc/gemm_kernels.hip: the training step's contractions on the library's own f32 MFMA kernel; rocBLAS until round 3):
     every transpose combination, beta 0 / 1, batched, sizes that are no tile multiples, against float64 matmul."""
     import torch
     from deepctr_amd import ops
