@@ -299,7 +299,7 @@ class fieldconv(object):
 
 
 class mtl(object):
-    """dctr_mtl_args_t / dctr_mtl_mix_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
+    """dctr_mtl_args_t / dctr_mtl_mix_args_t / dctr_mtl_mix_bwd_args_t / dctr_mtl_loss_args_t, one level down for the same reason as interacting.Args (tests/test_mtl_cpu.py checks the
     layout)."""
     LEVEL, TOWERS = 0, 1
     ROUTE_AUTO, ROUTE_FUSED, ROUTE_LAYERED = 0, 1, 2
@@ -317,6 +317,19 @@ class mtl(object):
         _fields_ = [("batch", c_i64), ("h", c_vp), ("h_stride", c_i64), ("n_experts", c_i32), ("width", c_i32), ("n_gates", c_i32),
                     ("z_dim", c_i32), ("z", c_vp), ("z_stride", c_vp), ("gate_kernel", c_vp), ("gate_n", c_vp), ("members", c_vp),
                     ("members_dev", c_vp), ("out", c_vp), ("out_stride", c_i64), ("out_offset", c_i64)]
+
+    LOSS_BCE, LOSS_MSE = 0, 1
+
+    class MixBwdArgs(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("h", c_vp), ("h_stride", c_i64), ("n_experts", c_i32), ("width", c_i32), ("n_gates", c_i32),
+                    ("z_dim", c_i32), ("z", c_vp), ("z_stride", c_vp), ("gate_kernel", c_vp), ("gate_n", c_vp), ("members", c_vp),
+                    ("members_dev", c_vp), ("d_out", c_vp), ("d_out_stride", c_i64), ("d_out_offset", c_i64), ("dh", c_vp),
+                    ("dh_stride", c_i64), ("ds", c_vp), ("ds_stride", c_i64), ("logits", c_vp), ("logits_stride", c_i64)]
+
+    class LossArgs(ctypes.Structure):
+        _fields_ = [("batch", c_i64), ("n_tasks", c_i32), ("esmm", c_i32), ("pred", c_vp), ("pred_stride", c_i64), ("y", c_vp),
+                    ("y_stride", c_i64), ("loss_kind", c_vp), ("binary", c_vp), ("loss_weight", c_vp), ("dlogit", c_vp),
+                    ("dlogit_stride", c_i64), ("loss_sum", c_vp), ("dbias", c_vp)]
 
 
 class CinBwdArgs(ctypes.Structure):
@@ -439,6 +452,9 @@ SYMBOLS = {
     "dctr_mtl_level_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),
     "dctr_mtl_towers_fwd": (ctypes.c_int, [ctypes.POINTER(mtl.Args), c_vp]),
     "dctr_mtl_mix": (ctypes.c_int, [ctypes.POINTER(mtl.MixArgs), c_vp]),
+    "dctr_mtl_mix_bwd": (ctypes.c_int, [ctypes.POINTER(mtl.MixBwdArgs), c_vp]),
+    "dctr_mtl_loss_grad": (ctypes.c_int, [ctypes.POINTER(mtl.LossArgs), c_vp]),
+    "dctr_mtl_sum_slots": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_i64, c_i64, c_i32, c_vp]),
     "dctr_edcn_regulate": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "dctr_edcn_bridge": (ctypes.c_int, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "dctr_afm_fwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),

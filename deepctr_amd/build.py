@@ -55,6 +55,7 @@ SOURCES = [
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",
     "mtl_kernels.hip",
+    "mtl_bwd_kernels.hip",
     "transformer_kernels.hip",
     "gru_kernels.hip",
     "lstm_kernels.hip",

@@ -174,6 +174,166 @@ class MultiTaskModel(FeatureModel):
             return [ctr, ctr * torch.sigmoid(logits[1])], [True, False]
         return [torch.sigmoid(l) if t == "binary" else l for l, t in zip(logits, self.task_types)], [True] * self.num_tasks
 
+    # ---- the HIP training step (training_hip.HipTrainer; DESIGN.md §4.15 "Training") --------------------------------------------------
+    def _hip_supported(self):
+        """Every DNN is a plain relu / linear / sigmoid / tanh stack (no BatchNormalization, no dropout, no Dice / PReLU) and every task
+        pairs binary with binary_crossentropy or regression with mse (the compiled losses; the defaults before compile())."""
+        for d in self.dnn_layers:
+            if (d.activation not in ("relu", "linear", "sigmoid", "tanh") or d.bn_layers or getattr(d, "dice_layers", None)
+                    or float(getattr(d, "dropout_rate", 0) or 0) > 0 or getattr(d, "output_activation", None) not in (None, d.activation)
+                    or len(d.kernels) > 8):
+                return False
+        losses = (self._compiled or {}).get("loss") or ["binary_crossentropy" if t == "binary" else "mse" for t in self.task_types]
+        return all((t == "binary") == (l in _BCE) and (l in _BCE or l in _MSE) for t, l in zip(self.task_types, losses))
+
+    def _hip_params(self, tr):
+        l2d = float((getattr(self, "regularizers", None) or {}).get("dnn", 0.0))
+        tr.own["dnn"] = {id(d): ([tr.param(k, l2d) for k in d.kernels], [tr.param(b) for b in d.biases]) for d in self.dnn_layers}
+        tr.own["gates"] = [[tr.param(g.w("kernel")) for g in lv.gate_dense] for lv in self.levels]
+        tr.own["heads"] = [tr.param(h.w("kernel")) for h in self.heads]
+        tr.own["gbias"] = [tr.param(p.w("global_bias")) if p.use_bias else None for p in self.predictions]
+
+    def _hip_buffers(self, buf, B):
+        """The step's own per-batch buffers, kept in the trainer's ``buf`` of this batch size."""
+        m = buf.get("mtl")
+        if m is not None:
+            return m
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        m = buf["mtl"] = {"acts": {id(d): [new(B, k.shape[1]) for k in d.kernels] for d in self.dnn_layers}, "levels": [], "scratch": {},
+                          "ws": {}}
+        in_dim = self.stage_plan.in_dim
+        for lv in self.levels:
+            E, G, H, n_all = len(lv.experts), len(lv.gate_dense), lv.experts[0].hidden_units[-1], sum(len(ms) for ms in lv.members)
+            dz = lv.gate_dnns[0].hidden_units[-1] if lv.gate_dnns[0].hidden_units else in_dim
+            m["levels"].append({"h": new(B, E * H), "out": new(B, G * H), "d_out": new(B, G * H), "dh": new(B, E * H), "ds": new(B, n_all),
+                                "logits": new(B, n_all), "z": [new(B, dz) for _ in range(G)] if lv.gate_dnns[0].hidden_units else None,
+                                "dz": [new(B, dz) for _ in range(G)] if lv.gate_dnns[0].hidden_units else None})
+            in_dim = H
+        if self.bottom is not None and self.bottom.hidden_units:
+            m["bottom"], m["d_bottom"] = new(B, self.bottom.hidden_units[-1]), new(B, self.bottom.hidden_units[-1])
+        return m
+
+    def _hip_scratch(self, m, i, B, n):
+        """The i-th [B, n] scratch gradient of the step (reused by every stage: a stage's sums are launched before the next writes)."""
+        t = m["scratch"].get((i, n))
+        if t is None:
+            t = m["scratch"][(i, n)] = torch.empty(B, n, dtype=torch.float32, device=self.device)
+        return t
+
+    def _hip_reader_grads(self, m, B, n, dst, offsets, backward):
+        """The gradient of slots that several DNNs may read.  ``offsets[r]``: the first column in ``dst`` of the slot reader r reads;
+        ``backward(r, dx)`` runs reader r's backward, writing dx [B, n].  A slot with one reader gets its columns written in place; with
+        several, each writes to scratch and ops.mtl_sum_slots forms the sum in reader order."""
+        by_slot = {}
+        for r, off in enumerate(offsets):
+            by_slot.setdefault(off, []).append(r)
+        used = 0
+        for off, readers in by_slot.items():
+            if len(readers) == 1:
+                backward(readers[0], dst[:, off:off + n])
+                continue
+            parts = []
+            for r in readers:
+                parts.append(self._hip_scratch(m, used, B, n))
+                used += 1
+                backward(r, parts[-1])
+            for k in range(0, len(parts), 16):
+                ops.mtl_sum_slots(parts[k:k + 16], n, dst, dst_offset=off, accumulate=k > 0)
+        return set(by_slot)
+
+    def _hip_dnn_bwd(self, tr, m, d, x, in_dim, d_out, dx):
+        pk, pb = tr.own["dnn"][id(d)]
+        ops.mlp_bwd(x, in_dim, d.kernels, m["acts"][id(d)], d.activation, None, None, [p.g for p in pk], [p.g for p in pb], None, dx=dx,
+                    d_out=d_out, workspace=m["ws"])
+
+    def _hip_forward_backward(self, tr, staged, lo, hi, ws, buf, y, binary):
+        """Forward by the layered route with the activations saved, ops.mtl_loss_grad, then backwards: the towers, the bottom, and per
+        level ops.mtl_mix_bwd, the gates' softmax Dense, the gate DNNs and the experts; ``y``: float32 [T, B]."""
+        B, T = hi - lo, self.num_tasks
+        m = self._hip_buffers(buf, B)
+        acts, c = m["acts"], self._compiled or {}
+        x, in_dim, offsets = ws["dnn_in"], self.stage_plan.in_dim, [0]
+        stages = []                                                     # (input buffer, its width per slot, slot offsets) of every level
+        for lv, lb in zip(self.levels, m["levels"]):
+            H = lv.experts[0].hidden_units[-1]
+            slot = lambda s: x[:, offsets[s if len(offsets) > 1 else 0]:][:, :in_dim]      # noqa: E731
+            for e, (d, s) in enumerate(zip(lv.experts, lv.expert_src)):
+                ops.mlp(slot(s), d.kernels, d.biases, d.activation, in_dim=in_dim, out=lb["h"][:, e * H:(e + 1) * H], save_acts=acts[id(d)])
+            zs = []
+            for d, s in zip(lv.gate_dnns, lv.gate_src):
+                if d.hidden_units:
+                    zs.append(ops.mlp(slot(s), d.kernels, d.biases, d.activation, in_dim=in_dim, out=lb["z"][len(zs)], save_acts=acts[id(d)]))
+                else:
+                    zs.append(slot(s))
+            ops.mtl_mix(lb["h"], len(lv.experts), H, zs, [g.w("kernel") for g in lv.gate_dense], lv.members, out=lb["out"])
+            stages.append((x, in_dim, offsets, zs))
+            x, in_dim, offsets = lb["out"], H, [g * H for g in range(len(lv.gate_dense))]
+        bottom = self.bottom if self.bottom is not None and self.bottom.hidden_units else None
+        if bottom is not None:
+            bx, b_in = x, in_dim
+            x = ops.mlp(bx, bottom.kernels, bottom.biases, bottom.activation, in_dim=b_in, out=m["bottom"], save_acts=acts[id(bottom)])
+            in_dim, offsets = bottom.hidden_units[-1], [0]
+        if len(offsets) == 1:
+            offsets = offsets * T
+        offsets = offsets[:T]
+        pred, gb = buf["pred"], tr.own["gbias"]
+        for t, (d, hd, off) in enumerate(zip(self.towers, self.heads, offsets)):
+            ops.mlp(x[:, off:off + in_dim], d.kernels, d.biases, d.activation if d.kernels else "linear", head_w=hd.w("kernel"),
+                    global_bias=None if gb[t] is None else gb[t].w, sigmoid_out=self.task_types[t] == "binary", in_dim=in_dim, out=pred[t],
+                    save_acts=acts[id(d)] if d.kernels else None)
+        acc = tr._loss_acc
+        if acc is None:
+            acc = buf["loss"].zero_()
+        losses = c.get("loss") or ["binary_crossentropy" if t == "binary" else "mse" for t in self.task_types]
+        ops.mtl_loss_grad(pred, y, buf["dlogit"], acc, losses, [t == "binary" for t in self.task_types], c.get("loss_weights"),
+                          esmm=self.esmm, dbias=[None if p is None else p.g for p in gb])
+        # backwards: the towers write the gradient of what they read
+        if self.levels and bottom is None:
+            d_x = m["levels"][-1]["d_out"]
+        else:
+            d_x = m["d_bottom"] if bottom is not None else buf["dx"]
+
+        def tower_bwd(t, dx):
+            d, hd, xt = self.towers[t], tr.own["heads"][t], x[:, offsets[t]:offsets[t] + in_dim]
+            if d.kernels:
+                pk, pb = tr.own["dnn"][id(d)]
+                ops.mlp_bwd(xt, in_dim, d.kernels, acts[id(d)], d.activation, hd.w, buf["dlogit"][t], [p.g for p in pk], [p.g for p in pb],
+                            hd.g, dx=dx, workspace=m["ws"])
+            else:
+                ops.dense1_bwd(xt, in_dim, hd.w, buf["dlogit"][t], dx, hd.g)
+        written = self._hip_reader_grads(m, B, in_dim, d_x, offsets, tower_bwd)
+        if bottom is not None:
+            d_prev = m["levels"][-1]["d_out"] if self.levels else buf["dx"]
+            self._hip_dnn_bwd(tr, m, bottom, bx, b_in, d_x, d_prev)
+            written = {0}
+        for i in range(len(self.levels) - 1, -1, -1):
+            lv, lb = self.levels[i], m["levels"][i]
+            xin, k_in, offs, zs = stages[i]
+            E, G, H = len(lv.experts), len(lv.gate_dense), lv.experts[0].hidden_units[-1]
+            for off in [g * H for g in range(G) if g * H not in written]:
+                lb["d_out"][:, off:off + H].zero_()                     # (a gate output nothing downstream reads)
+            gk = [g.w("kernel") for g in lv.gate_dense]
+            ops.mtl_mix_bwd(lb["h"], E, H, zs, gk, lv.members, lb["d_out"], lb["dh"], lb["ds"], logits=lb["logits"])
+            d_prev = m["levels"][i - 1]["d_out"] if i else buf["dx"]
+            slot_of = lambda s: offs[s if len(offs) > 1 else 0]        # noqa: E731
+            firsts = [sum(len(ms) for ms in lv.members[:g]) for g in range(G)]
+
+            def reader_bwd(r, dx):
+                if r < E:
+                    xs = xin[:, slot_of(lv.expert_src[r]):][:, :k_in]
+                    self._hip_dnn_bwd(tr, m, lv.experts[r], xs, k_in, lb["dh"][:, r * H:(r + 1) * H], dx)
+                    return
+                g = r - E
+                n, d = len(lv.members[g]), lv.gate_dnns[g]
+                dz = zs[g].shape[1] if d.hidden_units else k_in
+                cols = slice(firsts[g], firsts[g] + n)
+                # the gate's softmax Dense: a bias-free linear layer over z_g with d_out = d loss / d gate logits
+                ops.mlp_bwd(zs[g], dz, [gk[g]], [lb["logits"][:, cols]], "linear", None, None, [tr.own["gates"][i][g].g], [None], None,
+                            dx=lb["dz"][g] if d.hidden_units else dx, d_out=lb["ds"][:, cols], workspace=m["ws"])
+                if d.hidden_units:
+                    self._hip_dnn_bwd(tr, m, d, xin[:, slot_of(lv.gate_src[g]):][:, :k_in], k_in, lb["dz"][g], dx)
+            written = self._hip_reader_grads(m, B, k_in, d_prev, [slot_of(s) for s in list(lv.expert_src) + list(lv.gate_src)], reader_bwd)
+
     # ---- the multi-output surface -------------------------------------------------------------------------------------------------
     def _pipeline(self, x, batch_size):
         return None

@@ -1,7 +1,9 @@
-"""fit() of the multi-output models on the torch-autograd step: the loop of training._fit_torch over T labelled outputs.
+"""fit() of the multi-output models: the loop of training.fit_model over T labelled outputs.
 loss = sum_t w_t * mean_b(loss_t) + l2 penalties; a binary task that has a logit takes its gradient from the logit form and reports the
 value from probabilities clipped to [1e-7, 1 - 1e-7], as training._fit_torch does; ESMM's ctcvr output has no logit and takes the
-clipped-probability form for both.  A HIP training step for these models does not exist yet."""
+clipped-probability form for both.  Two steps compute it (DESIGN.md §4.15 "Training"): the HIP step (``fit_hip``: training_hip.HipTrainer
+with MultiTaskModel._hip_forward_backward, no autograd and no torch optimizer) where the model, the losses and the optimizer allow it, under
+the rule of training.fit_model, and the torch-autograd step (``fit_torch``) for everything else."""
 import numpy as np
 import torch
 
@@ -128,6 +130,67 @@ def fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end):
     return epoch_end.finish()
 
 
+def fit_hip(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end):
+    """The epochs on the HIP training step.  The trainer (optimizer moments, step count) lives on the model as ``_hip_trainer``, so
+    train_on_batch and a second fit() continue the same optimisation.  Per epoch ONE device matrix [steps, T] takes every step's summed
+    task losses (dctr_mtl_loss_grad adds into its row), the l2 penalties ride the optimizer launch (HipTrainer.penalty_acc, as
+    training._fit_hip), and the steps' outputs are gathered on the device for the compiled metrics: one copy to the host per epoch."""
+    from ...training_hip import HipTrainer
+    c = model._compiled
+    tr = getattr(model, "_hip_trainer", None)
+    if tr is None or tr.kind != c["optimizer"].lower():
+        tr = model._hip_trainer = HipTrainer(model, c["optimizer"])
+    T, names, metrics, w = model.num_tasks, model.task_names, list(c["metrics"]), np.asarray(c["loss_weights"], dtype=np.float64)
+    yrows = yt.t().contiguous()         # [n_tr, T]: permute_staged_ permutes dimension 0
+
+    def permute():
+        tops.permute_staged_(staged, yrows, torch.from_numpy(np.random.permutation(n_tr)).to(yrows.device))
+    cursor = tops._BatchCursor(n_tr, bs, None, permute if shuffle else None)
+    pen_acc = torch.zeros(1, dtype=torch.float64, device=model.device)
+    tr.penalty_acc = pen_acc
+    try:
+        for ep in range(epochs):
+            tot = torch.zeros(max(cursor.steps, 1), T, dtype=torch.float32, device=model.device)
+            pen_acc.zero_()
+            rows = 0
+            preds = torch.empty(T, n_tr, dtype=torch.float32, device=model.device) if metrics else None
+            seen = torch.empty(T, n_tr, dtype=torch.float32, device=model.device) if metrics else None
+            for i, (lo, hi) in enumerate(cursor.epoch()):
+                lo, hi = int(lo), int(hi)
+                ys = yrows[lo:hi].t().contiguous()
+                tr.penalty_rows = hi - lo
+                tr.step(staged, lo, hi, ys, loss_acc=tot[i])
+                if metrics:
+                    preds[:, rows:rows + hi - lo].copy_(tr._buffers(hi - lo)["pred"])
+                    seen[:, rows:rows + hi - lo].copy_(ys)
+                rows += hi - lo
+            model._check_status()
+            per = tot.double().sum(0).cpu().numpy() / max(rows, 1)
+            total = float((w * per).sum()) + float(pen_acc.item()) / max(rows, 1)
+            logs = dict([("loss", total)] + [("%s_loss" % n, float(v)) for n, v in zip(names, per)])
+            if metrics:
+                if model.esmm:
+                    preds[1, :rows].mul_(preds[0, :rows])       # (the step keeps sigmoid(l_cvr): the output is the product)
+                p, yy = preds[:, :rows].cpu().numpy().astype(np.float64), seen[:, :rows].cpu().numpy().astype(np.float64)
+                for t, n in enumerate(names):
+                    for mt in metrics:
+                        logs["%s_%s" % (n, model._metric_name(mt))] = model._metric(mt, p[t], yy[t])
+            if epoch_end(ep, logs):
+                break
+    finally:
+        tr.penalty_acc, tr.penalty_rows = None, 0
+    return epoch_end.finish()
+
+
+def takes_hip_step(model):
+    """The rule of training.fit_model: ``model.hip_training`` (default True), an optimizer given by a name the HIP step has, and a model /
+    loss combination it covers (training_hip.supported -> MultiTaskModel._hip_supported)."""
+    from ... import training_hip
+    opt = model._compiled["optimizer"]
+    return bool(getattr(model, "hip_training", True) and isinstance(opt, str) and opt.lower() in training_hip.OPT_DEFAULTS
+                and training_hip.supported(model))
+
+
 def fit_multitask(model, x, y, batch_size=256, epochs=1, verbose=1, validation_split=0.0, shuffle=True, validation_data=None, **kwargs):
     from ... import _C
     if model._compiled is None:
@@ -159,4 +222,5 @@ def fit_multitask(model, x, y, batch_size=256, epochs=1, verbose=1, validation_s
     staged = model.stage({k: np.asarray(v)[:n_tr] for k, v in feed.items()})
     yt = torch.from_numpy(np.ascontiguousarray(ys[:, :n_tr])).to(model.device)
     bs = int(batch_size) if batch_size else n_tr
-    return fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, EpochEnd(model, val, bs, epochs, verbose))
+    fit = fit_hip if takes_hip_step(model) else fit_torch
+    return fit(model, staged, yt, n_tr, bs, epochs, shuffle, EpochEnd(model, val, bs, epochs, verbose))

@@ -1604,12 +1604,7 @@ def mtl_mix(h, n_experts, width, z, gate_kernels, members, out=None, out_offset=
         out, out_offset = torch.empty(B, G * H, dtype=torch.float32, device=h.device), 0
     out_stride = _rows2d(op, "out", out, B, G * H, out_offset)
     _dev_check(h, out, *(list(z) + list(gate_kernels)))
-    key = (h.device, tuple(tuple(ms) for ms in members))
-    mdev = _MTL_MEMBERS.get(key)
-    if mdev is None:
-        if len(_MTL_MEMBERS) >= 64:
-            _MTL_MEMBERS.clear()
-        mdev = _MTL_MEMBERS[key] = torch.tensor([m for ms in members for m in ms], dtype=torch.int32).to(h.device)
+    mdev = _mtl_members_dev(h.device, members)
     keep = [_ptr_array(list(z)), _i64_array(z_strides), _ptr_array(list(gate_kernels)), _i32_array([len(ms) for ms in members]),
             _i32_array([m for ms in members for m in ms])]
     cast = lambda p: ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
@@ -1618,6 +1613,134 @@ def mtl_mix(h, n_experts, width, z, gate_kernels, members, out=None, out_offset=
                        members_dev=mdev.data_ptr(), out=out.data_ptr(), out_stride=out_stride, out_offset=int(out_offset))
     _C.check(_C.lib().dctr_mtl_mix(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_mix")
     return out
+
+
+def _mtl_members_dev(device, members):
+    key = (device, tuple(tuple(ms) for ms in members))
+    mdev = _MTL_MEMBERS.get(key)
+    if mdev is None:
+        if len(_MTL_MEMBERS) >= 64:
+            _MTL_MEMBERS.clear()
+        mdev = _MTL_MEMBERS[key] = torch.tensor([m for ms in members for m in ms], dtype=torch.int32).to(device)
+    return mdev
+
+
+def mtl_mix_bwd(h, n_experts, width, z, gate_kernels, members, d_out, dh, ds, d_out_offset=0, logits=None):
+    """Backward of mtl_mix (dctr_mtl_mix_bwd); h, z, gate_kernels, members as the forward took them, nothing saved by it.  d_out: float32
+    2-D view, gate g's gradient in columns [d_out_offset + g * width, + width).  Written: dh [B, >= n_experts * width] (expert e's
+    gradient in columns [e * width, + width), summed over the gates in order; zeros for an expert no gate mixes), ds [B, >= sum n_g]
+    (d loss / d gate logits, gate g from column sum_{g' < g} n_g') and, when given, logits [B, >= sum n_g] (the gate logits themselves).
+    The gates' weight gradient and dz are a bias-free linear layer's: ops.mlp_bwd(z_g, dz, [Wg_g], [logits_g], "linear", ...,
+    d_out=ds_g)."""
+    op = "mtl_mix_bwd"
+    E, H, G = int(n_experts), int(width), len(gate_kernels)
+    if h.dim() != 2:
+        raise ValueError("mtl_mix_bwd: h must be a float32 [B, >= n_experts * width] view with unit column stride")
+    B = h.shape[0]
+    h_stride = _rows2d(op, "h", h, B, E * H)
+    if not (G >= 1 and len(z) == G and len(members) == G):
+        raise ValueError("mtl_mix_bwd: one input, kernel and member list per gate")
+    dz = int(gate_kernels[0].shape[0])
+    members = [[int(m) for m in ms] for ms in members]
+    z_strides = []
+    for g in range(G):
+        if not members[g]:
+            raise ValueError("mtl_mix_bwd: gate %d mixes no expert" % g)
+        if any(m < 0 or m >= E for m in members[g]):
+            raise ValueError("mtl_mix_bwd: gate %d: members %s with %d experts" % (g, members[g], E))
+        if gate_kernels[g].dim() != 2 or gate_kernels[g].shape[0] != dz:
+            raise ValueError("mtl_mix_bwd: gate_kernels[%d] must be [%d, n_g]" % (g, dz))
+        _vec(op, "gate_kernels[%d]" % g, gate_kernels[g], dz * len(members[g]))
+        z_strides.append(_rows2d(op, "z[%d]" % g, z[g], B, dz))
+    n_all = sum(len(ms) for ms in members)
+    d_out_stride = _rows2d(op, "d_out", d_out, B, G * H, int(d_out_offset))
+    dh_stride = _rows2d(op, "dh", dh, B, E * H)
+    ds_stride = _rows2d(op, "ds", ds, B, n_all)
+    lg_stride = 0 if logits is None else _rows2d(op, "logits", logits, B, n_all)
+    _dev_check(h, d_out, dh, ds, logits, *(list(z) + list(gate_kernels)))
+    mdev = _mtl_members_dev(h.device, members)
+    keep = [_ptr_array(list(z)), _i64_array(z_strides), _ptr_array(list(gate_kernels)), _i32_array([len(ms) for ms in members]),
+            _i32_array([m for ms in members for m in ms])]
+    cast = lambda p: ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    a = _C.mtl.MixBwdArgs(batch=B, h=h.data_ptr(), h_stride=h_stride, n_experts=E, width=H, n_gates=G, z_dim=dz, z=cast(keep[0]),
+                          z_stride=cast(keep[1]), gate_kernel=cast(keep[2]), gate_n=cast(keep[3]), members=cast(keep[4]),
+                          members_dev=mdev.data_ptr(), d_out=d_out.data_ptr(), d_out_stride=d_out_stride, d_out_offset=int(d_out_offset),
+                          dh=dh.data_ptr(), dh_stride=dh_stride, ds=ds.data_ptr(), ds_stride=ds_stride,
+                          logits=None if logits is None else logits.data_ptr(), logits_stride=lg_stride)
+    _C.check(_C.lib().dctr_mtl_mix_bwd(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_mix_bwd")
+    return dh, ds
+
+
+_MTL_LOSS_KINDS = {"binary_crossentropy": _C.mtl.LOSS_BCE, "logloss": _C.mtl.LOSS_BCE, "bce": _C.mtl.LOSS_BCE, "mse": _C.mtl.LOSS_MSE,
+                   "mean_squared_error": _C.mtl.LOSS_MSE}
+
+
+def _f32_array(vals):
+    arr = (ctypes.c_float * max(1, len(vals)))()
+    for i, v in enumerate(vals):
+        arr[i] = float(v)
+    return arr
+
+
+def mtl_loss_grad(pred, y, dlogit, loss_sum, losses, binary, loss_weights=None, esmm=False, dbias=None):
+    """The multi-task loss gradient (dctr_mtl_loss_grad).  pred, y, dlogit: float32 [T, B] with unit column stride; pred[t] = the tower's
+    output (sigmoid applied where binary[t]; with ``esmm`` row 1 is sigmoid(l_cvr), not the product).  losses[t]: 'binary_crossentropy' |
+    'mse' (binary + BCE and regression + MSE only).  dlogit = d(sum_t w_t mean_b loss_t) / d logit_t is written; loss_sum (float32 [T],
+    contiguous) and the device scalars dbias[t] (None to skip one) are ADDED to: the tasks' summed reported losses and sum_b dlogit[t]."""
+    op = "mtl_loss_grad"
+    T = len(losses)
+    if T < 1 or pred.dim() != 2 or pred.shape[0] != T:
+        raise ValueError("mtl_loss_grad: pred must be a float32 [T, B] view with one row per loss")
+    B = pred.shape[1]
+    binary = [bool(b) for b in binary]
+    weights = [1.0] * T if loss_weights is None else [float(w) for w in loss_weights]
+    if len(binary) != T or len(weights) != T or (dbias is not None and len(dbias) != T):
+        raise ValueError("mtl_loss_grad: one task type, loss weight (and bias gradient) per task")
+    kinds = []
+    for t, name in enumerate(losses):
+        if not isinstance(name, str) or name.lower() not in _MTL_LOSS_KINDS:
+            raise ValueError("mtl_loss_grad: unknown loss %r (binary_crossentropy, mse)" % (name,))
+        kinds.append(_MTL_LOSS_KINDS[name.lower()])
+        if binary[t] != (kinds[t] == _C.mtl.LOSS_BCE):
+            raise ValueError("mtl_loss_grad: task %d: %s on a %s output (binary + binary_crossentropy or regression + mse)"
+                             % (t, name, "binary" if binary[t] else "regression"))
+    if esmm and not (T == 2 and all(binary)):
+        raise ValueError("mtl_loss_grad: esmm takes two binary tasks")
+    strides = [_rows2d(op, name, t_, T, B) if T > 1 else max(_rows2d(op, name, t_, T, B), B)
+               for name, t_ in (("pred", pred), ("y", y), ("dlogit", dlogit))]
+    _vec(op, "loss_sum", loss_sum, T)
+    for b_ in dbias or []:
+        if b_ is not None:
+            _vec(op, "dbias entry", b_, 1)
+    _dev_check(pred, y, dlogit, loss_sum, *(dbias or []))
+    keep = [_i32_array(kinds), _i32_array([int(b) for b in binary]), _f32_array(weights), None if dbias is None else _ptr_array(list(dbias))]
+    cast = lambda p: None if p is None else ctypes.cast(p, ctypes.c_void_p)       # noqa: E731
+    a = _C.mtl.LossArgs(batch=B, n_tasks=T, esmm=int(bool(esmm)), pred=pred.data_ptr(), pred_stride=strides[0], y=y.data_ptr(),
+                        y_stride=strides[1], loss_kind=cast(keep[0]), binary=cast(keep[1]), loss_weight=cast(keep[2]),
+                        dlogit=dlogit.data_ptr(), dlogit_stride=strides[2], loss_sum=loss_sum.data_ptr(), dbias=cast(keep[3]))
+    _C.check(_C.lib().dctr_mtl_loss_grad(ctypes.byref(a), _C.stream_ptr()), "dctr_mtl_loss_grad")
+    return dlogit
+
+
+def mtl_sum_slots(srcs, n, dst, dst_offset=0, accumulate=False):
+    """dst[:, dst_offset : dst_offset + n] = (``accumulate``: +=) srcs[0][:, :n] + srcs[1][:, :n] + ..., summed in that order
+    (dctr_mtl_sum_slots).  srcs: 1 .. 16 float32 [B, >= n] views with unit column stride, each with its own row stride.  The gradient of
+    a slot that several DNNs read: ops.mlp_bwd writes its dx, so each reader writes to scratch and this launch forms the sum."""
+    op = "mtl_sum_slots"
+    srcs, n = list(srcs), int(n)
+    if not 1 <= len(srcs) <= 16:
+        raise ValueError("mtl_sum_slots: 1 .. 16 sources (%d given)" % len(srcs))
+    if dst.dim() != 2 or n < 1:
+        raise ValueError("mtl_sum_slots: dst must be a float32 2-D view with unit column stride, n >= 1")
+    B = dst.shape[0]
+    dst_stride = _rows2d(op, "dst", dst, B, n, int(dst_offset))
+    strides = [_rows2d(op, "srcs[%d]" % k, s, B, n) for k, s in enumerate(srcs)]
+    _dev_check(dst, *srcs)
+    keep = [_ptr_array(srcs), _i64_array(strides)]
+    _C.check(_C.lib().dctr_mtl_sum_slots(ctypes.cast(keep[0], ctypes.c_void_p), ctypes.cast(keep[1], ctypes.c_void_p), len(srcs), B, n,
+                                         dst.data_ptr(), dst_stride, int(dst_offset), int(bool(accumulate)), _C.stream_ptr()),
+             "dctr_mtl_sum_slots")
+    return dst
 
 
 def mtl_level(x, in_dim, x_offsets, expert_kernels, expert_biases, gate_kernels, members, expert_src=None, gate_src=None,

@@ -10,8 +10,9 @@ What lies between the stage and the loss is the model class's, beside its forwar
 of ``models/_common.py:FeatureModel``): ``_hip_supported`` says whether an instance trains here, ``_hip_params`` registers its
 private parameters through ``HipTrainer.param``, ``_hip_forward_backward`` is its part of the step.  DeepFM / WDL / FNN
 (models/deepfm.py), NFM and PNN (interaction kernel in front of the DNN), AFM (AFMLayer instead of the DNN), DCN and DCNMix
-(``dctr_crossnet_bwd`` / ``dctr_crossnet_mix_bwd``), xDeepFM (``dctr_cin_bwd``), FLEN (``dctr_fieldwise_bwd``) and DIN (attention input / weighted sum / lookup scatter
-kernels, Dice as tf.keras runs it under fit()) bring one; a model without, ``afm_dropout`` and a PReLU DNN keep ``training.py``'s step.
+(``dctr_crossnet_bwd`` / ``dctr_crossnet_mix_bwd``), xDeepFM (``dctr_cin_bwd``), FLEN (``dctr_fieldwise_bwd``), DIN (attention input / weighted sum / lookup scatter
+kernels, Dice as tf.keras runs it under fit()) and the multi-task models (models/multitask/_base.py: ``dctr_mtl_mix_bwd``, ``dctr_mtl_loss_grad``,
+``dctr_mtl_sum_slots``; T outputs, ``y`` [T, B]) bring one; a model without, ``afm_dropout`` and a PReLU DNN keep ``training.py``'s step.
 
 Semantics follow tf.keras as the reference uses it (``model.compile("adam", "binary_crossentropy")``,
 examples/run_classification_criteo.py:44-50; also "adagrad", "rmsprop", "sgd" by name with tf.keras' defaults): Adam lr
@@ -143,7 +144,9 @@ class HipTrainer(object):
         self.penalty_acc, self.penalty_rows = None, 0   # (fit(): device float64 accumulator of rows * l2 penalties; rows of the next update)
         self.own = {}               # the model's private parameter handles and per-trainer state (FeatureModel._hip_params)
         model._hip_params(self)
-        self.p_gbias = param(model.prediction.w("global_bias")) if model.prediction.use_bias else None
+        # (a multi-output model has ``predictions``, one per task, and registers their biases itself: FeatureModel._hip_params)
+        pred = getattr(model, "prediction", None)
+        self.p_gbias = param(pred.w("global_bias")) if pred is not None and pred.use_bias else None
         self._buf = {}
         if self.init_acc:
             for p in self.params:
@@ -174,6 +177,8 @@ class HipTrainer(object):
             dev = self.model.device
             sp = self.model.stage_plan
             units = [k.shape[1] for k in self.model.dnn.kernels] if self.model.dnn is not None else []
+            # one output per sample, or per task and sample (models/multitask: pred / dlogit [T, B], one summed loss per task)
+            outs = (len(self.model.predictions),) if getattr(self.model, "prediction", None) is None else ()
             if len(self._buf) >= 4:            # ragged remainder sizes (N % span) must not pile up per-B buffers
                 self._buf.clear()
             b = self._buf[B] = {
@@ -182,10 +187,10 @@ class HipTrainer(object):
                 "dpre": [torch.empty(B, n, dtype=torch.float32, device=dev) for n in units] if self.slow_dnn else None,
                 "bn_stat": [(torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
                             for n in units] if self.bn_layers else None,
-                "pred": torch.empty(B, dtype=torch.float32, device=dev),
-                "dlogit": torch.empty(B, dtype=torch.float32, device=dev),
+                "pred": torch.empty(outs + (B,), dtype=torch.float32, device=dev),
+                "dlogit": torch.empty(outs + (B,), dtype=torch.float32, device=dev),
                 "dx": torch.empty(B, sp.out_stride, dtype=torch.float32, device=dev),
-                "loss": torch.zeros(1, dtype=torch.float32, device=dev),
+                "loss": torch.zeros(outs or (1,), dtype=torch.float32, device=dev),
                 "pooled_g": {}, "pooled_lin_g": {},
             }
             entries = []

@@ -850,6 +850,75 @@ typedef struct {
     int64_t out_offset;
 } dctr_mtl_mix_args_t;
 int dctr_mtl_mix(const dctr_mtl_mix_args_t* args, void* stream);
+/* Backward of dctr_mtl_mix (the multi-task training step).  h, z, gate_kernel, gate_n, members, members_dev as the forward
+ * took them; d_out [B, d_out_stride]: gate g's gradient in columns [d_out_offset + g * width, + width).  Per row b and gate g, with
+ * p = softmax(z_g kernel_g) recomputed:  a_j = <d_out_g[b,:], h_{members[g][j]}[b,:]>,
+ *     ds[b, first_g + j] = p_j (a_j - sum_i p_i a_i)       first_g = sum of gate_n before g: d loss / d (z_g kernel_g)
+ *     dh[b, e * width + c] = sum over (g, j) with members[g][j] == e of p_j d_out_g[b, c]   (g ascending, then j; zeros for an expert no
+ *                                                                                             gate mixes: all n_experts * width columns are written)
+ *     logits (optional) [b, first_g + j] = (z_g kernel_g)[j]
+ * No weight gradient and no dz: those are a bias-free linear layer's (dctr_mlp_bwd over z_g with d_out = ds_g).  dh, ds and logits must
+ * not overlap the inputs.  Any shape; gates go out eight per launch; no atomics (the same bits on every call). */
+typedef struct {
+    int64_t batch;
+    const float* h;
+    int64_t h_stride;
+    int32_t n_experts;
+    int32_t width;
+    int32_t n_gates;
+    int32_t z_dim;
+    const float* const* z;                /* HOST [G] of DEVICE pointers */
+    const int64_t* z_stride;              /* HOST [G] */
+    const float* const* gate_kernel;      /* HOST [G] */
+    const int32_t* gate_n;                /* HOST [G] */
+    const int32_t* members;               /* HOST [sum gate_n] */
+    const int32_t* members_dev;           /* DEVICE copy of members */
+    const float* d_out;
+    int64_t d_out_stride;
+    int64_t d_out_offset;
+    float* dh;                            /* [B, dh_stride], dh_stride >= n_experts * width */
+    int64_t dh_stride;
+    float* ds;                            /* [B, ds_stride], ds_stride >= sum gate_n */
+    int64_t ds_stride;
+    float* logits;                        /* NULL, or [B, logits_stride >= sum gate_n] */
+    int64_t logits_stride;
+} dctr_mtl_mix_bwd_args_t;
+int dctr_mtl_mix_bwd(const dctr_mtl_mix_bwd_args_t* args, void* stream);
+/* The multi-task loss gradient.  pred [T, pred_stride]: the towers' outputs — sigmoid(logit_t) where binary[t], else logit_t; with esmm
+ * (two binary tasks) row 1 is sigmoid(l_cvr), NOT the product.  y [T, y_stride] labels.  Writes
+ *     dlogit[t * dlogit_stride + b] = d (sum_t loss_weight[t] * mean_b loss_t) / d logit_t[b]
+ * and ADDS  loss_sum[t] += sum_b (reported loss of task t),  dbias[t][0] += sum_b dlogit[t, b]  (where dbias and dbias[t] are not NULL).
+ *     binary + DCTR_MTL_LOSS_BCE:      gradient w (p - y) / B (the logit form); reported: -(y log pc + (1 - y) log(1 - pc)), pc = p
+ *                                      clipped to [1e-7, 1 - 1e-7] (Keras' epsilon; in float32 the upper bound is 1 - 2^-23)
+ *     regression + DCTR_MTL_LOSS_MSE:  gradient 2 w (l - y) / B; reported (l - y)^2
+ *     esmm: p0 = pred[0], c = pred[1], p1 = p0 c.  Task 0 as above; task 1 reports the clipped form on p1 and takes its gradient from it:
+ *           g = w_1 (-y / pc + (1 - y) / (1 - pc)) / B where 1e-7 <= p1 <= 1 - 1e-7, else 0;  dlogit[0] += g p1 (1 - p0),
+ *           dlogit[1] = g p1 (1 - c).
+ * Every other (binary, loss kind) pair answers DCTR_E_UNSUPPORTED, an unknown loss kind DCTR_E_ENUM.  One workgroup per task reduces in a
+ * fixed order: no atomics. */
+enum { DCTR_MTL_LOSS_BCE = 0, DCTR_MTL_LOSS_MSE = 1 };
+typedef struct {
+    int64_t batch;
+    int32_t n_tasks;
+    int32_t esmm;                         /* 0 | 1 */
+    const float* pred;
+    int64_t pred_stride;                  /* >= batch */
+    const float* y;
+    int64_t y_stride;
+    const int32_t* loss_kind;             /* HOST [T]: DCTR_MTL_LOSS_* */
+    const int32_t* binary;                /* HOST [T] */
+    const float* loss_weight;             /* HOST [T] */
+    float* dlogit;                        /* [T, dlogit_stride] */
+    int64_t dlogit_stride;
+    float* loss_sum;                      /* DEVICE [T], added to */
+    float* const* dbias;                  /* NULL, or HOST [T] of device scalars (entries may be NULL), added to */
+} dctr_mtl_loss_args_t;
+int dctr_mtl_loss_grad(const dctr_mtl_loss_args_t* args, void* stream);
+/* dst[b, dst_offset + c] = (accumulate ? dst[b, dst_offset + c] : 0) + src[0][b, c] + src[1][b, c] + ... for c < n, summed in that order.
+ * src / src_stride: HOST arrays of n_src <= 16 device pointers and their row strides (>= n).  The gradient of a slot that several DNNs
+ * read: dctr_mlp_bwd WRITES dx, so each reader writes to scratch and this launch forms the sum.  dst must not overlap a source. */
+int dctr_mtl_sum_slots(const float* const* src, const int64_t* src_stride, int32_t n_src, int64_t batch, int32_t n, float* dst,
+                       int64_t dst_stride, int64_t dst_offset, int32_t accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Transformer.call x n_layers — deepctr/layers/sequence.py:523-635 with PositionEncoding (:683-689) and LayerNormalization

@@ -5,9 +5,11 @@ the whole forward (staged ids -> [T, rows] probabilities: fused gather, ops.mtl_
 torch-ops forward (autograd_logits + autograd_outputs under no_grad) and beside the forced-layered route; and dctr_mtl_level_fwd alone
 (the first level, on the model's own dnn_in) beside its f32-MFMA bound and at each tile height.  The bound is arithmetic, not a
 measurement: 2 K N FLOP per row and layer of every expert and gate DNN plus the gate logits, at 157.3 TFLOP/s.  Device-event timing
-after warm-up.  Prints one JSON line.
+after warm-up.  Training (DESIGN.md §4.15 "Training"): one HIP training step (training_hip.HipTrainer, Adam) beside one torch-autograd step
+(the loop body of models/multitask/_fit.py:fit_torch, Adam) of the same model on ``--train-rows`` rows, and dctr_mtl_mix_bwd alone on
+``--rows`` rows of the first level beside its byte bound — h and d_out read, dh written, at 6.3 TB/s.  Prints one JSON line.
 
-    python scripts/bench_mtl.py [--rows 65536] [--iters 20]"""
+    python scripts/bench_mtl.py [--rows 65536] [--train-rows 4096] [--iters 20]"""
 import argparse
 import json
 import os
@@ -21,6 +23,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 MFMA_F32_TFLOPS = 157.3
+HBM_TBPS = 6.3               # achievable streaming rate the bound is quoted at
 
 
 def _time(fn, iters):
@@ -44,13 +47,73 @@ def level_flops(in_dim, lv):
     return len(lv.experts) * per_expert + sum(per_gate + 2 * gd[-1] * len(ms) for ms in lv.members)
 
 
+def train_times(model, cols, rows, iters, with_torch, rng):
+    """One HIP step and one autograd step (both Adam, both with the l2 penalties) of ``model`` on ``rows`` rows, in ms."""
+    from deepctr_amd import engine, training, training_hip
+    from deepctr_amd.feature_column import SparseFeat
+    from deepctr_amd.models.multitask import _fit
+    feed = {fc.name: (rng.randint(0, fc.vocabulary_size, rows).astype(np.int32) if isinstance(fc, SparseFeat) else
+                      rng.rand(rows).astype(np.float32)) for fc in cols}
+    staged = engine.Staged(rows)
+    model._stage_inputs(feed, staged)
+    yt = torch.from_numpy((rng.rand(model.num_tasks, rows) > 0.5).astype(np.float32)).to(model.device)
+    model.compile("adam")
+    r = {"rows": rows, "hip_supported": bool(training_hip.supported(model))}
+    if with_torch:          # first: the HIP step moves the weights through raw pointers
+        params = [t for k, t in model.named_weights() if "moving_" not in k]
+        for t in params:
+            t.requires_grad_(True)
+        opt = training._OPTS["adam"](params)
+        regs = training.regularized_weights(model)
+        w = model._compiled["loss_weights"]
+
+        def autograd_step():
+            model._begin()
+            pairs = _fit.task_losses(model, model.autograd_logits(staged, 0, rows, training=True), yt)
+            loss = sum(wt * l for wt, (l, _) in zip(w, pairs))
+            for t, l2 in regs:
+                loss = loss + l2 * (t * t).sum()
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+        try:
+            r["autograd_step_ms"] = round(_time(autograd_step, max(2, iters // 4)), 4)
+        finally:
+            for t in params:
+                t.requires_grad_(False)
+        del opt
+    if r["hip_supported"]:
+        tr = training_hip.HipTrainer(model, "adam")
+        acc = torch.zeros(model.num_tasks, dtype=torch.float32, device=model.device)
+        r["hip_step_ms"] = round(_time(lambda: tr.step(staged, 0, rows, yt, loss_acc=acc), iters), 4)
+        if with_torch:
+            r["hip_step_speedup"] = round(r["autograd_step_ms"] / r["hip_step_ms"], 2)
+    return r
+
+
+def mix_bwd_time(model, x, n, iters):
+    """dctr_mtl_mix_bwd on the first level (expert outputs and gate inputs of random values) beside its byte bound."""
+    from deepctr_amd import ops
+    lv, dev = model.levels[0], model.device
+    E, G, H, n_all = len(lv.experts), len(lv.gate_dense), lv.experts[0].hidden_units[-1], sum(len(ms) for ms in lv.members)
+    dz = lv.gate_dnns[0].hidden_units[-1] if lv.gate_dnns[0].hidden_units else model.stage_plan.in_dim
+    new = lambda cols: torch.randn(n, cols, dtype=torch.float32, device=dev)      # noqa: E731
+    h, d_out, dh, ds = new(E * H), new(G * H), new(E * H), new(n_all)
+    zs = [x[:, :dz] if not lv.gate_dnns[0].hidden_units else new(dz) for _ in range(G)]
+    gk = [g.w("kernel") for g in lv.gate_dense]
+    ms = _time(lambda: ops.mtl_mix_bwd(h, E, H, zs, gk, lv.members, d_out, dh, ds), iters)
+    bound = n * (2 * E * H + G * H) * 4 / (HBM_TBPS * 1e12) * 1e3
+    return {"mix_bwd_ms": round(ms, 4), "mix_bwd_bound_ms": round(bound, 4), "mix_bwd_share_of_bound": round(bound / ms, 3)}
+
+
 def main():
     from deepctr_amd import engine, models
     from deepctr_amd.feature_column import DenseFeat, SparseFeat
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--no-torch", action="store_true", help="skip the torch-ops forward")
+    ap.add_argument("--train-rows", type=int, default=4096, help="rows of the training steps (0: skip them)")
+    ap.add_argument("--no-torch", action="store_true", help="skip the torch-ops forward and the autograd step")
     args = ap.parse_args()
     device = torch.device("cuda:0")
     n = args.rows
@@ -108,6 +171,9 @@ def main():
                                                  gate_src=lv.gate_src, out=lout, tile_rows=rows, **kwl), args.iters)
                 r["level_fused_ms_rows%d" % rows] = round(ms, 4)
             r["level_share_of_bound"] = round(bound / r["level_fused_ms_rows0"], 3)
+        r.update(mix_bwd_time(model, ws["dnn_in"], n, args.iters))
+        if args.train_rows:
+            r["train"] = train_times(model, cols, args.train_rows, args.iters, not args.no_torch, rng)
         del model
         torch.cuda.empty_cache()
     print(json.dumps(res))
