@@ -47,6 +47,7 @@ SOURCES = [
     "interaction_kernels.hip",
     "cin_kernels.hip",
     "cin_bwd_kernels.hip",
+    "cin_layered_kernels.hip",
     "interacting_kernels.hip",
     "bilinear_kernels.hip",
     "fieldpair_kernels.hip",
@@ -65,6 +66,8 @@ SOURCES = [
     "gemm_kernels.hip",
     "mlp_bwd_kernels.hip",
     "train_kernels.hip",
+    "interaction_bwd_kernels.hip",
+    "din_train_kernels.hip",
 ]
 
 ARCH = "gfx950"

@@ -6,6 +6,7 @@
 // the dpre and x0 tiles sit in LDS, a wave walks 16-row blocks of W (the MFMA A operand: M = i*Fk + j, the four k-slots of a
 // lane being four consecutive h of one 16-B load), T^T tiles [16 (i,j) x 16 rows] come out of v_mfma_f32_16x16x4_f32 and are
 // contracted at once, mostly in registers.  W streams from L2 one tile ahead of the MFMAs.
+#include "cin_internal.h"
 #include "dctr_common.h"
 #include "mfma_tile.h"
 

@@ -11,6 +11,7 @@
 // j of the same i; B streams W_k rows from L2; the layer output y[b,h,d] is written back to LDS where it
 // is both the next layer's x_{k+1} and the source of the sum over D.  Exact fp32 (fmaf-chain numerics).
 // Cost model (C3, F0=26, D=16, H=128,128): 9.58 MFLOP/sample -> 155 TF f32-MFMA => >= 253 us / 4096.
+#include "cin_internal.h"
 #include "dctr_common.h"
 #include "mfma_tile.h"
 
@@ -579,9 +580,7 @@ static int cin_pick_slice(const dctr_cin_args_t* a) {
     return 0;
 }
 
-// train_kernels.hip: CIN layer by layer on the library's GEMM (z materialised per chunk of samples) — any layer sizes
-size_t dctr_cin_layered_sample_floats(const dctr_cin_args_t* a);
-int dctr_cin_fwd_layered(const dctr_cin_args_t* a, void* workspace, size_t workspace_bytes, void* stream);
+// cin_layered_kernels.hip (declared in cin_internal.h): CIN layer by layer on the library's GEMM (z materialised per chunk of samples) — any layer sizes
 constexpr int CIN_LAYERED_SAMPLES = 256;       // samples per chunk the workspace query provides for (any room for >= 16 works)
 
 // the argument checks every route shares (sizes, enums): what is left to fail in cin_fwd_impl afterwards is the LDS the shape needs
@@ -598,7 +597,7 @@ static int cin_shape_checks(const dctr_cin_args_t* a) {
     return DCTR_OK;
 }
 
-// 1: the one-kernel form takes the sample whole; 2: in slices of *dd dimensions; 3: neither — layer by layer (train_kernels.hip)
+// 1: the one-kernel form takes the sample whole; 2: in slices of *dd dimensions; 3: neither — layer by layer (cin_layered_kernels.hip)
 static int cin_route_of(const dctr_cin_args_t* a, int* dd) {
     *dd = cin_pick_slice(a);
     if (*dd == a->dim) return 1;

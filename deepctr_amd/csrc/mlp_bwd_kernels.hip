@@ -5,6 +5,7 @@
 // layers, weights streamed through the three-stage register pipeline) as ONE launch: the dX GEMM + act' kernel pair per layer
 // (2 L launches, ~25 + 7 us each on a 4096-row step whatever their size) is gone; every dZ_l also goes to HBM for dW_l = X_l^T dZ_l.
 #include "mlp_device.h"
+#include "train_common.h"
 
 namespace dctr_mlp {
 

@@ -1,26 +1,29 @@
-// SURVEY.md §8(f) rank 1 — backward + optimizer for the hot path's ops, so that `fit()` runs on HIP kernels:
-//   dctr_bce_grad             loss + d(loss)/d(logit) of PredictionLayer('binary') + binary_crossentropy / of mse
-//   dctr_embed_gather_fm_bwd  backward of dctr_embed_gather_fm: embedding_lookup + concat (inputs.py:101-117,
-//                             layers/utils.py:336-346), get_linear_logit (feature_column.py:171-210) and FM
-//                             (layers/interaction.py:588-604): row gradients scatter-added into dense gradient tables
-//   dctr_mlp_bwd              backward of DNN.call + Dense(1) head (layers/core.py:189-208): the two GEMMs per layer
-//                             are plain GEMMs on the own MFMA kernel of gemm_kernels.hip (dctr_gemm; rocBLAS until round 3); masks, bias sums and the head are kernels here
-//   dctr_adam_step            Keras Adam (non-lazy: every row of a table moves every step, as TF's
-//                             _resource_apply_sparse does) with the reference's l2 regulariser folded in
-// The reference has no code of its own for any of this (Keras autodiff + tf.keras.optimizers); the formulas are the
-// derivatives of the forward expressions cited above.
+// The core of the HIP training step.  What is here:
+//   dctr_bce_grad, dctr_bce_grad_w   loss + d(loss)/d(logit) of PredictionLayer('binary') + binary_crossentropy / of mse
+//   dctr_embed_gather_fm_bwd, dctr_embed_pool_bwd, dctr_embed_lookup_bwd
+//                             backward of embedding_lookup + concat (inputs.py:101-117, layers/utils.py:336-346), get_linear_logit
+//                             (feature_column.py:171-210), FM (layers/interaction.py:588-604) and of the sequence pooling
+//                             (inputs.py:120-158, layers/sequence.py:76-106, :155-183): row gradients scatter-added into
+//                             dense gradient tables
+//   dctr_mlp_bwd (+ _workspace_bytes, _join), dctr_dense1_bwd, dctr_dice_train_fwd, dctr_dnn_train_layer_fwd / _bwd
+//                             backward of DNN.call + Dense(1) head (layers/core.py:189-208) on dctr_gemm (gemm_kernels.hip) and
+//                             the chain of mlp_bwd_kernels.hip; Dice, BatchNormalization and Dropout under training=True
+//   dctr_crossnet_bwd, dctr_crossnet_mix_bwd (+ _workspace_bytes)   CrossNet / CrossNetMix (layers/interaction.py:405-424, :511-549)
+//   dctr_opt_multi, dctr_opt_multi_l2, dctr_adam_step, dctr_adam_multi
+//                             tf.keras Adam / Adagrad / RMSprop / SGD over all parameters in one launch (non-lazy: every row of a
+//                             table moves every step, as TF's _resource_apply_sparse does), the reference's l2 regulariser folded in
+// What is NOT here: CIN (cin_layered_kernels.hip, cin_bwd_kernels.hip), the pairwise interaction layers
+// (interaction_bwd_kernels.hip) and DIN's attention pieces (din_train_kernels.hip).  train_common.h holds what those units and the
+// families still here share; the launchers of namespace dctr_train are defined in the DNN section below.  The reference has no code
+// of its own for any of this (Keras autodiff + tf.keras.optimizers); the formulas are the derivatives of the forward expressions
+// cited at each section.
 #include <stdlib.h>
 
 #include "dctr_gemm.h"
 
 #include "dctr_common.h"
 #include "embed_device.h"
-
-namespace dctr_mlp {   // mlp_bwd_kernels.hip
-int launch_bwd_chain(hipStream_t stream, int64_t batch, int in_dim, int n_layers, const int32_t* units_fwd, const float* const* Wt,
-                     const float* const* acts, int activation, const float* dz_in, float* const* dz_out, float* dx, int64_t dx_stride);
-bool bwd_chain_fits(int in_dim, int n_layers, const int32_t* units_fwd);
-}
+#include "train_common.h"
 
 namespace {
 
@@ -332,8 +335,6 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(dctr_pool_args_t a, const
 // ---------------------------------------------------------------------------------------------------
 // DNN backward helpers
 // ---------------------------------------------------------------------------------------------------
-constexpr int BWD_ROWS = 16;     // batch rows per iteration of the generic Dice passes further down (the 16-B forms take over when N % 4 == 0)
-
 // dZ[b, n] = dlogit[b] * head_w[n] * act'(h[b, n]);   d_head_w[n] += sum_b dlogit[b] * h[b, n]
 // (any N / strides: thread = one column (blockIdx.y * 256 + threadIdx.x), rows grid-strided over blockIdx.x; the 16-B forms below
 // take over when the shapes allow)
@@ -382,50 +383,6 @@ __global__ __launch_bounds__(256) void act_bwd_colsum_kernel(float* __restrict__
 // The two helpers above with 16-B accesses and the rows spread over the workgroup: thread (rl, c) owns columns 4c .. 4c+3 of rows
 // rl, rl + RL, ... (RL = 256 / (N/4) row lanes; a workgroup sweeps RL x N contiguous floats per iteration, grid-stride), the column
 // sums meet in LDS and leave as ONE atomic per column and workgroup (N % 4 == 0, N <= 1024, strides % 4 == 0, 16-B aligned).
-constexpr int COLSUM_MAX_WG = 64;      // workgroups of a pass that ends in one atomic per column and workgroup
-
-// workgroups of a column-sum pass over `rows` rows: enough of them to keep the loads in flight, few enough that the final atomics
-// (one per column and workgroup, ~90 ns each on one address) stay a short tail
-static unsigned colsum_grid(int64_t rows, int RL) {
-    int64_t g = dctr_ceil_div(rows, (int64_t)RL * 4);
-    const int64_t cap = rows >= 32768 ? 128 : COLSUM_MAX_WG;
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-// grid of the BWD_ROWS-rows-per-iteration kernels (grid-stride over row blocks)
-static unsigned rows_grid(int64_t rows, bool column_sums) {
-    const int64_t nb = dctr_ceil_div(rows, (int64_t)BWD_ROWS), cap = column_sums ? COLSUM_MAX_WG : 16384;
-    return (unsigned)(nb < 1 ? 1 : (nb > cap ? cap : nb));
-}
-
-__device__ __forceinline__ float4 act_grad4(float4 d, float4 hv, int act) {
-    if (act == DCTR_ACT_RELU) {
-        d.x = hv.x > 0.f ? d.x : 0.f; d.y = hv.y > 0.f ? d.y : 0.f; d.z = hv.z > 0.f ? d.z : 0.f; d.w = hv.w > 0.f ? d.w : 0.f;
-    } else if (act == DCTR_ACT_SIGMOID) {
-        d.x *= hv.x * (1.f - hv.x); d.y *= hv.y * (1.f - hv.y); d.z *= hv.z * (1.f - hv.z); d.w *= hv.w * (1.f - hv.w);
-    } else if (act == DCTR_ACT_TANH) {
-        d.x *= 1.f - hv.x * hv.x; d.y *= 1.f - hv.y * hv.y; d.z *= 1.f - hv.z * hv.z; d.w *= 1.f - hv.w * hv.w;
-    }
-    return d;
-}
-
-__device__ __forceinline__ void colsum4_finish(float4 acc, int N4, int RL, int c, float* __restrict__ out) {
-    __shared__ float4 red[256];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (out != nullptr && (int)threadIdx.x < N4) {
-        float4 t = red[c];
-        for (int r = 1; r < RL; ++r) {
-            const float4 u = red[r * N4 + c];
-            t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
-        }
-        unsafeAtomicAdd(out + 4 * c + 0, t.x);
-        unsafeAtomicAdd(out + 4 * c + 1, t.y);
-        unsafeAtomicAdd(out + 4 * c + 2, t.z);
-        unsafeAtomicAdd(out + 4 * c + 3, t.w);
-    }
-}
-
 __global__ __launch_bounds__(256) void head_bwd4_kernel(const float* __restrict__ dlogit, const float* __restrict__ head_w,
                                                         const float* __restrict__ h, int64_t h_stride, int64_t batch, int N,
                                                         int act, float* __restrict__ dz, int64_t dz_stride,
@@ -466,8 +423,42 @@ __global__ __launch_bounds__(256) void act_bwd_colsum4_kernel(float* __restrict_
     colsum4_finish(acc, N4, RL, c, db);
 }
 
+// out[b, c] (+)= src[b, c]   (strided rows)
+__global__ __launch_bounds__(256) void add_rows_kernel(const float* __restrict__ src, int64_t src_stride, int64_t batch, int d,
+                                                       float* __restrict__ out, int64_t out_stride, int accumulate) {
+    const int64_t total = batch * d;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / d;
+        const int c = (int)(i - b * d);
+        out[b * out_stride + c] = (accumulate ? out[b * out_stride + c] : 0.f) + src[b * src_stride + c];
+    }
+}
+
+// out[i] += sum_s parts[s * n + i]
+__global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ parts, int64_t n, int n_parts,
+                                                        float* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;          // four independent chains: the loads of 4 slices in flight per step
+        int s = 0;
+        for (; s + 4 <= n_parts; s += 4) {
+            a0 += parts[(int64_t)s * n + i];
+            a1 += parts[(int64_t)(s + 1) * n + i];
+            a2 += parts[(int64_t)(s + 2) * n + i];
+            a3 += parts[(int64_t)(s + 3) * n + i];
+        }
+        for (; s < n_parts; ++s) a0 += parts[(int64_t)s * n + i];
+        out[i] += (a0 + a1) + (a2 + a3);
+    }
+}
+
+}  // namespace
+
+// the launchers of the kernels above: declared in train_common.h, called from the DNN and CrossNet hosts below and from
+// cin_layered_kernels.hip
+namespace dctr_train {
+
 // launch either form: the 16-B one when the shapes allow it
-static void launch_act_bwd_colsum(hipStream_t st, float* dh, const float* h, int64_t batch, int N, int act, float* db) {
+void launch_act_bwd_colsum(hipStream_t st, float* dh, const float* h, int64_t batch, int N, int act, float* db) {
     if (N % 4 == 0 && N <= 1024 && dctr_aligned16(dh) && (h == nullptr || dctr_aligned16(h))) {
         const int RL = 256 / (N / 4);
         int64_t g = dctr_ceil_div(batch, (int64_t)RL * 4);           // >= 4 rows per thread where the batch has them
@@ -483,8 +474,8 @@ static void launch_act_bwd_colsum(hipStream_t st, float* dh, const float* h, int
     }
 }
 
-static void launch_head_bwd(hipStream_t st, const float* dlogit, const float* head_w, const float* h, int64_t h_stride, int64_t batch,
-                            int N, int act, float* dz, int64_t dz_stride, float* d_head_w) {
+void launch_head_bwd(hipStream_t st, const float* dlogit, const float* head_w, const float* h, int64_t h_stride, int64_t batch,
+                     int N, int act, float* dz, int64_t dz_stride, float* d_head_w) {
     if (N % 4 == 0 && N <= 1024 && h_stride % 4 == 0 && dz_stride % 4 == 0 && dctr_aligned16(h) && dctr_aligned16(dz) &&
         dctr_aligned16(head_w)) {
         const int RL = 256 / (N / 4);
@@ -497,6 +488,19 @@ static void launch_head_bwd(hipStream_t st, const float* dlogit, const float* he
                            dim3(256), 0, st, dlogit, head_w, h, h_stride, batch, N, act, dz, dz_stride, d_head_w);
     }
 }
+
+void launch_add_rows(hipStream_t st, unsigned blocks, const float* src, int64_t src_stride, int64_t batch, int d, float* out,
+                     int64_t out_stride, int accumulate) {
+    hipLaunchKernelGGL(add_rows_kernel, dim3(blocks), dim3(256), 0, st, src, src_stride, batch, d, out, out_stride, accumulate);
+}
+
+void launch_sum_parts(hipStream_t st, unsigned blocks, const float* parts, int64_t n, int n_parts, float* out) {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(blocks), dim3(256), 0, st, parts, n, n_parts, out);
+}
+
+}  // namespace dctr_train
+
+namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // Adam (Keras): m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  w -= alpha * m / (sqrt(v) + eps),
@@ -671,6 +675,88 @@ static void launch_mark_rows(hipStream_t st, const void* ids, int64_t n_rows, in
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ids, n_rows, n_cols, row_stride, is_i64, hash_mode, vocab,
                        dim4, touched);
+}
+
+// backward of dctr_embed_lookup: g_table[row(idx[i]), :] += d_out[i, :dim]   (rows out of range are skipped, as the forward
+// zero-fills them and raises the status flag)
+__global__ __launch_bounds__(256) void lookup_bwd_kernel(dctr_lookup_args_t a, const float* __restrict__ d_out, int64_t d_stride,
+                                                         float* __restrict__ g_table) {
+    const int64_t total = a.n * a.dim;
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
+        const int64_t i = o / a.dim;
+        const int c = (int)(o - i * a.dim);
+        const float g = d_out[i * d_stride + c];
+        if (g == 0.f) continue;
+        const int64_t row = resolve_row(read_id(a.idx, i, a.idx_is_i64), a.hash_mode, a.idx_is_i64, a.vocab);
+        if ((uint64_t)row < (uint64_t)a.vocab) unsafeAtomicAdd(g_table + row * a.dim + c, g);
+    }
+}
+
+// The same scatter for skewed ids (DIN's behaviour sequences: half of the B*T positions are padding id 0, and under training-mode
+// Dice the padded keys DO receive gradient through the batch statistics — 51,000 x 32 atomics on ONE row took 1.6 ms per table):
+// a workgroup sorts a tile of LB_TILE positions by row in LDS (bitonic), then 64 / dimP walkers per wave run over contiguous
+// stretches of the sorted tile, summing runs of equal rows in registers: one atomic per (run, column) instead of one per position.
+constexpr int LB_TILE = 1024;
+__global__ __launch_bounds__(256) void lookup_bwd_tile_kernel(dctr_lookup_args_t a, const float* __restrict__ d_out, int64_t d_stride,
+                                                              float* __restrict__ g_table, int dimP) {
+    __shared__ uint32_t key[LB_TILE];
+    __shared__ uint16_t pos[LB_TILE];
+    constexpr uint32_t NONE = 0xffffffffu;
+    const int64_t base = (int64_t)blockIdx.x * LB_TILE;
+    for (int j = threadIdx.x; j < LB_TILE; j += 256) {
+        const int64_t i = base + j;
+        uint32_t k = NONE;
+        if (i < a.n) {
+            const int64_t row = resolve_row(read_id(a.idx, i, a.idx_is_i64), a.hash_mode, a.idx_is_i64, a.vocab);
+            if ((uint64_t)row < (uint64_t)a.vocab) k = (uint32_t)row;
+        }
+        key[j] = k;
+        pos[j] = (uint16_t)j;
+    }
+    __syncthreads();
+    for (int size = 2; size <= LB_TILE; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < LB_TILE / 2; t += 256) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool up = (lo & size) == 0;
+                const uint32_t k0 = key[lo], k1 = key[hi];
+                if ((k0 > k1) == up) {
+                    key[lo] = k1; key[hi] = k0;
+                    const uint16_t p0 = pos[lo]; pos[lo] = pos[hi]; pos[hi] = p0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int sub_n = 64 / dimP, sub = lane / dimP, c = lane % dimP;
+    const int per = LB_TILE / (4 * sub_n);
+    const int j0 = (wave * sub_n + sub) * per;
+    const bool col = c < a.dim;
+    uint32_t cur = NONE;
+    float acc = 0.f;
+    constexpr int U = 8;
+    for (int j = j0; j < j0 + per; j += U) {
+        uint32_t kk[U];
+        float gg[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            kk[u] = key[j + u];
+            const int64_t i = base + pos[j + u];
+            gg[u] = (kk[u] != NONE && col) ? d_out[i * d_stride + c] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (kk[u] != cur) {
+                if (cur != NONE && col && acc != 0.f) unsafeAtomicAdd(g_table + (int64_t)cur * a.dim + c, acc);
+                cur = kk[u];
+                acc = gg[u];
+            } else {
+                acc += gg[u];
+            }
+        }
+    }
+    if (cur != NONE && col && acc != 0.f) unsafeAtomicAdd(g_table + (int64_t)cur * a.dim + c, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -853,330 +939,6 @@ __global__ __launch_bounds__(256) void cross_matrix_bwd_elem_kernel(const float*
         const float gv = g[i];
         du[i] = gv * x0[b * x_stride + c];
         dx0[i] += gv * (u[i] + bias[c]);
-    }
-}
-
-// out[b, c] (+)= src[b, c]   (strided rows)
-__global__ __launch_bounds__(256) void add_rows_kernel(const float* __restrict__ src, int64_t src_stride, int64_t batch, int d,
-                                                       float* __restrict__ out, int64_t out_stride, int accumulate) {
-    const int64_t total = batch * d;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / d;
-        const int c = (int)(i - b * d);
-        out[b * out_stride + c] = (accumulate ? out[b * out_stride + c] : 0.f) + src[b * src_stride + c];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// CIN backward (interaction.py:277-325), first version: the reference's own formulation — z materialised per layer,
-// 1x1 conv = GEMM — in the (b,d)-major row layout R = B*D:  X0t [R,F0],  X_k = Y_{k-1}[:, :Hn] [R,F_k],
-//   z_k[r, i*F_k+j] = X0t[r,i] X_k[r,j];   Y_k = act(z_k W_k + b_k) [R,H_k];   out[b, .] = sum_d of the direct maps.
-// The GEMMs (forward recompute, dW = z^T dpre, dz = dpre W^T) are dctr_gemm; the rest are the kernels below.
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cin_to_rows_kernel(const float* __restrict__ x, int64_t x_stride, int64_t batch, int F0,
-                                                          int D, float* __restrict__ xt) {
-    const int64_t total = batch * D * F0;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int i = (int)(o % F0);
-        const int64_t r = o / F0;
-        const int64_t b = r / D;
-        const int d = (int)(r - b * D);
-        xt[o] = x[b * x_stride + (int64_t)i * D + d];
-    }
-}
-
-__global__ __launch_bounds__(256) void cin_from_rows_kernel(const float* __restrict__ dxt, int64_t batch, int F0, int D,
-                                                            float* __restrict__ dx, int64_t dx_stride, int accumulate) {
-    const int64_t total = batch * F0 * D;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int d = (int)(o % D);
-        const int64_t t = o / D;
-        const int i = (int)(t % F0);
-        const int64_t b = t / F0;
-        float* dst = dx + b * dx_stride + (int64_t)i * D + d;
-        *dst = (accumulate ? *dst : 0.f) + dxt[(b * D + d) * F0 + i];
-    }
-}
-
-__global__ __launch_bounds__(256) void cin_outer_kernel(const float* __restrict__ x0t, int F0, const float* __restrict__ xk,
-                                                        int64_t ldk, int Fk, int64_t rows, float* __restrict__ z) {
-    const int K = F0 * Fk;
-    const int64_t total = rows * K;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t r = o / K;
-        const int c = (int)(o - r * K);
-        const int i = c / Fk, j = c - i * Fk;
-        z[o] = x0t[r * F0 + i] * xk[r * ldk + j];
-    }
-}
-
-// the same with 16-B stores: thread = four consecutive j of one (row, i)   (Fk % 4 == 0, ldk % 4 == 0, 16-B aligned xk / z)
-__global__ __launch_bounds__(256) void cin_outer4_kernel(const float* __restrict__ x0t, int F0, const float* __restrict__ xk,
-                                                         int64_t ldk, int Fk, int64_t rows, float* __restrict__ z) {
-    const int Fk4 = Fk >> 2, K4 = F0 * Fk4;
-    const int64_t total = rows * K4;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t r = o / K4;
-        const int c = (int)(o - r * K4);
-        const int i = c / Fk4, j4 = c - i * Fk4;
-        const float a = x0t[r * F0 + i];
-        const float4 b = *reinterpret_cast<const float4*>(xk + r * ldk + 4 * j4);
-        *reinterpret_cast<float4*>(z + r * (int64_t)(F0 * Fk) + i * Fk + 4 * j4) = make_float4(a * b.x, a * b.y, a * b.z, a * b.w);
-    }
-}
-
-// dpre[r,h] = (hidden part: dxnext[r,h] for h < Hn) + (direct part: d_out[b, off + h - d0] for h >= d0), times act'(Y)
-__global__ __launch_bounds__(256) void cin_dpre_kernel(const float* __restrict__ y, const float* __restrict__ dxnext, int64_t ldn,
-                                                       int Hn, const float* __restrict__ d_out, int64_t out_dim, int off, int d0,
-                                                       int64_t rows, int H, int D, int act, float* __restrict__ dpre) {
-    const int64_t total = rows * H;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t r = o / H;
-        const int h = (int)(o - r * H);
-        float g = 0.f;
-        if (dxnext != nullptr && h < Hn) g += dxnext[r * ldn + h];
-        if (h >= d0) g += d_out[(r / D) * out_dim + off + (h - d0)];
-        const float v = y[o];
-        if (act == DCTR_ACT_RELU) g = v > 0.f ? g : 0.f;
-        else if (act == DCTR_ACT_SIGMOID) g *= v * (1.f - v);
-        else if (act == DCTR_ACT_TANH) g *= 1.f - v * v;
-        dpre[o] = g;
-    }
-}
-
-// from dz [R, F0*Fk]:  dX0t[r,i] += sum_j dz[r, i*Fk+j] Xk[r,j];   dXk[r,j] = sum_i dz[r, i*Fk+j] X0t[r,i]
-// One wave per row: the row of dz (F0*Fk floats) is staged once in LDS (coalesced) and both sums read it from there,
-// so dz crosses HBM once (two independent thread-per-output passes read it twice: 860 us per step at C3).
-__global__ __launch_bounds__(256) void cin_outer_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ x0t, int F0,
-                                                            const float* __restrict__ xk, int64_t ldk, int Fk, int64_t rows,
-                                                            float* __restrict__ dx0t, float* __restrict__ dxk) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int K = F0 * Fk;
-    float* zr = smem + (size_t)wave * (K + F0 + Fk);        // [K] dz row, [F0] x0t row, [Fk] xk row
-    float* x0r = zr + K;
-    float* xkr = x0r + F0;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < rows; r += (int64_t)gridDim.x * 4) {
-        const float* dzr = dz + r * K;
-        for (int c = lane; c < K; c += 64) zr[c] = dzr[c];
-        for (int i = lane; i < F0; i += 64) x0r[i] = x0t[r * F0 + i];
-        for (int j = lane; j < Fk; j += 64) xkr[j] = xk[r * ldk + j];
-        // (same wave: LDS operations complete in order)
-        for (int i = lane; i < F0; i += 64) {
-            float acc = 0.f;
-            for (int j = 0; j < Fk; ++j) acc = fmaf(zr[i * Fk + j], xkr[j], acc);
-            dx0t[r * F0 + i] += acc;
-        }
-        if (dxk != nullptr) {
-            for (int j = lane; j < Fk; j += 64) {
-                float acc = 0.f;
-                for (int i = 0; i < F0; ++i) acc = fmaf(zr[i * Fk + j], x0r[i], acc);
-                dxk[r * Fk + j] = acc;
-            }
-        }
-    }
-}
-
-// out[i] += sum_s parts[s * n + i]
-__global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ parts, int64_t n, int n_parts,
-                                                        float* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;          // four independent chains: the loads of 4 slices in flight per step
-        int s = 0;
-        for (; s + 4 <= n_parts; s += 4) {
-            a0 += parts[(int64_t)s * n + i];
-            a1 += parts[(int64_t)(s + 1) * n + i];
-            a2 += parts[(int64_t)(s + 2) * n + i];
-            a3 += parts[(int64_t)(s + 3) * n + i];
-        }
-        for (; s < n_parts; ++s) a0 += parts[(int64_t)s * n + i];
-        out[i] += (a0 + a1) + (a2 + a3);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// sibling interaction layers: backward of BiInteractionPooling (NFM) and InnerProductLayer(reduce_sum) (PNN).
-// One thread per (row, e); the F embeddings of the row are re-read from the forward's input (HBM/L2, F*E*4 B per row).
-// ---------------------------------------------------------------------------------------------------
-// y[b,e] = 0.5((sum_f x)^2 - sum_f x^2)  =>  dx[b,f,e] = dy[b,e] * (sum_f' x[b,f',e] - x[b,f,e])
-// (dy_estride 1: dy [B, E] — BiInteractionPooling; 0: dy [B] broadcast over e — FM, whose logit is that pooling summed over e)
-__global__ __launch_bounds__(256) void bi_interaction_bwd_kernel(const float* __restrict__ x, int64_t x_stride, int64_t batch, int F,
-                                                                 int E, const float* __restrict__ dy, int64_t dy_stride,
-                                                                 float* __restrict__ dx, int64_t dx_stride, int accumulate,
-                                                                 int dy_estride = 1) {
-    const int64_t total = batch * E;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t b = o / E;
-        const int e = (int)(o - b * E);
-        const float* xb = x + b * x_stride + e;
-        float s = 0.f;
-        for (int f = 0; f < F; ++f) s += xb[(int64_t)f * E];
-        const float g = dy[b * dy_stride + (int64_t)e * dy_estride];
-        float* db = dx + b * dx_stride + e;
-        for (int f = 0; f < F; ++f) {
-            const float v = g * (s - xb[(int64_t)f * E]);
-            db[(int64_t)f * E] = accumulate ? db[(int64_t)f * E] + v : v;
-        }
-    }
-}
-
-// y[b,p(i,j)] = <x_i, x_j> (i<j, pairs ordered by i then j)  =>  dx[b,i,e] = sum_{j != i} dy[b,p(min,max)] * x[b,j,e]
-__global__ __launch_bounds__(256) void inner_product_bwd_kernel(const float* __restrict__ x, int64_t x_stride, int64_t batch, int F,
-                                                                int E, const float* __restrict__ dy, int64_t dy_stride,
-                                                                float* __restrict__ dx, int64_t dx_stride, int accumulate) {
-    const int64_t total = batch * F * E;
-    const int FE = F * E;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t b = o / FE;
-        const int c = (int)(o - b * FE);
-        const int i = c / E, e = c - i * E;
-        const float* xb = x + b * x_stride + e;
-        const float* gb = dy + b * dy_stride;
-        float acc = 0.f;
-        for (int j = 0; j < i; ++j) acc = fmaf(gb[j * (2 * F - j - 1) / 2 + (i - j - 1)], xb[(int64_t)j * E], acc);
-        const int base = i * (2 * F - i - 1) / 2 - i - 1;
-        for (int j = i + 1; j < F; ++j) acc = fmaf(gb[base + j], xb[(int64_t)j * E], acc);
-        float* d = dx + b * dx_stride + c;
-        *d = accumulate ? *d + acc : acc;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// backward of AFMLayer (interaction.py:116-146).  Same shape as the forward kernel: one wave per sample, the sample's [F,E]
-// tile and the layer's weights in LDS, lanes walk the F(F-1)/2 pairs; nothing was saved by the forward, so the attention
-// logits and the softmax are recomputed.  With bi_p = x_i * x_j, pre_pa = b_a + sum_e bi_pe W_ea, s_p = sum_a relu(pre_pa) h_a,
-// alpha = softmax_p(s), t_p = bi_p . proj_p, y = sum_p alpha_p t_p and g = dy:
-//     ds_p = alpha_p (g t_p - g y),  d pre_pa = ds_p h_a [pre_pa > 0],  d bi_pe = g alpha_p proj_p[e] + sum_a d pre_pa W_ea,
-//     d x_i += d bi_p * x_j,  d x_j += d bi_p * x_i;   weight gradients are summed in LDS per workgroup, then one atomic each.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void afm_pair_ij(int p, int F, int& i, int& j) {
-    int ii = 0, rem = p;
-    while (rem >= F - 1 - ii) {
-        rem -= F - 1 - ii;
-        ++ii;
-    }
-    i = ii;
-    j = ii + 1 + rem;
-}
-
-__global__ __launch_bounds__(256) void afm_bwd_kernel(const float* __restrict__ x, int64_t x_stride, int64_t batch, int F, int E,
-                                                      const float* __restrict__ att_w, const float* __restrict__ att_b,
-                                                      const float* __restrict__ proj_h, const float* __restrict__ proj_p, int A,
-                                                      const float* __restrict__ dy, float* __restrict__ dx, int64_t dx_stride,
-                                                      int accumulate, float* __restrict__ g_w, float* __restrict__ g_b,
-                                                      float* __restrict__ g_h, float* __restrict__ g_p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int P = F * (F - 1) / 2;
-    const int NW = E * A + 2 * A + E;
-    float* wsh = smem;                       // [E*A] attention_W, then b[A], h[A], p[E]
-    float* bsh = wsh + E * A;
-    float* hsh = bsh + A;
-    float* psh = hsh + A;
-    float* gsh = psh + E;                    // gradients in the same order: W, b, h, p
-    float* per_wave = gsh + NW;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* xs = per_wave + wave * (2 * F * E + P);   // [F*E] sample tile
-    float* dxs = xs + F * E;                         // [F*E] its gradient
-    float* alpha = dxs + F * E;                      // [P]
-    for (int i = threadIdx.x; i < E * A; i += 256) wsh[i] = att_w[i];
-    for (int i = threadIdx.x; i < A; i += 256) {
-        bsh[i] = att_b[i];
-        hsh[i] = proj_h[i];
-    }
-    for (int i = threadIdx.x; i < E; i += 256) psh[i] = proj_p[i];
-    for (int i = threadIdx.x; i < NW; i += 256) gsh[i] = 0.f;
-    const int64_t b = (int64_t)blockIdx.x * 4 + wave;
-    const bool valid = b < batch;
-    if (valid)
-        for (int i = lane; i < F * E; i += 64) {
-            xs[i] = x[b * x_stride + i];
-            dxs[i] = 0.f;
-        }
-    __syncthreads();
-    if (valid) {
-        // forward recompute: logits, softmax, y
-        float mx = -INFINITY;
-        for (int p = lane; p < P; p += 64) {
-            int i, j;
-            afm_pair_ij(p, F, i, j);
-            float lg = 0.f;
-            for (int a = 0; a < A; ++a) {
-                float t = bsh[a];
-                for (int e = 0; e < E; ++e) t = fmaf(xs[i * E + e] * xs[j * E + e], wsh[e * A + a], t);
-                lg = fmaf(fmaxf(t, 0.f), hsh[a], lg);
-            }
-            alpha[p] = lg;
-            mx = fmaxf(mx, lg);
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-        float den = 0.f;
-        for (int p = lane; p < P; p += 64) {
-            const float e_ = expf(alpha[p] - mx);
-            alpha[p] = e_;
-            den += e_;
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) den += __shfl_xor(den, m, 64);
-        float yv = 0.f;
-        for (int p = lane; p < P; p += 64) {
-            int i, j;
-            afm_pair_ij(p, F, i, j);
-            const float sc = alpha[p] / den;
-            alpha[p] = sc;
-            float t = 0.f;
-            for (int e = 0; e < E; ++e) t = fmaf(xs[i * E + e] * xs[j * E + e], psh[e], t);
-            yv = fmaf(sc, t, yv);
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) yv += __shfl_xor(yv, m, 64);
-        // backward per pair
-        const float g = dy[b];
-        for (int p = lane; p < P; p += 64) {
-            int i, j;
-            afm_pair_ij(p, F, i, j);
-            const float sc = alpha[p];
-            float t = 0.f;
-            for (int e = 0; e < E; ++e) t = fmaf(xs[i * E + e] * xs[j * E + e], psh[e], t);
-            const float ds = sc * g * (t - yv);
-            const float gsc = g * sc;
-            for (int e = 0; e < E; ++e) {
-                const float bi = xs[i * E + e] * xs[j * E + e];
-                atomicAdd(&gsh[E * A + 2 * A + e], gsc * bi);                        // d proj_p
-                const float dbi = gsc * psh[e];
-                atomicAdd(&dxs[i * E + e], dbi * xs[j * E + e]);
-                atomicAdd(&dxs[j * E + e], dbi * xs[i * E + e]);
-            }
-            for (int a = 0; a < A; ++a) {
-                float pre = bsh[a];
-                for (int e = 0; e < E; ++e) pre = fmaf(xs[i * E + e] * xs[j * E + e], wsh[e * A + a], pre);
-                if (pre > 0.f) {
-                    atomicAdd(&gsh[E * A + A + a], ds * pre);                        // d proj_h
-                    const float dpre = ds * hsh[a];
-                    atomicAdd(&gsh[E * A + a], dpre);                                // d attention_b
-                    for (int e = 0; e < E; ++e) {
-                        const float xi = xs[i * E + e], xj = xs[j * E + e];
-                        atomicAdd(&gsh[e * A + a], dpre * xi * xj);                  // d attention_W
-                        const float dbi = dpre * wsh[e * A + a];
-                        atomicAdd(&dxs[i * E + e], dbi * xj);
-                        atomicAdd(&dxs[j * E + e], dbi * xi);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (valid) {
-        float* d = dx + b * dx_stride;
-        for (int i = lane; i < F * E; i += 64) d[i] = accumulate ? d[i] + dxs[i] : dxs[i];
-    }
-    for (int i = threadIdx.x; i < NW; i += 256) {
-        const float v = gsh[i];
-        if (v != 0.f) {
-            float* dst = i < E * A ? g_w + i : i < E * A + A ? g_b + (i - E * A) : i < E * A + 2 * A ? g_h + (i - E * A - A)
-                                                                                                   : g_p + (i - E * A - 2 * A);
-            unsafeAtomicAdd(dst, v);
-        }
     }
 }
 
@@ -1441,10 +1203,6 @@ __global__ __launch_bounds__(256) void dice_train_bwd_reduce4_kernel(const float
     colsum4_finish_k<3>(acc, N4, RL, c, outs);
 }
 
-static bool rowlane4_ok(int N, const void* a, const void* b, int64_t stride) {
-    return N % 4 == 0 && N >= 4 && N <= 1024 && stride % 4 == 0 && dctr_aligned16(a) && (b == nullptr || dctr_aligned16(b));
-}
-
 extern "C" int dctr_dice_train_fwd(const float* z, int64_t z_stride, const float* bias, int64_t rows, int32_t n, const float* alpha,
                                    float eps, float momentum, float* moving_mean, float* moving_var, float* batch_mean,
                                    float* batch_var, float* h, int64_t h_stride, void* stream) {
@@ -1498,18 +1256,6 @@ __device__ __forceinline__ TrainLayerCol train_layer_col(const dctr_dnn_train_la
         c.bt = a.bn_beta != nullptr ? a.bn_beta[n] : 0.f;
     }
     return c;
-}
-__device__ __forceinline__ float act_value(float y, int act) {
-    if (act == DCTR_ACT_RELU) return fmaxf(y, 0.f);
-    if (act == DCTR_ACT_SIGMOID) return 1.f / (1.f + expf(-y));
-    if (act == DCTR_ACT_TANH) return tanhf(y);
-    return y;
-}
-__device__ __forceinline__ float act_deriv(float y, int act) {
-    if (act == DCTR_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-    if (act == DCTR_ACT_SIGMOID) { const float s = 1.f / (1.f + expf(-y)); return s * (1.f - s); }
-    if (act == DCTR_ACT_TANH) { const float t = tanhf(y); return 1.f - t * t; }
-    return 1.f;
 }
 
 __global__ __launch_bounds__(256) void train_layer_fwd_kernel(dctr_dnn_train_layer_t a) {
@@ -1638,315 +1384,7 @@ extern "C" int dctr_dnn_train_layer_bwd(const dctr_dnn_train_layer_t* a, void* s
     return dctr_launch_status("dctr_dnn_train_layer_bwd");
 }
 
-// ---------------------------------------------------------------------------------------------------
-// DIN's LocalActivationUnit as a training step (layers/core.py:94-108, layers/sequence.py:261-298): the attention input
-// [q, k, q - k, q * k] is materialised once per batch ([B*T, 4E]) so that the attention MLP runs through dctr_mlp_fwd /
-// dctr_mlp_bwd with saved activations; the masked weighted sum and the scatter of the key gradients are kernels here.
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void din_att_in_kernel(const float* __restrict__ q, const float* __restrict__ k, int64_t rows, int T,
-                                                         int E, float* __restrict__ a) {
-    // one thread per (row = b*T + t, e)
-    const int64_t total = rows * E;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t r = o / E;
-        const int e = (int)(o - r * E);
-        const float qv = q[(r / T) * E + e], kv = k[o];
-        float* ar = a + r * 4 * E;
-        ar[e] = qv;
-        ar[E + e] = kv;
-        ar[2 * E + e] = qv - kv;
-        ar[3 * E + e] = qv * kv;
-    }
-}
-
-// out[b, e] = sum_t (mask ? score : 0) k[b,t,e]                         (weight_normalization=False, sequence.py:286-296)
-__global__ __launch_bounds__(256) void din_wsum_kernel(const float* __restrict__ score, const uint8_t* __restrict__ mask,
-                                                       const float* __restrict__ k, int64_t batch, int T, int E,
-                                                       float* __restrict__ out, int64_t out_stride) {
-    const int64_t total = batch * E;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t b = o / E;
-        const int e = (int)(o - b * E);
-        float acc = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const float s = mask[b * T + t] ? score[b * T + t] : 0.f;
-            acc = fmaf(s, k[(b * T + t) * E + e], acc);
-        }
-        out[b * out_stride + e] = acc;
-    }
-}
-
-// d_score[b,t] = mask ? <d_out[b,:], k[b,t,:]> : 0;  dk[b,t,:] = (mask ? score : 0) d_out[b,:] (written);
-// d_bias += sum d_score (the bias of the unit's final Dense(1));  one wave per (b, t)
-__global__ __launch_bounds__(256) void din_wsum_bwd_kernel(const float* __restrict__ d_out, int64_t d_stride,
-                                                           const float* __restrict__ score, const uint8_t* __restrict__ mask,
-                                                           const float* __restrict__ k, int64_t batch, int T, int E,
-                                                           float* __restrict__ d_score, float* __restrict__ dk,
-                                                           float* __restrict__ d_bias) {
-    const int lane = threadIdx.x & 63;
-    const int64_t rows = batch * T;
-    float bsum = 0.f;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
-        const int64_t b = r / T;
-        const bool m = mask[r] != 0;
-        const float s = m ? score[r] : 0.f;
-        float dot = 0.f;
-        for (int e = lane; e < E; e += 64) {
-            const float g = d_out[b * d_stride + e];
-            dot = fmaf(g, k[r * E + e], dot);
-            dk[r * E + e] = s * g;
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) dot += __shfl_xor(dot, o, 64);
-        const float ds = m ? dot : 0.f;
-        if (lane == 0) d_score[r] = ds;
-        bsum += ds;
-    }
-    // one atomic per workgroup (B*T / 4 of them on ONE address serialised to 0.5 ms at C4)
-    __shared__ float wsum[4];
-    if (lane == 0) wsum[threadIdx.x >> 6] = bsum;
-    __syncthreads();
-    if (d_bias != nullptr && threadIdx.x == 0) {
-        const float t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        if (t != 0.f) unsafeAtomicAdd(d_bias, t);
-    }
-}
-
-// out[0] += sum_i v[i]: grid-stride, wave sums, one atomic per workgroup
-__global__ __launch_bounds__(256) void sum_vec_kernel(const float* __restrict__ v, int64_t n, float* __restrict__ out) {
-    __shared__ float ws4[4];
-    float a = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a += v[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) ws4[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float t = (ws4[0] + ws4[1]) + (ws4[2] + ws4[3]);
-        if (t != 0.f) unsafeAtomicAdd(out, t);
-    }
-}
-
-// da [B*T, 4E] -> dq[b,e] = sum_t (d0 + d2 + d3 k), added into dx[b, qcol[e]];  dk[b,t,e] += d1 - d2 + d3 q
-__global__ __launch_bounds__(256) void din_att_in_bwd_kernel(const float* __restrict__ da, const float* __restrict__ q,
-                                                             const float* __restrict__ k, int64_t batch, int T, int E,
-                                                             float* __restrict__ dk, float* __restrict__ dx, int64_t dx_stride,
-                                                             const int32_t* __restrict__ qcol) {
-    const int64_t total = batch * E;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t b = o / E;
-        const int e = (int)(o - b * E);
-        const float qv = q[o];
-        float dq = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const int64_t r = b * T + t;
-            const float* ar = da + r * 4 * E;
-            const float d0 = ar[e], d1 = ar[E + e], d2 = ar[2 * E + e], d3 = ar[3 * E + e];
-            const float kv = k[r * E + e];
-            dq += d0 + d2 + d3 * kv;
-            dk[r * E + e] += d1 - d2 + d3 * qv;
-        }
-        dx[b * dx_stride + qcol[e]] += dq;
-    }
-}
-
-// backward of dctr_embed_lookup: g_table[row(idx[i]), :] += d_out[i, :dim]   (rows out of range are skipped, as the forward
-// zero-fills them and raises the status flag)
-__global__ __launch_bounds__(256) void lookup_bwd_kernel(dctr_lookup_args_t a, const float* __restrict__ d_out, int64_t d_stride,
-                                                         float* __restrict__ g_table) {
-    const int64_t total = a.n * a.dim;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t i = o / a.dim;
-        const int c = (int)(o - i * a.dim);
-        const float g = d_out[i * d_stride + c];
-        if (g == 0.f) continue;
-        const int64_t row = resolve_row(read_id(a.idx, i, a.idx_is_i64), a.hash_mode, a.idx_is_i64, a.vocab);
-        if ((uint64_t)row < (uint64_t)a.vocab) unsafeAtomicAdd(g_table + row * a.dim + c, g);
-    }
-}
-
-// The same scatter for skewed ids (DIN's behaviour sequences: half of the B*T positions are padding id 0, and under training-mode
-// Dice the padded keys DO receive gradient through the batch statistics — 51,000 x 32 atomics on ONE row took 1.6 ms per table):
-// a workgroup sorts a tile of LB_TILE positions by row in LDS (bitonic), then 64 / dimP walkers per wave run over contiguous
-// stretches of the sorted tile, summing runs of equal rows in registers: one atomic per (run, column) instead of one per position.
-constexpr int LB_TILE = 1024;
-__global__ __launch_bounds__(256) void lookup_bwd_tile_kernel(dctr_lookup_args_t a, const float* __restrict__ d_out, int64_t d_stride,
-                                                              float* __restrict__ g_table, int dimP) {
-    __shared__ uint32_t key[LB_TILE];
-    __shared__ uint16_t pos[LB_TILE];
-    constexpr uint32_t NONE = 0xffffffffu;
-    const int64_t base = (int64_t)blockIdx.x * LB_TILE;
-    for (int j = threadIdx.x; j < LB_TILE; j += 256) {
-        const int64_t i = base + j;
-        uint32_t k = NONE;
-        if (i < a.n) {
-            const int64_t row = resolve_row(read_id(a.idx, i, a.idx_is_i64), a.hash_mode, a.idx_is_i64, a.vocab);
-            if ((uint64_t)row < (uint64_t)a.vocab) k = (uint32_t)row;
-        }
-        key[j] = k;
-        pos[j] = (uint16_t)j;
-    }
-    __syncthreads();
-    for (int size = 2; size <= LB_TILE; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < LB_TILE / 2; t += 256) {
-                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint32_t k0 = key[lo], k1 = key[hi];
-                if ((k0 > k1) == up) {
-                    key[lo] = k1; key[hi] = k0;
-                    const uint16_t p0 = pos[lo]; pos[lo] = pos[hi]; pos[hi] = p0;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int sub_n = 64 / dimP, sub = lane / dimP, c = lane % dimP;
-    const int per = LB_TILE / (4 * sub_n);
-    const int j0 = (wave * sub_n + sub) * per;
-    const bool col = c < a.dim;
-    uint32_t cur = NONE;
-    float acc = 0.f;
-    constexpr int U = 8;
-    for (int j = j0; j < j0 + per; j += U) {
-        uint32_t kk[U];
-        float gg[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            kk[u] = key[j + u];
-            const int64_t i = base + pos[j + u];
-            gg[u] = (kk[u] != NONE && col) ? d_out[i * d_stride + c] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (kk[u] != cur) {
-                if (cur != NONE && col && acc != 0.f) unsafeAtomicAdd(g_table + (int64_t)cur * a.dim + c, acc);
-                cur = kk[u];
-                acc = gg[u];
-            } else {
-                acc += gg[u];
-            }
-        }
-    }
-    if (cur != NONE && col && acc != 0.f) unsafeAtomicAdd(g_table + (int64_t)cur * a.dim + c, acc);
-}
-
 }  // namespace
-
-extern "C" int dctr_din_att_in_fwd(const float* q, const float* k, int64_t batch, int32_t maxlen, int32_t dim, float* a, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1 && dim >= 1, DCTR_E_DIM, "din_att_in_fwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(q && k && a, DCTR_E_NULL, "din_att_in_fwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * maxlen * dim, (int64_t)256);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(din_att_in_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, q, k, batch * maxlen, (int)maxlen,
-                       (int)dim, a);
-    return dctr_launch_status("dctr_din_att_in_fwd");
-}
-
-extern "C" int dctr_din_wsum_fwd(const float* score, const uint8_t* mask, const float* k, int64_t batch, int32_t maxlen, int32_t dim,
-                                 float* out, int64_t out_stride, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1 && dim >= 1 && out_stride >= dim, DCTR_E_DIM, "din_wsum_fwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(score && mask && k && out, DCTR_E_NULL, "din_wsum_fwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * dim, (int64_t)256);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(din_wsum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, score, mask, k, batch, (int)maxlen,
-                       (int)dim, out, out_stride);
-    return dctr_launch_status("dctr_din_wsum_fwd");
-}
-
-extern "C" int dctr_din_wsum_bwd(const float* d_out, int64_t d_stride, const float* score, const uint8_t* mask, const float* k,
-                                 int64_t batch, int32_t maxlen, int32_t dim, float* d_score, float* dk, float* d_bias, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1 && dim >= 1 && d_stride >= dim, DCTR_E_DIM, "din_wsum_bwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(d_out && score && mask && k && d_score && dk, DCTR_E_NULL, "din_wsum_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * maxlen, (int64_t)4);
-    if (blocks > 16384) blocks = 16384;
-    // the bias gradient (sum of d_score) is taken by a second small kernel: as one atomic per workgroup of this one it either
-    // serialised thousands of atomics on one address (0.5 ms at C4) or capped the grid at 256 workgroups (86 us)
-    hipLaunchKernelGGL(din_wsum_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_out, d_stride, score, mask, k,
-                       batch, (int)maxlen, (int)dim, d_score, dk, (float*)nullptr);
-    if (d_bias != nullptr) {
-        const int64_t n = batch * maxlen;
-        int64_t g = dctr_ceil_div(n, (int64_t)256 * 8);
-        g = g < 1 ? 1 : (g > COLSUM_MAX_WG ? COLSUM_MAX_WG : g);
-        hipLaunchKernelGGL(sum_vec_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const float*)d_score, n, d_bias);
-    }
-    return dctr_launch_status("dctr_din_wsum_bwd");
-}
-
-// att_weight_normalization=True (layers/sequence.py:283-289): p = softmax over ALL T positions of where(mask, score, -2^32 + 1) — a
-// row without valid positions gets the uniform 1/T, as tf.nn.softmax gives it — and the weighted sum then runs over every position.
-// One wave per row.  Backward: ds = p (dp - <p, dp>), kept where the mask is set (a padded position's input is the constant).
-__global__ __launch_bounds__(256) void din_softmax_kernel(const float* __restrict__ score, const uint8_t* __restrict__ mask, int64_t batch,
-                                                          int T, float* __restrict__ p) {
-    const int lane = threadIdx.x & 63;
-    const float pad = -4294967295.f;                       // float(-2 ** 32 + 1)
-    for (int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < batch; b += (int64_t)gridDim.x * 4) {
-        float mx = -__builtin_inff();
-        for (int t = lane; t < T; t += 64) mx = fmaxf(mx, mask[b * T + t] ? score[b * T + t] : pad);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float sum = 0.f;
-        for (int t = lane; t < T; t += 64) sum += expf((mask[b * T + t] ? score[b * T + t] : pad) - mx);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        for (int t = lane; t < T; t += 64) p[b * T + t] = expf((mask[b * T + t] ? score[b * T + t] : pad) - mx) / sum;
-    }
-}
-__global__ __launch_bounds__(256) void din_softmax_bwd_kernel(const float* __restrict__ p, const uint8_t* __restrict__ mask,
-                                                              const float* __restrict__ dp, int64_t batch, int T, float* __restrict__ ds) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < batch; b += (int64_t)gridDim.x * 4) {
-        float dot = 0.f;
-        for (int t = lane; t < T; t += 64) dot = fmaf(p[b * T + t], dp[b * T + t], dot);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) dot += __shfl_xor(dot, o, 64);
-        for (int t = lane; t < T; t += 64) ds[b * T + t] = mask[b * T + t] ? p[b * T + t] * (dp[b * T + t] - dot) : 0.f;
-    }
-}
-
-extern "C" int dctr_din_softmax_fwd(const float* score, const uint8_t* mask, int64_t batch, int32_t maxlen, float* p, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1, DCTR_E_DIM, "din_softmax_fwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(score && mask && p, DCTR_E_NULL, "din_softmax_fwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch, (int64_t)4);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(din_softmax_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, score, mask, batch, (int)maxlen, p);
-    return dctr_launch_status("dctr_din_softmax_fwd");
-}
-
-// d_score (may alias dp) = softmax backward masked; d_bias (NULL ok) += sum d_score
-extern "C" int dctr_din_softmax_bwd(const float* p, const uint8_t* mask, const float* dp, int64_t batch, int32_t maxlen, float* d_score,
-                                    float* d_bias, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1, DCTR_E_DIM, "din_softmax_bwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(p && mask && dp && d_score, DCTR_E_NULL, "din_softmax_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch, (int64_t)4);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(din_softmax_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, mask, dp, batch, (int)maxlen, d_score);
-    if (d_bias != nullptr) {
-        const int64_t n = batch * maxlen;
-        int64_t g = dctr_ceil_div(n, (int64_t)256 * 8);
-        g = g < 1 ? 1 : (g > COLSUM_MAX_WG ? COLSUM_MAX_WG : g);
-        hipLaunchKernelGGL(sum_vec_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (const float*)d_score, n, d_bias);
-    }
-    return dctr_launch_status("dctr_din_softmax_bwd");
-}
-
-extern "C" int dctr_din_att_in_bwd(const float* da, const float* q, const float* k, int64_t batch, int32_t maxlen, int32_t dim,
-                                   float* dk, float* dx, int64_t dx_stride, const int32_t* qcol, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && maxlen >= 1 && dim >= 1, DCTR_E_DIM, "din_att_in_bwd: bad sizes");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(da && q && k && dk && dx && qcol, DCTR_E_NULL, "din_att_in_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * dim, (int64_t)256);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(din_att_in_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, da, q, k, batch, (int)maxlen,
-                       (int)dim, dk, dx, dx_stride, qcol);
-    return dctr_launch_status("dctr_din_att_in_bwd");
-}
 
 extern "C" int dctr_embed_lookup_bwd(const dctr_lookup_args_t* fwd, const float* d_out, int64_t d_stride, float* g_table, uint8_t* touched,
                                      void* stream) {
@@ -1972,73 +1410,6 @@ extern "C" int dctr_embed_lookup_bwd(const dctr_lookup_args_t* fwd, const float*
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(lookup_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *fwd, d_out, d_stride, g_table);
     return dctr_launch_status("dctr_embed_lookup_bwd");
-}
-
-extern "C" int dctr_afm_bwd(const dctr_afm_bwd_args_t* a, void* stream) {
-    DCTR_REQUIRE(a != nullptr, DCTR_E_NULL, "afm_bwd: null args");
-    DCTR_REQUIRE(a->batch >= 0 && a->fields >= 2 && a->dim >= 1 && a->att_factor >= 1, DCTR_E_DIM, "afm_bwd: bad sizes");
-    DCTR_REQUIRE(a->x_stride >= (int64_t)a->fields * a->dim && a->dx_stride >= (int64_t)a->fields * a->dim, DCTR_E_DIM,
-                 "afm_bwd: stride smaller than fields*dim");
-    if (a->batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(a->x && a->att_w && a->att_b && a->proj_h && a->proj_p && a->dy && a->dx, DCTR_E_NULL, "afm_bwd: null pointer");
-    DCTR_REQUIRE(a->d_att_w && a->d_att_b && a->d_proj_h && a->d_proj_p, DCTR_E_NULL, "afm_bwd: null gradient pointer");
-    const int P = a->fields * (a->fields - 1) / 2;
-    const size_t nw = (size_t)a->dim * a->att_factor + 2 * a->att_factor + a->dim;
-    const size_t lds = (2 * nw + 4 * (2 * (size_t)a->fields * a->dim + P)) * sizeof(float);
-    DCTR_REQUIRE(lds <= 160 * 1024, DCTR_E_UNSUPPORTED, "afm_bwd: needs %zu B of LDS", lds);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)afm_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        DCTR_REQUIRE(e == hipSuccess, (int)e, "afm_bwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-    }
-    const int64_t blocks = dctr_ceil_div(a->batch, (int64_t)4);
-    DCTR_REQUIRE(blocks <= 0x7fffffffLL, DCTR_E_DIM, "afm_bwd: batch too large");
-    hipLaunchKernelGGL(afm_bwd_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a->x, a->x_stride, a->batch,
-                       (int)a->fields, (int)a->dim, a->att_w, a->att_b, a->proj_h, a->proj_p, (int)a->att_factor, a->dy, a->dx,
-                       a->dx_stride, (int)a->dx_accumulate, a->d_att_w, a->d_att_b, a->d_proj_h, a->d_proj_p);
-    return dctr_launch_status("dctr_afm_bwd");
-}
-
-extern "C" int dctr_bi_interaction_bwd(const float* x, int64_t batch, int64_t x_stride, int32_t fields, int32_t dim, const float* dy,
-                                       int64_t dy_stride, float* dx, int64_t dx_stride, int32_t accumulate, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && fields >= 1 && dim >= 1, DCTR_E_DIM, "bi_interaction_bwd: bad sizes");
-    DCTR_REQUIRE(x_stride >= (int64_t)fields * dim && dx_stride >= (int64_t)fields * dim && dy_stride >= dim, DCTR_E_DIM,
-                 "bi_interaction_bwd: stride smaller than a row");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(x && dy && dx, DCTR_E_NULL, "bi_interaction_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * dim, (int64_t)256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(bi_interaction_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, batch,
-                       (int)fields, (int)dim, dy, dy_stride, dx, dx_stride, (int)accumulate);
-    return dctr_launch_status("dctr_bi_interaction_bwd");
-}
-
-// FM.call backward (interaction.py:588-604) on a strided [B, >= F*E] buffer: dx[b,f,:] (+)= dlogit[b] * (sum_f' x[b,f',:] - x[b,f,:])
-extern "C" int dctr_fm_bwd(const float* x, int64_t batch, int64_t x_stride, int32_t fields, int32_t dim, const float* dlogit, float* dx,
-                           int64_t dx_stride, int32_t accumulate, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && fields >= 1 && dim >= 1, DCTR_E_DIM, "fm_bwd: bad sizes");
-    DCTR_REQUIRE(x_stride >= (int64_t)fields * dim && dx_stride >= (int64_t)fields * dim, DCTR_E_DIM, "fm_bwd: stride < fields*dim");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(x && dlogit && dx, DCTR_E_NULL, "fm_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * dim, (int64_t)256);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(bi_interaction_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, batch, (int)fields,
-                       (int)dim, dlogit, (int64_t)1, dx, dx_stride, (int)accumulate, 0);
-    return dctr_launch_status("dctr_fm_bwd");
-}
-
-extern "C" int dctr_inner_product_bwd(const float* x, int64_t batch, int64_t x_stride, int32_t fields, int32_t dim, const float* dy,
-                                      int64_t dy_stride, float* dx, int64_t dx_stride, int32_t accumulate, void* stream) {
-    DCTR_REQUIRE(batch >= 0 && fields >= 2 && fields <= 1024 && dim >= 1, DCTR_E_DIM, "inner_product_bwd: bad sizes");
-    DCTR_REQUIRE(x_stride >= (int64_t)fields * dim && dx_stride >= (int64_t)fields * dim &&
-                     dy_stride >= (int64_t)fields * (fields - 1) / 2,
-                 DCTR_E_DIM, "inner_product_bwd: stride smaller than a row");
-    if (batch == 0) return DCTR_OK;
-    DCTR_REQUIRE(x && dy && dx, DCTR_E_NULL, "inner_product_bwd: null pointer");
-    int64_t blocks = dctr_ceil_div(batch * fields * dim, (int64_t)256);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(inner_product_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, x_stride, batch,
-                       (int)fields, (int)dim, dy, dy_stride, dx, dx_stride, (int)accumulate);
-    return dctr_launch_status("dctr_inner_product_bwd");
 }
 
 extern "C" int dctr_bce_grad_w(const float* pred, const float* y, const float* weight, int64_t batch, int32_t task, float* dlogit,
@@ -2231,22 +1602,6 @@ static size_t mlp_bwd_chain_floats(const dctr_mlp_bwd_args_t* a) {
     return f;
 }
 
-// dW = X^T dZ has a small output and a reduction as long as the batch: it runs as a strided batch of row slices into partial
-// products + a sum (deterministic), 512 rows per slice from 1024 rows on, at most 32 slices (as ONE gemm a 429 x 256 output is 28
-// workgroups walking the whole batch: 64 us per layer at B = 4096; round 2's rocBLAS call split K by itself at small batches and took
-// 1.78 ms per layer at B = 65,536)
-// (a SMALL output under a very long reduction — DIN's attention unit: 256 x 80 over 102,400 rows — gets up to 128 slices: as 32 slices
-//  of 3,200 rows on 10 tiles it ran 268 us per layer on 320 workgroups)
-static int mlp_dw_parts(int64_t batch, int64_t out_elems) {
-    if (batch < 1024) return 1;
-    const int64_t tiles = out_elems / 4096 > 1 ? out_elems / 4096 : 1;
-    int64_t cap = 1024 / tiles;
-    cap = cap < 32 ? 32 : (cap > 128 ? 128 : cap);
-    int parts = (int)(batch / 512 > cap ? cap : batch / 512);
-    while (parts > 1 && batch % parts != 0) --parts;
-    return parts;
-}
-
 static size_t mlp_bwd_main_floats(const dctr_mlp_bwd_args_t* a, int w) {
     // two ping-pong buffers [B, widest layer]; Dice needs a third for the recomputed pre-activations
     // ... and, with batch statistics, 2 x widest for the two column sums of the BatchNormalization backward
@@ -2306,14 +1661,14 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
         // head: dZ_last = dlogit (x) head_w .* act'(h_last);  d_head_w = h_last^T dlogit   (headless: d_out .* act'(h_last))
         const int NL = a->units[L - 1];
         if (a->head_w != nullptr) {
-            launch_head_bwd(st, a->dlogit, a->head_w, a->acts[L - 1], (int64_t)NL, a->batch, NL, (int)a->activation, dz[L - 1], (int64_t)NL,
-                            a->d_head_w);
+            dctr_train::launch_head_bwd(st, a->dlogit, a->head_w, a->acts[L - 1], (int64_t)NL, a->batch, NL, (int)a->activation, dz[L - 1], (int64_t)NL,
+                                        a->d_head_w);
         } else {
             hipError_t ce = hipMemcpy2DAsync(dz[L - 1], (size_t)NL * sizeof(float), a->d_out, (size_t)a->d_out_stride * sizeof(float),
                                              (size_t)NL * sizeof(float), (size_t)a->batch, hipMemcpyDeviceToDevice, st);
             DCTR_REQUIRE(ce == hipSuccess, (int)ce, "mlp_bwd: copy of d_out failed: %s", hipGetErrorString(ce));
             if (a->activation != DCTR_ACT_LINEAR)
-                launch_act_bwd_colsum(st, dz[L - 1], a->acts[L - 1], a->batch, NL, (int)a->activation, (float*)nullptr);
+                dctr_train::launch_act_bwd_colsum(st, dz[L - 1], a->acts[L - 1], a->batch, NL, (int)a->activation, (float*)nullptr);
         }
         const int l_first = a->dx != nullptr ? 0 : 1;       // layers whose transposed kernel the chain multiplies by
         if (l_first < L) {
@@ -2439,15 +1794,15 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
     // head: dZ_last = dlogit (x) head_w .* act'(h_last);  d_head_w = h_last^T dlogit
     const int NL = a->units[L - 1];
     if (a->head_w != nullptr) {
-        launch_head_bwd(st, a->dlogit, a->head_w, a->acts[L - 1], (int64_t)NL, a->batch, NL,
-                        dice ? (int)DCTR_ACT_LINEAR : (int)a->activation, bufA, (int64_t)NL, a->d_head_w);
+        dctr_train::launch_head_bwd(st, a->dlogit, a->head_w, a->acts[L - 1], (int64_t)NL, a->batch, NL,
+                                    dice ? (int)DCTR_ACT_LINEAR : (int)a->activation, bufA, (int64_t)NL, a->d_head_w);
     } else {
         // headless (the DNN branch of DCN): the caller hands d(loss)/d(h_last); dZ_last = d_out .* act'(h_last)
         hipError_t ce = hipMemcpy2DAsync(bufA, (size_t)NL * sizeof(float), a->d_out, (size_t)a->d_out_stride * sizeof(float),
                                          (size_t)NL * sizeof(float), (size_t)a->batch, hipMemcpyDeviceToDevice, st);
         DCTR_REQUIRE(ce == hipSuccess, (int)ce, "mlp_bwd: copy of d_out failed: %s", hipGetErrorString(ce));
         if (a->activation != DCTR_ACT_LINEAR && !dice)
-            launch_act_bwd_colsum(st, bufA, a->acts[L - 1], a->batch, NL, (int)a->activation, (float*)nullptr);
+            dctr_train::launch_act_bwd_colsum(st, bufA, a->acts[L - 1], a->batch, NL, (int)a->activation, (float*)nullptr);
     }
     if (dice) {
         const int rc = dice_bwd(L - 1, bufA);
@@ -2461,7 +1816,7 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
         const int ldx = l == 0 ? (int)a->x_stride : K;
         // d_bias[n] += sum_b dZ[b, n]   (dZ is final here: the head / the previous iteration applied act')
         if (a->d_biases != nullptr && a->d_biases[l] != nullptr)
-            launch_act_bwd_colsum(st, dz, (const float*)nullptr, a->batch, N, 0, a->d_biases[l]);
+            dctr_train::launch_act_bwd_colsum(st, dz, (const float*)nullptr, a->batch, N, 0, a->d_biases[l]);
         // dW[K, N] (row-major) += X^T dZ:  column-major  dW'(N x K) = dZ'(N x B) * X'(K x B)^T
         int rs;
         const int n_parts = mlp_dw_parts(a->batch, (int64_t)K * N);
@@ -2502,7 +1857,7 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
                 const int rc = dice_bwd(l - 1, other);
                 DCTR_REQUIRE(rc == 0, DCTR_E_UNSUPPORTED, "mlp_bwd: sgemm(Z) failed (%d)", rc);
             } else if (a->activation != DCTR_ACT_LINEAR) {
-                launch_act_bwd_colsum(st, other, a->acts[l - 1], a->batch, K, (int)a->activation, (float*)nullptr);
+                dctr_train::launch_act_bwd_colsum(st, other, a->acts[l - 1], a->batch, K, (int)a->activation, (float*)nullptr);
             }
             float* t = dz;
             dz = other;
@@ -2585,7 +1940,7 @@ extern "C" int dctr_dense1_bwd(const float* x, int64_t x_stride, int64_t batch, 
     DCTR_REQUIRE(batch >= 0 && n >= 1 && x_stride >= n && dx_stride >= n, DCTR_E_DIM, "dense1_bwd: bad sizes");
     if (batch == 0) return DCTR_OK;
     DCTR_REQUIRE(x && w && dlogit && dx && d_w, DCTR_E_NULL, "dense1_bwd: null pointer");
-    launch_head_bwd((hipStream_t)stream, dlogit, w, x, x_stride, batch, (int)n, (int)DCTR_ACT_LINEAR, dx, dx_stride, d_w);
+    dctr_train::launch_head_bwd((hipStream_t)stream, dlogit, w, x, x_stride, batch, (int)n, (int)DCTR_ACT_LINEAR, dx, dx_stride, d_w);
     return dctr_launch_status("dctr_dense1_bwd");
 }
 
@@ -2715,7 +2070,7 @@ extern "C" int dctr_crossnet_bwd(const dctr_crossnet_bwd_args_t* a, void* stream
         const float* W = a->kernels + (size_t)l * d * d;
         hipLaunchKernelGGL(cross_matrix_bwd_elem_kernel, dim3(eb), dim3(256), 0, st, a->x, a->x_stride, g, us_r + (size_t)l * bd,
                            a->bias + (size_t)l * d, a->batch, d, du, dx0);
-        launch_act_bwd_colsum(st, du, (const float*)nullptr, a->batch, d, 0, a->d_bias + (size_t)l * d);
+        dctr_train::launch_act_bwd_colsum(st, du, (const float*)nullptr, a->batch, d, 0, a->d_bias + (size_t)l * d);
         // dW[n][k] += sum_b du[b][n] x_l[b][k]:  column-major  dW'(k x n) = X'(k x B) * du'(n x B)^T
         // g[b][k] += sum_n du[b][n] W[n][k]:  column-major  g'(k x B) += W'(k x n) * du'(n x B)
         // both read du and nothing of each other: ONE grouped launch (the dW reduction over the batch as row slices + a sum)
@@ -2749,302 +2104,6 @@ extern "C" int dctr_crossnet_bwd(const dctr_crossnet_bwd_args_t* a, void* stream
     hipLaunchKernelGGL(add_rows_kernel, dim3(eb), dim3(256), 0, st, dx0, (int64_t)d, a->batch, d, a->dx, a->dx_stride,
                        (int)a->dx_accumulate);
     return dctr_launch_status("dctr_crossnet_bwd");
-}
-
-// ---------------------------------------------------------------------------------------------------
-// CIN.call, layer by layer (interaction.py:277-325 as the reference writes it: z materialised per layer, 1x1 conv = GEMM) — the route of
-// dctr_cin_fwd for layer sizes no LDS tile of the one-kernel form holds (a layer of more than ~480 maps: cin_kernels.hip refuses it for
-// every tile height).  Rows r = (b, d); samples in chunks of what the workspace holds; per chunk and layer: z = x_0 (outer) x_k
-// (cin_outer_kernel), y = z W_k on dctr_gemm, bias + activation in place, the direct maps summed over d into `out`; y goes straight to
-// save_y[k] when the caller asked for the activations (the same [B * D, H_k] rows).  Not part of the ABI: called by cin_kernels.hip.
-// ---------------------------------------------------------------------------------------------------
-namespace {
-__global__ __launch_bounds__(256) void cin_bias_act_kernel(float* __restrict__ y, int64_t rows, int H, const float* __restrict__ bias, int act) {
-    const int64_t total = rows * H;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256)
-        y[o] = act_value(y[o] + bias[(int)(o % H)], act);
-}
-// out[b, off + j] = sum_d y[(b D + d), d0 + j]   (j < nd): deterministic serial sum over d, as the one-kernel form's LDS sum
-__global__ __launch_bounds__(256) void cin_sum_d_kernel(const float* __restrict__ y, int H, int64_t batch, int D, int d0, int nd,
-                                                        float* __restrict__ out, int64_t out_dim, int off) {
-    const int64_t total = batch * nd;
-    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-        const int64_t b = o / nd;
-        const int j = (int)(o - b * nd);
-        const float* yp = y + (b * D) * H + d0 + j;
-        float acc = 0.f;
-        for (int d = 0; d < D; ++d) acc += yp[(int64_t)d * H];
-        out[b * out_dim + off + j] = acc;
-    }
-}
-}  // namespace
-
-// floats of workspace per SAMPLE of the layered route: x0t [D, F0] + z [D, max F0 F_k] + two y buffers [D, max H]
-size_t dctr_cin_layered_sample_floats(const dctr_cin_args_t* a) {
-    size_t kmax = 0, hmax = 0;
-    int fk = a->fields;
-    for (int k = 0; k < a->n_layers; ++k) {
-        const int H = a->layer_size[k];
-        const bool last = k == a->n_layers - 1;
-        kmax = (size_t)a->fields * fk > kmax ? (size_t)a->fields * fk : kmax;
-        hmax = (size_t)H > hmax ? (size_t)H : hmax;
-        fk = last ? 0 : (a->split_half ? H / 2 : H);
-    }
-    return (size_t)a->dim * ((((size_t)a->fields + 3) & ~(size_t)3) + ((kmax + 3) & ~(size_t)3) + 2 * ((hmax + 3) & ~(size_t)3));
-}
-
-int dctr_cin_fwd_layered(const dctr_cin_args_t* a, void* workspace, size_t workspace_bytes, void* stream) {
-    const int F0 = a->fields, D = a->dim, L = a->n_layers;
-    const size_t per = dctr_cin_layered_sample_floats(a) * sizeof(float);
-    DCTR_REQUIRE(workspace != nullptr && dctr_aligned16(workspace) && workspace_bytes >= 16 * per, DCTR_E_NULL,
-                 "cin_fwd: these layer sizes run layer by layer and need a 16-B aligned workspace (dctr_cin_workspace_bytes; at least %zu B)", 16 * per);
-    DCTR_REQUIRE(a->x != nullptr && a->out != nullptr && a->filters != nullptr && a->bias != nullptr, DCTR_E_NULL, "cin_fwd: null pointer");
-    int64_t cap = (int64_t)(workspace_bytes / per);
-    cap = cap > 65536 ? 65536 : cap & ~(int64_t)3;
-    size_t kmax = 0, hmax = 0;
-    int out_dim = 0;
-    {
-        int fk = F0;
-        for (int k = 0; k < L; ++k) {
-            const int H = a->layer_size[k];
-            const bool last = k == L - 1;
-            DCTR_REQUIRE(a->filters[k] && a->bias[k], DCTR_E_NULL, "cin_fwd: filters/bias[%d] null", k);
-            kmax = (size_t)F0 * fk > kmax ? (size_t)F0 * fk : kmax;
-            hmax = (size_t)H > hmax ? (size_t)H : hmax;
-            out_dim += a->split_half ? (last ? H : H - H / 2) : H;
-            fk = last ? 0 : (a->split_half ? H / 2 : H);
-        }
-    }
-    // (the GEMM's sizes and element offsets are ints: a chunk's z stays below 2^31 elements)
-    while (cap > 16 && (int64_t)cap * D * (int64_t)(kmax > hmax ? kmax : hmax) >= 0x7fffffffLL) cap = (cap >> 1) & ~(int64_t)3;
-    DCTR_REQUIRE((int64_t)cap * D * (int64_t)(kmax > hmax ? kmax : hmax) < 0x7fffffffLL, DCTR_E_DIM, "cin_fwd: layer too large (%zu products per row)", kmax);
-    float* ws = static_cast<float*>(workspace);
-    const size_t f0p = ((size_t)F0 + 3) & ~(size_t)3, kp = (kmax + 3) & ~(size_t)3, hp = (hmax + 3) & ~(size_t)3;
-    float* x0t = ws;
-    float* z = x0t + (size_t)cap * D * f0p;
-    float* ybuf[2] = {z + (size_t)cap * D * kp, z + (size_t)cap * D * kp + (size_t)cap * D * hp};
-    hipStream_t st = (hipStream_t)stream;
-    auto grid = [](int64_t n) { int64_t b = dctr_ceil_div(n, (int64_t)256); return dim3((unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b))); };
-    for (int64_t r0 = 0; r0 < a->batch; r0 += cap) {
-        const int64_t nb = a->batch - r0 < cap ? a->batch - r0 : cap;
-        const int64_t R = nb * D;
-        hipLaunchKernelGGL(cin_to_rows_kernel, grid(R * F0), dim3(256), 0, st, a->x + r0 * a->x_stride, a->x_stride, nb, F0, D, x0t);
-        const float* xk = x0t;
-        int64_t ldk = F0;
-        int fk = F0, off = 0;
-        for (int k = 0; k < L; ++k) {
-            const int H = a->layer_size[k];
-            const bool last = k == L - 1;
-            const int Hn = last ? 0 : (a->split_half ? H / 2 : H), d0 = a->split_half ? (last ? 0 : H / 2) : 0;
-            const int K = F0 * fk;
-            hipLaunchKernelGGL(cin_outer_kernel, grid(R * K), dim3(256), 0, st, (const float*)x0t, F0, xk, ldk, fk, R, z);
-            float* y = (a->save_y != nullptr && a->save_y[k] != nullptr) ? a->save_y[k] + (size_t)r0 * D * H : ybuf[k & 1];
-            // row-major y [R, H] = z [R, K] W [K, H]  <=>  column-major y' (H x R) = W' (H x K) z' (K x R)
-            const int rs = dctr_gemm::sgemm(st, dctr_gemm::OP_N, dctr_gemm::OP_N, H, (int)R, K, a->filters[k], H, z, K, 0.f, y, H);
-            DCTR_REQUIRE(rs == 0, DCTR_E_UNSUPPORTED, "cin_fwd: sgemm(layer %d) failed (%d)", k, rs);
-            hipLaunchKernelGGL(cin_bias_act_kernel, grid(R * H), dim3(256), 0, st, y, R, H, a->bias[k], (int)a->activation);
-            hipLaunchKernelGGL(cin_sum_d_kernel, grid(nb * (H - d0)), dim3(256), 0, st, (const float*)y, H, nb, D, d0, H - d0, a->out + r0 * out_dim,
-                               (int64_t)out_dim, off);
-            off += H - d0;
-            xk = y;
-            ldk = H;
-            fk = Hn;
-        }
-    }
-    return dctr_launch_status("dctr_cin_fwd");
-}
-
-namespace dctr_cinbwd {      // cin_bwd_kernels.hip: the z-free backward of one CIN layer (filter gradient; input gradients)
-bool fused_shape_ok(int F0, int Fk, int H);
-int64_t dw_parts_floats(int F0, int Fk, int H, int64_t rows);
-int launch_dw_fused(const float* dpre, const float* x0t, const float* xk, int64_t ldk, int F0, int Fk, int H, int64_t rows,
-                    float* parts, int* n_parts, hipStream_t st);
-int launch_dz_fused(const float* dpre, const float* W, const float* x0t, const float* xk, int64_t ldk, int F0, int Fk, int H,
-                    int64_t rows, float* dx0t, float* dxk, hipStream_t st);
-}  // namespace dctr_cinbwd
-
-namespace {
-struct CinPlan {
-    int L, F0, D;
-    int H[8], Fk[8], Hn[8], d0[8], off[8];
-    bool fused[8];         // layer runs on the z-free kernels of cin_bwd_kernels.hip: no z / dz for it
-    int64_t R;
-    size_t x0t, y[8], z[8], dpre, dz, dx0t, dxk[2], fwd_out, fwd_ws, fwd_ws_bytes, parts, total;
-    int out_dim;
-};
-bool cin_plan(const dctr_cin_args_t* f, CinPlan& p) {
-    p.L = f->n_layers;
-    p.F0 = f->fields;
-    p.D = f->dim;
-    p.R = f->batch * (int64_t)f->dim;
-    if (p.L < 1 || p.L > 8) return false;
-    int fk = p.F0, off = 0;
-    size_t cur = 0;
-    auto take = [&](size_t n) { size_t o = cur; cur += (n + 3) & ~(size_t)3; return o; };
-    p.x0t = take((size_t)p.R * p.F0);
-    size_t zmax = 0, hmax = 0, fkmax = 0, pmax = 0;
-    for (int k = 0; k < p.L; ++k) {
-        const int H = f->layer_size[k];
-        const bool last = k == p.L - 1;
-        p.H[k] = H;
-        p.Fk[k] = fk;
-        p.Hn[k] = last ? 0 : (f->split_half ? H / 2 : H);
-        p.d0[k] = f->split_half ? (last ? 0 : H / 2) : 0;
-        p.off[k] = off;
-        off += H - p.d0[k];
-        p.y[k] = take((size_t)p.R * H);
-        p.fused[k] = dctr_cinbwd::fused_shape_ok(p.F0, fk, H);
-        p.z[k] = take(p.fused[k] ? 0 : (size_t)p.R * p.F0 * fk);
-        if (!p.fused[k]) zmax = (size_t)p.R * p.F0 * fk > zmax ? (size_t)p.R * p.F0 * fk : zmax;
-        else {
-            const size_t pf = (size_t)dctr_cinbwd::dw_parts_floats(p.F0, fk, H, p.R);
-            pmax = pf > pmax ? pf : pmax;
-        }
-        hmax = (size_t)H > hmax ? H : hmax;
-        fkmax = (size_t)fk > fkmax ? fk : fkmax;
-        fk = p.Hn[k];
-    }
-    p.out_dim = off;
-    p.fwd_out = take((size_t)f->batch * off);          // the forward kernel's [B, featuremap_num] output when it is re-run for y_k
-    p.dpre = take((size_t)p.R * hmax);
-    p.dz = take(zmax);
-    p.parts = take(pmax);                              // the z-free dW kernel's per-row-slice partial products
-    p.dx0t = take((size_t)p.R * p.F0);
-    p.dxk[0] = take((size_t)p.R * fkmax);
-    p.dxk[1] = take((size_t)p.R * fkmax);
-    // the re-run forward's own workspace (layer 0's fold; REQUIRED by the sliced / layer-by-layer routes of wide samples / layers)
-    p.fwd_ws_bytes = dctr_cin_workspace_bytes(f);
-    p.fwd_ws = take((p.fwd_ws_bytes + 3) / 4);
-    p.total = cur;
-    return true;
-}
-}  // namespace
-
-extern "C" size_t dctr_cin_bwd_workspace_bytes(const dctr_cin_bwd_args_t* a) {
-    CinPlan p;
-    if (a == nullptr || a->fwd == nullptr || a->fwd->batch <= 0 || !cin_plan(a->fwd, p)) return 0;
-    return p.total * sizeof(float);
-}
-
-extern "C" int dctr_cin_bwd(const dctr_cin_bwd_args_t* a, void* stream) {
-    DCTR_REQUIRE(a != nullptr && a->fwd != nullptr, DCTR_E_NULL, "cin_bwd: null args");
-    const dctr_cin_args_t* f = a->fwd;
-    DCTR_REQUIRE(f->batch >= 0 && f->fields >= 1 && f->dim >= 1, DCTR_E_DIM, "cin_bwd: bad sizes");
-    if (f->batch == 0) return DCTR_OK;
-    CinPlan p;
-    DCTR_REQUIRE(cin_plan(f, p), DCTR_E_DIM, "cin_bwd: 1..8 layers");
-    DCTR_REQUIRE(f->x && f->layer_size && f->filters && f->bias && a->d_out && a->d_filters && a->d_bias, DCTR_E_NULL,
-                 "cin_bwd: null pointer");
-    DCTR_REQUIRE(f->activation >= DCTR_ACT_LINEAR && f->activation <= DCTR_ACT_TANH, DCTR_E_ENUM, "cin_bwd: activation %d",
-                 f->activation);
-    DCTR_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= p.total * sizeof(float), DCTR_E_NULL,
-                 "cin_bwd: needs a workspace of dctr_cin_bwd_workspace_bytes() bytes");
-    DCTR_REQUIRE(p.R < 0x7fffffffLL, DCTR_E_DIM, "cin_bwd: batch * dim too large");
-    hipStream_t st = (hipStream_t)stream;
-    float* ws = static_cast<float*>(a->workspace);
-    const int R = (int)p.R, F0 = p.F0, D = p.D;
-    auto grid = [](int64_t n) { int64_t b = dctr_ceil_div(n, (int64_t)256); return dim3((unsigned)(b > 8192 ? 8192 : b)); };
-    float* x0t = ws + p.x0t;
-    hipLaunchKernelGGL(cin_to_rows_kernel, grid(p.R * F0), dim3(256), 0, st, f->x, f->x_stride, f->batch, F0, D, x0t);
-    // the activations y_k: written by the forward call (saved_y), else the forward kernel is re-run here with the workspace as its
-    // save_y (one launch; the first version recomputed them as z W with a GEMM per layer)
-    const float* yk[8];
-    bool rerun = false;
-    for (int k = 0; k < p.L; ++k) {
-        yk[k] = (a->saved_y != nullptr && a->saved_y[k] != nullptr) ? a->saved_y[k] : ws + p.y[k];
-        rerun = rerun || yk[k] == ws + p.y[k];
-    }
-    if (rerun) {
-        dctr_cin_args_t fa = *f;
-        float* sv[8];
-        for (int k = 0; k < p.L; ++k) sv[k] = yk[k] == ws + p.y[k] ? ws + p.y[k] : nullptr;
-        fa.save_y = sv;
-        fa.out = ws + p.fwd_out;
-        if (p.fwd_ws_bytes > 0 && (fa.workspace == nullptr || fa.workspace_bytes < p.fwd_ws_bytes)) {   // (fwd->workspace is documented unused here)
-            fa.workspace = ws + p.fwd_ws;
-            fa.workspace_bytes = p.fwd_ws_bytes;
-            fa.workspace_ready = 0;
-        }
-        const int rc = dctr_cin_fwd(&fa, stream);
-        if (rc != 0) return rc;
-    }
-    // z only for layers outside the z-free kernels' shapes (the dW GEMM's operand)
-    for (int k = 0; k < p.L; ++k) {
-        if (p.fused[k]) continue;
-        const int Fk = p.Fk[k], K = F0 * Fk;
-        const float* xk = k == 0 ? x0t : yk[k - 1];
-        const int64_t ldk = k == 0 ? F0 : p.H[k - 1];
-        float* z = ws + p.z[k];
-        if (Fk % 4 == 0 && ldk % 4 == 0 && dctr_aligned16(xk) && dctr_aligned16(z))
-            hipLaunchKernelGGL(cin_outer4_kernel, grid(p.R * (K / 4)), dim3(256), 0, st, x0t, F0, xk, ldk, Fk, p.R, z);
-        else
-            hipLaunchKernelGGL(cin_outer_kernel, grid(p.R * K), dim3(256), 0, st, x0t, F0, xk, ldk, Fk, p.R, z);
-    }
-    hipError_t me = hipMemsetAsync(ws + p.dx0t, 0, (size_t)p.R * F0 * sizeof(float), st);
-    DCTR_REQUIRE(me == hipSuccess, (int)me, "cin_bwd: memset failed: %s", hipGetErrorString(me));
-    const float* dxnext = nullptr;
-    int64_t ldn = 0;
-    for (int k = p.L - 1; k >= 0; --k) {
-        const int Fk = p.Fk[k], H = p.H[k], K = F0 * Fk;
-        const float* xk = k == 0 ? x0t : yk[k - 1];
-        const int64_t ldk = k == 0 ? F0 : p.H[k - 1];
-        float* dpre = ws + p.dpre;
-        float* dz = ws + p.dz;
-        hipLaunchKernelGGL(cin_dpre_kernel, grid(p.R * H), dim3(256), 0, st, yk[k], dxnext, ldn, p.Hn[k], a->d_out,
-                           (int64_t)a->out_dim, p.off[k], p.d0[k], p.R, H, D, (int)f->activation, dpre);
-        launch_act_bwd_colsum(st, dpre, (const float*)nullptr, p.R, H, 0, a->d_bias[k]);
-        // dW[K,H] += z^T dpre:  column-major  dW'(H x K) = dpre'(H x R) z'(K x R)^T.  The output is small (H x K) and the
-        // reduction long (R = B*D): as ONE gemm it runs on ~18 workgroups (1.8 ms at C3); split the rows into `parts`
-        // slices computed as a strided batch of partial products in the (now free) dz buffer, then summed.
-        const int64_t hk = (int64_t)H * K;
-        int parts = (int)((size_t)p.R * K / (size_t)hk);                 // partials fit the dz buffer: parts*H*K <= R*K
-        if (parts > 32) parts = 32;
-        while (parts > 1 && R % parts != 0) --parts;
-        int rs = 0;
-        if (p.fused[k]) {
-            // z-free: x0[r,i] xk[r,j] formed in registers as the MFMA A operand, rows = the K dimension (cin_bwd_kernels.hip)
-            DCTR_REQUIRE(dctr_aligned16(dpre) && dctr_aligned16(f->filters[k]), DCTR_E_ALIGN,
-                         "cin_bwd: workspace / filters[%d] must be 16-B aligned", k);
-            int n_parts = 0;
-            const int rc = dctr_cinbwd::launch_dw_fused(dpre, x0t, xk, ldk, F0, Fk, H, p.R, ws + p.parts, &n_parts, st);
-            DCTR_REQUIRE(rc == 0, rc, "cin_bwd: cannot launch the fused dW kernel (%d)", rc);
-            hipLaunchKernelGGL(sum_parts_kernel, grid(hk), dim3(256), 0, st, (const float*)(ws + p.parts), hk, n_parts, a->d_filters[k]);
-        } else if (parts > 1) {
-            const int rs_ = R / parts;
-            rs = dctr_gemm::sgemm_strided_batched(st, dctr_gemm::OP_N, dctr_gemm::OP_T, H, K, rs_, dpre, H, (int64_t)rs_ * H, ws + p.z[k], K, (int64_t)rs_ * K, 0.f, dz, H, (int64_t)hk, parts);
-            DCTR_REQUIRE(rs == 0, DCTR_E_UNSUPPORTED, "cin_bwd: sgemm_strided_batched(dW) failed (%d)", (int)rs);
-            hipLaunchKernelGGL(sum_parts_kernel, grid(hk), dim3(256), 0, st, dz, hk, parts, a->d_filters[k]);
-        } else {
-            rs = dctr_gemm::sgemm(st, dctr_gemm::OP_N, dctr_gemm::OP_T, H, K, R, dpre, H, ws + p.z[k], K, 1.f, a->d_filters[k], H);
-            DCTR_REQUIRE(rs == 0, DCTR_E_UNSUPPORTED, "cin_bwd: sgemm(dW) failed (%d)", (int)rs);
-        }
-        float* dxk = ws + p.dxk[k & 1];          // layer 0: x_0 is also its x_k; that second-factor gradient lands in dxk[0]
-        if (p.fused[k]) {
-            // dz = dpre W^T is formed tile by tile on the matrix cores and contracted with x_0 / x_k at once (never stored)
-            const int rc = dctr_cinbwd::launch_dz_fused(dpre, f->filters[k], x0t, xk, ldk, F0, Fk, H, p.R, ws + p.dx0t, dxk, st);
-            DCTR_REQUIRE(rc == 0, rc, "cin_bwd: cannot launch the fused dz kernel (%d)", rc);
-        } else {
-            // dz[R,K] = dpre[R,H] W^T:  column-major  dz'(K x R) = W'(H x K)^T dpre'(H x R)
-            rs = dctr_gemm::sgemm(st, dctr_gemm::OP_T, dctr_gemm::OP_N, K, R, H, f->filters[k], H, dpre, H, 0.f, dz, K);
-            DCTR_REQUIRE(rs == 0, DCTR_E_UNSUPPORTED, "cin_bwd: sgemm(dz) failed (%d)", (int)rs);
-            const size_t lds = (size_t)4 * (K + F0 + Fk) * sizeof(float);
-            DCTR_REQUIRE(lds <= 64 * 1024, DCTR_E_UNSUPPORTED, "cin_bwd: F0*Fk = %d too large for the row-staging kernel", K);
-            int64_t nb = dctr_ceil_div(p.R, (int64_t)4);
-            if (nb > 256 * 16) nb = 256 * 16;
-            hipLaunchKernelGGL(cin_outer_bwd_kernel, dim3((unsigned)nb), dim3(256), lds, st, dz, x0t, F0, xk, ldk, Fk, p.R,
-                               ws + p.dx0t, dxk);
-        }
-        dxnext = dxk;
-        ldn = Fk;
-    }
-    if (a->dx != nullptr) {
-        // d x0 = dX0t (first factor, all layers) + layer 0's second factor (in dxk[0], [R, F0])
-        hipLaunchKernelGGL(add_rows_kernel, grid(p.R * F0), dim3(256), 0, st, ws + p.dxk[0], (int64_t)F0, p.R, F0, ws + p.dx0t,
-                           (int64_t)F0, 1);
-        hipLaunchKernelGGL(cin_from_rows_kernel, grid(p.R * F0), dim3(256), 0, st, ws + p.dx0t, f->batch, F0, D, a->dx, a->dx_stride,
-                           (int)a->dx_accumulate);
-    }
-    return dctr_launch_status("dctr_cin_bwd");
 }
 
 // ---------------------------------------------------------------------------------------------------
