@@ -29,6 +29,21 @@ struct DzParams {
     int32_t sd, s0, sk;       // LDS row strides (floats) of the dpre / x0 / xk tiles
 };
 
+// Staging of the 64-row dpre tile of both kernels: 64 * H contiguous floats = KS * 256 float4 (KS = H / 16), H4 = H / 4 of them per row.
+// Element u of thread t is float4 t + 256 u of the tile.  With t = dm * H4 + dc and 256 = Q * H4 + REM that is row dm + u Q + carry,
+// column dc + u REM - carry * H4, carry = (dc + u REM) / H4.  Where H4 divides 256 (H = 16, 32, 64, 128) REM = 0 and the row steps by
+// Q with the column fixed (the expressions below are written so that they fold to exactly that: the same instructions as without
+// the carry); a version that stepped so for EVERY H left rows 60..63 of the tile partly unstaged at H = 48, 80, 96 and 112.
+template <int KS>
+struct DpreStage {
+    static constexpr int H4 = KS * 4, Q = 256 / H4, REM = 256 % H4;
+    int dm, dc;
+    __device__ __forceinline__ explicit DpreStage(int t) : dm(t / H4), dc(t - (t / H4) * H4) {}
+    __device__ __forceinline__ int carry(int u) const { return u * REM == 0 ? 0 : (dc + u * REM) / H4; }
+    __device__ __forceinline__ int step(int u) const { return u * Q + carry(u); }              // row of element u = dm + step(u)
+    __device__ __forceinline__ int col(int u) const { return dc + u * REM - carry(u) * H4; }
+};
+
 // KS = H / 16 is a template parameter and the prefetch of the next tile is unconditional (clamped): with branches between the
 // loads hipcc cannot count them and waits for vmcnt(0) — i.e. for the tile just requested — before the first MFMA.
 //
@@ -53,13 +68,12 @@ __global__ __launch_bounds__(256, 2) void cin_dz_fused_kernel(DzParams p) {
     const int64_t r0 = (int64_t)blockIdx.x * RB;
     {
         // all loads of the tile in flight before the LDS stores (RB * H / 4 = KS * 256 float4: KS per thread, compile-time steps)
-        constexpr int H4 = KS * 4, DROWS = 256 / H4;
-        const int dm = threadIdx.x / H4, dc = threadIdx.x - dm * H4;
+        const DpreStage<KS> ds(threadIdx.x);
         float4 v[KS];
 #pragma unroll
         for (int u = 0; u < KS; ++u) {
             v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + dm + u * DROWS < p.rows) v[u] = *reinterpret_cast<const float4*>(p.dpre + (r0 + dm + u * DROWS) * H + 4 * dc);
+            if (r0 + ds.dm + ds.step(u) < p.rows) v[u] = *reinterpret_cast<const float4*>(p.dpre + (r0 + ds.dm + ds.step(u)) * H + 4 * ds.col(u));
         }
         float xv[DZ_X0N];
 #pragma unroll
@@ -68,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void cin_dz_fused_kernel(DzParams p) {
             xv[u] = (idx < RB * F0 && r0 * F0 + idx < p.rows * F0) ? p.x0t[r0 * F0 + idx] : 0.f;
         }
 #pragma unroll
-        for (int u = 0; u < KS; ++u) *reinterpret_cast<float4*>(dps + (dm + u * DROWS) * p.sd + 4 * dc) = v[u];
+        for (int u = 0; u < KS; ++u) *reinterpret_cast<float4*>(dps + (ds.dm + ds.step(u)) * p.sd + 4 * ds.col(u)) = v[u];
 #pragma unroll
         for (int u = 0; u < DZ_X0N; ++u) {
             const int idx = threadIdx.x + u * 256;
@@ -260,9 +274,9 @@ __global__ __launch_bounds__(256, 2) void cin_dw_fused_kernel(DwParams p) {
     // after them (a loop of load -> LDS store per element serialised ~30 memory latencies per tile: 2x the MFMA time)
     float4 sd4[NH];
     float sx0[DW_X0N];
-    // dpre tile: DW_TR * H / 4 = NH * 256 float4, element u of a thread = row dm + u * DROWS, float4 column dc (compile-time steps)
-    constexpr int H4 = NH * 4, DROWS = 256 / H4;
-    const int dm = threadIdx.x / H4, dc = threadIdx.x - dm * H4;
+    // dpre tile: DW_TR * H / 4 = NH * 256 float4, element u of a thread = float4 tid + 256 u of the tile (DpreStage), which lies
+    // u (Q H + 4 REM) = 1024 u floats behind element 0
+    const DpreStage<NH> ds(threadIdx.x);
     // x0 / xk tiles as flat [DW_TR][F0] / [DW_TR][Fk] index spaces, (row, column) of element u stepped incrementally
     const int x0_m0 = threadIdx.x / F0, x0_i0 = threadIdx.x - x0_m0 * F0, x0_dm = 256 / F0, x0_di = 256 - x0_dm * F0;
     // xk: XK4: flat over [DW_TR][Fk/4] float4; else flat over [DW_TR][Fk] floats
@@ -272,11 +286,11 @@ __global__ __launch_bounds__(256, 2) void cin_dw_fused_kernel(DwParams p) {
     float4 sxk4[XK4 ? XKN : 1];
     float sxk1[XK4 ? 1 : XKN];
     auto request = [&](int64_t r0) {
-        const float* dsrc = p.dpre + (r0 + dm) * H + 4 * dc;
+        const float* dsrc = p.dpre + (r0 + ds.dm) * H + 4 * ds.dc;
 #pragma unroll
         for (int u = 0; u < NH; ++u) {
             sd4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + dm + u * DROWS < rhi) sd4[u] = *reinterpret_cast<const float4*>(dsrc + (int64_t)u * DROWS * H);
+            if (r0 + ds.dm + ds.step(u) < rhi) sd4[u] = *reinterpret_cast<const float4*>(dsrc + (int64_t)u * ds.Q * H + 4 * u * ds.REM);
         }
         int m = x0_m0, i = x0_i0;
 #pragma unroll
@@ -298,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void cin_dw_fused_kernel(DwParams p) {
     };
     auto commit = [&]() {
 #pragma unroll
-        for (int u = 0; u < NH; ++u) *reinterpret_cast<float4*>(dps + (dm + u * DROWS) * p.sd + 4 * dc) = sd4[u];
+        for (int u = 0; u < NH; ++u) *reinterpret_cast<float4*>(dps + (ds.dm + ds.step(u)) * p.sd + 4 * ds.col(u)) = sd4[u];
         int m = x0_m0, i = x0_i0;
 #pragma unroll
         for (int u = 0; u < DW_X0N; ++u) {

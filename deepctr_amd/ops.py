@@ -3095,9 +3095,11 @@ def crossnet_bwd(x, d, kernels, bias, parameterization, dy, d_kernels, d_bias, d
 
 
 def cin_bwd(x, filters, biases, layer_size, split_half, activation, d_out, d_filters, d_biases, dx=None, accumulate=False,
-            fields=None, dim=None, saved_y=None):
+            fields=None, dim=None, saved_y=None, workspace=None):
     """Backward of dctr_cin_fwd: x as in ``cin`` (3-D, or the leading F0*D columns of a 2-D buffer with fields/dim);
-    d_out [B, featuremap_num]; d_filters / d_biases are ACCUMULATED; dx (2-D, same layout as x) written or added to."""
+    d_out [B, featuremap_num]; d_filters / d_biases are ACCUMULATED; dx (2-D, same layout as x) written or added to.
+    ``workspace``: a dict the caller keeps alive, as ``mlp_bwd`` takes it: the tensor is cached under "ws" and replaced only when it
+    is missing, on another device or smaller than dctr_cin_bwd_workspace_bytes (default: a fresh tensor per call)."""
     _dev_check(x, d_out, *filters)
     x, B, F0, D, x_stride, _ = _x_in_place("cin_bwd", x, fields, dim)
     n = len(layer_size)
@@ -3119,6 +3121,11 @@ def cin_bwd(x, filters, biases, layer_size, split_half, activation, d_out, d_fil
         syp = _ptr_array(list(saved_y))
         a.saved_y = ctypes.cast(syp, ctypes.c_void_p)
     need = int(_C.lib().dctr_cin_bwd_workspace_bytes(ctypes.byref(a)))
-    ws = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
+    if workspace is not None:
+        ws = workspace.get("ws")
+        if ws is None or ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < need or ws.device != x.device:
+            ws = workspace["ws"] = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
+    else:
+        ws = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
     a.workspace, a.workspace_bytes = ws.data_ptr(), need
     _C.check(_C.lib().dctr_cin_bwd(ctypes.byref(a), _C.stream_ptr()), "dctr_cin_bwd")
