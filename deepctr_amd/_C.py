@@ -368,6 +368,23 @@ class AdamSeg(ctypes.Structure):
     _fields_ = [("w", c_vp), ("m", c_vp), ("v", c_vp), ("g", c_vp), ("n", c_i64), ("l2", c_f32), ("pad_", c_i32), ("touched", c_vp)]
 
 
+class opt(object):
+    """dctr_opt_seg_t / dctr_opt_args_t of dctr_opt_apply and dctr_grad_clip_scales, one level down like interacting.Args
+    (tests/test_optimizers_cpu.py checks the layout)."""
+    ADAM, ADAGRAD, RMSPROP, SGD, ADAMAX, ADADELTA, FTRL = range(7)
+    CLIP_PER_SEGMENT, CLIP_GLOBAL = 0, 1
+
+    class Seg(ctypes.Structure):
+        _fields_ = [("w", c_vp), ("g", c_vp), ("s0", c_vp), ("s1", c_vp), ("s2", c_vp), ("n", c_i64), ("l2", c_f32), ("pad_", c_i32),
+                    ("touched", c_vp)]
+
+    class Args(ctypes.Structure):
+        _fields_ = [("kind", c_i32), ("lr", c_f32), ("beta1", c_f32), ("beta2", c_f32), ("eps", c_f32), ("momentum", c_f32),
+                    ("lr_power", c_f32), ("l1", c_f32), ("l2_ftrl", c_f32), ("l2_shrinkage", c_f32), ("nesterov", c_i32),
+                    ("centered", c_i32), ("amsgrad", c_i32), ("clipvalue", c_f32), ("clip_scale", c_vp), ("zero_grad", c_i32),
+                    ("penalty_scale", c_f32), ("l2_penalty", c_vp)]
+
+
 class DinAttnArgs(ctypes.Structure):
     _fields_ = [("query", c_vp), ("keys", c_vp), ("key_mask", c_vp), ("batch", c_i64), ("maxlen", c_i32),
                 ("dim", c_i32), ("n_layers", c_i32), ("activation", c_i32), ("units", c_vp), ("kernels", c_vp),
@@ -505,6 +522,9 @@ SYMBOLS = {
     "dctr_opt_multi": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_i32, c_vp]),
     "dctr_opt_multi_l2": (ctypes.c_int, [ctypes.c_int32, c_vp, c_i32, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                           c_i32, c_vp, ctypes.c_float, c_vp]),
+    "dctr_opt_apply": (ctypes.c_int, [ctypes.POINTER(opt.Args), c_vp, c_i32, c_i64, c_vp]),
+    "dctr_grad_clip_scales_workspace_bytes": (c_sz, [c_i32, c_i64]),
+    "dctr_grad_clip_scales": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_f32, c_vp, c_sz, c_vp, c_vp]),
     "dctr_din_attn_workspace_bytes": (c_sz, [ctypes.POINTER(DinAttnArgs)]),
     "dctr_din_attn_pool_fwd": (ctypes.c_int, [ctypes.POINTER(DinAttnArgs), c_vp]),
     "dctr_din_attn_gather_fwd": (ctypes.c_int, [ctypes.POINTER(DinAttnArgs), ctypes.POINTER(DinGatherArgs), c_vp]),

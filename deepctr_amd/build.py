@@ -66,6 +66,7 @@ SOURCES = [
     "gemm_kernels.hip",
     "mlp_bwd_kernels.hip",
     "train_kernels.hip",
+    "opt_kernels.hip",
     "interaction_bwd_kernels.hip",
     "din_train_kernels.hip",
 ]

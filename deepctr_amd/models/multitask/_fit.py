@@ -69,13 +69,7 @@ def fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end):
     params = [t for name, t in model.named_weights() if "moving_" not in name and t.data_ptr() not in frozen]
     for t in params:
         t.requires_grad_(True)
-    opt = c["optimizer"]
-    if isinstance(opt, str):
-        if opt.lower() not in tops._OPTS:
-            raise ValueError("optimizer %r not supported (adam, adagrad, sgd, rmsprop or a torch.optim factory)" % opt)
-        opt = tops._OPTS[opt.lower()](params)
-    elif callable(opt):
-        opt = opt(params)
+    opt = tops.torch_optimizer(model, params)
     regs = [(t, l2) for t, l2 in tops.regularized_weights(model) if t.data_ptr() not in frozen]
     yrows = yt.t().contiguous()         # [n_tr, T]: permute_staged_ permutes dimension 0
 
@@ -135,11 +129,9 @@ def fit_hip(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end):
     train_on_batch and a second fit() continue the same optimisation.  Per epoch ONE device matrix [steps, T] takes every step's summed
     task losses (dctr_mtl_loss_grad adds into its row), the l2 penalties ride the optimizer launch (HipTrainer.penalty_acc, as
     training._fit_hip), and the steps' outputs are gathered on the device for the compiled metrics: one copy to the host per epoch."""
-    from ...training_hip import HipTrainer
+    from ...training_hip import trainer_for
     c = model._compiled
-    tr = getattr(model, "_hip_trainer", None)
-    if tr is None or tr.kind != c["optimizer"].lower():
-        tr = model._hip_trainer = HipTrainer(model, c["optimizer"])
+    tr = trainer_for(model)
     T, names, metrics, w = model.num_tasks, model.task_names, list(c["metrics"]), np.asarray(c["loss_weights"], dtype=np.float64)
     yrows = yt.t().contiguous()         # [n_tr, T]: permute_staged_ permutes dimension 0
 
@@ -183,12 +175,10 @@ def fit_hip(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end):
 
 
 def takes_hip_step(model):
-    """The rule of training.fit_model: ``model.hip_training`` (default True), an optimizer given by a name the HIP step has, and a model /
-    loss combination it covers (training_hip.supported -> MultiTaskModel._hip_supported)."""
+    """The rule of training.fit_model: ``model.hip_training`` (default True), an optimizer given by a name the HIP step has or as an
+    ``optimizers`` object, and a model / loss combination it covers (training_hip.supported -> MultiTaskModel._hip_supported)."""
     from ... import training_hip
-    opt = model._compiled["optimizer"]
-    return bool(getattr(model, "hip_training", True) and isinstance(opt, str) and opt.lower() in training_hip.OPT_DEFAULTS
-                and training_hip.supported(model))
+    return bool(getattr(model, "hip_training", True) and training_hip.takes_optimizer(model) and training_hip.supported(model))
 
 
 def fit_multitask(model, x, y, batch_size=256, epochs=1, verbose=1, validation_split=0.0, shuffle=True, validation_data=None, **kwargs):

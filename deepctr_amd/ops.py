@@ -3041,6 +3041,65 @@ def opt_multi(kind, segs, n_segs, max_n, lr, beta1=0.9, beta2=0.999, eps=1e-7, z
                                      float(beta2), float(eps), int(bool(zero_grad)), _C.stream_ptr()), "dctr_opt_multi")
 
 
+def make_opt_segments(params, device):
+    """DEVICE array of dctr_opt_seg_t from [(w, g, [state slots ...], l2[, touched bytes or None]), ...] for opt_apply /
+    grad_clip_scales; returns (tensor, n_segs, max_n)."""
+    arr = (_C.opt.Seg * max(1, len(params)))()
+    mx = 0
+    for i, e in enumerate(params):
+        w, g, slots, l2 = e[:4]
+        tch = e[4] if len(e) > 4 else None
+        if len(slots) > 3 or any(s.numel() != w.numel() or s.dtype != torch.float32 for s in list(slots) + [g]):
+            raise ValueError("opt segments: at most three float32 state slots, each (and g) of w's size")
+        arr[i].w, arr[i].g = w.data_ptr(), g.data_ptr()
+        for name, s in zip(("s0", "s1", "s2"), slots):
+            setattr(arr[i], name, s.data_ptr())
+        arr[i].n, arr[i].l2 = w.numel(), float(l2)
+        if tch is not None:
+            if tch.dtype != torch.uint8 or tch.numel() != w.numel() // 4 or w.numel() % 4 or any(
+                    t.data_ptr() % 16 for t in [w, g] + list(slots)):
+                raise ValueError("touched: uint8 [n / 4] beside 16-byte aligned buffers of n %% 4 == 0 elements")
+            arr[i].touched = tch.data_ptr()
+        mx = max(mx, w.numel())
+    return _upload(arr, device), len(params), mx
+
+
+def opt_apply(rule, segs, n_segs, max_n, lr, zero_grad=True, clip_scale=None, penalty=None, penalty_scale=0.0):
+    """One update of an optimizer object's rule over every segment in one launch (dctr_opt_apply).  ``rule``: kind (an _C.opt code)
+    and the rule's scalars / flags, as optimizers.Optimizer._rule() names them (+ clipvalue); ``lr``: the step's rate (Adam / Adamax:
+    bias correction folded in).  ``clip_scale``: device float32 [n_segs] from grad_clip_scales.  ``penalty``: as opt_multi."""
+    if penalty is not None and (penalty.dtype != torch.float64 or penalty.numel() != 1 or not penalty.is_cuda):
+        raise ValueError("opt_apply: penalty must be a device float64 tensor of one element")
+    if clip_scale is not None and (clip_scale.dtype != torch.float32 or clip_scale.numel() != n_segs or not clip_scale.is_cuda):
+        raise ValueError("opt_apply: clip_scale must be a device float32 tensor of n_segs elements")
+    lr = float(lr)
+    l2f = float(rule.get("l2_ftrl", 0.0))
+    if rule.get("beta"):                     # Ftrl's beta enters as l2 + beta / (2 lr), as tf.keras adjusts it
+        l2f += float(rule["beta"]) / (2.0 * lr)
+    a = _C.opt.Args(kind=int(rule["kind"]), lr=lr, beta1=float(rule.get("beta1", 0.0)), beta2=float(rule.get("beta2", 0.0)),
+                    eps=float(rule.get("eps", 0.0)), momentum=float(rule.get("momentum", 0.0)), lr_power=float(rule.get("lr_power", 0.0)),
+                    l1=float(rule.get("l1", 0.0)), l2_ftrl=l2f, l2_shrinkage=float(rule.get("l2_shrinkage", 0.0)),
+                    nesterov=int(bool(rule.get("nesterov"))), centered=int(bool(rule.get("centered"))), amsgrad=int(bool(rule.get("amsgrad"))),
+                    clipvalue=float(rule.get("clipvalue") or 0.0), clip_scale=None if clip_scale is None else clip_scale.data_ptr(), zero_grad=int(bool(zero_grad)),
+                    penalty_scale=float(penalty_scale) if penalty is not None else 0.0, l2_penalty=None if penalty is None else penalty.data_ptr())
+    _C.check(_C.lib().dctr_opt_apply(ctypes.byref(a), _ptr(segs), int(n_segs), int(max_n), _C.stream_ptr()), "dctr_opt_apply")
+
+
+def grad_clip_workspace(n_segs, max_n, device):
+    """(workspace, clip_scale) device tensors for grad_clip_scales over such a segment list."""
+    nbytes = int(_C.lib().dctr_grad_clip_scales_workspace_bytes(int(n_segs), int(max_n)))
+    return (torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device),
+            torch.empty(max(int(n_segs), 1), dtype=torch.float32, device=device))
+
+
+def grad_clip_scales(segs, n_segs, max_n, clip, workspace, clip_scale, global_norm=False):
+    """Keras' clipnorm (per segment) / global_clipnorm scales of g + 2 l2 w into ``clip_scale`` [n_segs], on the device
+    (dctr_grad_clip_scales: float64 partial sums added in a fixed order)."""
+    _C.check(_C.lib().dctr_grad_clip_scales(_ptr(segs), int(n_segs), int(max_n), _C.opt.CLIP_GLOBAL if global_norm else _C.opt.CLIP_PER_SEGMENT,
+                                            float(clip), _ptr(workspace), workspace.numel() * workspace.element_size(), _ptr(clip_scale),
+                                            _C.stream_ptr()), "dctr_grad_clip_scales")
+
+
 def dense1_bwd(x, n, w, dlogit, dx, d_w):
     """Backward of Dense(1, use_bias=False) on the first n columns of a strided [B, >= n] input (include/dctr.h)."""
     _dev_check(x, w, dlogit, dx, d_w)

@@ -509,6 +509,142 @@ _OPTS = {"adam": lambda p: KerasAdam(p, lr=1e-3, eps=1e-7), "adagrad": lambda p:
          "sgd": lambda p: torch.optim.SGD(p, lr=1e-2), "rmsprop": lambda p: torch.optim.RMSprop(p, lr=1e-3, alpha=0.9, eps=1e-7)}
 
 
+class KerasOptimizer(torch.optim.Optimizer):
+    """The update rules of ``deepctr_amd.optimizers`` on torch tensors, for the autograd step — and the float32
+    comparison of dctr_opt_apply's tests.  ``opt``: an optimizers object; its schedule is evaluated at ``iterations`` before the
+    increment, clipnorm / global_clipnorm / clipvalue act on the gradient as it arrives (the l2 penalties are part of the loss here, so
+    it already holds 2 l2 w), and ``iterations`` is written back.  Non-lazy: every element moves on every update."""
+
+    def __init__(self, params, opt):
+        super(KerasOptimizer, self).__init__(params, {})
+        self.opt = opt
+        self.rule = opt._rule()
+
+    def _clipped(self, params):
+        opt = self.opt
+        grads = [p.grad for p in params]
+        if opt.clipnorm is not None:
+            grads = [g * (opt.clipnorm / torch.clamp(torch.linalg.vector_norm(g.double()), min=opt.clipnorm)).to(g.dtype) for g in grads]
+        elif opt.global_clipnorm is not None:
+            total = torch.sqrt(sum(torch.linalg.vector_norm(g.double()) ** 2 for g in grads))
+            scale = opt.global_clipnorm / torch.clamp(total, min=opt.global_clipnorm)
+            grads = [g * scale.to(g.dtype) for g in grads]
+        if opt.clipvalue is not None:
+            grads = [g.clamp(-opt.clipvalue, opt.clipvalue) for g in grads]
+        return grads
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from .optimizers import KIND_ADAGRAD, KIND_ADADELTA, KIND_ADAM, KIND_ADAMAX, KIND_FTRL, KIND_RMSPROP, KIND_SGD
+        params = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        t = int(self.opt.iterations) + 1           # (the object counts: it may serve more than one model)
+        r, kind = self.rule, self.rule["kind"]
+        lr = self.opt._step_lr(t)             # (Adam / Adamax: with the bias correction, as the HIP launch takes it)
+        for p, g in zip(params, self._clipped(params)):
+            st = self.state[p]
+            if not st:
+                st["s"] = [torch.full_like(p, v) for v in r["slots"]]
+            s = st["s"]
+            if kind == KIND_SGD:
+                if not s:
+                    p.add_(g, alpha=-lr)
+                else:
+                    s[0].mul_(r["momentum"]).add_(g, alpha=-lr)
+                    if r["nesterov"]:
+                        p.add_(s[0], alpha=r["momentum"]).add_(g, alpha=-lr)
+                    else:
+                        p.add_(s[0])
+            elif kind == KIND_ADAGRAD:
+                s[0].addcmul_(g, g)
+                p.addcdiv_(g, s[0].sqrt().add_(r["eps"]), value=-lr)
+            elif kind == KIND_RMSPROP:
+                rho = r["beta2"]
+                s[0].mul_(rho).addcmul_(g, g, value=1.0 - rho)
+                den = s[0]
+                if r["centered"]:
+                    s[1].mul_(rho).add_(g, alpha=1.0 - rho)
+                    den = s[0] - s[1] * s[1]
+                if r["momentum"] > 0:
+                    s[-1].mul_(r["momentum"]).addcdiv_(g, (den + r["eps"]).sqrt_(), value=lr)
+                    p.sub_(s[-1])
+                else:
+                    p.addcdiv_(g, den.sqrt().add_(r["eps"]), value=-lr)
+            elif kind == KIND_ADAM:
+                s[0].mul_(r["beta1"]).add_(g, alpha=1.0 - r["beta1"])
+                s[1].mul_(r["beta2"]).addcmul_(g, g, value=1.0 - r["beta2"])
+                v = s[1]
+                if r["amsgrad"]:
+                    torch.maximum(s[2], s[1], out=s[2])
+                    v = s[2]
+                p.addcdiv_(s[0], v.sqrt().add_(r["eps"]), value=-lr)
+            elif kind == KIND_ADAMAX:
+                s[0].mul_(r["beta1"]).add_(g, alpha=1.0 - r["beta1"])
+                torch.maximum(s[1] * r["beta2"], g.abs(), out=s[1])
+                p.addcdiv_(s[0], s[1] + r["eps"], value=-lr)
+            elif kind == KIND_ADADELTA:
+                rho = r["beta2"]
+                s[0].mul_(rho).addcmul_(g, g, value=1.0 - rho)
+                d = (s[1] + r["eps"]).sqrt_() / (s[0] + r["eps"]).sqrt_() * g
+                s[1].mul_(rho).addcmul_(d, d, value=1.0 - rho)
+                p.add_(d, alpha=-lr)
+            elif kind == KIND_FTRL:
+                pw, l1 = -r["lr_power"], r["l1"]
+                l2 = r["l2_ftrl"] + r["beta"] / (2.0 * lr)
+                gs = g + (2.0 * r["l2_shrinkage"]) * p
+                n1 = s[0] + g * g
+                pn1, pn0 = (n1.sqrt(), s[0].sqrt()) if pw == 0.5 else (n1.pow(pw), s[0].pow(pw))
+                s[1].add_(gs - (pn1 - pn0) / lr * p)
+                q = pn1 / lr + 2.0 * l2
+                p.copy_(torch.where(s[1].abs() > l1, (torch.sign(s[1]) * l1 - s[1]) / q, torch.zeros_like(p)))
+                s[0].copy_(n1)
+            else:
+                raise ValueError("optimizer kind %r" % (kind,))
+        self.opt.iterations = t
+
+
+def compiled_optimizer(model):
+    """What compile() holds, as the two training steps take it: one of _OPTS' names in lower case; an ``optimizers`` object — for one
+    of those objects itself, a Keras config dict, a foreign object with ``get_config()`` (a tf.keras optimizer) or a name only
+    ``optimizers.get`` knows, converted once and kept while compile() holds the same value; or the value unchanged (a torch.optim
+    factory, an unknown name: _fit_torch's business)."""
+    from . import optimizers
+    opt = model._compiled["optimizer"]
+    if isinstance(opt, str):
+        if opt.lower() in _OPTS:
+            return opt.lower()
+        if opt.lower() not in ("adamax", "adadelta", "ftrl"):
+            return opt
+    elif isinstance(opt, type) and issubclass(opt, optimizers.Optimizer):
+        raise ValueError("compile() got the class %s, not an instance: compile(%s(...))" % (opt.__name__, opt.__name__))
+    elif isinstance(opt, (optimizers.Optimizer, torch.optim.Optimizer)) or callable(opt):
+        return opt
+    kept = getattr(model, "_optimizer_object", None)
+    if kept is None or kept[0] is not opt:
+        kept = model._optimizer_object = (opt, optimizers.get(opt))
+    return kept[1]
+
+
+def torch_optimizer(model, params):
+    """The torch.optim.Optimizer of the autograd step for what compile() holds (compiled_optimizer)."""
+    from . import optimizers
+    opt = compiled_optimizer(model)
+    if isinstance(opt, optimizers.Optimizer):
+        # kept on the model while compile() holds the same object and the weights are the same tensors, as the HIP step keeps its
+        # trainer: a second fit() continues the moments on either path
+        kept = getattr(model, "_keras_optimizer", None)
+        ptrs = [p.data_ptr() for p in params]
+        if kept is None or kept[0].opt is not opt or kept[1] != ptrs or any(a is not b for a, b in zip(kept[0].param_groups[0]["params"], params)):
+            kept = model._keras_optimizer = (KerasOptimizer(params, opt), ptrs)
+        return kept[0]
+    if isinstance(opt, str):
+        if opt not in _OPTS:
+            raise ValueError("optimizer %r not supported (adam, adagrad, sgd, rmsprop or a torch.optim factory)" % opt)
+        return _OPTS[opt](params)
+    if callable(opt):
+        return opt(params)
+    return opt
+
+
 def permute_staged_(staged, yt, perm, wt=None):
     """Row permutation, IN PLACE, of everything staged per sample (id matrix [F,N], dense [N,ND], sequences, lengths, weights)
     and of the labels (and per-sample loss weights ``wt``): tf.keras' fit(shuffle=True) permutes samples each epoch.  In place so
@@ -724,10 +860,8 @@ def _fit_hip(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end, wt=None, s
     l * sum(w^2) of the constructor's regularisers at THAT step's weights].  The penalties (they also enter the gradients, as 2 l w inside
     the optimizer launch) are summed by the optimizer launch itself, on the weights it is about to update (dctr_opt_multi_l2: no further
     pass over the tables) — round 6; before, they were taken at the epoch's two ends and averaged."""
-    from .training_hip import HipTrainer
-    tr = getattr(model, "_hip_trainer", None)
-    if tr is None or tr.kind != model._compiled["optimizer"].lower():
-        tr = model._hip_trainer = HipTrainer(model, model._compiled["optimizer"])
+    from .training_hip import trainer_for
+    tr = trainer_for(model)
     perm_of = np.random.permutation if dp is None else dp.permutation
     cursor = _BatchCursor(n_tr, bs, steps, (lambda: permute_staged_(
         staged, yt, torch.from_numpy(perm_of(n_tr)).to(yt.device), wt)) if shuffle else None)
@@ -888,8 +1022,7 @@ def fit_model(model, x, y, batch_size=256, epochs=1, verbose=1, validation_split
     wt = None if w is None else torch.from_numpy(w).to(model.device)
     loss_name0 = model._compiled["loss"] or ("binary_crossentropy" if model.task == "binary" else "mse")
     from . import training_hip
-    if (getattr(model, "hip_training", True) and isinstance(model._compiled["optimizer"], str)
-            and model._compiled["optimizer"].lower() in training_hip.OPT_DEFAULTS and training_hip.supported(model)
+    if (getattr(model, "hip_training", True) and training_hip.takes_optimizer(model) and training_hip.supported(model)
             and ((loss_name0 in ("binary_crossentropy", "logloss") and model.task == "binary")
                  or (loss_name0 in ("mse", "mean_squared_error") and model.task != "binary"))):
         fit = _fit_hip
@@ -942,13 +1075,7 @@ def _fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end, wt=None,
     params = [t for name, t in model.named_weights() if "moving_" not in name and t.data_ptr() not in frozen]
     for t in params:
         t.requires_grad_(True)
-    opt = model._compiled["optimizer"]
-    if isinstance(opt, str):
-        if opt.lower() not in _OPTS:
-            raise ValueError("optimizer %r not supported (adam, adagrad, sgd, rmsprop or a torch.optim factory)" % opt)
-        opt = _OPTS[opt.lower()](params)
-    elif callable(opt):
-        opt = opt(params)
+    opt = torch_optimizer(model, params)
     loss_name = model._compiled["loss"] or ("binary_crossentropy" if model.task == "binary" else "mse")
     regs = [(t, l2) for t, l2 in regularized_weights(model) if t.data_ptr() not in frozen]
     perm_of = np.random.permutation if dp is None else dp.permutation

@@ -4,7 +4,8 @@
 ``model.dense`` / the global bias, the DNN's forward and backward (``_dnn_forward`` / ``_dnn_backward``, their layer-by-layer forms for
 ``dnn_dropout``, ``dnn_use_bn`` and a Dice DNN), the loss gradient and the frame of ``step()``: ``dctr_embed_pool`` per sequence feature +
 ``dctr_embed_gather_fm`` forward, then the model's part, then ``dctr_embed_gather_fm_bwd`` → ``dctr_embed_pool_bwd`` → ``dctr_opt_multi``
-(one launch over every parameter).  No torch autograd, no torch optimizer: PyTorch only owns the buffers.
+(one launch over every parameter; ``dctr_opt_apply`` when compile() holds an ``optimizers`` object: DESIGN.md §7.1).  No torch autograd,
+no torch optimizer: PyTorch only owns the buffers.
 
 What lies between the stage and the loss is the model class's, beside its forward and its ``_autograd_logit`` (the ``_hip_*`` hooks
 of ``models/_common.py:FeatureModel``): ``_hip_supported`` says whether an instance trains here, ``_hip_params`` registers its
@@ -35,12 +36,18 @@ def supported(model):
 
 
 class _Param(object):
-    __slots__ = ("w", "m", "v", "g", "l2", "touched")
+    __slots__ = ("w", "m", "v", "g", "l2", "touched", "slots")
 
-    def __init__(self, w, l2=0.0):
+    def __init__(self, w, l2=0.0, slots=None):
         self.w = w
-        self.m = torch.zeros_like(w)
-        self.v = torch.zeros_like(w)
+        if slots is None:               # an optimizer given by name: the two moments of dctr_adam_seg_t
+            self.m = torch.zeros_like(w)
+            self.v = torch.zeros_like(w)
+            self.slots = None
+        else:                           # an optimizers object: only the state its rule needs, at its initial values (dctr_opt_seg_t)
+            self.slots = [torch.full_like(w, v) if v else torch.zeros_like(w) for v in slots]
+            self.m = self.slots[0] if len(self.slots) > 0 else None
+            self.v = self.slots[1] if len(self.slots) > 1 else None
         self.g = torch.zeros_like(w)
         self.l2 = float(l2)
         self.touched = None     # embedding tables: one byte per 16-B group of g (include/dctr.h, dctr_field_grad_t)
@@ -78,22 +85,50 @@ OPT_DEFAULTS = {"adam": dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7), "adagra
                 "rmsprop": dict(lr=1e-3, beta2=0.9, eps=1e-7), "sgd": dict(lr=1e-2)}
 
 
+def trainer_for(model):
+    """The trainer of ``model`` under what compile() holds now (training.compiled_optimizer): the one on ``model._hip_trainer`` while
+    that is the same name or the same optimizers object — a second fit() continues its moments — and a new one otherwise."""
+    from .training import compiled_optimizer
+    opt = compiled_optimizer(model)
+    tr = getattr(model, "_hip_trainer", None)
+    if tr is None or not (tr.optimizer is opt or (isinstance(opt, str) and tr.optimizer == opt)):
+        tr = model._hip_trainer = HipTrainer(model, opt)
+    return tr
+
+
+def takes_optimizer(model):
+    """Does compile()'s optimizer run on the HIP step: one of OPT_DEFAULTS' names, or an optimizers object (training.compiled_optimizer)."""
+    from . import optimizers
+    from .training import compiled_optimizer
+    opt = compiled_optimizer(model)
+    return isinstance(opt, optimizers.Optimizer) or (isinstance(opt, str) and opt in OPT_DEFAULTS)
+
+
 class HipTrainer(object):
     def __init__(self, model, optimizer="adam", lr=None, beta1=None, beta2=None, eps=None):
         if not supported(model):
             raise ValueError("model is outside the HIP training step's family (see training_hip.supported)")
-        optimizer = optimizer.lower()
-        if optimizer not in OPT_DEFAULTS:
-            raise ValueError("optimizer %r not supported (adam, adagrad, rmsprop, sgd)" % optimizer)
-        d = OPT_DEFAULTS[optimizer]
-        self.kind = optimizer
+        # a name keeps dctr_opt_multi with tf.keras' defaults, bit for bit; an optimizers object (or what optimizers.get makes one of)
+        # runs dctr_opt_apply over dctr_opt_seg_t segments that carry only the state slots its rule needs
         self.model = model
-        self.lr = float(d["lr"] if lr is None else lr)
-        self.b1 = float(d.get("beta1", 0.0) if beta1 is None else beta1)
-        self.b2 = float(d.get("beta2", 0.0) if beta2 is None else beta2)
-        self.eps = float(d.get("eps", 0.0) if eps is None else eps)
-        self.init_acc = float(d.get("init_acc", 0.0))
-        self.t = 0
+        self.opt, self.rule = None, None
+        if isinstance(optimizer, str):
+            optimizer = optimizer.lower()
+            if optimizer not in OPT_DEFAULTS:
+                raise ValueError("optimizer %r not supported (adam, adagrad, rmsprop, sgd)" % optimizer)
+            d = OPT_DEFAULTS[optimizer]
+            self.optimizer = self.kind = optimizer
+            self.lr = float(d["lr"] if lr is None else lr)
+            self.b1 = float(d.get("beta1", 0.0) if beta1 is None else beta1)
+            self.b2 = float(d.get("beta2", 0.0) if beta2 is None else beta2)
+            self.eps = float(d.get("eps", 0.0) if eps is None else eps)
+            self.init_acc = float(d.get("init_acc", 0.0))
+        else:
+            from . import optimizers
+            self.optimizer = self.opt = optimizers.get(optimizer)
+            self.rule = dict(self.opt._rule(), clipvalue=self.opt.clipvalue)
+            self.kind = type(self.opt).__name__.lower()
+        self.t = 0 if self.opt is None else int(self.opt.iterations)
         sp = model.stage_plan
         reg = getattr(model, "regularizers", {})
         l2e, l2l, l2d = reg.get("embedding", 0.0), reg.get("linear", 0.0), reg.get("dnn", 0.0)
@@ -148,6 +183,13 @@ class HipTrainer(object):
         pred = getattr(model, "prediction", None)
         self.p_gbias = param(pred.w("global_bias")) if pred is not None and pred.use_bias else None
         self._buf = {}
+        if self.opt is not None:
+            self.segs, self.n_segs, self.max_n = ops.make_opt_segments([(p.w, p.g, p.slots, p.l2, p.touched) for p in self.params],
+                                                                       model.device)
+            self.clip_ws = self.clip_scale = None
+            if self.opt.clipnorm is not None or self.opt.global_clipnorm is not None:
+                self.clip_ws, self.clip_scale = ops.grad_clip_workspace(self.n_segs, self.max_n, model.device)
+            return
         if self.init_acc:
             for p in self.params:
                 p.v.fill_(self.init_acc)            # Adagrad's initial_accumulator_value
@@ -162,7 +204,7 @@ class HipTrainer(object):
             if key in self._frozen:
                 self._by_ptr[key] = _Frozen(t)
             else:
-                self._by_ptr[key] = _Param(t, l2)
+                self._by_ptr[key] = _Param(t, l2, None if self.rule is None else self.rule["slots"])
                 self.params.append(self._by_ptr[key])
         return self._by_ptr[key]
 
@@ -404,6 +446,9 @@ class HipTrainer(object):
     def apply_update(self):
         """The optimizer step over every parameter in one launch (the gradients are zeroed behind it).  Separate from ``step`` so
         that a data-parallel fit can exchange the gradients of a step between its backward and its update (training._DataParallel)."""
+        if self.opt is not None:
+            self.t = int(self.opt.iterations) + 1   # (the object counts: it may serve more than one model)
+            return self._apply_object()
         self.t += 1
         lr = self.lr
         if self.kind == "adam":
@@ -414,6 +459,24 @@ class HipTrainer(object):
         ops.opt_multi(self.kind, self.segs, self.n_segs, self.max_n, lr, self.b1, self.b2, self.eps, penalty=pen,
                       penalty_scale=float(self.penalty_rows) if pen is not None else 0.0)
         # the weights moved through raw pointers (torch's version counters did not): derived inference copies are stale
+        self.model._raw_weight_writes = getattr(self.model, "_raw_weight_writes", 0) + 1
+
+    def _apply_object(self):
+        """apply_update for an optimizers object: the scheduled rate of this update (evaluated on the host at ``iterations`` before
+        the increment: a launch scalar, no device sync), the clipnorm / global_clipnorm pre-pass when the object asks for one (one
+        more read of w and g; the scales stay on the device), dctr_opt_apply, and ``iterations`` written back."""
+        opt = self.opt
+        lr = opt._step_lr(self.t)
+        scale = None
+        if self.clip_scale is not None:
+            g_clip = opt.global_clipnorm is not None
+            ops.grad_clip_scales(self.segs, self.n_segs, self.max_n, opt.global_clipnorm if g_clip else opt.clipnorm, self.clip_ws,
+                                 self.clip_scale, global_norm=g_clip)
+            scale = self.clip_scale
+        pen = self.penalty_acc if self.penalty_rows else None
+        ops.opt_apply(self.rule, self.segs, self.n_segs, self.max_n, lr, clip_scale=scale, penalty=pen,
+                      penalty_scale=float(self.penalty_rows) if pen is not None else 0.0)
+        opt.iterations = self.t
         self.model._raw_weight_writes = getattr(self.model, "_raw_weight_writes", 0) + 1
 
     def batch_statistics(self):

@@ -1733,6 +1733,70 @@ int dctr_opt_multi_l2(int32_t kind, const dctr_adam_seg_t* segs, int32_t n_segs,
                       float beta2, float eps, int32_t zero_grad, double* l2_penalty, float penalty_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Optimizer OBJECTS (deepctr_amd/optimizers.py): every tf.keras rule and variant in one multi-segment launch of its own; the entry
+ * points above are untouched.  g below is  clip(g_raw + 2*l2*w):  times clip_scale[segment] when given, then clamped to
+ * [-clipvalue, clipvalue] when clipvalue > 0.  State slots of a segment, in order (NULL beyond what the rule needs):
+ *   SGD       momentum == 0: w -= lr g.              else s0 = a:  a = momentum a - lr g;  w += nesterov ? momentum a - lr g : a
+ *   ADAGRAD   s0 = v (caller-filled with initial_accumulator_value):  v += g^2;  w -= lr g / (sqrt(v) + eps)
+ *   RMSPROP   s0 = ms, then mg when centered, then mom when momentum > 0 (beta2 = rho):  ms = rho ms + (1-rho) g^2;
+ *             mg = rho mg + (1-rho) g;  den = centered ? ms - mg^2 : ms;
+ *             momentum == 0: w -= lr g / (sqrt(den) + eps);   else mom = momentum mom + lr g / sqrt(den + eps);  w -= mom
+ *   ADAM      s0 = m, s1 = v, s2 = vhat when amsgrad; lr = lr0 sqrt(1-b2^t)/(1-b1^t) from the caller, as dctr_adam_multi:
+ *             m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  vhat = max(vhat, v);  w -= lr m / (sqrt(amsgrad ? vhat : v) + eps)
+ *   ADAMAX    s0 = m, s1 = u; lr = lr0 / (1-b1^t) from the caller:  m = b1 m + (1-b1) g;  u = max(b2 u, |g|);  w -= lr m / (u + eps)
+ *   ADADELTA  s0 = a, s1 = s (beta2 = rho):  a = rho a + (1-rho) g^2;  d = sqrt(s+eps)/sqrt(a+eps) g;  s = rho s + (1-rho) d^2;  w -= lr d
+ *   FTRL      s0 = n (caller-filled), s1 = z;  p = -lr_power;  gs = g + 2 l2_shrinkage w;  n' = n + g^2;
+ *             z += gs - (n'^p - n^p)/lr w;  q = n'^p/lr + 2 l2_ftrl (the caller folds beta/(2 lr) into l2_ftrl);
+ *             w = |z| > l1 ? (sign(z) l1 - z)/q : 0;  n = n'   (p == 0.5: sqrt, not pow)
+ * Non-lazy like the entry points above; `touched` as dctr_adam_seg_t documents it.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_OPT_ADAMAX = 4, DCTR_OPT_ADADELTA = 5, DCTR_OPT_FTRL = 6 };
+typedef struct {
+    float* w;
+    float* g;
+    float* s0;
+    float* s1;
+    float* s2;
+    int64_t n;
+    float l2;
+    int32_t pad_;
+    uint8_t* touched;
+} dctr_opt_seg_t;
+typedef struct {
+    int32_t kind;                 /* DCTR_OPT_*                                                           */
+    float lr;
+    float beta1;
+    float beta2;                  /* rho of RMSPROP / ADADELTA                                            */
+    float eps;
+    float momentum;               /* SGD, RMSPROP                                                         */
+    float lr_power;               /* FTRL: learning_rate_power (<= 0)                                     */
+    float l1;
+    float l2_ftrl;
+    float l2_shrinkage;
+    int32_t nesterov;
+    int32_t centered;
+    int32_t amsgrad;
+    float clipvalue;              /* <= 0: off                                                            */
+    const float* clip_scale;      /* NULL, or DEVICE float [n_segs] (dctr_grad_clip_scales)               */
+    int32_t zero_grad;
+    float penalty_scale;          /* with l2_penalty: exactly as dctr_opt_multi_l2                        */
+    double* l2_penalty;           /* NULL, or a DEVICE double accumulated into                            */
+} dctr_opt_args_t;
+/* segs: DEVICE array, 8-B aligned.  A segment whose w / g / slots are all 16-B aligned takes 16-byte accesses for its n / 4 groups and
+ * a scalar tail; any other segment (which must not carry `touched`) runs element by element.  A segment that lacks a slot its rule
+ * needs is left untouched.  DCTR_E_ENUM: kind (or lr_power > 0);  DCTR_E_NULL: args / segs;  DCTR_E_ALIGN: segs, clip_scale, l2_penalty. */
+int dctr_opt_apply(const dctr_opt_args_t* args, const dctr_opt_seg_t* segs, int32_t n_segs, int64_t max_n, void* stream);
+
+/* Keras' clipnorm / global_clipnorm as a pre-pass: clip_scale[i] = clip / max(norm, clip) with norm = ||g + 2 l2 w|| of segment i
+ * (PER_SEGMENT) or of all segments together (GLOBAL).  Sums of squares go per workgroup into the workspace in float64 and a second
+ * launch adds them in a fixed order: no float atomics, the same bits on every call.  A segment with l2 == 0 skips the groups whose
+ * `touched` byte is clear.  Everything stays on the device.  DCTR_E_NULL also answers a workspace smaller than the query's. */
+enum { DCTR_CLIP_PER_SEGMENT = 0, DCTR_CLIP_GLOBAL = 1 };
+size_t dctr_grad_clip_scales_workspace_bytes(int32_t n_segs, int64_t max_n);
+int dctr_grad_clip_scales(const dctr_opt_seg_t* segs, int32_t n_segs, int64_t max_n, int32_t mode, float clip, void* workspace,
+                          size_t workspace_bytes, float* clip_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * the plain fp32 contractions of the backward step — dW = X^T dZ, dH = dZ W^T of DNN.call
  * (deepctr/layers/core.py:189-208 under Keras autodiff), the matrix CrossNet and CrossNetMix projections
  * (layers/interaction.py:405-424, :511-549) — on the library's own v_mfma_f32_16x16x4_f32 GEMM (csrc/gemm_kernels.hip; no BLAS
