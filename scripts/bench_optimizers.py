@@ -5,7 +5,8 @@ The gradient buffers and touched maps are what one real backward pass leaves (Hi
 with zero_grad off so that every one of them meets that same state (a real step also clears the touched groups, about a tenth of
 all groups at this batch).  Per rule: device-event time of a window of launches, the median over rounds that alternate with the baseline, and
 the bytes the launch has to move — w and every state slot read and written, the touched bytes read, g read where touched — as a rate.
-Not read by bench.py.      python scripts/bench_optimizers.py [--rounds 7] [--reps 200]"""
+Then Adam / Adagrad / RMSprop / SGD on both entry points, pair by pair, without and with the l2 penalty sum.
+Not read by bench.py.      python scripts/bench_optimizers.py [--rounds 7] [--reps 200] [--own-slots]"""
 import argparse
 import os
 import statistics
@@ -42,6 +43,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--own-slots", action="store_true", help="pair table: dctr_opt_apply on state slots of its own, not on dctr_opt_multi's m / v")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -96,6 +98,51 @@ def main():
         print("%-78s %7.1f us (min %7.1f, max %7.1f)  %6.1f MB  %5.2f TB/s  x%.3f of the baseline"
               % (label, med, min(ts), max(ts), nbytes / 1e6, nbytes / med / 1e6, med / ref), flush=True)
 
+    # The four kinds both entry points have, pair by pair, without and with the l2 penalty sum fit() asks of every launch.  The old
+    # launch and the new one alternate within a round, by default on the SAME buffers (the name path's m / v): where a buffer lies
+    # moves a launch by more than the two entry points differ — the last row, the old launch against itself on a second set of m / v,
+    # says by how much.  "spread" is (max - min) / median of the old launch's own rounds; a pair holds when the new launch is slower
+    # by no more than that, and never by more than 3 % (what two machines differ by).
+    pen = torch.zeros(1, dtype=torch.float64, device=dev)
+    pairs = []
+    for kind, cls, b1, b2 in (("adam", "Adam", 0.9, 0.999), ("adagrad", "Adagrad", 0.0, 0.0), ("rmsprop", "RMSprop", 0.0, 0.9),
+                              ("sgd", "SGD", 0.0, 0.0)):
+        rule = dict(getattr(optimizers, cls)(1e-6)._rule(), clipvalue=None)
+        if args.own_slots:
+            slots = [[torch.full_like(p.w, v) for v in rule["slots"]] for p in tr.params]
+        else:
+            slots = [{2: [p.m, p.v], 1: [p.v], 0: []}[len(rule["slots"])] for p in tr.params]
+        segs = ops.make_opt_segments([(p.w, p.g, s, p.l2, p.touched) for p, s in zip(tr.params, slots)], dev)
+        keep.append((slots, segs))
+        for with_pen in (False, True):
+            pk = dict(penalty=pen, penalty_scale=float(B)) if with_pen else {}
+
+            def old(kind=kind, b1=b1, b2=b2, pk=pk):
+                ops.opt_multi(kind, tr.segs, tr.n_segs, tr.max_n, 1e-6, b1, b2, 1e-7, zero_grad=False, **pk)
+
+            def new(rule=rule, segs=segs, pk=pk):
+                ops.opt_apply(rule, segs[0], segs[1], segs[2], 1e-6, zero_grad=False, **pk)
+            pairs.append(("%s%s" % (kind, " + penalty" if with_pen else ""), len(rule["slots"]), old, new))
+    mv2 = [(torch.zeros_like(p.w), torch.zeros_like(p.w)) for p in tr.params]
+    segs2 = ops.make_adam_segments([(p.w, m, v, p.g, p.l2, p.touched) for p, (m, v) in zip(tr.params, mv2)], dev)
+    pairs.append(("adam: old vs old", 2, pairs[0][2],
+                  lambda: ops.opt_multi("adam", segs2[0], segs2[1], segs2[2], 1e-6, 0.9, 0.999, 1e-7, zero_grad=False)))
+    for _, _, old, new in pairs:
+        window(old, 3), window(new, 3)
+    pt = [([], []) for _ in pairs]
+    for _ in range(args.rounds):
+        for (_, _, old, new), (to, tn) in zip(pairs, pt):
+            to.append(window(old, args.reps))
+            tn.append(window(new, args.reps))
+    print("\nthe new launch on %s" % ("state slots of its own" if args.own_slots else "the old launch's own m / v"))
+    print("pair                  slots   dctr_opt_multi us (min, max, spread)   dctr_opt_apply us (min, max)   new / old   margin   verdict")
+    for (label, ns, _, _), (to, tn) in zip(pairs, pt):
+        mo, mn = statistics.median(to), statistics.median(tn)
+        spread = (max(to) - min(to)) / mo
+        margin = min(spread, 0.03)
+        print("%-21s %5d   %7.1f (%7.1f, %7.1f, %5.2f %%)          %7.1f (%7.1f, %7.1f)       %6.3f   %5.2f %%   %s"
+              % (label, ns, mo, min(to), max(to), 100 * spread, mn, min(tn), max(tn), mn / mo, 100 * margin,
+                 "ok" if mn <= mo * (1 + margin) else "MISS"), flush=True)
 
 if __name__ == "__main__":
     main()
