@@ -21,11 +21,18 @@ POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2
 CROSS_VECTOR, CROSS_MATRIX = 0, 1
 OPT_CODES = {"adam": 0, "adagrad": 1, "rmsprop": 2, "sgd": 3}
 ACT_LINEAR, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_DICE = 0, 1, 2, 3, 4
+ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_EXPONENTIAL, ACT_HARD_SIGMOID, ACT_SWISH, ACT_GELU = 5, 6, 7, 8, 9, 10, 11, 12
 STATUS_INDEX_OOR = 1
 STATUS_TIMEOUT = 2
 
 ACT_CODES = {None: ACT_LINEAR, "linear": ACT_LINEAR, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID, "tanh": ACT_TANH,
              "dice": ACT_DICE, "Dice": ACT_DICE}
+# The tf.keras 2.x activation names the DNN entry points take beside ACT_CODES (dctr_mlp_fwd / dctr_embed_mlp_fwd, dctr_mlp_bwd,
+# dctr_dnn_train_layer_*).  Every other op keeps ACT_CODES: to it these names are unknown.
+KERAS_ACT_CODES = {"elu": ACT_ELU, "selu": ACT_SELU, "softplus": ACT_SOFTPLUS, "softsign": ACT_SOFTSIGN, "exponential": ACT_EXPONENTIAL,
+                   "hard_sigmoid": ACT_HARD_SIGMOID, "swish": ACT_SWISH, "silu": ACT_SWISH, "gelu": ACT_GELU}
+DNN_ACT_CODES = dict(ACT_CODES, **KERAS_ACT_CODES)
+ACT_FROM_Z = (ACT_DICE, ACT_SWISH, ACT_GELU)      # act' needs the pre-activation: dctr_mlp_bwd recomputes it or takes saved_z
 POOL_CODES = {"sum": POOL_SUM, "mean": POOL_MEAN, "max": POOL_MAX}
 
 

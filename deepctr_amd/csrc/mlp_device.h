@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 #include "dctr_common.h"
+#include "act_device.h"
 #include "embed_device.h"
 #include "mfma_tile.h"
 
@@ -105,14 +106,17 @@ __device__ __forceinline__ float cross_logit(const float (&dots)[CROSS_NV], cons
 }
 
 constexpr int ACT_BWD = 64;     // internal epilogue mode of the backward chain (not a DCTR_ACT_* value of the ABI)
+constexpr int ACT_EXT = 65;     // internal epilogue mode of the forward: DCTR_ACT_ELU .. DCTR_ACT_GELU, switched on p.activation at run time
 
-// act'(h) from the activation's OUTPUT h (relu, sigmoid, tanh, linear — the forms dctr_mlp_bwd's row kernels use)
+// act'(h) from the activation's OUTPUT h (relu, sigmoid, tanh, linear — the forms dctr_mlp_bwd's row kernels use — and the six of
+// act_device.h that have such a form: elu, selu, softplus, softsign, exponential, hard_sigmoid)
 __device__ __forceinline__ float act_deriv_from_output(int act, float h) {
     switch (act) {
         case DCTR_ACT_RELU: return h > 0.f ? 1.f : 0.f;
         case DCTR_ACT_SIGMOID: return h * (1.f - h);
         case DCTR_ACT_TANH: return 1.f - h * h;
-        default: return 1.f;
+        case DCTR_ACT_LINEAR: return 1.f;
+        default: return dctr_act::deriv_from_output(act, h);
     }
 }
 
@@ -136,6 +140,25 @@ __device__ __forceinline__ float act_t(float v, float al, float mu, float var, f
     else if constexpr (ACT == DCTR_ACT_TANH) return tanhf(v);
     else return v;
 }
+
+// The layers' epilogue by activation.  EXT == false: the kernels of relu / sigmoid / tanh / Dice / linear with one epilogue instantiation
+// each — the code they had before the tf.keras names of act_device.h came.  EXT == true: the kernel instantiation that serves
+// DCTR_ACT_ELU .. DCTR_ACT_GELU with ONE epilogue (ACT_EXT) that switches on the code at run time; the host picks the kernel.
+// M(ACT) is the caller's statement for one epilogue instantiation.
+#define DCTR_BY_ACT(EXT, act, M)                                  \
+    do {                                                          \
+        if constexpr (EXT) {                                      \
+            M(ACT_EXT);                                           \
+        } else {                                                  \
+            switch (act) {                                        \
+                case DCTR_ACT_RELU: M(DCTR_ACT_RELU); break;      \
+                case DCTR_ACT_SIGMOID: M(DCTR_ACT_SIGMOID); break; \
+                case DCTR_ACT_TANH: M(DCTR_ACT_TANH); break;      \
+                case DCTR_ACT_DICE: M(DCTR_ACT_DICE); break;      \
+                default: M(DCTR_ACT_LINEAR); break;               \
+            }                                                     \
+        }                                                         \
+    } while (0)
 
 // B fragments of 8 consecutive k-steps of one wave-tile.  MFMA slot g = lane>>4 takes row k = 4*t + g, so the four
 // slots (x the waves' column slices) read 4 ADJACENT weight rows = one contiguous 4 KB; the A tile in LDS is stored
@@ -293,7 +316,9 @@ __device__ __forceinline__ void tile_epilogue(const MlpParams& p, int l, float* 
                 for (int r = 0; r < 4; ++r) {
                     float z = acc[rt][c][r] + bv;
                     if (bn) z = fmaf(z, bsc, bsh);              // keras: x * inv + (beta - mean * inv)
-                    const float v = act_t<ACT>(z, al, mu, var, p.dice_eps);
+                    float v;
+                    if constexpr (ACT == ACT_EXT) v = dctr_act::value(p.activation, z);
+                    else v = act_t<ACT>(z, al, mu, var, p.dice_eps);
                     out[(rt * 16 + 4 * g + r) * p.lda + lds_pos(n, KQn)] = v;
                     if (sv != nullptr) {
                         const int64_t b = row0 + rt * 16 + 4 * g + r;
@@ -700,7 +725,7 @@ __device__ __forceinline__ void zero_acc(dctr::f32x4 (&acc)[RT][TPW]) {
         for (int c = 0; c < TPW; ++c) acc[rt][c] = dctr::f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-template <int RT>
+template <int RT, bool EXT = false>
 __global__ __launch_bounds__(NTHR, RT <= 2 ? 4 : 2) void mlp_kernel(MlpParams p, FusedGather fg) {
     constexpr int ROWS = 16 * RT;
     constexpr int SD = StageDepth<RT>::value;
@@ -786,13 +811,7 @@ __global__ __launch_bounds__(NTHR, RT <= 2 ? 4 : 2) void mlp_kernel(MlpParams p,
         if (wide) tile_epilogue<2, ACT, RT>(p, 0, buf1, N, n_base, acc2);          \
         else tile_epilogue<1, ACT, RT>(p, 0, buf1, N, n_base, acc1);               \
     } while (0)
-            switch (p.activation) {
-                case DCTR_ACT_RELU: DCTR_EPI(DCTR_ACT_RELU); break;
-                case DCTR_ACT_SIGMOID: DCTR_EPI(DCTR_ACT_SIGMOID); break;
-                case DCTR_ACT_TANH: DCTR_EPI(DCTR_ACT_TANH); break;
-                case DCTR_ACT_DICE: DCTR_EPI(DCTR_ACT_DICE); break;
-                default: DCTR_EPI(DCTR_ACT_LINEAR); break;
-            }
+            DCTR_BY_ACT(EXT, p.activation, DCTR_EPI);
 #undef DCTR_EPI
         }
         zero_k_padding<RT>(p, buf1, N);
@@ -805,13 +824,9 @@ __global__ __launch_bounds__(NTHR, RT <= 2 ? 4 : 2) void mlp_kernel(MlpParams p,
 
     for (; l < p.n_layers; ++l) {
         const int N = p.units[l];
-        switch (p.activation) {
-            case DCTR_ACT_RELU: layer_dispatch<DCTR_ACT_RELU, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_SIGMOID: layer_dispatch<DCTR_ACT_SIGMOID, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_TANH: layer_dispatch<DCTR_ACT_TANH, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_DICE: layer_dispatch<DCTR_ACT_DICE, RT>(p, l, in, out, K, N); break;
-            default: layer_dispatch<DCTR_ACT_LINEAR, RT>(p, l, in, out, K, N); break;
-        }
+#define DCTR_LAYER(ACT) layer_dispatch<ACT, RT>(p, l, in, out, K, N)
+        DCTR_BY_ACT(EXT, p.activation, DCTR_LAYER);
+#undef DCTR_LAYER
         __syncthreads();
         float* t = in;
         in = out;
@@ -1041,7 +1056,8 @@ __device__ __forceinline__ void layer_dispatch_dma(const MlpParams& p, int l, co
     else layer_tiles_dma<1, ACT>(p, l, in, out, K, N, wring, prefetched);
 }
 
-template <int UNUSED = 0>      // (a template so that the header may be included by several translation units; instantiated in mlp_kernels_ring.hip)
+template <int EXT = 0>      // (a template so that the header may be included by several translation units; instantiated in
+                            //  mlp_kernels_ring.hip: <0> relu / sigmoid / tanh / Dice / linear, <1> DCTR_ACT_ELU .. DCTR_ACT_GELU — DCTR_BY_ACT)
 __global__ __launch_bounds__(NTHR, 1) void mlp_ring_kernel(MlpParams p, FusedGather fg, int ring_off) {
     constexpr int RT = 1, ROWS = 16;
     using dctr::f32x4;
@@ -1087,13 +1103,9 @@ __global__ __launch_bounds__(NTHR, 1) void mlp_ring_kernel(MlpParams p, FusedGat
     }
     for (int l = 0; l < p.n_layers; ++l) {
         const int N = p.units[l];
-        switch (p.activation) {
-            case DCTR_ACT_RELU: layer_dispatch_dma<DCTR_ACT_RELU>(p, l, in, out, K, N, wring, l > 0); break;
-            case DCTR_ACT_SIGMOID: layer_dispatch_dma<DCTR_ACT_SIGMOID>(p, l, in, out, K, N, wring, l > 0); break;
-            case DCTR_ACT_TANH: layer_dispatch_dma<DCTR_ACT_TANH>(p, l, in, out, K, N, wring, l > 0); break;
-            case DCTR_ACT_DICE: layer_dispatch_dma<DCTR_ACT_DICE>(p, l, in, out, K, N, wring, l > 0); break;
-            default: layer_dispatch_dma<DCTR_ACT_LINEAR>(p, l, in, out, K, N, wring, l > 0); break;
-        }
+#define DCTR_LAYER(ACT) layer_dispatch_dma<ACT>(p, l, in, out, K, N, wring, l > 0)
+        DCTR_BY_ACT(EXT != 0, p.activation, DCTR_LAYER);
+#undef DCTR_LAYER
         __syncthreads();
         float* t = in;
         in = out;

@@ -89,7 +89,7 @@ static int mlp_launch(const dctr_mlp_args_t* a, const dctr_gather_fm_args_t* ga,
     if (a->batch == 0) return DCTR_OK;
     DCTR_REQUIRE((ga != nullptr || a->x) && a->y, DCTR_E_NULL, "mlp_fwd: null x / y");
     DCTR_REQUIRE(a->n_layers == 0 || (a->units && a->kernels && a->biases), DCTR_E_NULL, "mlp_fwd: null layer arrays");
-    DCTR_REQUIRE(a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_DICE, DCTR_E_ENUM, "mlp_fwd: activation %d",
+    DCTR_REQUIRE(a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_GELU, DCTR_E_ENUM, "mlp_fwd: activation %d",
                  a->activation);
     DCTR_REQUIRE(!a->has_head || a->head_w, DCTR_E_NULL, "mlp_fwd: has_head without head_w");
     if (a->activation == DCTR_ACT_DICE && a->n_layers > 0)

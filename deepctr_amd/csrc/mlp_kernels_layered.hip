@@ -3,7 +3,8 @@
 // i.e. <= 1,216 units); the reference's DNN takes any `hidden_units`.  Here a layer is
 //     Z = X W          dctr_gemm::sgemm (gemm_kernels.hip: f32 MFMA, any m / n / k), rows in chunks that fit the caller's workspace
 //     H = act(bn(Z + b))   one elementwise launch in place (BatchNormalization inference form, relu / sigmoid / tanh / linear / Dice
-//                          with the stored statistics: activation.py:59-64), optionally copied to save_acts[l]
+//                          with the stored statistics: activation.py:59-64, or a tf.keras name of act_device.h), optionally copied to
+//                          save_acts[l]
 // and the head (Dense(1, no bias) + add[] + global bias + PredictionLayer) goes back through dctr_mlp_fwd with no hidden layer, whose
 // 16-row workgroups walk an input row of any width in K chunks (mlp_kernels_wide.hip).  Same arithmetic as the one-launch kernels
 // (exact fp32 products, fp32 accumulation); the summation order over k is the GEMM's.
@@ -44,7 +45,8 @@ __global__ __launch_bounds__(256) void layer_epilogue_kernel(EpiParams p) {
             case DCTR_ACT_SIGMOID: v = dctr::sigmoidf_(z); break;
             case DCTR_ACT_TANH: v = tanhf(z); break;
             case DCTR_ACT_DICE: v = dctr::dice_act(z, p.dice_alpha[c], p.dice_mean[c], p.dice_var[c], p.dice_eps); break;
-            default: v = z; break;
+            case DCTR_ACT_LINEAR: v = z; break;
+            default: v = dctr_act::value(p.act, z); break;        // DCTR_ACT_ELU .. DCTR_ACT_GELU (act_device.h)
         }
         p.z[r * p.ldz + c] = v;
         if (p.save != nullptr) p.save[i] = v;

@@ -21,6 +21,7 @@ __device__ __forceinline__ void wide_epilogue(const MlpParams& p, float* out, in
     }
 }
 
+template <bool EXT>      // false: relu / sigmoid / tanh / Dice / linear; true: DCTR_ACT_ELU .. DCTR_ACT_GELU (mlp_device.h: DCTR_BY_ACT)
 __global__ __launch_bounds__(NTHR, 1) void mlp_wide_kernel(MlpParams p, int kc) {
     constexpr int RT = 1, ROWS = 16, SD = StageDepth<1>::value;
     using dctr::f32x4;
@@ -54,13 +55,9 @@ __global__ __launch_bounds__(NTHR, 1) void mlp_wide_kernel(MlpParams p, int kc) 
                 }
                 __syncthreads();                              // buf0 is rebuilt by the next chunk
             }
-            switch (p.activation) {
-                case DCTR_ACT_RELU: wide_epilogue<DCTR_ACT_RELU>(p, buf1, N, n_tiles, t0, wave, acc); break;
-                case DCTR_ACT_SIGMOID: wide_epilogue<DCTR_ACT_SIGMOID>(p, buf1, N, n_tiles, t0, wave, acc); break;
-                case DCTR_ACT_TANH: wide_epilogue<DCTR_ACT_TANH>(p, buf1, N, n_tiles, t0, wave, acc); break;
-                case DCTR_ACT_DICE: wide_epilogue<DCTR_ACT_DICE>(p, buf1, N, n_tiles, t0, wave, acc); break;
-                default: wide_epilogue<DCTR_ACT_LINEAR>(p, buf1, N, n_tiles, t0, wave, acc); break;
-            }
+#define DCTR_EPI(ACT) wide_epilogue<ACT>(p, buf1, N, n_tiles, t0, wave, acc)
+            DCTR_BY_ACT(EXT, p.activation, DCTR_EPI);
+#undef DCTR_EPI
         }
         zero_k_padding<RT>(p, buf1, N);
         __syncthreads();
@@ -83,13 +80,9 @@ __global__ __launch_bounds__(NTHR, 1) void mlp_wide_kernel(MlpParams p, int kc) 
     }
     for (; l < p.n_layers; ++l) {
         const int N = p.units[l];
-        switch (p.activation) {
-            case DCTR_ACT_RELU: layer_dispatch<DCTR_ACT_RELU, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_SIGMOID: layer_dispatch<DCTR_ACT_SIGMOID, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_TANH: layer_dispatch<DCTR_ACT_TANH, RT>(p, l, in, out, K, N); break;
-            case DCTR_ACT_DICE: layer_dispatch<DCTR_ACT_DICE, RT>(p, l, in, out, K, N); break;
-            default: layer_dispatch<DCTR_ACT_LINEAR, RT>(p, l, in, out, K, N); break;
-        }
+#define DCTR_LAYER(ACT) layer_dispatch<ACT, RT>(p, l, in, out, K, N)
+        DCTR_BY_ACT(EXT, p.activation, DCTR_LAYER);
+#undef DCTR_LAYER
         __syncthreads();
         float* t = in;
         in = out;
@@ -127,10 +120,12 @@ __global__ __launch_bounds__(NTHR, 1) void mlp_wide_kernel(MlpParams p, int kc) 
 
 // kc: the chunk width (a multiple of 64); p.lda = pad64(max(kc, every layer width)) + 4
 int launch_wide(const MlpParams& p, int kc, unsigned blocks, size_t lds, hipStream_t stream) {
-    static thread_local size_t granted[DCTR_MAX_DEVICES] = {0};
-    hipError_t e = dctr_grant_lds((const void*)mlp_wide_kernel, lds, granted);
+    static thread_local size_t granted[2][DCTR_MAX_DEVICES] = {{0}, {0}};
+    const bool ext = dctr_act::is_extended(p.activation);
+    hipError_t e = dctr_grant_lds(ext ? (const void*)mlp_wide_kernel<true> : (const void*)mlp_wide_kernel<false>, lds, granted[ext ? 1 : 0]);
     DCTR_REQUIRE(e == hipSuccess, (int)e, "mlp_fwd(wide): cannot raise dynamic LDS to %zu B: %s", lds, hipGetErrorString(e));
-    DCTR_LAUNCH(mlp_wide_kernel, dim3(blocks), dim3(NTHR), lds, stream, p, kc);
+    if (ext) DCTR_LAUNCH(mlp_wide_kernel<true>, dim3(blocks), dim3(NTHR), lds, stream, p, kc);
+    else DCTR_LAUNCH(mlp_wide_kernel<false>, dim3(blocks), dim3(NTHR), lds, stream, p, kc);
     return dctr_launch_status("dctr_mlp_fwd(wide)");
 }
 

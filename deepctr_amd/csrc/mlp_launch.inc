@@ -9,12 +9,15 @@ namespace dctr_mlp {
 
 int DCTR_CAT(launch_rt, DCTR_MLP_RT)(const MlpParams& p, const FusedGather& fg, unsigned blocks, size_t lds,
                                      hipStream_t stream) {
+    // DCTR_ACT_ELU .. DCTR_ACT_GELU: the instantiation whose epilogue switches on the code (mlp_device.h: DCTR_BY_ACT)
+    const bool ext = dctr_act::is_extended(p.activation);
+    const void* fn = ext ? (const void*)mlp_kernel<DCTR_MLP_RT, true> : (const void*)mlp_kernel<DCTR_MLP_RT>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)mlp_kernel<DCTR_MLP_RT>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         DCTR_REQUIRE(e == hipSuccess, (int)e, "mlp_fwd: cannot raise dynamic LDS to %zu B: %s", lds, hipGetErrorString(e));
     }
-    DCTR_LAUNCH(mlp_kernel<DCTR_MLP_RT>, dim3(blocks), dim3(NTHR), lds, stream, p, fg);
+    if (ext) DCTR_LAUNCH((mlp_kernel<DCTR_MLP_RT, true>), dim3(blocks), dim3(NTHR), lds, stream, p, fg);
+    else DCTR_LAUNCH(mlp_kernel<DCTR_MLP_RT>, dim3(blocks), dim3(NTHR), lds, stream, p, fg);
     return dctr_launch_status("dctr_mlp_fwd");
 }
 

@@ -5,6 +5,7 @@
 // through the launcher next to it.
 #pragma once
 #include "dctr_common.h"
+#include "act_device.h"
 
 constexpr int BWD_ROWS = 16;     // batch rows per iteration of the generic Dice passes (the 16-B forms take over when N % 4 == 0)
 constexpr int COLSUM_MAX_WG = 64;      // workgroups of a pass that ends in one atomic per column and workgroup
@@ -51,6 +52,9 @@ __device__ __forceinline__ float4 act_grad4(float4 d, float4 hv, int act) {
         d.x *= hv.x * (1.f - hv.x); d.y *= hv.y * (1.f - hv.y); d.z *= hv.z * (1.f - hv.z); d.w *= hv.w * (1.f - hv.w);
     } else if (act == DCTR_ACT_TANH) {
         d.x *= 1.f - hv.x * hv.x; d.y *= 1.f - hv.y * hv.y; d.z *= 1.f - hv.z * hv.z; d.w *= 1.f - hv.w * hv.w;
+    } else if (dctr_act::is_extended(act)) {      // elu, selu, softplus, softsign, exponential, hard_sigmoid: act' from the output
+        d.x *= dctr_act::deriv_from_output(act, hv.x); d.y *= dctr_act::deriv_from_output(act, hv.y);
+        d.z *= dctr_act::deriv_from_output(act, hv.z); d.w *= dctr_act::deriv_from_output(act, hv.w);
     }
     return d;
 }
@@ -76,13 +80,13 @@ __device__ __forceinline__ float act_value(float y, int act) {
     if (act == DCTR_ACT_RELU) return fmaxf(y, 0.f);
     if (act == DCTR_ACT_SIGMOID) return 1.f / (1.f + expf(-y));
     if (act == DCTR_ACT_TANH) return tanhf(y);
-    return y;
+    return dctr_act::value(act, y);             // DCTR_ACT_ELU .. DCTR_ACT_GELU; anything else: y
 }
 __device__ __forceinline__ float act_deriv(float y, int act) {
     if (act == DCTR_ACT_RELU) return y > 0.f ? 1.f : 0.f;
     if (act == DCTR_ACT_SIGMOID) { const float s = 1.f / (1.f + expf(-y)); return s * (1.f - s); }
     if (act == DCTR_ACT_TANH) { const float t = tanhf(y); return 1.f - t * t; }
-    return 1.f;
+    return dctr_act::deriv_from_z(act, y);      // DCTR_ACT_ELU .. DCTR_ACT_GELU; anything else: 1
 }
 
 namespace dctr_train {   // defined in train_kernels.hip, next to their kernels

@@ -353,10 +353,20 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
         if (act == DCTR_ACT_RELU) d = hv > 0.f ? d : 0.f;
         else if (act == DCTR_ACT_SIGMOID) d *= hv * (1.f - hv);
         else if (act == DCTR_ACT_TANH) d *= 1.f - hv * hv;
+        else if (dctr_act::is_extended(act)) d *= dctr_act::deriv_from_output(act, hv);
         dz[b * dz_stride + n] = d;
         acc = fmaf(dl, hv, acc);
     }
     unsafeAtomicAdd(d_head_w + n, acc);
+}
+
+// in place: dh[i] *= act'(z[i] + bias[i % N]) with act' taken from the PRE-activation (swish / gelu: dctr_mlp_bwd's layer-by-layer form)
+__global__ __launch_bounds__(256) void act_bwd_from_z_kernel(float* __restrict__ dh, const float* __restrict__ z,
+                                                             const float* __restrict__ bias, int64_t total, int N, int act) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const float zv = z[i] + (bias != nullptr ? bias[(int)(i % N)] : 0.f);
+        dh[i] *= dctr_act::deriv_from_z(act, zv);
+    }
 }
 
 // in place: dh[b, n] *= act'(h[b, n]);  db[n] += sum_b dz[b, n]   (also used with h == NULL: only the column sums)
@@ -373,6 +383,7 @@ __global__ __launch_bounds__(256) void act_bwd_colsum_kernel(float* __restrict__
             if (act == DCTR_ACT_RELU) d = hv > 0.f ? d : 0.f;
             else if (act == DCTR_ACT_SIGMOID) d *= hv * (1.f - hv);
             else if (act == DCTR_ACT_TANH) d *= 1.f - hv * hv;
+            else if (dctr_act::is_extended(act)) d *= dctr_act::deriv_from_output(act, hv);
             dh[b * N + n] = d;
         }
         acc += d;
@@ -1327,7 +1338,8 @@ static int train_layer_check(const dctr_dnn_train_layer_t* a, const char* what) 
     DCTR_REQUIRE(a != nullptr, DCTR_E_NULL, "%s: null args", what);
     DCTR_REQUIRE(a->rows >= 0 && a->n >= 1 && a->z_stride >= a->n, DCTR_E_DIM, "%s: bad sizes (rows=%lld n=%d z_stride=%lld)", what,
                  (long long)a->rows, a->n, (long long)a->z_stride);
-    DCTR_REQUIRE(a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_TANH, DCTR_E_ENUM, "%s: activation %d", what, a->activation);
+    DCTR_REQUIRE((a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_TANH) || dctr_act::is_extended(a->activation), DCTR_E_ENUM,
+                 "%s: activation %d", what, a->activation);
     DCTR_REQUIRE(a->dropout_rate >= 0.f && a->dropout_rate < 1.f, DCTR_E_DIM, "%s: dropout_rate %g outside [0, 1)", what, (double)a->dropout_rate);
     DCTR_REQUIRE(a->z != nullptr, DCTR_E_NULL, "%s: null z", what);
     DCTR_REQUIRE(!a->use_bn || (a->bn_batch_mean != nullptr && a->bn_batch_var != nullptr), DCTR_E_NULL,
@@ -1511,7 +1523,7 @@ extern "C" int dctr_embed_pool_bwd(const dctr_pool_bwd_args_t* a, void* stream) 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// dctr_mlp_bwd, chained form (relu / linear / sigmoid / tanh): head -> dZ_{L-1};  W_l^T of every layer (one launch);  the backward
+// dctr_mlp_bwd, chained form (relu / linear / sigmoid / tanh; elu / selu / softplus / softsign / exponential / hard_sigmoid): head -> dZ_{L-1};  W_l^T of every layer (one launch);  the backward
 // chain (mlp_bwd_kernels.hip: every dZ_l and dX in ONE launch);  dW_l (+ d_bias_l as one more output row) of every layer as row
 // slices in ONE grouped GEMM launch;  one launch that sums the slices into the gradient buffers.  Five launches per step where the
 // layer-by-layer form below took 4 L + 1 (a 3-layer DNN at B = 4096: ~60 us against ~210).
@@ -1586,8 +1598,10 @@ static bool chain_disabled() {
     static const bool v = [] { const char* e = dctr_lab_env("DCTR_MLP_BWD_CHAIN"); return e != nullptr && atoi(e) == 0; }();
     return v;
 }
+// act' needs the pre-activation: Dice, swish, gelu — the layer-by-layer form with saved_z or the recompute GEMM
+static bool mlp_bwd_from_z(int act) { return act == DCTR_ACT_DICE || dctr_act::needs_z(act); }
 static bool mlp_bwd_chained(const dctr_mlp_bwd_args_t* a) {
-    return !chain_disabled() && a->activation != DCTR_ACT_DICE && a->n_layers <= 8 && dctr_mlp::bwd_chain_fits(a->in_dim, a->n_layers, a->units);
+    return !chain_disabled() && !mlp_bwd_from_z(a->activation) && a->n_layers <= 8 && dctr_mlp::bwd_chain_fits(a->in_dim, a->n_layers, a->units);
 }
 // workspace of the chained form, in floats: dZ_l [B, units[l]] | W_l^T | dW slices [(K_l + 1) units[l]] x slices   (each 4-float aligned)
 static size_t mlp_bwd_chain_floats(const dctr_mlp_bwd_args_t* a) {
@@ -1603,9 +1617,9 @@ static size_t mlp_bwd_chain_floats(const dctr_mlp_bwd_args_t* a) {
 }
 
 static size_t mlp_bwd_main_floats(const dctr_mlp_bwd_args_t* a, int w) {
-    // two ping-pong buffers [B, widest layer]; Dice needs a third for the recomputed pre-activations
-    // ... and, with batch statistics, 2 x widest for the two column sums of the BatchNormalization backward
-    return ((size_t)(a->activation == DCTR_ACT_DICE ? 3 : 2) * a->batch * w + (a->activation == DCTR_ACT_DICE ? 2 * (size_t)w : 0) + 3) &
+    // two ping-pong buffers [B, widest layer]; Dice / swish / gelu need a third for the recomputed pre-activations
+    // ... and Dice, with batch statistics, 2 x widest for the two column sums of the BatchNormalization backward
+    return ((size_t)(mlp_bwd_from_z(a->activation) ? 3 : 2) * a->batch * w + (a->activation == DCTR_ACT_DICE ? 2 * (size_t)w : 0) + 3) &
            ~(size_t)3;
 }
 
@@ -1638,8 +1652,9 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
                      (a->head_w == nullptr && a->d_out != nullptr && a->d_out_stride >= a->units[a->n_layers - 1]),
                  DCTR_E_NULL, "mlp_bwd: needs either (head_w, dlogit, d_head_w) or d_out");
     const bool dice = a->activation == DCTR_ACT_DICE;
-    DCTR_REQUIRE((a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_TANH) || dice, DCTR_E_UNSUPPORTED,
-                 "mlp_bwd: activation %d has no backward (linear, relu, sigmoid, tanh, dice)", a->activation);
+    const bool zact = dctr_act::needs_z(a->activation);        // swish / gelu: act' from the pre-activations, as Dice
+    DCTR_REQUIRE(a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_GELU, DCTR_E_UNSUPPORTED,
+                 "mlp_bwd: activation %d has no backward (DCTR_ACT_LINEAR .. DCTR_ACT_GELU)", a->activation);
     DCTR_REQUIRE(!dice || (a->dice_alpha && a->dice_mean && a->dice_var), DCTR_E_NULL, "mlp_bwd: dice needs alpha / mean / var");
     DCTR_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= dctr_mlp_bwd_workspace_bytes(a), DCTR_E_NULL,
                  "mlp_bwd: needs a workspace of dctr_mlp_bwd_workspace_bytes() bytes");
@@ -1791,21 +1806,40 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
                                a->dice_eps, a->batch, N, dal);
         return 0;
     };
+    // swish / gelu: dH of layer l (in `buf`, in place) -> dZ = dH .* act'(z), z from saved_z or recomputed as for Dice
+    auto zact_bwd = [&](int l, float* buf) -> int {
+        const int N = a->units[l], K = l == 0 ? a->in_dim : a->units[l - 1];
+        const float* zsrc = bufZ;
+        const float* bl = a->biases != nullptr ? a->biases[l] : nullptr;
+        if (a->saved_z != nullptr && a->saved_z[l] != nullptr) {
+            zsrc = a->saved_z[l];
+            bl = nullptr;
+        } else {
+            int rs = dctr_gemm::sgemm(st, dctr_gemm::OP_N, dctr_gemm::OP_N, N, B, K, a->kernels[l], N, l == 0 ? a->x : a->acts[l - 1],
+                                      l == 0 ? (int)a->x_stride : K, 0.f, bufZ, N);
+            if (rs != 0) return (int)rs;
+        }
+        const int64_t g = dctr_ceil_div(a->batch * N, (int64_t)256);
+        hipLaunchKernelGGL(act_bwd_from_z_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, st, buf, zsrc, bl, a->batch * N, N,
+                           (int)a->activation);
+        return 0;
+    };
+    const bool from_z = dice || zact;
     // head: dZ_last = dlogit (x) head_w .* act'(h_last);  d_head_w = h_last^T dlogit
     const int NL = a->units[L - 1];
     if (a->head_w != nullptr) {
         dctr_train::launch_head_bwd(st, a->dlogit, a->head_w, a->acts[L - 1], (int64_t)NL, a->batch, NL,
-                                    dice ? (int)DCTR_ACT_LINEAR : (int)a->activation, bufA, (int64_t)NL, a->d_head_w);
+                                    from_z ? (int)DCTR_ACT_LINEAR : (int)a->activation, bufA, (int64_t)NL, a->d_head_w);
     } else {
         // headless (the DNN branch of DCN): the caller hands d(loss)/d(h_last); dZ_last = d_out .* act'(h_last)
         hipError_t ce = hipMemcpy2DAsync(bufA, (size_t)NL * sizeof(float), a->d_out, (size_t)a->d_out_stride * sizeof(float),
                                          (size_t)NL * sizeof(float), (size_t)a->batch, hipMemcpyDeviceToDevice, st);
         DCTR_REQUIRE(ce == hipSuccess, (int)ce, "mlp_bwd: copy of d_out failed: %s", hipGetErrorString(ce));
-        if (a->activation != DCTR_ACT_LINEAR && !dice)
+        if (a->activation != DCTR_ACT_LINEAR && !from_z)
             dctr_train::launch_act_bwd_colsum(st, bufA, a->acts[L - 1], a->batch, NL, (int)a->activation, (float*)nullptr);
     }
-    if (dice) {
-        const int rc = dice_bwd(L - 1, bufA);
+    if (from_z) {
+        const int rc = dice ? dice_bwd(L - 1, bufA) : zact_bwd(L - 1, bufA);
         DCTR_REQUIRE(rc == 0, DCTR_E_UNSUPPORTED, "mlp_bwd: sgemm(Z) failed (%d)", rc);
     }
     float* dz = bufA;
@@ -1853,8 +1887,8 @@ extern "C" int dctr_mlp_bwd(const dctr_mlp_bwd_args_t* a, void* stream) {
         }
         if (!to_dx) {
             // dZ_prev = dH_prev .* act'(h_prev)
-            if (dice) {
-                const int rc = dice_bwd(l - 1, other);
+            if (from_z) {
+                const int rc = dice ? dice_bwd(l - 1, other) : zact_bwd(l - 1, other);
                 DCTR_REQUIRE(rc == 0, DCTR_E_UNSUPPORTED, "mlp_bwd: sgemm(Z) failed (%d)", rc);
             } else if (a->activation != DCTR_ACT_LINEAR) {
                 dctr_train::launch_act_bwd_colsum(st, other, a->acts[l - 1], a->batch, K, (int)a->activation, (float*)nullptr);

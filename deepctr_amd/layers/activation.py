@@ -1,5 +1,10 @@
 """``Dice`` (reference deepctr/layers/activation.py:28-72) and ``activation_layer`` (:75-85), inference form:
-BatchNormalization(center=False, scale=False, epsilon=1e-9) uses its moving statistics."""
+BatchNormalization(center=False, scale=False, epsilon=1e-9) uses its moving statistics.
+
+The reference hands any other string to ``tf.keras.layers.Activation(name)`` (:75-85; layers/core.py:176-184).  Of tf.keras 2.x's
+names this build runs relu / sigmoid / tanh / linear and ``KERAS_ACTIVATIONS`` — elu (alpha 1), selu, softplus, softsign, exponential,
+hard_sigmoid (clip(0.2 z + 0.5, 0, 1), the Keras 2 form), swish (alias silu) and gelu (approximate=False) — in the DNN's kernels
+(csrc/act_device.h); softmax and the names only Keras 3 knows raise the ValueError they always did."""
 import torch
 
 from ..initializers import Ones, Zeros
@@ -43,7 +48,19 @@ class Dice(Layer):
         return dict(list(base.items()) + list(config.items()))
 
 
-SUPPORTED = ("relu", "sigmoid", "tanh", "linear", "dice", "Dice", None)
+# what every kernel that reads an activation code takes (EDCN's tower, the multi-task level / tower kernels, DIN's attention unit)
+BASE_ACTIVATIONS = ("relu", "sigmoid", "tanh", "linear", "dice", "Dice", None)
+# the tf.keras 2.x names the DNN kernels take beside them (dctr_mlp_fwd / dctr_mlp_bwd / dctr_dnn_train_layer_*)
+KERAS_ACTIVATIONS = ("elu", "selu", "softplus", "softsign", "exponential", "hard_sigmoid", "swish", "silu", "gelu")
+SUPPORTED = BASE_ACTIVATIONS + KERAS_ACTIVATIONS
+
+
+def require_base_activation(who, activation):
+    """For the callers of ``DNN`` whose own kernels read the activation code and take ``BASE_ACTIVATIONS`` only: refuse the other
+    names at construction, as ``DNN`` itself refuses a name it does not know."""
+    if (isinstance(activation, str) or activation is None) and activation not in BASE_ACTIVATIONS:
+        raise ValueError("Invalid activation,found %s.%s runs relu / sigmoid / tanh / linear / dice (its kernels do not take the "
+                         "other tf.keras names a plain DNN does)." % (activation, who))
 
 
 def activation_layer(activation):

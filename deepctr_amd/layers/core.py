@@ -6,7 +6,7 @@ import torch
 
 from .. import ops
 from ..initializers import GlorotNormal, Ones, Zeros
-from .activation import SUPPORTED, Dice
+from .activation import SUPPORTED, Dice, require_base_activation
 from .base import Layer
 
 
@@ -211,6 +211,7 @@ class LocalActivationUnit(Layer):
         self.seed = seed
         super(LocalActivationUnit, self).__init__(**kwargs)
         self.supports_masking = True
+        require_base_activation("LocalActivationUnit", activation)        # (the attention kernels, dctr_din_*, read the code themselves)
 
     def build(self, input_shape):
         if not isinstance(input_shape, list) or len(input_shape) != 2:

@@ -10,6 +10,7 @@ import torch
 
 from .. import ops
 from ..initializers import Constant, GlorotUniform, Orthogonal, TruncatedNormal
+from .activation import require_base_activation
 from .base import Layer, next_auto_name
 from .core import LocalActivationUnit
 from .normalization import LayerNormalization
@@ -112,6 +113,7 @@ class AttentionSequencePoolingLayer(Layer):
         self.return_score = return_score
         super(AttentionSequencePoolingLayer, self).__init__(**kwargs)
         self.supports_masking = supports_masking
+        require_base_activation("AttentionSequencePoolingLayer", att_activation)     # (as its LocalActivationUnit)
 
     def build(self, input_shape):
         if not self.supports_masking:

@@ -6,6 +6,7 @@ from ..engine import Model
 from ..feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
 from ..initializers import Zeros
 from ..inputs import create_embedding_matrix
+from ..layers.activation import KERAS_ACTIVATIONS
 from ..layers.utils import Linear
 from .. import training as tops
 
@@ -98,7 +99,8 @@ class FeatureModel(Model):
         # (HipTrainer._dnn_forward), but not together
         if dnn.activation in ("dice", "Dice"):
             return not (getattr(dnn, "dropout_rate", 0) or getattr(dnn, "bn_layers", None) or dnn.dice_params() is None)
-        return dnn.activation in ("relu", "linear", "sigmoid", "tanh")
+        # (the tf.keras names of layers/activation.py:KERAS_ACTIVATIONS: dctr_mlp_bwd and dctr_dnn_train_layer_* take them all)
+        return dnn.activation in ("relu", "linear", "sigmoid", "tanh") + KERAS_ACTIVATIONS
 
     def _hip_add(self, ws):
         """The logits the step's head adds: linear (the linear-only features' already summed into it), FM, further FM groups."""

@@ -11,6 +11,7 @@ from .. import ops
 from .. import training as tops
 from ..engine import EmbeddingStage
 from ..feature_column import DenseFeat
+from ..layers.activation import require_base_activation
 from ..layers.base import name_scope
 from ..layers.core import DNN, Dense, PredictionLayer, RegulationModule
 from ..layers.interaction import BridgeModule, CrossNet
@@ -24,6 +25,7 @@ class _EDCN(FeatureModel):
             raise ValueError("Cross layer num must > 0")
         if bridge_type not in BridgeModule.TYPES:
             raise ValueError("bridge_type must be one of %s, got %r" % (", ".join(BridgeModule.TYPES), bridge_type))
+        require_base_activation("EDCN", dnn_activation)          # (the fused tower, dctr_edcn_fwd, reads the activation code itself)
         if any(isinstance(fc, DenseFeat) for fc in dnn_feature_columns):
             raise ValueError("DenseFeat is not supported in dnn_feature_columns")      # inputs.py:224-225 (support_dense=False)
         known = set(fc.name for fc in dnn_feature_columns)

@@ -6,6 +6,7 @@ import torch
 from ... import ops
 from ... import training as tops
 from ...engine import EmbeddingStage, Staged, on_model_device
+from ...layers.activation import require_base_activation
 from ...layers.core import DNN, Dense, PredictionLayer
 from .._common import FeatureModel
 
@@ -56,6 +57,8 @@ class MultiTaskModel(FeatureModel):
 
     def _dnn(self, units, in_dim, name=None):
         kw = {} if name is None else {"name": name}
+        # the expert / gate level and tower kernels (dctr_mtl_*) read the activation code themselves
+        require_base_activation(type(self).__name__, self._dnn_cfg["activation"])
         d = self._add(DNN(tuple(units), self._dnn_cfg["activation"], self._dnn_cfg["l2"], self._dnn_cfg["dropout"], self._dnn_cfg["bn"],
                           seed=self._dnn_cfg["seed"], device=self.device, **kw).build_for(in_dim))
         self.dnn_layers.append(d)

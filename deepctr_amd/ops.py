@@ -2528,11 +2528,22 @@ def mlp_fwd_supported(gather, m, add_fm_logit=False, add_lin_logit=False):
                                                 int(bool(add_lin_logit))))
 
 
+def _dnn_act_code(op, activation):
+    """DCTR_ACT_* of a DNN activation name: relu / sigmoid / tanh / linear / dice and the tf.keras 2.x names elu, selu, softplus, softsign,
+    exponential, hard_sigmoid, swish (= silu), gelu (the DNN entry points take them: include/dctr.h)."""
+    try:
+        return _C.DNN_ACT_CODES[activation]
+    except (KeyError, TypeError):
+        raise ValueError("%s: unknown activation %r" % (op, activation))
+
+
 def mlp(x, kernels, biases, activation="relu", dice=None, dice_eps=1e-9, head_w=None, add=(), global_bias=None,
         sigmoid_out=False, in_dim=None, out=None, gather=None, add_fm_logit=False, add_lin_logit=False, batch=None,
         tile_rows=0, save_acts=None, probe=None, launch=True, bn=None, precision=0, workspace=None, cross=None):
     """DNN.call (reference core.py:189-208) for x [B, >=in_dim]; optional fused head:
     logit = h . head_w + sum(add) + global_bias, sigmoid (Dense(1) + add_func + PredictionLayer).
+    ``activation``: relu / sigmoid / tanh / linear / dice, or a tf.keras 2.x name (elu, selu, softplus, softsign, exponential,
+    hard_sigmoid, swish = silu, gelu: every route but the row-chained and streaming kernels, which decline them).
     ``dice`` = list of (alpha, moving_mean, moving_variance) per layer when activation == 'dice'.
     ``bn`` = list of (scale, shift) per layer (or None) for DNN(use_bn=True): inference BatchNormalization between bias_add
     and the activation, see dctr_mlp_args_t.bn_scale.
@@ -2554,7 +2565,7 @@ def mlp(x, kernels, biases, activation="relu", dice=None, dice_eps=1e-9, head_w=
     units = [k.shape[1] for k in kernels]
     kernels = [_f32c(k, "kernel") for k in kernels]
     biases = [None if b is None else _f32c(b, "bias") for b in biases]
-    act = _C.ACT_CODES[activation]
+    act = _dnn_act_code("mlp", activation)
     has_head = head_w is not None
     last = units[-1] if n else in_dim
     if out is None:
@@ -2847,7 +2858,10 @@ def dnn_train_layer(z, activation, h=None, bn=None, dropout_rate=0.0, dropout_se
     Backward (``dh`` given): dz [R, n] contiguous (may be dh itself) from dh, the same ``bn`` dict (batch statistics as the forward left
     them) and the same dropout_rate / dropout_seed; d_gamma / d_beta are accumulated."""
     R, n = z.shape
-    a = _C.DnnTrainLayer(z=z.data_ptr(), z_stride=z.stride(0), rows=R, n=n, activation=_C.ACT_CODES[activation],
+    act = _dnn_act_code("dnn_train_layer", activation)
+    if act == _C.ACT_DICE:
+        raise ValueError("dnn_train_layer: activation 'dice' has its own training form (dice_train_fwd)")
+    a = _C.DnnTrainLayer(z=z.data_ptr(), z_stride=z.stride(0), rows=R, n=n, activation=act,
                          dropout_rate=float(dropout_rate), dropout_seed=int(dropout_seed) & 0xFFFFFFFFFFFFFFFF)
     keep = [z]
     if bn is not None:
@@ -2878,7 +2892,7 @@ def mlp_bwd(x, in_dim, kernels, acts, activation, head_w, dlogit, d_kernels, d_b
     """Backward of dctr_mlp_fwd (+ head).  Gradients are ACCUMULATED into d_kernels / d_biases / d_head_w; dx is written.
     Headless form: head_w = dlogit = d_head_w = None and ``d_out`` [B, >= units[-1]] = gradient w.r.t. the last layer.
     activation "dice": ``biases`` and ``dice`` = [(alpha, mean, var)] per layer as in the forward; ``d_dice_alpha`` (list,
-    accumulated) optional; ``dice_batch`` = [(batch_mean, batch_var)] per layer (dice_train_fwd) switches to training-mode Dice:
+    accumulated) optional; activation "swish" / "gelu": ``biases`` (act' is taken from the pre-activations); ``dice_batch`` = [(batch_mean, batch_var)] per layer (dice_train_fwd) switches to training-mode Dice:
     the gradient flows through the batch statistics; ``saved_z`` = the layers' pre-activations (bias included) when a forward kept them.
     ``dw_stream`` (a torch.cuda.Stream) sends the weight-gradient launches of the chained form there (include/dctr.h); it needs a
     ``workspace`` the caller keeps alive (a dict: the tensor is cached under "ws") and a join by the caller."""
@@ -2888,6 +2902,14 @@ def mlp_bwd(x, in_dim, kernels, acts, activation, head_w, dlogit, d_kernels, d_b
     ua, kp, ap = _i32_array(units), _ptr_array(kernels), _ptr_array(acts)
     dkp, dbp = _ptr_array(d_kernels), _ptr_array(d_biases)
     extra = {}
+    act = _dnn_act_code("mlp_bwd", activation)
+    if act in (_C.ACT_SWISH, _C.ACT_GELU):
+        # act' needs the pre-activations, as Dice: saved_z when a forward kept them, else recomputed from the layer inputs and `biases`
+        if biases is None and (saved_z is None or any(z is None for z in saved_z)):
+            raise ValueError("mlp_bwd: activation %r needs the forward's biases (or saved_z of every layer)" % (activation,))
+        if biases is not None:
+            bp = _ptr_array([None if t is None else _f32c(t, "bias") for t in biases])
+            extra = dict(biases=ctypes.cast(bp, ctypes.c_void_p))
     if activation in ("dice", "Dice"):
         if dice is None or biases is None:
             raise ValueError("mlp_bwd: activation 'dice' needs the forward's biases and dice parameters")
@@ -2900,6 +2922,7 @@ def mlp_bwd(x, in_dim, kernels, acts, activation, head_w, dlogit, d_kernels, d_b
         if dice_batch is not None:
             bmp, bvp = (_ptr_array([_f32c(d[i], "dice batch statistics") for d in dice_batch]) for i in range(2))
             extra.update(dice_batch_mean=ctypes.cast(bmp, ctypes.c_void_p), dice_batch_var=ctypes.cast(bvp, ctypes.c_void_p))
+    if act in _C.ACT_FROM_Z:
         if saved_z is not None:       # the forward's pre-activations (bias included), dense [B, units[l]]: no recompute GEMM
             for z, u in zip(saved_z, units):
                 if z is not None and (z.dtype != torch.float32 or not z.is_contiguous() or z.shape[-1] != u or z.numel() != x.shape[0] * u):
@@ -2908,7 +2931,7 @@ def mlp_bwd(x, in_dim, kernels, acts, activation, head_w, dlogit, d_kernels, d_b
             extra.update(saved_z=ctypes.cast(szp, ctypes.c_void_p))
     a = _C.MlpBwdArgs(x=x.data_ptr(), batch=x.shape[0], x_stride=x.stride(0), in_dim=in_dim, n_layers=n,
                       units=ctypes.cast(ua, ctypes.c_void_p), kernels=ctypes.cast(kp, ctypes.c_void_p),
-                      acts=ctypes.cast(ap, ctypes.c_void_p), activation=_C.ACT_CODES[activation],
+                      acts=ctypes.cast(ap, ctypes.c_void_p), activation=act,
                       head_w=None if head_w is None else head_w.data_ptr(),
                       dlogit=None if dlogit is None else dlogit.data_ptr(), d_kernels=ctypes.cast(dkp, ctypes.c_void_p),
                       d_biases=ctypes.cast(dbp, ctypes.c_void_p), d_head_w=None if d_head_w is None else d_head_w.data_ptr(),

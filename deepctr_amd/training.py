@@ -133,7 +133,16 @@ def _act(name, x, dice=None, training=False):
             mean, var = bm, bv
         xp = torch.sigmoid((x - mean) / torch.sqrt(var + 1e-9))
         return alpha * (1 - xp) * x + xp * x
-    return {"relu": torch.relu, "sigmoid": torch.sigmoid, "tanh": torch.tanh, "linear": lambda v: v, None: lambda v: v}[name](x)
+    return _ACTS[name](x)
+
+
+# the tf.keras 2.x definitions (keras/activations.py) in torch ops: what csrc/act_device.h computes
+_F = torch.nn.functional
+_ACTS = {"relu": torch.relu, "sigmoid": torch.sigmoid, "tanh": torch.tanh, "linear": lambda v: v, None: lambda v: v,
+         "elu": _F.elu, "selu": _F.selu, "softsign": _F.softsign, "exponential": torch.exp, "swish": _F.silu, "silu": _F.silu,
+         "gelu": _F.gelu,                                                                # (the erf form: approximate=False)
+         "softplus": lambda v: torch.clamp(v, min=0) + torch.log1p(torch.exp(-v.abs())),   # (no threshold: keras has none)
+         "hard_sigmoid": lambda v: torch.clamp(0.2 * v + 0.5, 0.0, 1.0)}                 # (Keras 2; torch's hardsigmoid is relu6(z + 3) / 6)
 
 
 def _dropout(x, rate, training):

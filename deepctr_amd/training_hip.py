@@ -172,6 +172,8 @@ class HipTrainer(object):
         self.bn_layers = list(getattr(dnn, "bn_layers", None) or []) if dnn is not None else []
         self.slow_dnn = bool(self.drop_rate > 0 or self.bn_layers)
         self.dice_dnn = dnn is not None and dnn.activation in ("dice", "Dice")
+        # swish / gelu: act' needs the pre-activations, so the forward keeps them (buf["pre"]) as Dice's does
+        self.zact_dnn = dnn is not None and dnn.activation in ("swish", "silu", "gelu")
         self.p_dice_alpha = [param(d[0]) for d in dnn.dice_params()] if self.dice_dnn else []
         self.p_bn = [(param(b.w("gamma")) if b.scale else None, param(b.w("beta")) if b.center else None) for b in self.bn_layers]
         self.drop_base = int(getattr(dnn, "seed", 1024) or 0) * 0x9E3779B1 + 12345 if dnn is not None else 0
@@ -225,7 +227,7 @@ class HipTrainer(object):
                 self._buf.clear()
             b = self._buf[B] = {
                 "acts": [torch.empty(B, n, dtype=torch.float32, device=dev) for n in units],
-                "pre": [torch.empty(B, n, dtype=torch.float32, device=dev) for n in units] if (self.slow_dnn or self.dice_dnn) else None,
+                "pre": [torch.empty(B, n, dtype=torch.float32, device=dev) for n in units] if (self.slow_dnn or self.dice_dnn or self.zact_dnn) else None,
                 "dpre": [torch.empty(B, n, dtype=torch.float32, device=dev) for n in units] if self.slow_dnn else None,
                 "bn_stat": [(torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
                             for n in units] if self.bn_layers else None,
@@ -290,7 +292,7 @@ class HipTrainer(object):
         dnn = self.model.dnn
         hk = dict(head_w=self.p_head.w, add=list(add), global_bias=None if self.p_gbias is None else self.p_gbias.w,
                   sigmoid_out=binary) if head else {}
-        if not (self.dice_dnn or self.slow_dnn):
+        if not (self.dice_dnn or self.slow_dnn or self.zact_dnn):
             ops.mlp(x, dnn.kernels, dnn.biases, dnn.activation, in_dim=in_dim, out=out, save_acts=buf["acts"], **hk)
             return
         if self.dice_dnn:
@@ -298,6 +300,7 @@ class HipTrainer(object):
             if not head:
                 out[:, :kin].copy_(xin)             # (the stack's tail may carry alignment padding)
         else:   # training-mode BatchNormalization / Dropout: dense part (one-layer linear launch) -> dctr_dnn_train_layer_fwd, layer by layer
+            # (swish / gelu without either: the same two launches per layer leave the pre-activations in buf["pre"] for the backward)
             L = len(dnn.kernels)
             xin, kin = x, in_dim
             for l, (W, b) in enumerate(zip(dnn.kernels, dnn.biases)):
@@ -319,6 +322,10 @@ class HipTrainer(object):
             ops.mlp_bwd(x, in_dim, dnn.kernels, buf["acts"], "dice", hw, dlogit, dk, db, hg, dx=dx, d_out=d_out, biases=dnn.biases,
                         dice=dnn.dice_params(), d_dice_alpha=[p.g for p in self.p_dice_alpha], dice_batch=buf["dice_batch"],
                         saved_z=buf["pre"], workspace=buf.setdefault("mlp_bwd_ws_dice", {}))
+            return
+        if self.zact_dnn and not self.slow_dnn:
+            ops.mlp_bwd(x, in_dim, dnn.kernels, buf["acts"], dnn.activation, hw, dlogit, dk, db, hg, dx=dx, d_out=d_out, biases=dnn.biases,
+                        saved_z=buf["pre"], workspace=buf.setdefault("mlp_bwd_ws_z", {}))
             return
         if not self.slow_dnn:
             # the weight-gradient launches go to a second stream (dctr_mlp_bwd_args_t.dw_stream): they run beside the embedding

@@ -328,7 +328,14 @@ int dctr_crossnet_matrix_step(const float* x0, int64_t x0_stride, const float* x
  *     x [B,F0,D];  filters[k]: [F0*F_k, H_k] row-major (the reference's [1,F0*F_k,H_k] squeezed,
  *     row index i*F_k + j);  bias[k]: [H_k];  out [B, featuremap_num] (already summed over D).
  * ------------------------------------------------------------------------------------------------ */
-enum { DCTR_ACT_LINEAR = 0, DCTR_ACT_RELU = 1, DCTR_ACT_SIGMOID = 2, DCTR_ACT_TANH = 3, DCTR_ACT_DICE = 4 };
+enum { DCTR_ACT_LINEAR = 0, DCTR_ACT_RELU = 1, DCTR_ACT_SIGMOID = 2, DCTR_ACT_TANH = 3, DCTR_ACT_DICE = 4,
+       /* tf.keras 2.x activation names of the DNN (reference layers/activation.py:75-85 hands the name to tf.keras.layers.Activation).
+        * Taken by dctr_mlp_fwd / dctr_embed_mlp_fwd (+ _supported, _workspace_bytes), dctr_mlp_bwd (+ _workspace_bytes) and
+        * dctr_dnn_train_layer_fwd / _bwd ONLY; every other entry point that reads a DCTR_ACT_* answers them as it answers an
+        * unknown code.  elu: alpha = 1; hard_sigmoid: clip(0.2 z + 0.5, 0, 1) (the Keras 2 form); swish = silu = z sigmoid(z);
+        * gelu: the exact form 0.5 z (1 + erf(z / sqrt 2)) (approximate=False). */
+       DCTR_ACT_ELU = 5, DCTR_ACT_SELU = 6, DCTR_ACT_SOFTPLUS = 7, DCTR_ACT_SOFTSIGN = 8, DCTR_ACT_EXPONENTIAL = 9,
+       DCTR_ACT_HARD_SIGMOID = 10, DCTR_ACT_SWISH = 11, DCTR_ACT_GELU = 12 };
 typedef struct {
     const float* x;               /* sample b at x + b * x_stride, then [F0, D] row-major */
     int64_t batch;
@@ -1231,7 +1238,8 @@ typedef struct {
     const int32_t* units;         /* HOST array [n_layers] */
     const float* const* kernels;  /* HOST array of DEVICE pointers */
     const float* const* biases;   /* HOST array of DEVICE pointers */
-    int32_t activation;           /* DCTR_ACT_* (DICE: dice_* arrays below) */
+    int32_t activation;           /* DCTR_ACT_LINEAR .. DCTR_ACT_GELU (DICE: dice_* arrays below).  ELU .. GELU: every route but the
+                                     row-chained and streaming kernels, which decline them (the tile kernels take the launch) */
     int32_t has_head;
     const float* const* dice_alpha;   /* HOST arrays of DEVICE pointers [n_layers] or NULL */
     const float* const* dice_mean;
@@ -1451,10 +1459,12 @@ typedef struct {
 int dctr_embed_pool_bwd(const dctr_pool_bwd_args_t* args, void* stream);
 
 /* backward of dctr_mlp_fwd with has_head (layers/core.py:189-208 + Dense(1, use_bias=False)): needs the activations the
- * forward saved through save_acts.  relu / linear / sigmoid / tanh: FIVE launches whatever the depth — head, W_l^T of every layer,
+ * forward saved through save_acts.  relu / linear / sigmoid / tanh and the six activations whose derivative can be written in the
+ * OUTPUT (elu: h > 0 ? 1 : h + 1; selu: h > 0 ? s : h + s a; softplus: -expm1(-h); softsign: (1 - |h|)^2; exponential: h;
+ * hard_sigmoid: 0 < h < 1 ? 0.2 : 0): FIVE launches whatever the depth — head, W_l^T of every layer,
  * the backward chain (every dZ_l and dX in one launch on the forward's whole-MLP kernel), the dW_l (+ d_bias_l) row slices of every
- * layer as one grouped GEMM, the slice sum.  Dice: layer by layer (two GEMMs + the recomputed pre-activations per layer) on dctr_sgemm's
- * kernel. */
+ * layer as one grouped GEMM, the slice sum.  Dice, swish and gelu (act' needs the pre-activation): layer by layer (two GEMMs + the
+ * recomputed pre-activations per layer, or saved_z) on dctr_sgemm's kernel. */
 typedef struct {
     const float* x;               /* [B, x_stride] the forward's input (dnn_in)                          */
     int64_t batch;
@@ -1464,7 +1474,7 @@ typedef struct {
     const int32_t* units;         /* HOST [n_layers]                                                     */
     const float* const* kernels;  /* HOST array of DEVICE pointers, as in the forward                    */
     const float* const* acts;     /* HOST array of DEVICE pointers: saved activations [B, units[l]]      */
-    int32_t activation;           /* DCTR_ACT_LINEAR | RELU | SIGMOID | TANH | DICE                      */
+    int32_t activation;           /* DCTR_ACT_LINEAR .. DCTR_ACT_GELU                                    */
     int32_t pad_;
     const float* head_w;          /* [units[last]]                                                       */
     const float* dlogit;          /* [B]                                                                 */
@@ -1478,8 +1488,8 @@ typedef struct {
     const float* d_out;           /* headless form (head_w == NULL): [B, d_out_stride] gradient w.r.t. the last
                                      layer's activations (the DNN branch of DCN feeds a wider Dense(1))  */
     int64_t d_out_stride;
-    /* DCTR_ACT_DICE only (layers/activation.py:59-64 with the moving statistics): Dice is not invertible from its output,
-     * so the pre-activations are recomputed (one more GEMM per layer) from `biases` and the layer inputs. */
+    /* DCTR_ACT_DICE (layers/activation.py:59-64 with the moving statistics), DCTR_ACT_SWISH, DCTR_ACT_GELU: not invertible from the
+     * output, so the pre-activations are recomputed (one more GEMM per layer) from `biases` and the layer inputs. */
     const float* const* biases;       /* HOST array of DEVICE pointers [out_l] (entries may be NULL), as in the forward */
     const float* const* dice_alpha;   /* HOST arrays of DEVICE pointers [out_l]                           */
     const float* const* dice_mean;
@@ -1497,7 +1507,7 @@ typedef struct {
                                      The CALLER joins the two streams (dctr_mlp_bwd_join) before it reads d_kernels / d_biases or
                                      reuses the workspace — and before anything on `stream` OVERWRITES what the side stream still
                                      reads: x, acts[l] (the layers' inputs X_l) and the dZ_l slices inside the workspace. */
-    const float* const* saved_z;  /* ABI 6, DCTR_ACT_DICE.  NULL, or HOST array of DEVICE pointers [out_l] (entries may be NULL): layer l's
+    const float* const* saved_z;  /* ABI 6, DCTR_ACT_DICE / SWISH / GELU.  NULL, or HOST array of DEVICE pointers [out_l] (entries may be NULL): layer l's
                                      pre-activations z_l = x_l W_l + b_l, dense [B, units[l]], as a forward launch wrote them (training-mode
                                      Dice runs the layers one by one and has them): the recompute GEMM of that layer is skipped         */
 } dctr_mlp_bwd_args_t;
@@ -1531,7 +1541,7 @@ typedef struct {
     int64_t z_stride;
     int64_t rows;
     int32_t n;                    /* columns (units of the layer)                                          */
-    int32_t activation;           /* DCTR_ACT_LINEAR | RELU | SIGMOID | TANH                               */
+    int32_t activation;           /* DCTR_ACT_LINEAR | RELU | SIGMOID | TANH | ELU .. GELU (not DICE); act' from y */
     int32_t use_bn;
     float bn_eps;
     float bn_momentum;
