@@ -867,8 +867,9 @@ def _fit_hip(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end, wt=None, s
     moments, step count) lives on the model, so successive fit / train_on_batch calls continue the same optimisation.
     The reported loss is what tf.keras reports: the batch-size-weighted mean over the epoch's steps of [data loss + the l2 penalties
     l * sum(w^2) of the constructor's regularisers at THAT step's weights].  The penalties (they also enter the gradients, as 2 l w inside
-    the optimizer launch) are summed by the optimizer launch itself, on the weights it is about to update (dctr_opt_multi_l2: no further
-    pass over the tables) — round 6; before, they were taken at the epoch's two ends and averaged."""
+    the optimizer launch) are summed by the optimizer launch itself, on the weights it is about to update (dctr_opt_multi_l2 /
+    dctr_opt_apply: no further pass over the tables).  Only a model whose optimizer segments do not carry exactly its regularisers
+    (checked below, by value) keeps the penalties of the epoch's two ends, averaged; tests/test_gpu_l2.py holds that none does."""
     from .training_hip import trainer_for
     tr = trainer_for(model)
     perm_of = np.random.permutation if dp is None else dp.permutation

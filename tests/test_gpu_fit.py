@@ -159,13 +159,61 @@ def test_validation_steps_freq_and_penalties(device):
         model.fit(feed, y, batch_size=100, epochs=1, verbose=0, validation_data=(xv, yv), validation_steps=9)
 
 
-@pytest.mark.parametrize("kind", ["DeepFM", "DCN", "xDeepFM"])
+def _penalty_model(kind, device):
+    """(make(), feed, regularised weight names that must be there) of the kinds test_fit_loss_carries_every_steps_l2_penalties added to its
+    first three: every regulariser family of the kind at 1e-3 (AFM, which has no DNN kernels to weigh in: 1e-2), weights drawn at the
+    scale of trained ones so that the penalties matter beside the data loss."""
+    from deepctr_amd import models
+    from deepctr_amd.feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
+    rng = np.random.RandomState(3)
+    n = 2 * 256 + 77
+    r = 1e-2 if kind == "AFM" else 1e-3
+    base = dict(l2_reg_embedding=r, device=device)
+    full = dict(base, l2_reg_linear=r, l2_reg_dnn=r, dnn_hidden_units=(16, 8))
+    g = (lambda i: dict(group_name="g%d" % i)) if kind == "FLEN" else (lambda i: {})
+    sparse = [SparseFeat("a", 50, 8, **g(0)), SparseFeat("b", 70, 8, use_hash=True, **g(1)), SparseFeat("c", 9, 8, **g(2))]
+    dense = [DenseFeat("d", 3)]
+    feed = {"a": rng.randint(0, 50, n), "b": rng.randint(0, 10 ** 6, n), "c": rng.randint(0, 9, n), "d": rng.rand(n, 3).astype(np.float32)}
+    if kind == "AFM":
+        feed.pop("d")
+        make, must = (lambda: models.AFM(sparse, sparse, l2_reg_linear=r, l2_reg_att=r, **base)), ["afm_layer/attention_W"]
+    elif kind == "PNN":
+        make, must = (lambda: models.PNN(sparse + dense, l2_reg_dnn=r, dnn_hidden_units=(16, 8), **base)), ["dnn/kernel0"]
+    elif kind in ("NFM", "FLEN"):
+        make, must = (lambda: getattr(models, kind)(sparse + dense, sparse + dense, **full)), ["dnn/kernel0", "linear/linear_kernel"]
+    elif kind == "DCNMatrix":
+        make = lambda: models.DCN(sparse + dense, sparse + dense, cross_num=2, cross_parameterization="matrix", l2_reg_cross=r, **full)  # noqa: E731
+        must = ["cross_net/kernel0", "cross_net/kernel1"]
+    elif kind == "DCNMix":
+        make = lambda: models.DCNMix(sparse + dense, sparse + dense, cross_num=2, low_rank=4, num_experts=2, l2_reg_cross=r, **full)    # noqa: E731
+        must = ["cross_net_mix/U_list0", "cross_net_mix/V_list1", "cross_net_mix/C_list0"]
+    else:
+        assert kind == "DIN"
+        cols = [SparseFeat("user", 50, 8), SparseFeat("item_id", 31, 8, use_hash=True), SparseFeat("cate_id", 11, 8), DenseFeat("d", 3),
+                VarLenSparseFeat(SparseFeat("hist_item_id", 31, 8, embedding_name="item_id", use_hash=True), maxlen=6),
+                VarLenSparseFeat(SparseFeat("hist_cate_id", 11, 8, embedding_name="cate_id"), maxlen=6)]
+        lens = rng.randint(0, 7, n)
+        hi, hc = rng.randint(1, 10 ** 6, (n, 6)).astype(np.int32), rng.randint(1, 11, (n, 6)).astype(np.int32)
+        hi[np.arange(6)[None, :] >= lens[:, None]] = 0
+        hc[np.arange(6)[None, :] >= lens[:, None]] = 0
+        feed = {"user": rng.randint(0, 50, n), "item_id": rng.randint(1, 10 ** 6, n), "cate_id": rng.randint(1, 11, n), "d": feed["d"],
+                "hist_item_id": hi, "hist_cate_id": hc}
+        make = lambda: models.DIN(cols, ["item_id", "cate_id"], att_activation="sigmoid", att_hidden_size=(12, 6), l2_reg_dnn=r,   # noqa: E731
+                                  dnn_hidden_units=(16, 8), **base)
+        must = ["dnn_1/kernel0", "sparse_emb_item_id/embeddings"]
+    return make, feed, (rng.rand(n) > 0.5).astype(np.float32), must
+
+
+@pytest.mark.parametrize("kind", ["DeepFM", "DCN", "xDeepFM", "AFM", "DCNMatrix", "DCNMix", "NFM", "PNN", "FLEN", "DIN"])
 def test_fit_loss_carries_every_steps_l2_penalties(device, kind):
     """tf.keras.Model.fit's `loss` = batch-size-weighted mean over the epoch's steps of [data loss + the regularisation losses at that
     step's weights] (regularisers: reference inputs.py:22, layers/core.py:170, interaction.py:100,258,387).  With regularisers large enough
     to matter (1e-3: the penalties are ~ the data loss) and a ragged last batch, the HIP step's epoch loss — the optimizer launch sums the
     penalties of the weights it is about to update (dctr_opt_multi_l2) — equals the formula evaluated step by step with train_on_batch-free
-    means: per step, evaluate()-style data loss is not needed — the penalties are recomputed on the host from copies of the weights."""
+    means: per step, evaluate()-style data loss is not needed — the penalties are recomputed on the host from copies of the weights.
+    The kinds after the first three (_penalty_model) bring the regularisers those lack — l2_reg_att, the matrix CrossNet's and CrossNetMix's
+    trainer-packed kernels, FLEN's shared Dense(1) kernel, DIN's shared tables — with real labels: the one check of the penalties beside a
+    non-zero data gradient (tests/test_gpu_l2.py isolates them with a zero one)."""
     from deepctr_amd import models, training
     from deepctr_amd.feature_column import DenseFeat, SparseFeat
     rng = np.random.RandomState(3)
@@ -178,12 +226,21 @@ def test_fit_loss_carries_every_steps_l2_penalties(device, kind):
         kw.update(l2_reg_cross=1e-3, cross_num=2)
     if kind == "xDeepFM":
         kw.update(l2_reg_cin=1e-3, cin_layer_size=(8, 8))
+    make, must = (lambda: getattr(models, kind)(cols, cols, **kw)), []
+    if kind not in ("DeepFM", "DCN", "xDeepFM"):
+        make, feed, y, must = _penalty_model(kind, device)
     losses = {}
     for hip in (True, False):
-        model = getattr(models, kind)(cols, cols, **kw)
+        model = make()
         model.compile("adam", "binary_crossentropy")
         model.hip_training = hip
-        w0 = model.get_weights_by_name() if hip else w0
+        if hip:
+            w0 = model.get_weights_by_name()
+            if must:
+                from tests.test_gpu_models import _randomise
+                w0 = _randomise(model, np.random.RandomState(8))
+                regs = {n for n, t in model.named_weights() if t.data_ptr() in {r.data_ptr() for r, _ in training.regularized_weights(model)}}
+                assert set(must) <= regs, (kind, sorted(regs))
         model.set_weights_by_name(w0)
         # two epochs: the second starts from moved weights and Adam moments
         h = model.fit(feed, y, batch_size=bs, epochs=2, verbose=0, shuffle=False)

@@ -327,7 +327,7 @@ def _check_fit(meta, feed, n, seed, bs, device, must_be_supported=False):
     what = "fit fuzz %d %s %s bs=%d" % (seed, meta["model"], optimizer, bs)
     if not (np.isfinite(loss_ref) and loss_ref < 50.0):
         pytest.skip("%s: the random weights diverge under this optimizer (loss %.3g): nothing to compare" % (what, loss_ref))
-    # (the HIP step takes the l2 penalties at the epoch's two ends, the autograd step at every batch: second order in the weight change)
+    # (both steps add the l2 penalties at every batch's weights — the HIP step inside its optimizer launch: tests/test_gpu_l2.py)
     assert_close(np.array([loss_hip]), np.array([loss_ref]), rtol=1e-3, atol=1e-6, what=what + " loss")
     w_hip, w_ref = m_hip.get_weights_by_name(), m_ref.get_weights_by_name()
     for k in w_ref:

@@ -7,6 +7,9 @@ against the float64 oracle on the same inputs; the kernel — another float32 ev
 order, fused multiply-adds and sqrt / pow rounding — may sit at most 4 E plus one float32 ulp of the weight from the oracle.
 Measured on an MI355X (largest kernel error over E): 0.70 - 1.19 for every rule but Adam, whose 3.42 (clipvalue) / 4.00 / 4.40 (amsgrad)
 come from `1 - beta_2` formed in float32, as dctr_adam_multi forms it.
+The rule tests, the clip pre-pass and the in-launch l2 penalty also run on a second layout (_layout_l2) that puts l2 > 0 where real models
+have it and _layout() does not: the touched table, the unaligned segment, the tail-only segments.  The penalty's bar is derived
+(_penalty_bar), not measured.
 
 The whole-model tests hold the HIP fit's UPDATES (w3 - w0) to the bars of tests/test_gpu_train_reg.py::_autograd_check against the
 torch restatement fed the gradients the HIP step itself produced (_updates_match), the two fits' losses to tests/test_gpu_fit.py's bar and
@@ -37,6 +40,14 @@ def _layout():
     return [(n, 0.0, "plain") for n in SIZES] + [(1023, 0.0, "offset"), (4096 + 7, 0.01, "plain"), (TABLE[0] * TABLE[1], 0.0, "table")]
 
 
+def _layout_l2():
+    """_layout()'s segments with l2 > 0 on every route a regulariser can take: the touched table (every embedding table of a real model),
+    the offset segment (element by element), the segments of 1, 3 and 5 elements (tail loop only) and one plain 4,103; three segments
+    stay at l2 = 0.  One value per segment, so that a swapped l2 shows."""
+    l2 = {1: 0.02, 3: 0.03, 4: 0.0, 5: 0.04, 1023: 0.0, 4096 + 7: 0.0}
+    return [(n, l2[n], "plain") for n in SIZES] + [(1023, 0.05, "offset"), (4096 + 7, 0.01, "plain"), (TABLE[0] * TABLE[1], 0.025, "table")]
+
+
 def _buf(n, kind, device, fill=0.0):
     if kind == "offset":
         return torch.full((n + 1,), fill, dtype=torch.float32, device=device)[1:]
@@ -46,9 +57,9 @@ def _buf(n, kind, device, fill=0.0):
 class Segments(object):
     """The device side of one case: w / g / slots per segment, the touched map of the table, dctr_opt_seg_t array."""
 
-    def __init__(self, device, ws, inits):
+    def __init__(self, device, ws, inits, lay=None):
         from deepctr_amd import ops
-        self.lay = _layout()
+        self.lay = _layout() if lay is None else lay
         self.w = [_buf(n, k, device) for n, _, k in self.lay]
         self.g = [_buf(n, k, device) for n, _, k in self.lay]
         self.slots = [[_buf(n, k, device, v) for v in inits] for n, _, k in self.lay]
@@ -69,11 +80,11 @@ class Segments(object):
         self.touched.copy_(torch.from_numpy(mask.astype(np.uint8)))
 
 
-def _inputs(case, seed):
+def _inputs(case, seed, lay=None):
     """weights, per-update effective gradients and touched maps (about a tenth of the table's groups set) of a case."""
     cid, name, kw, rule, okw = case
     rng = np.random.RandomState(seed)
-    lay = _layout()
+    lay = _layout() if lay is None else lay
     shapes, l2s = [(n,) for n, _, _ in lay], [l2 for _, l2, _ in lay]
     masks = [rng.rand(lay[-1][0] // 4) < 0.1 for _ in range(UPDATES)]
 
@@ -89,10 +100,10 @@ def _inputs(case, seed):
     return ws, gs, masks, l2s
 
 
-def _run_hip(device, opt, ws, gs, masks):
+def _run_hip(device, opt, ws, gs, masks, lay=None):
     from deepctr_amd import ops
     rule = dict(opt._rule(), clipvalue=opt.clipvalue)
-    sg = Segments(device, ws, rule["slots"])
+    sg = Segments(device, ws, rule["slots"], lay)
     clip = ops.grad_clip_workspace(sg.n_segs, sg.max_n, device) if (opt.clipnorm or opt.global_clipnorm) else None
     for t, (g, m) in enumerate(zip(gs, masks), 1):
         sg.load_grads(g, m)
@@ -111,8 +122,9 @@ def _run_hip(device, opt, ws, gs, masks):
     return [w.cpu().numpy() for w in sg.w], sg
 
 
-def _run_torch(opt, ws, gs, l2s, dtype):
+def _run_torch(opt, ws, gs, lay, dtype):
     from deepctr_amd import training
+    l2s = [l2 for _, l2, _ in lay]
     params = [torch.tensor(w, dtype=dtype) for w in ws]
     ko = training.KerasOptimizer(params, opt)
     for g in gs:
@@ -124,16 +136,32 @@ def _run_torch(opt, ws, gs, l2s, dtype):
 
 @pytest.mark.parametrize("case", RO.CASES, ids=RO.CASE_IDS)
 def test_opt_apply_matches_the_float64_oracle(device, case):
+    _updates_against_the_oracle(device, case, _layout())
+
+
+@pytest.mark.parametrize("case", RO.CASES, ids=RO.CASE_IDS)
+def test_opt_apply_matches_the_float64_oracle_with_l2_on_every_route(device, case):
+    """The same comparison at the same bar on _layout_l2(): 2 l2 w enters on the touched table — where nine groups in ten have a clear byte
+    and move by the l2 term alone —, on the element-by-element route and in the tail loop."""
+    _updates_against_the_oracle(device, case, _layout_l2())
+
+
+def _updates_against_the_oracle(device, case, lay):
     from deepctr_amd import optimizers
     cid, name, kw, rule, okw = case
-    ws, gs, masks, l2s = _inputs(case, zlib.crc32(cid.encode()) % 1000)
+    ws, gs, masks, l2s = _inputs(case, zlib.crc32(cid.encode()) % 1000, lay)
     oracle = RO.Oracle(rule, **okw)
     want = [w.astype(np.float64) for w in ws]
     for g in gs:
         oracle.update(want, g, l2s, kw["learning_rate"])
-    t32 = _run_torch(getattr(optimizers, name)(**kw), ws, gs, l2s, torch.float32)
+    if l2s[-1] > 0:
+        # groups of the table no update touched: the oracle moved every element of them (by the l2 term alone), so the comparison below
+        # says something about the kernel's clear-byte path
+        never = ~np.any(masks, axis=0)
+        assert never.sum() >= 32 and np.all(want[-1].reshape(-1, 4)[never] != ws[-1].reshape(-1, 4)[never].astype(np.float64))
+    t32 = _run_torch(getattr(optimizers, name)(**kw), ws, gs, lay, torch.float32)
     opt = getattr(optimizers, name)(**kw)
-    got, _ = _run_hip(device, opt, ws, gs, masks)
+    got, _ = _run_hip(device, opt, ws, gs, masks, lay)
     e_torch = max(float(np.abs(a.astype(np.float64) - b).max()) for a, b in zip(t32, want))
     worst = 0.0
     for i, (a, b) in enumerate(zip(got, want)):
@@ -208,25 +236,118 @@ def test_the_old_kinds_give_dctr_opt_multis_bits(device, kind):
         assert torch.equal(t_old, t_new)
     # the l2 penalties ride the launch as they do dctr_opt_multi_l2's
     pen_old, pen_new = torch.zeros(1, dtype=torch.float64, device=device), torch.zeros(1, dtype=torch.float64, device=device)
+    want = 200.0 * _penalty64([p["w"] for p in old], lay)          # (of the weights BEFORE the update)
     ops.opt_multi(kind, segs_old[0], segs_old[1], segs_old[2], 0.01, rule["beta1"], rule["beta2"], rule["eps"], penalty=pen_old, penalty_scale=200.0)
     ops.opt_apply(rule, segs_new[0], segs_new[1], segs_new[2], 0.01, penalty=pen_new, penalty_scale=200.0)
-    want = 200.0 * sum(l2 * float((p["w"].double() ** 2).sum()) for p, (_, l2, _) in zip(old, lay))
     assert float(pen_old) > 0 and abs(float(pen_old) - float(pen_new)) <= 1e-12 * float(pen_old)
     for po, pn in zip(old, new):
         assert torch.equal(po["w"], pn["w"])
     assert want > 0
+    assert abs(float(pen_old) - want) <= _penalty_bar(lay) * want and abs(float(pen_new) - want) <= _penalty_bar(lay) * want, (
+        float(pen_old), float(pen_new), want)
+
+
+def _penalty64(ws, lay):
+    """sum over the segments of l2 * sum(w^2) in float64, from host copies of the weights (device tensors or arrays)."""
+    host = [w.detach().cpu().numpy() if torch.is_tensor(w) else np.asarray(w) for w in ws]
+    return sum(l2 * float((w.astype(np.float64) ** 2).sum()) for w, (_, l2, _) in zip(host, lay))
+
+
+def _penalty_bar(lay):
+    """The relative error the in-launch penalty may have against float64.  A thread adds its squares up in float32 and everything
+    behind that — the sum over the workgroup, the products with l2 and penalty_scale, the atomic add — is float64.  Every segment gets
+    at least one workgroup of 256 threads, each thread takes every 256th group (or element) at the closest, so no thread adds more than
+    k = ceil(n_max / 256) squares: each square carries one rounding (2^-24 relative) and a float32 sum of k non-negative terms k - 1
+    more, which bounds a thread's share, and so the sum of the shares, by k 2^-24 relative; the segment's l2 is a float32 (one more
+    rounding of the Python value the reference multiplies by) and one 2^-24 is kept for the second-order terms: (k + 2) 2^-24."""
+    n_max = max(n for n, _, _ in lay)
+    return (-(-n_max // 256) + 2) * 2.0 ** -24
+
+
+APPLY_RULES = {      # one rule per number of state slots of dctr_opt_apply's kernel (NS), and Ftrl
+    "sgd_ns0": ("SGD", dict(learning_rate=0.05)), "adagrad_ns1": ("Adagrad", dict(learning_rate=0.1)),
+    "adam_ns2": ("Adam", dict(learning_rate=0.01)), "adam_amsgrad_ns3": ("Adam", dict(learning_rate=0.01, amsgrad=True)),
+    "ftrl_ns2": ("Ftrl", dict(learning_rate=0.05, l1_regularization_strength=0.01)),
+}
+
+
+def _penalty_grads(rng, lay, sg_g, touched):
+    """One update's gradients on the device: NaN in the clear groups of the table, a tenth of its bytes set."""
+    mask = rng.rand(lay[-1][0] // 4) < 0.1
+    for t, (n, _, k) in zip(sg_g, lay):
+        g = rng.normal(0, 0.1, n).astype(np.float32)
+        if k == "table":
+            g.reshape(-1, 4)[~mask] = np.nan
+        t.copy_(torch.from_numpy(g))
+    touched.copy_(torch.from_numpy(mask.astype(np.uint8)))
+
+
+@pytest.mark.parametrize("entry", sorted(APPLY_RULES) + ["multi_adam", "multi_adagrad", "multi_rmsprop", "multi_sgd"])
+def test_the_launch_adds_the_float64_l2_penalty(device, entry):
+    """penalty += penalty_scale * sum_segments l2 * sum(w^2) of the weights BEFORE the update, against float64 from host copies at
+    _penalty_bar; a second launch ADDS the penalty at the then-current weights; with every l2 at 0 the accumulator stays exactly 0.0.
+    dctr_opt_multi takes 16-byte aligned buffers only: the offset segment runs on dctr_opt_apply alone."""
+    from deepctr_amd import ops, optimizers
+    multi = entry.startswith("multi_")
+    full = [s for s in _layout_l2() if not (multi and s[2] == "offset")]
+    scale = 200.0
+    for lay in (full, [(n, 0.0, k) for n, _, k in full]):
+        rng = np.random.RandomState(zlib.crc32(entry.encode()) % 1000)
+        ws = [rng.uniform(-0.5, 0.5, n).astype(np.float32) for n, _, _ in lay]
+        pen = torch.zeros(1, dtype=torch.float64, device=device)
+        if multi:
+            kind = entry[len("multi_"):]
+            mk = lambda w, fill: torch.full((w.size,), fill, dtype=torch.float32, device=device)     # noqa: E731
+            ps = [dict(w=torch.from_numpy(w).to(device), m=mk(w, 0.0), v=mk(w, 0.1 if kind == "adagrad" else 0.0), g=mk(w, 0.0)) for w in ws]
+            touched = torch.zeros(lay[-1][0] // 4, dtype=torch.uint8, device=device)
+            segs = ops.make_adam_segments([(p["w"], p["m"], p["v"], p["g"], l2, touched if k == "table" else None)
+                                           for p, (_, l2, k) in zip(ps, lay)], device)
+            w_dev, g_dev = [p["w"] for p in ps], [p["g"] for p in ps]
+            launch = lambda t: ops.opt_multi(kind, segs[0], segs[1], segs[2], 0.01, 0.9, 0.999 if kind == "adam" else 0.9, 1e-7,    # noqa: E731
+                                             penalty=pen, penalty_scale=scale)
+        else:
+            name, kw = APPLY_RULES[entry]
+            opt = getattr(optimizers, name)(**kw)
+            rule = dict(opt._rule(), clipvalue=opt.clipvalue)
+            assert "ns%d" % len(rule["slots"]) in entry
+            sg = Segments(device, ws, rule["slots"], lay)
+            w_dev, g_dev, touched = sg.w, sg.g, sg.touched
+            launch = lambda t: ops.opt_apply(rule, sg.segs, sg.n_segs, sg.max_n, opt._step_lr(t), penalty=pen, penalty_scale=scale)  # noqa: E731
+        want = 0.0
+        for t in (1, 2):
+            _penalty_grads(rng, lay, g_dev, touched)
+            want += scale * _penalty64(w_dev, lay)
+            before = [w.clone() for w in w_dev]
+            launch(t)
+            torch.cuda.synchronize()
+            assert all(not torch.equal(a, b) and bool(torch.isfinite(b).all()) for a, b in zip(before, w_dev)), "the update itself ran"
+            got = float(pen)
+            if all(l2 == 0.0 for _, l2, _ in lay):
+                assert got == 0.0 and want == 0.0
+            else:
+                assert want > 0 and abs(got - want) <= _penalty_bar(lay) * want, (entry, t, got, want, abs(got - want) / want, _penalty_bar(lay))
+                print("%s launch %d: penalty off by %.3g relative, bar %.3g" % (entry, t, abs(got - want) / want, _penalty_bar(lay)))
 
 
 def test_grad_clip_scales(device):
+    _clip_scales_against_float64(device, _layout())
+
+
+def test_grad_clip_scales_with_l2_on_every_route(device):
+    """clipnorm and global_clipnorm over g + 2 l2 w on _layout_l2(): the table's clear groups add (2 l2 w)^2 without their (poisoned)
+    gradient being read, the offset segment and the tails carry the term element by element."""
+    _clip_scales_against_float64(device, _layout_l2())
+
+
+def _clip_scales_against_float64(device, lay):
     from deepctr_amd import _C, ops
     rng = np.random.RandomState(13)
-    lay = _layout()
     ws = [rng.uniform(-0.5, 0.5, n).astype(np.float32) for n, _, _ in lay]
     amp = [0.5, 0.001, 0.3, 0.001, 0.02, 0.01, 0.02, 0.01, 0.05]            # some norms above the clip value, some below
     gs = [(rng.normal(0, a, n)).astype(np.float32) for (n, _, _), a in zip(lay, amp)]
     mask = rng.rand(lay[-1][0] // 4) < 0.1
     gs[-1].reshape(-1, 4)[~mask] = 0.0
-    sg = Segments(device, ws, [])
+    sg = Segments(device, ws, [], lay)
     ws_, scale = ops.grad_clip_workspace(sg.n_segs, sg.max_n, device)
     eff = [g.astype(np.float64) + 2.0 * l2 * w.astype(np.float64) for g, w, (_, l2, _) in zip(gs, ws, lay)]
     out = {}
@@ -245,7 +366,7 @@ def test_grad_clip_scales(device):
         out[(mode, clip)] = first
     assert (out[(False, 0.25)] == 1.0).any() and (out[(False, 0.25)] < 1.0).any() and np.all(out[(True, 0.9)] < 1.0) and np.all(out[(True, 100.0)] == 1.0)
     # the dense route (no touched map, zeros where the map is clear) gives the touched route's bits
-    dense = Segments(device, ws, [])
+    dense = Segments(device, ws, [], lay)
     for t, g in zip(dense.g, gs):
         t.copy_(torch.from_numpy(g))
     dsegs = ops.make_opt_segments([(w, g, [], l2) for w, g, (_, l2, _) in zip(dense.w, dense.g, lay)], device)
