@@ -501,6 +501,7 @@ SYMBOLS = {
     "dctr_embed_gather_fm_bwd": (ctypes.c_int, [ctypes.POINTER(GatherFmBwdArgs), c_vp]),
     "dctr_embed_pool_bwd": (ctypes.c_int, [ctypes.POINTER(PoolBwdArgs), c_vp]),
     "dctr_afm_bwd": (ctypes.c_int, [c_vp, c_vp]),
+    "dctr_afm_bwd_supported": (ctypes.c_int, [c_i32, c_i32, c_i32]),
     "dctr_din_att_in_fwd": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "dctr_din_wsum_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "dctr_din_wsum_bwd": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
@@ -518,6 +519,7 @@ SYMBOLS = {
     "dctr_mlp_bwd": (ctypes.c_int, [ctypes.POINTER(MlpBwdArgs), c_vp]),
     "dctr_crossnet_mix_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(CrossMixBwdArgs)]),
     "dctr_crossnet_mix_bwd": (ctypes.c_int, [ctypes.POINTER(CrossMixBwdArgs), c_vp]),
+    "dctr_crossnet_mix_bwd_supported": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32]),
     "dctr_fm_bwd": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "dctr_din_softmax_fwd": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "dctr_din_softmax_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),

@@ -194,20 +194,32 @@ __global__ __launch_bounds__(256) void afm_bwd_kernel(const float* __restrict__ 
     }
 }
 
+// what dctr_afm_bwd and its dry check share: the sizes the op takes, and the dynamic LDS of afm_bwd_kernel for them (the weights and
+// their gradients once per workgroup, a sample tile, its gradient and the pair scores per wave)
+constexpr size_t AFM_BWD_LDS_MAX = 160 * 1024;
+bool afm_bwd_sizes_ok(int fields, int dim, int att_factor) { return fields >= 2 && dim >= 1 && att_factor >= 1; }
+size_t afm_bwd_lds_bytes(int fields, int dim, int att_factor) {
+    const size_t P = (size_t)fields * (fields - 1) / 2;
+    const size_t nw = (size_t)dim * att_factor + 2 * (size_t)att_factor + dim;
+    return (2 * nw + 4 * (2 * (size_t)fields * dim + P)) * sizeof(float);
+}
+
 }  // namespace
+
+extern "C" int dctr_afm_bwd_supported(int32_t fields, int32_t dim, int32_t att_factor) {
+    return afm_bwd_sizes_ok(fields, dim, att_factor) && afm_bwd_lds_bytes(fields, dim, att_factor) <= AFM_BWD_LDS_MAX ? 1 : 0;
+}
 
 extern "C" int dctr_afm_bwd(const dctr_afm_bwd_args_t* a, void* stream) {
     DCTR_REQUIRE(a != nullptr, DCTR_E_NULL, "afm_bwd: null args");
-    DCTR_REQUIRE(a->batch >= 0 && a->fields >= 2 && a->dim >= 1 && a->att_factor >= 1, DCTR_E_DIM, "afm_bwd: bad sizes");
+    DCTR_REQUIRE(a->batch >= 0 && afm_bwd_sizes_ok(a->fields, a->dim, a->att_factor), DCTR_E_DIM, "afm_bwd: bad sizes");
     DCTR_REQUIRE(a->x_stride >= (int64_t)a->fields * a->dim && a->dx_stride >= (int64_t)a->fields * a->dim, DCTR_E_DIM,
                  "afm_bwd: stride smaller than fields*dim");
     if (a->batch == 0) return DCTR_OK;
     DCTR_REQUIRE(a->x && a->att_w && a->att_b && a->proj_h && a->proj_p && a->dy && a->dx, DCTR_E_NULL, "afm_bwd: null pointer");
     DCTR_REQUIRE(a->d_att_w && a->d_att_b && a->d_proj_h && a->d_proj_p, DCTR_E_NULL, "afm_bwd: null gradient pointer");
-    const int P = a->fields * (a->fields - 1) / 2;
-    const size_t nw = (size_t)a->dim * a->att_factor + 2 * a->att_factor + a->dim;
-    const size_t lds = (2 * nw + 4 * (2 * (size_t)a->fields * a->dim + P)) * sizeof(float);
-    DCTR_REQUIRE(lds <= 160 * 1024, DCTR_E_UNSUPPORTED, "afm_bwd: needs %zu B of LDS", lds);
+    const size_t lds = afm_bwd_lds_bytes(a->fields, a->dim, a->att_factor);
+    DCTR_REQUIRE(lds <= AFM_BWD_LDS_MAX, DCTR_E_UNSUPPORTED, "afm_bwd: needs %zu B of LDS", lds);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)afm_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         DCTR_REQUIRE(e == hipSuccess, (int)e, "afm_bwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));

@@ -2307,7 +2307,14 @@ MixPlan mix_plan(int64_t B, int d, int L, int ne, int r) {
     return m;
 }
 
+// the sizes dctr_crossnet_mix_bwd takes (the row kernels keep a row's gate in MIX_MAX_EXPERTS registers); its dry check asks the same
+bool mix_bwd_sizes_ok(int d, int L, int ne, int r) { return d >= 1 && L >= 0 && ne >= 1 && ne <= MIX_MAX_EXPERTS && r >= 1; }
+
 }  // namespace
+
+extern "C" int dctr_crossnet_mix_bwd_supported(int32_t dim, int32_t layers, int32_t experts, int32_t low_rank) {
+    return mix_bwd_sizes_ok(dim, layers, experts, low_rank) ? 1 : 0;
+}
 
 extern "C" size_t dctr_crossnet_mix_bwd_workspace_bytes(const dctr_crossnet_mix_bwd_args_t* a) {
     if (a == nullptr || a->batch <= 0 || a->dim <= 0 || a->layers <= 0 || a->experts <= 0 || a->low_rank <= 0) return 0;
@@ -2316,9 +2323,9 @@ extern "C" size_t dctr_crossnet_mix_bwd_workspace_bytes(const dctr_crossnet_mix_
 
 extern "C" int dctr_crossnet_mix_bwd(const dctr_crossnet_mix_bwd_args_t* a, void* stream) {
     DCTR_REQUIRE(a != nullptr, DCTR_E_NULL, "crossnet_mix_bwd: null args");
-    DCTR_REQUIRE(a->batch >= 0 && a->dim >= 1 && a->layers >= 0 && a->experts >= 1 && a->experts <= MIX_MAX_EXPERTS && a->low_rank >= 1,
-                 DCTR_E_DIM, "crossnet_mix_bwd: bad sizes (batch=%lld dim=%d layers=%d experts=%d (max %d) low_rank=%d)",
-                 (long long)a->batch, a->dim, a->layers, a->experts, MIX_MAX_EXPERTS, a->low_rank);
+    DCTR_REQUIRE(a->batch >= 0 && mix_bwd_sizes_ok(a->dim, a->layers, a->experts, a->low_rank), DCTR_E_DIM,
+                 "crossnet_mix_bwd: bad sizes (batch=%lld dim=%d layers=%d experts=%d (max %d) low_rank=%d)", (long long)a->batch,
+                 a->dim, a->layers, a->experts, MIX_MAX_EXPERTS, a->low_rank);
     if (a->batch == 0) return DCTR_OK;
     DCTR_REQUIRE(a->x && a->dy && a->dx && a->x_stride >= a->dim && a->dy_stride >= a->dim && a->dx_stride >= a->dim, DCTR_E_NULL,
                  "crossnet_mix_bwd: null x / dy / dx or a stride < dim");

@@ -75,7 +75,11 @@ class _AFM(FeatureModel):
 
     # ---- the HIP training step (training_hip.HipTrainer): no DNN — linear logit + AFMLayer per group (or the gather's FM groups) ------
     def _hip_supported(self):
-        return self._hip_family_ok(extra_fm=True, need_dnn=False) and not any(getattr(l, "dropout_rate", 0) for l in self.afm_layers)
+        # dctr_afm_fwd streams any shape, dctr_afm_bwd holds four samples' tiles in LDS: a group past that trains on the autograd step
+        sp = self.stage_plan
+        return (self._hip_family_ok(extra_fm=True, need_dnn=False) and not any(getattr(l, "dropout_rate", 0) for l in self.afm_layers)
+                and all(ops.afm_bwd_supported(sp.group_slices[g][1], sp.group_slices[g][2], l.attention_factor)
+                        for g, l in zip(self.groups, self.afm_layers)))
 
     def _hip_params(self, tr):          # l2_reg_att applies to attention_W only (interaction.py:100)
         tr.own["afm"] = [(tr.param(l.w("attention_W"), getattr(l, "l2_reg_w", 0.0)), tr.param(l.w("attention_b")),

@@ -38,6 +38,12 @@ class _DCNMix(_DCN):
         return xl
 
     # ---- the HIP training step: _DCN's, on CrossNetMix's five packed parameter tensors and dctr_crossnet_mix_fwd / _bwd ---------------
+    def _hip_supported(self):
+        # dctr_crossnet_mix_fwd takes any number of experts, dctr_crossnet_mix_bwd sixteen: past that the autograd step
+        cr = self.cross
+        return super(_DCNMix, self)._hip_supported() and (
+            cr is None or ops.crossnet_mix_bwd_supported(self.stage_plan.in_dim, cr.layer_num, cr.num_experts, cr.low_rank))
+
     def _hip_pack_cross(self, tr, l2):
         # U / V / C stacked over layers, the experts' gating kernels, the biases, in the C ABI's layout.  l2 on U / V / C only (the
         # reference regularises U_list / V_list / C_list, interaction.py:481-500)

@@ -2820,9 +2820,27 @@ def embed_gather_fm_bwd(fwd_args, grads_dev, d_dnn_in=None, d_fm=None, d_lin=Non
     _C.check(_C.lib().dctr_embed_gather_fm_bwd(ctypes.byref(a), _C.stream_ptr()), "dctr_embed_gather_fm_bwd")
 
 
-def crossnet_mix_bwd(x, dim, packed, dy, grads, dx, accumulate=False):
+def _bwd_workspace(workspace, need, device):
+    """The float32 workspace of a backward op: a fresh tensor per call, or with ``workspace`` (a dict the caller keeps alive, as
+    ``mlp_bwd`` and ``cin_bwd`` take it) the tensor cached under "ws", replaced only when it is missing, on another device or smaller
+    than ``need`` bytes."""
+    if workspace is not None:
+        ws = workspace.get("ws")
+        if ws is None or ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() * 4 < need or ws.device != device:
+            ws = workspace["ws"] = torch.empty(max(1, need // 4), dtype=torch.float32, device=device)
+        return ws
+    return torch.empty(max(1, need // 4), dtype=torch.float32, device=device)
+
+
+def crossnet_mix_bwd_supported(dim, layers, experts, low_rank):
+    """Does dctr_crossnet_mix_bwd take these sizes (at most 16 experts; the forward takes any number)?"""
+    return bool(_C.lib().dctr_crossnet_mix_bwd_supported(int(dim), int(layers), int(experts), int(low_rank)))
+
+
+def crossnet_mix_bwd(x, dim, packed, dy, grads, dx, accumulate=False, workspace=None):
     """Backward of crossnet_mix: ``packed`` = (U, V, C, gating, bias) as the forward takes them, ``grads`` the same five shapes
-    (accumulated into), dy [B, >= dim] gradient w.r.t. the output, dx [B, >= dim] written (or added to)."""
+    (accumulated into), dy [B, >= dim] gradient w.r.t. the output, dx [B, >= dim] written (or added to).  ``workspace``: a dict the
+    caller keeps alive, as ``cin_bwd`` takes it (default: a fresh tensor per call)."""
     U, V, C, gating, bias = packed
     dU, dV, dC, dG, dB = grads
     _dev_check(x, dy, dx, U, V, C, gating, bias, dU, dV, dC, dG, dB)
@@ -2832,7 +2850,7 @@ def crossnet_mix_bwd(x, dim, packed, dy, grads, dx, accumulate=False):
                            dy_stride=dy.stride(0), dU=_ptr(dU), dV=_ptr(dV), dC=_ptr(dC), dgating=_ptr(dG), dbias=_ptr(dB),
                            dx=dx.data_ptr(), dx_stride=dx.stride(0), dx_accumulate=int(bool(accumulate)))
     need = int(_C.lib().dctr_crossnet_mix_bwd_workspace_bytes(ctypes.byref(a))) if L else x.shape[0] * dim * 4
-    ws = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
+    ws = _bwd_workspace(workspace, need, x.device)
     a.workspace, a.workspace_bytes = ws.data_ptr(), need
     _C.check(_C.lib().dctr_crossnet_mix_bwd(ctypes.byref(a), _C.stream_ptr()), "dctr_crossnet_mix_bwd")
 
@@ -3130,6 +3148,11 @@ def dense1_bwd(x, n, w, dlogit, dx, d_w):
                                       _ptr(d_w), _C.stream_ptr()), "dctr_dense1_bwd")
 
 
+def afm_bwd_supported(fields, dim, att_factor):
+    """Does dctr_afm_bwd take these shapes (the weights and four samples' tiles fit 160 KiB of LDS; afm() itself streams any shape)?"""
+    return bool(_C.lib().dctr_afm_bwd_supported(int(fields), int(dim), int(att_factor)))
+
+
 def afm_bwd(x, fields, dim, attention_W, attention_b, projection_h, projection_p, dy, dx, d_W, d_b, d_h, d_p, accumulate=False):
     """Backward of afm() on a strided [B, >= F*E] buffer: dy [B]; dx [B, >= F*E] written (or added to); the four weight
     gradients (shapes of the weights) are ACCUMULATED (include/dctr.h)."""
@@ -3159,10 +3182,12 @@ def inner_product_bwd(x, fields, dim, dy, dx, accumulate=False):
              "dctr_inner_product_bwd")
 
 
-def crossnet_bwd(x, d, kernels, bias, parameterization, dy, d_kernels, d_bias, dx, accumulate=False, saved_u=None, saved_x=None):
+def crossnet_bwd(x, d, kernels, bias, parameterization, dy, d_kernels, d_bias, dx, accumulate=False, saved_u=None, saved_x=None,
+                 workspace=None):
     """Backward of dctr_crossnet_fwd: x [B, >= d] the forward input, dy [B, >= d]; d_kernels / d_bias are ACCUMULATED,
     dx [B, >= d] is written (or added to with ``accumulate``).  saved_u [L, B, d] / saved_x [L - 1, B, d] (matrix form): what the
-    forward wrote through dctr_crossnet_args_t.save_u / save_x — the backward then recomputes nothing."""
+    forward wrote through dctr_crossnet_args_t.save_u / save_x — the backward then recomputes nothing.  ``workspace``: a dict the
+    caller keeps alive, as ``cin_bwd`` takes it (default: a fresh tensor per call)."""
     _dev_check(x, dy, dx, kernels, bias)
     L = 0 if kernels is None else kernels.shape[0]
     mode = _C.CROSS_VECTOR if parameterization == "vector" else _C.CROSS_MATRIX
@@ -3171,7 +3196,7 @@ def crossnet_bwd(x, d, kernels, bias, parameterization, dy, d_kernels, d_bias, d
                         dy_stride=dy.stride(0), d_kernels=_ptr(d_kernels), d_bias=_ptr(d_bias), dx=dx.data_ptr(),
                         dx_stride=dx.stride(0), saved_u=_ptr(saved_u), saved_x=_ptr(saved_x))
     need = int(_C.lib().dctr_crossnet_bwd_workspace_bytes(ctypes.byref(a)))
-    ws = torch.empty(max(1, need // 4), dtype=torch.float32, device=x.device)
+    ws = _bwd_workspace(workspace, need, x.device)
     a.workspace, a.workspace_bytes = ws.data_ptr(), need
     _C.check(_C.lib().dctr_crossnet_bwd(ctypes.byref(a), _C.stream_ptr()), "dctr_crossnet_bwd")
 

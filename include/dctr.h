@@ -1626,6 +1626,10 @@ typedef struct {
     float* d_proj_p;
 } dctr_afm_bwd_args_t;
 int dctr_afm_bwd(const dctr_afm_bwd_args_t* args, void* stream);
+/* 1: dctr_afm_bwd takes these sizes; 0: it answers DCTR_E_DIM or, past 160 KiB of LDS for the weights and four samples' tiles
+ * ((2 (dim att_factor + 2 att_factor + dim) + 4 (2 fields dim + fields (fields - 1) / 2)) * 4 bytes), DCTR_E_UNSUPPORTED — the forward
+ * streams such shapes, the backward does not.  Host arithmetic, the op's own predicate. */
+int dctr_afm_bwd_supported(int32_t fields, int32_t dim, int32_t att_factor);
 
 /* backward of dctr_crossnet_fwd (interaction.py:405-424).  vector: one fused kernel (x_l recomputed) while a wave's x_l and its d w / d b
  * accumulators fit the LDS and a row's gradient the registers (dim <= 2048, 48 * layers * dim bytes <= 160 KiB); wider inputs (ABI 13: any
@@ -1683,6 +1687,9 @@ typedef struct {
 } dctr_crossnet_mix_bwd_args_t;
 size_t dctr_crossnet_mix_bwd_workspace_bytes(const dctr_crossnet_mix_bwd_args_t* args);
 int dctr_crossnet_mix_bwd(const dctr_crossnet_mix_bwd_args_t* args, void* stream);
+/* 1: dctr_crossnet_mix_bwd takes these sizes; 0: it answers DCTR_E_DIM (more than 16 experts: the forward takes any number).  Host
+ * arithmetic, the op's own predicate. */
+int dctr_crossnet_mix_bwd_supported(int32_t dim, int32_t layers, int32_t experts, int32_t low_rank);
 
 /* backward of dctr_cin_fwd (interaction.py:277-325).  Layers with H % 16 == 0, H <= 128, F0 <= 32, Fk <= 64 run z-free on two
  * MFMA kernels (filter gradient with x0*xk formed in registers; dz = dpre W^T contracted with x0 / xk tile by tile); other
