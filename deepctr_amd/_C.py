@@ -146,6 +146,12 @@ class interacting(object):
                     ("out", c_vp), ("out_stride", c_i64), ("head_w", c_vp), ("logit", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_interacting_bwd_args_t (tests/test_interacting_bwd_oracle_cpu.py checks the layout)
+interacting.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", interacting.Args), ("dy", c_vp), ("dy_stride", c_i64), ("dx", c_vp), ("dx_stride", c_i64), ("d_layers", c_vp),
+    ("accumulate", c_i32), ("max_blocks", c_i32)]})
+
+
 class bilinear(object):
     """dctr_bilinear_args_t, one level down for the same reason as interacting.Args (tests/test_fibinet_cpu.py checks its layout)."""
     ALL, EACH, INTERACTION = 0, 1, 2
@@ -440,6 +446,9 @@ SYMBOLS = {
     "dctr_cin_gather_fwd": (ctypes.c_int, [ctypes.POINTER(CinArgs), ctypes.POINTER(GatherFmArgs), c_vp, c_vp, c_vp]),
     "dctr_interacting_workspace_bytes": (c_sz, [ctypes.POINTER(interacting.Args)]),
     "dctr_interacting_fwd": (ctypes.c_int, [ctypes.POINTER(interacting.Args), c_vp]),
+    "dctr_interacting_bwd_supported": (ctypes.c_int, [ctypes.POINTER(interacting.BwdArgs)]),
+    "dctr_interacting_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(interacting.BwdArgs)]),
+    "dctr_interacting_bwd": (ctypes.c_int, [ctypes.POINTER(interacting.BwdArgs), c_vp]),
     "dctr_bilinear_workspace_bytes": (c_sz, [ctypes.POINTER(bilinear.Args)]),
     "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
     "dctr_fieldpair_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.Args)]),

@@ -49,6 +49,7 @@ SOURCES = [
     "cin_bwd_kernels.hip",
     "cin_layered_kernels.hip",
     "interacting_kernels.hip",
+    "interacting_bwd_kernels.hip",
     "bilinear_kernels.hip",
     "fieldpair_kernels.hip",
     "ffm_kernels.hip",

@@ -161,7 +161,12 @@ class InteractingLayer(Layer):
     def call(self, inputs, **kwargs):
         if inputs.dim() != 3:
             raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
-        y = ops.interacting(inputs, [self.weights_qkvr], self.att_embedding_size, self.head_num, self.use_res, self.scaling)
+        qkvr = self.weights_qkvr
+        if inputs.is_cuda and torch.is_grad_enabled() and (inputs.requires_grad or any(w is not None and w.requires_grad for w in qkvr)):
+            # differentiable: the same forward launch, dctr_interacting_bwd behind it
+            y = ops.InteractingFunction.apply(inputs, self.att_embedding_size, self.head_num, self.use_res, self.scaling, *qkvr)
+        else:
+            y = ops.interacting(inputs, [qkvr], self.att_embedding_size, self.head_num, self.use_res, self.scaling)
         return y.reshape(inputs.shape[0], inputs.shape[1], self.att_embedding_size * self.head_num)
 
     def compute_output_shape(self, input_shape):

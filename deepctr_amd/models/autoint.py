@@ -86,9 +86,7 @@ class _AutoInt(FeatureModel):
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # autoint.py:55-79
         outs = []
         if self.att_layers:
-            h = torch.stack(parts[:self.n_fields], dim=1)          # [B,F,E]
-            for layer in self.att_layers:
-                h = tops._interacting(layer, h)
+            h = tops.interacting_stack(self.att_layers, torch.stack(parts[:self.n_fields], dim=1))          # [B,F,E] -> [B,F,d*H]
             outs.append(h.reshape(h.shape[0], -1))
         if self.dnn is not None:
             outs.append(tops.dnn_forward(self.dnn, torch.cat(parts, dim=-1), training))

@@ -47,7 +47,7 @@ class _DIFM(InputAwareModel):
         bufs["m_vec"] = torch.zeros(B, self.n_fields, dtype=torch.float32, device=self.device)
 
     def _autograd_factor(self, x, h):
-        att = tops._interacting(self.att, x)
+        att = tops.interacting_stack([self.att], x)
         return att.reshape(att.shape[0], -1) @ self.dense.w("kernel") + h @ self.dense_1.w("kernel")
 
     def _forward(self, staged, lo, hi, out):

@@ -650,6 +650,103 @@ def interacting(x, weights, att_embedding_size, head_num, use_res, scaling, fiel
     return out if out is not None else logit
 
 
+def _interacting_bwd_shape(fields, dim, n_layers, att_embedding_size, head_num, use_res, batch=1):
+    dH = int(att_embedding_size) * int(head_num)
+    b = _C.interacting.BwdArgs(dy_stride=int(fields) * dH)
+    b.fwd = _C.interacting.Args(batch=int(batch), x_stride=int(fields) * int(dim), fields=int(fields), dim=int(dim),
+                                n_layers=int(n_layers), att_embedding_size=int(att_embedding_size), head_num=int(head_num),
+                                use_res=int(bool(use_res)))
+    return b
+
+
+def interacting_bwd_supported(fields, dim, n_layers, att_embedding_size, head_num, use_res=True):
+    """Does dctr_interacting_bwd take these shapes (read from the library)?"""
+    b = _interacting_bwd_shape(fields, dim, n_layers, att_embedding_size, head_num, use_res)
+    return bool(_C.lib().dctr_interacting_bwd_supported(ctypes.byref(b)))
+
+
+def interacting_bwd_workspace_bytes(batch, fields, dim, n_layers, att_embedding_size, head_num, use_res=True):
+    """Bytes of the workspace dctr_interacting_bwd needs for these shapes (0 on the LDS route; read from the library)."""
+    b = _interacting_bwd_shape(fields, dim, n_layers, att_embedding_size, head_num, use_res, batch)
+    return int(_C.lib().dctr_interacting_bwd_workspace_bytes(ctypes.byref(b)))
+
+
+def interacting_bwd(x, weights, att_embedding_size, head_num, use_res, scaling, dy, fields=None, dim=None, dx=None, accumulate=False,
+                    d_weights=None, max_blocks=0, workspace=None):
+    """Backward of interacting() over the whole stack, one launch (include/dctr.h: dctr_interacting_bwd); the forward saves nothing.
+    ``x`` / ``weights`` / ``fields`` / ``dim`` as interacting(); ``dy``: a float32 [B, >= F*d*H] view, the gradient w.r.t. the flattened
+    last layer.  ``dx`` [B, >= F*E] (2-D view): its leading F*E columns are written, or added to with ``accumulate``.  ``d_weights``: per
+    layer (d_query, d_key, d_value, d_res), contiguous and of the weights' shapes, ACCUMULATED into; any entry, or the list, may be None."""
+    x, B, F, E, x_stride, _ = _x_in_place("interacting_bwd", x, fields, dim)
+    weights = [[None if w is None else _f32c(w, "weight") for w in layer] for layer in weights]
+    dH = int(att_embedding_size) * int(head_num)
+    dy_stride = _rows2d("interacting_bwd", "dy", dy, B, F * dH)
+    dx_stride = 0 if dx is None else _rows2d("interacting_bwd", "dx", dx, B, F * E)
+    flat_d = []
+    if d_weights is not None:
+        if len(d_weights) != len(weights):
+            raise ValueError("interacting_bwd: d_weights must hold one entry per layer")
+        for l, layer in enumerate(d_weights):
+            layer = list(layer) + [None] * (4 - len(layer))
+            for m in range(4):
+                g = layer[m] if m < 3 or use_res else None
+                if g is not None:
+                    _vec("interacting_bwd", "d_weights[%d][%d]" % (l, m), g, (E if l == 0 else dH) * dH)
+                flat_d.append(g)
+    _dev_check(x, dy, dx, *([w for layer in weights for w in layer] + flat_d))
+    b = _C.interacting.BwdArgs(dy=dy.data_ptr(), dy_stride=dy_stride, accumulate=int(bool(accumulate)), max_blocks=int(max_blocks))
+    b.fwd, keep = _interacting_args(B, F, E, x_stride, weights, att_embedding_size, head_num, use_res, scaling)
+    b.fwd.x = x.data_ptr()
+    if dx is not None:
+        b.dx, b.dx_stride = dx.data_ptr(), dx_stride
+    keep_d = _ptr_array(flat_d)
+    if flat_d:
+        b.d_layers = ctypes.cast(keep_d, ctypes.c_void_p)
+    _workspace("interacting_bwd", b.fwd, int(_C.lib().dctr_interacting_bwd_workspace_bytes(ctypes.byref(b))), workspace, x.device)
+    _C.check(_C.lib().dctr_interacting_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_interacting_bwd")
+    del keep, keep_d
+
+
+class InteractingFunction(torch.autograd.Function):
+    """The InteractingLayer stack as one differentiable op: interacting() forward and interacting_bwd() backward, one launch each.
+    ``apply(x, att_embedding_size, head_num, use_res, scaling, *weights)``: x [B,F,E]; ``weights`` flat, four per layer (query, key,
+    value, res — res None when ``use_res`` is off).  Returns [B, F*d*H].  Only x and the weights are saved: the backward recomputes."""
+
+    @staticmethod
+    def forward(ctx, x, att_embedding_size, head_num, use_res, scaling, *weights):
+        ctx.cfg = (int(att_embedding_size), int(head_num), bool(use_res), bool(scaling))
+        x = x.detach()
+        ws = [None if w is None else w.detach() for w in weights]
+        out = torch.empty(x.shape[0], x.shape[1] * ctx.cfg[0] * ctx.cfg[1], dtype=torch.float32, device=x.device)
+        interacting(x, [ws[i:i + 4] for i in range(0, len(ws), 4)], ctx.cfg[0], ctx.cfg[1], ctx.cfg[2], ctx.cfg[3], out=out)
+        ctx.present = [w is not None for w in ws]
+        ctx.save_for_backward(x, *[w for w in ws if w is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        d, H, use_res, scaling = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        x, it = saved[0], iter(saved[1:])
+        ws = [next(it) if present else None for present in ctx.present]
+        if dy.dtype != torch.float32:
+            dy = dy.float()
+        if dy.stride(-1) != 1 or (dy.shape[0] > 1 and dy.stride(0) < dy.shape[1]):      # (the second: rows broadcast by expand())
+            dy = dy.contiguous()
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
+        # the op accumulates: the wanted weight gradients are views of ONE zeroed buffer (one fill for the whole stack)
+        wanted = [w is not None and ctx.needs_input_grad[5 + i] and (i % 4 < 3 or use_res) for i, w in enumerate(ws)]
+        flat = torch.zeros(sum(w.numel() for w, on in zip(ws, wanted) if on), dtype=torch.float32, device=x.device)
+        grads, at = [], 0
+        for w, on in zip(ws, wanted):
+            grads.append(flat[at:at + w.numel()].view(w.shape) if on else None)
+            at += w.numel() if on else 0
+        interacting_bwd(x, [ws[i:i + 4] for i in range(0, len(ws), 4)], d, H, use_res, scaling, dy,
+                        dx=None if dx is None else dx.view(dx.shape[0], -1),
+                        d_weights=[grads[i:i + 4] for i in range(0, len(ws), 4)])
+        return (dx, None, None, None, None) + tuple(grads)
+
+
 _BILINEAR_TABLES = {}
 
 

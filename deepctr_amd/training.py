@@ -290,6 +290,28 @@ def _interacting(layer, x):
     return torch.relu(o)
 
 
+HIP_AUTOGRAD_OPS = True     # the autograd step may run an operator as one differentiable HIP op (interacting_stack); off: torch ops only
+
+
+def interacting_stack(layers, x):
+    """A stack of InteractingLayers over x [B,F,E] -> [B,F,d*H] inside the autograd step.  On the GPU, with gradients enabled, the
+    whole stack is ops.InteractingFunction: dctr_interacting_fwd forward and dctr_interacting_bwd backward, one launch each, nothing
+    between the layers in HBM (profiles/autoint_interacting_bwd.txt: faster at 4,096 and at 65,536 rows, so no row threshold).
+    Everything else — the CPU, torch.no_grad() (model_logits as the reference of the HIP forward), HIP_AUTOGRAD_OPS off, layers that
+    differ in their options, a shape the backward refuses — takes the torch ops of _interacting, layer by layer."""
+    layers = list(layers)
+    if layers and x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32:
+        first = layers[0]
+        d, H, res, scaling = first.att_embedding_size, first.head_num, bool(first.use_res), bool(first.scaling)
+        same = all((l.att_embedding_size, l.head_num, bool(l.use_res), bool(l.scaling)) == (d, H, res, scaling) for l in layers)
+        if same and ops.interacting_bwd_supported(x.shape[1], x.shape[2], len(layers), d, H, res):
+            flat = [w for l in layers for w in l.weights_qkvr]
+            return ops.InteractingFunction.apply(x, d, H, res, scaling, *flat).reshape(x.shape[0], x.shape[1], d * H)
+    for layer in layers:
+        x = _interacting(layer, x)
+    return x
+
+
 def _layer_norm(ln, x):
     """LayerNormalization.call (reference layers/normalization.py:34-43) in torch ops."""
     mean = x.mean(dim=-1, keepdim=True)

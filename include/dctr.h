@@ -423,6 +423,35 @@ typedef struct {
 size_t dctr_interacting_workspace_bytes(const dctr_interacting_args_t* args);
 int dctr_interacting_fwd(const dctr_interacting_args_t* args, void* stream);
 
+/* Backward of dctr_interacting_fwd over the whole stack, one launch; nothing is saved by the forward (every layer's input is
+ * recomputed per tile of samples and kept on chip).  fwd: x, batch, x_stride, fields, dim, n_layers, att_embedding_size, head_num,
+ * use_res, scaling, layers and workspace (+ bytes) are read; out / out_stride / head_w / logit are ignored.  The upstream gradient is
+ * dy [B, dy_stride] w.r.t. the flattened last layer (index f*d*H + h*d + j).  Per layer, last to first, with s = 1/sqrt(d) when
+ * scaling else 1, Z = concat_h(P_h V_h) (+ X W_res), Y = relu(Z):
+ *     dZ = dY [Z > 0];   dV_h = P_h^T dZ_h;   dP = dZ_h V_h^T;   delta_i = sum_j P_ij dP_ij;   dS = s P (dP - delta);
+ *     dQ_h = dS K_h;   dK_h = dS^T Q_h;   dX = dQ W_q^T + dK W_k^T + dV W_v^T (+ dZ W_res^T);   dX of layer l is dY of layer l-1.
+ * dx [B, dx_stride]: columns [0, F*dim) are written (accumulate = 0) or added to (1), the others untouched; no atomics inside a
+ * sample, so dx is bit-identical from call to call.  ACCUMULATED (d_layers itself or any entry may be NULL):
+ * d_layers[4l + m] += X_l^T dM for M = Q, K, V (, Z for res) — summed per workgroup over all its tiles, one atomic per workgroup and
+ * element.  Arithmetic is fp32 on the f32 matrix cores for the projections and the dX / dW products, as the forward.
+ * A sample whose buffers exceed the LDS (large F, wide d*H, many layers) runs with them in fwd.workspace
+ * (dctr_interacting_bwd_workspace_bytes; REQUIRED then: DCTR_E_NULL without, DCTR_E_ALIGN when not 16-B aligned).  More than 32
+ * layers, or one sample's buffers past 2^31 floats, answer DCTR_E_UNSUPPORTED before anything is launched
+ * (dctr_interacting_bwd_supported: 1 / 0).  Argument errors (DCTR_E_NULL / _DIM / _ENUM / _ALIGN) launch and write nothing. */
+typedef struct {
+    dctr_interacting_args_t fwd;
+    const float* dy;              /* [B, dy_stride], dy_stride >= fields*d*H */
+    int64_t dy_stride;
+    float* dx;                    /* NULL, or [B, dx_stride], dx_stride >= fields*dim */
+    int64_t dx_stride;
+    float* const* d_layers;       /* NULL, or HOST array [n_layers * 4] of DEVICE pointers, shapes of fwd.layers; each may be NULL */
+    int32_t accumulate;           /* 0 | 1: dx written | added to */
+    int32_t max_blocks;           /* 0 = 2 per compute unit, else the most workgroups to launch (each walks its tiles) */
+} dctr_interacting_bwd_args_t;
+int dctr_interacting_bwd_supported(const dctr_interacting_bwd_args_t* args);          /* host only */
+size_t dctr_interacting_bwd_workspace_bytes(const dctr_interacting_bwd_args_t* args); /* host only; 0: none (or an argument error) */
+int dctr_interacting_bwd(const dctr_interacting_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * SENETLayer.call + BilinearInteraction.call — deepctr/layers/interaction.py:1067-1221, wired as deepctr/models/fibinet.py:50-58
  *     x_f [dim] for f < F (F >= 2, one dim).  SENET: Z = mean(x_f) [F]; A1 = relu(Z W_1) [r]; A2 = relu(A1 W_2) [F];
