@@ -175,6 +175,13 @@ class fieldpair(object):
                     ("pairs_offset", c_i64), ("add", c_vp), ("logit_out", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_fieldpair_bwd_args_t (tests/test_fieldpair_bwd_oracle_cpu.py checks the layout)
+fieldpair.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", fieldpair.Args), ("d_pairs", c_vp), ("d_pairs_stride", c_i64), ("d_pairs_offset", c_i64), ("d_logit", c_vp), ("dx", c_vp),
+    ("dx_stride", c_i64), ("dx_offset", c_i64), ("accumulate", c_i32), ("reserved", c_i32), ("d_weights", c_vp), ("max_blocks", c_i32),
+    ("reserved2", c_i32)]})
+
+
 class ffm(object):
     """dctr_ffm_field_t / dctr_ffm_args_t, one level down for the same reason as interacting.Args (tests/test_onn_cpu.py checks the layout)."""
     ROUTE_AUTO, ROUTE_DIRECT, ROUTE_LDS = 0, 1, 2
@@ -453,6 +460,9 @@ SYMBOLS = {
     "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
     "dctr_fieldpair_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.Args)]),
     "dctr_fieldpair_fwd": (ctypes.c_int, [ctypes.POINTER(fieldpair.Args), c_vp]),
+    "dctr_fieldpair_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.BwdArgs)]),
+    "dctr_fieldpair_bwd_supported": (ctypes.c_int, [ctypes.POINTER(fieldpair.BwdArgs)]),
+    "dctr_fieldpair_bwd": (ctypes.c_int, [ctypes.POINTER(fieldpair.BwdArgs), c_vp]),
     "dctr_ffm_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_route": (ctypes.c_int, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_fwd": (ctypes.c_int, [ctypes.POINTER(ffm.Args), c_vp]),

@@ -52,6 +52,7 @@ SOURCES = [
     "interacting_bwd_kernels.hip",
     "bilinear_kernels.hip",
     "fieldpair_kernels.hip",
+    "fieldpair_bwd_kernels.hip",
     "ffm_kernels.hip",
     "ifm_kernels.hip",
     "fieldwise_kernels.hip",

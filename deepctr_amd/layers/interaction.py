@@ -381,7 +381,12 @@ class FwFMLayer(Layer):
         if inputs.shape[1] != self.num_fields:
             raise ValueError("Mismatch in number of fields {} and concatenated embeddings dims {}".format(self.num_fields,
                                                                                                          inputs.shape[1]))
-        _, logit = ops.fieldpair(inputs, self.field_strengths, kind="fwfm")
+        r = self.field_strengths
+        if inputs.is_cuda and torch.is_grad_enabled() and (inputs.requires_grad or r.requires_grad):
+            # differentiable: the same forward launch, dctr_fieldpair_bwd behind it
+            _, logit = ops.FieldPairFunction.apply(inputs, "fwfm", False, True, r)
+        else:
+            _, logit = ops.fieldpair(inputs, r, kind="fwfm")
         return logit.reshape(-1, 1)
 
     def compute_output_shape(self, input_shape):
@@ -426,7 +431,12 @@ class FEFMLayer(Layer):
     def call(self, inputs, **kwargs):
         if inputs.dim() != 3:
             raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
-        pairs, _ = ops.fieldpair(inputs, self.matrices, kind="fefm", pairs=True)
+        ws = self.matrices
+        if inputs.is_cuda and torch.is_grad_enabled() and (inputs.requires_grad or any(w.requires_grad for w in ws)):
+            # differentiable: the same forward launch, dctr_fieldpair_bwd behind it
+            pairs, _ = ops.FieldPairFunction.apply(inputs, "fefm", True, False, *ws)
+        else:
+            pairs, _ = ops.fieldpair(inputs, ws, kind="fefm", pairs=True)
         return pairs
 
     def compute_output_shape(self, input_shape):

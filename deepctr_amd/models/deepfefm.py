@@ -105,7 +105,9 @@ class _DeepFEFM(FeatureModel):
             ops.mlp(rest[0].reshape(-1, 1), [], [], "linear", head_w=self._one(), add=rest[1:], in_dim=1, **kw)
 
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # deepfefm.py:62-99: the ablation switches
-        pairs = tops._fefm(self.fefm, torch.stack(tops._group_embeddings(self.stage_plan, parts, DEFAULT_GROUP_NAME), dim=1))
+        # the pairs only when they enter the DNN, their sum only when use_fefm; neither: nothing is computed
+        pairs, fefm_logit = tops.fefm_pairs(self.fefm, torch.stack(tops._group_embeddings(self.stage_plan, parts, DEFAULT_GROUP_NAME), dim=1),
+                                            want_pairs=self.dnn is not None and self.pairs_in_dnn, want_logit=self.use_fefm)
         logit = torch.zeros(hi - lo, device=self.device)
         if self.dnn is not None:
             if not self.pairs_in_dnn:
@@ -116,7 +118,7 @@ class _DeepFEFM(FeatureModel):
                 h = torch.cat(parts + [pairs], dim=-1)
             logit = logit + (tops.dnn_forward(self.dnn, h, training) @ self.dense.w("kernel")).reshape(-1)
         if self.use_fefm:
-            logit = logit + pairs.sum(-1)
+            logit = logit + fefm_logit
         return logit
 
     def _autograd_tail(self, logit, lin, fms):

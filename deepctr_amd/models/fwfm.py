@@ -75,9 +75,7 @@ class _FwFM(FeatureModel):
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # fwfm.py:51-66
         logit = torch.zeros(hi - lo, device=self.device)
         for g, layer in zip(self.groups, self.fwfm_layers):
-            x = torch.stack(tops._group_embeddings(self.stage_plan, parts, g), dim=1)
-            gram = torch.einsum("bie,bje->bij", x, x)
-            logit = logit + (gram * torch.triu(layer.field_strengths, diagonal=1)).sum((1, 2))
+            logit = logit + tops.fwfm_logit(layer, torch.stack(tops._group_embeddings(self.stage_plan, parts, g), dim=1))
         if self.dnn is not None:
             h = tops.dnn_forward(self.dnn, torch.cat(parts, dim=-1), training)
             logit = logit + (h @ self.dense.w("kernel")).reshape(-1)

@@ -925,6 +925,143 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
     return pairs, logit
 
 
+def _fieldpair_bwd_shape(kind, batch, fields, dim):
+    if kind not in _FIELDPAIR_KINDS:
+        raise ValueError("fieldpair_bwd: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
+    b = _C.fieldpair.BwdArgs()
+    b.fwd = _fieldpair_args(_FIELDPAIR_KINDS[kind], batch, fields, dim, int(fields) * int(dim))
+    return b
+
+
+def fieldpair_bwd_supported(fields, dim, kind="fefm"):
+    """Does dctr_fieldpair_bwd take these shapes (read from the library)?"""
+    return bool(_C.lib().dctr_fieldpair_bwd_supported(ctypes.byref(_fieldpair_bwd_shape(kind, 1, fields, dim))))
+
+
+def fieldpair_bwd_workspace_bytes(batch, fields, dim, kind="fefm"):
+    """Bytes of the workspace dctr_fieldpair_bwd needs for these shapes (0 on the LDS route; read from the library)."""
+    return int(_C.lib().dctr_fieldpair_bwd_workspace_bytes(ctypes.byref(_fieldpair_bwd_shape(kind, batch, fields, dim))))
+
+
+def fieldpair_bwd(x, weights, kind, d_pairs=None, d_pairs_offset=0, d_logit=None, fields=None, dim=None, x_offset=0, dx=None,
+                  dx_offset=0, accumulate=False, d_weights=None, max_blocks=0, workspace=None):
+    """Backward of fieldpair(), one launch (include/dctr.h: dctr_fieldpair_bwd); the forward saves nothing.  ``x`` / ``weights`` /
+    ``kind`` / ``fields`` / ``dim`` / ``x_offset`` as fieldpair().  ``d_pairs`` (FEFM only): a float32 2-D view whose row holds the
+    gradient of the P pair scalars from column ``d_pairs_offset``; ``d_logit`` [B]: the gradient of the logit; FEFM takes either or
+    both, FwFM ``d_logit``.  ``dx``: a 2-D view [B, >= dx_offset + F*E] (or [B,F,E] contiguous) whose F*E columns from ``dx_offset`` are
+    written, or added to with ``accumulate`` — bit-identical from call to call.  ``d_weights``: ACCUMULATED into; FEFM one contiguous
+    [P,E,E] tensor, FwFM [F,F] of which only the strict upper triangle is touched.  Weight gradients leave through float atomics and
+    may differ in the last bits from call to call."""
+    if kind not in _FIELDPAIR_KINDS:
+        raise ValueError("fieldpair_bwd: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
+    x, B, F, E, x_stride, x_offset = _x_in_place("fieldpair_bwd", x, fields, dim, x_offset)
+    if F < 2:
+        raise ValueError("fieldpair_bwd: %d field(s): a field pair needs at least 2" % F)
+    P = F * (F - 1) // 2
+    tensors = [x]
+    if kind == "fefm":
+        ws = [_f32c(w, "field_embeddings") for w in weights]
+        if len(ws) != P or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("fieldpair_bwd: FEFM over %d fields takes %d matrices [%d, %d]" % (F, P, E, E))
+        tensors += ws
+        wptr = bilinear_table(ws)
+        if d_pairs is None and d_logit is None:
+            raise ValueError("fieldpair_bwd: FEFM needs d_pairs and / or d_logit")
+    else:
+        r = _f32c(weights, "field_pair_strengths")
+        if tuple(r.shape) != (F, F):
+            raise ValueError("fieldpair_bwd: FwFM over %d fields takes field_pair_strengths [%d, %d]" % (F, F, F))
+        if d_pairs is not None:
+            raise ValueError("fieldpair_bwd: the FwFM kind has no pair gradients")
+        if d_logit is None:
+            raise ValueError("fieldpair_bwd: FwFM needs d_logit")
+        tensors.append(r)
+        wptr = r
+    d_pairs_stride = 0 if d_pairs is None else _rows2d("fieldpair_bwd", "d_pairs", d_pairs, B, P, d_pairs_offset)
+    if d_logit is not None:
+        _vec("fieldpair_bwd", "d_logit", d_logit, B)
+    dx_stride = 0
+    if dx is not None:
+        if dx.dim() == 3 and dx_offset == 0 and tuple(dx.shape) == (B, F, E) and dx.is_contiguous() and dx.dtype == torch.float32:
+            dx_stride = F * E
+        else:
+            dx_stride = _rows2d("fieldpair_bwd", "dx", dx, B, F * E, dx_offset)
+    if d_weights is not None:
+        _vec("fieldpair_bwd", "d_weights", d_weights, P * E * E if kind == "fefm" else F * F)
+    _dev_check(d_pairs, d_logit, dx, d_weights, *tensors)
+    b = _C.fieldpair.BwdArgs(d_pairs_stride=d_pairs_stride, d_pairs_offset=int(d_pairs_offset), dx_stride=dx_stride,
+                             dx_offset=int(dx_offset), accumulate=int(bool(accumulate)), max_blocks=int(max_blocks))
+    b.fwd = _fieldpair_args(_FIELDPAIR_KINDS[kind], B, F, E, x_stride, x_offset)
+    b.fwd.x, b.fwd.weights = x.data_ptr(), wptr.data_ptr()
+    if d_pairs is not None:
+        b.d_pairs = d_pairs.data_ptr()
+    if d_logit is not None:
+        b.d_logit = d_logit.data_ptr()
+    if dx is not None:
+        b.dx = dx.data_ptr()
+    if d_weights is not None:
+        b.d_weights = d_weights.data_ptr()
+    _workspace("fieldpair_bwd", b.fwd, int(_C.lib().dctr_fieldpair_bwd_workspace_bytes(ctypes.byref(b))), workspace, x.device)
+    _C.check(_C.lib().dctr_fieldpair_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_fieldpair_bwd")
+
+
+def _grad_operand(dy, rows2d):
+    """An incoming gradient as the op reads it: float32, unit column stride, rows not broadcast by expand()."""
+    if dy is None:
+        return None
+    if dy.dtype != torch.float32:
+        dy = dy.float()
+    if rows2d:
+        if dy.stride(-1) != 1 or (dy.shape[0] > 1 and dy.stride(0) < dy.shape[1]):
+            dy = dy.contiguous()
+    elif not dy.is_contiguous():
+        dy = dy.contiguous()
+    return dy
+
+
+class FieldPairFunction(torch.autograd.Function):
+    """FEFMLayer / FwFMLayer as one differentiable op: fieldpair() forward and fieldpair_bwd() backward, one launch each.
+    ``apply(x, kind, want_pairs, want_logit, *weights)``: x [B,F,E]; ``weights`` = the P pair matrices (FEFM) or field_pair_strengths
+    (FwFM).  Returns (pairs [B,P] or None, logit [B] or None).  Only x and the weights are saved: the backward loads x again.  Weight
+    gradients leave the kernel through float atomics and may differ in the last bits from call to call; dx does not."""
+
+    @staticmethod
+    def forward(ctx, x, kind, want_pairs, want_logit, *weights):
+        ctx.set_materialize_grads(False)
+        ctx.kind = kind
+        x = x.detach()
+        ws = [w.detach() for w in weights]
+        pairs, logit = fieldpair(x, ws if kind == "fefm" else ws[0], kind=kind, pairs=True if want_pairs else None,
+                                 logit=True if want_logit else None)
+        ctx.save_for_backward(x, *ws)
+        return pairs, logit
+
+    @staticmethod
+    def backward(ctx, d_pairs, d_logit):
+        saved = list(ctx.saved_tensors)
+        x, ws = saved[0], saved[1:]
+        fefm = ctx.kind == "fefm"
+        want_dx = ctx.needs_input_grad[0]
+        want_dw = any(ctx.needs_input_grad[4:])
+        if d_pairs is None and d_logit is None:
+            return (None,) * (4 + len(ws))
+        d_pairs, d_logit = _grad_operand(d_pairs, True), _grad_operand(d_logit, False)
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dx else None
+        # the op accumulates: the P FEFM weight gradients are views of ONE zeroed buffer
+        flat = None
+        if want_dw:
+            flat = torch.zeros((len(ws),) + tuple(ws[0].shape) if fefm else tuple(ws[0].shape), dtype=torch.float32, device=x.device)
+        if want_dx or want_dw:
+            fieldpair_bwd(x, ws if fefm else ws[0], ctx.kind, d_pairs=d_pairs, d_logit=d_logit, dx=dx, d_weights=flat)
+        if flat is None:
+            grads = [None] * len(ws)
+        elif fefm:
+            grads = [flat[i] if ctx.needs_input_grad[4 + i] else None for i in range(len(ws))]
+        else:
+            grads = [flat]
+        return (dx, None, None, None) + tuple(grads)
+
+
 _FFM_ROUTES = {None: _C.ffm.ROUTE_AUTO, "auto": _C.ffm.ROUTE_AUTO, "direct": _C.ffm.ROUTE_DIRECT}
 
 

@@ -312,6 +312,44 @@ def interacting_stack(layers, x):
     return x
 
 
+# Below this many rows FEFMLayer's autograd step stays on the torch ops: the HIP route validates the 325 weight tensors on the host in
+# both launches and hands autograd 325 gradient views, which at 4,096 rows of the Criteo shape costs more than the kernels save (6.82
+# against 6.27 ms a step; the two routes cross near 5,400 rows and at 8,192 HIP wins: profiles/fefm_fieldpair_bwd.txt).  FwFM has one
+# weight tensor and no threshold.
+FEFM_HIP_MIN_ROWS = 8192
+
+
+def _fieldpair_on_hip(x, weights, kind, min_rows=0):
+    """The gate of fefm_pairs / fwfm_logit: interacting_stack's, something must actually require grad, and FEFM's row threshold."""
+    return (x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32 and x.shape[0] >= min_rows
+            and (x.requires_grad or any(w.requires_grad for w in weights))
+            and ops.fieldpair_bwd_supported(x.shape[1], x.shape[2], kind))
+
+
+def fefm_pairs(layer, x, want_pairs=True, want_logit=False):
+    """FEFMLayer over x [B,F,E] inside the autograd step: (pairs [B,P] or None, their row sum [B] or None).  On the GPU, with gradients
+    enabled and something requiring grad, it is ops.FieldPairFunction: dctr_fieldpair_fwd forward and dctr_fieldpair_bwd backward, one
+    launch each, no [B,P,E] intermediate in HBM (profiles/fefm_fieldpair_bwd.txt).  Everything else — the CPU, torch.no_grad(),
+    HIP_AUTOGRAD_OPS off, fewer than FEFM_HIP_MIN_ROWS rows, a shape the backward refuses — takes the torch ops of _fefm."""
+    if not (want_pairs or want_logit):
+        return None, None
+    ws = layer.matrices
+    if _fieldpair_on_hip(x, ws, "fefm", FEFM_HIP_MIN_ROWS):
+        return ops.FieldPairFunction.apply(x, "fefm", bool(want_pairs), bool(want_logit), *ws)
+    pairs = _fefm(layer, x)
+    return (pairs if want_pairs else None), (pairs.sum(-1) if want_logit else None)
+
+
+def fwfm_logit(layer, x):
+    """FwFMLayer over x [B,F,E] inside the autograd step: the logit [B].  The gate of fefm_pairs; otherwise the einsum over the Gram
+    matrix and the strict upper triangle of field_pair_strengths."""
+    r = layer.field_strengths
+    if _fieldpair_on_hip(x, [r], "fwfm"):
+        return ops.FieldPairFunction.apply(x, "fwfm", False, True, r)[1]
+    gram = torch.einsum("bie,bje->bij", x, x)
+    return (gram * torch.triu(r, diagonal=1)).sum((1, 2))
+
+
 def _layer_norm(ln, x):
     """LayerNormalization.call (reference layers/normalization.py:34-43) in torch ops."""
     mean = x.mean(dim=-1, keepdim=True)

@@ -533,6 +533,41 @@ typedef struct {
 size_t dctr_fieldpair_workspace_bytes(const dctr_fieldpair_args_t* args);
 int dctr_fieldpair_fwd(const dctr_fieldpair_args_t* args, void* stream);
 
+/* Backward of dctr_fieldpair_fwd, one launch; nothing is saved by the forward (the kernel loads the same X tile again).  fwd: batch, x,
+ * x_stride, x_offset, fields, dim, kind, weights and workspace (+ bytes) are read as the forward reads them; pairs_out / pairs_stride /
+ * pairs_offset / add / logit_out are ignored.  With g_b,ij = d_pairs[b, ij] + d_logit[b] (a NULL term is 0) and S = W + W^T:
+ *   FEFM: dx_i = sum_{j != i} g_ij S_ij x_j, the pair (i, j) with j < i being the matrix of (j, i);
+ *         d_weights[ij] += A + A^T with A = sum_b g_b,ij x_i x_j^T.  At least one of d_pairs / d_logit.
+ *   FWFM: dx_i = d_logit sum_{j != i} r'_ij x_j with r' the strict upper triangle mirrored; d_weights[i][j] += sum_b d_logit_b <x_i, x_j>
+ *         for i < j: the diagonal and the lower triangle of d_weights are not touched.  d_logit is required, d_pairs must be NULL.
+ * dx: the F*dim columns from dx_offset of a row of dx_stride floats are written (accumulate = 0) or added to (1), the others
+ * untouched; one owner per (sample, field, column) and no atomics, so dx is bit-identical from call to call.  d_weights is ACCUMULATED
+ * into (zero it first): summed per workgroup over all the tiles it walks, one float atomic per element and workgroup (dim > 16: two per
+ * element and tile), so weight gradients may differ in the last bits from call to call.  Arithmetic is fp32, FEFM's products on the
+ * f32 matrix cores as the forward.  With neither dx nor d_weights nothing is launched.
+ * A tile too large for the LDS runs in fwd.workspace (dctr_fieldpair_bwd_workspace_bytes; REQUIRED then: DCTR_E_NULL without,
+ * DCTR_E_ALIGN when not 16-B aligned).  No shape the forward takes is refused, unless one tile's buffers pass 2^30 floats (FwFM over
+ * more than ~32,000 fields): DCTR_E_UNSUPPORTED before anything is launched, every output untouched (dctr_fieldpair_bwd_supported:
+ * 1 / 0).  Argument errors (DCTR_E_NULL / _DIM / _ENUM / _ALIGN) launch and write nothing. */
+typedef struct {
+    dctr_fieldpair_args_t fwd;
+    const float* d_pairs;         /* FEFM only, may be NULL: row b at d_pairs + b * d_pairs_stride + d_pairs_offset, P floats */
+    int64_t d_pairs_stride;       /* >= d_pairs_offset + P */
+    int64_t d_pairs_offset;       /* >= 0 */
+    const float* d_logit;         /* may be NULL (FEFM): [batch], the gradient w.r.t. logit_out */
+    float* dx;                    /* may be NULL: row b at dx + b * dx_stride + dx_offset, fields*dim floats */
+    int64_t dx_stride;            /* >= dx_offset + fields*dim */
+    int64_t dx_offset;            /* >= 0 */
+    int32_t accumulate;           /* 0 | 1: dx written | added to */
+    int32_t reserved;             /* 0 */
+    float* d_weights;             /* may be NULL; ACCUMULATED into.  FEFM: one contiguous [P, dim, dim]; FWFM: [F, F] */
+    int32_t max_blocks;           /* 0: the library's choice (FEFM: one workgroup per compute unit); > 0 caps the grid */
+    int32_t reserved2;            /* 0 */
+} dctr_fieldpair_bwd_args_t;
+size_t dctr_fieldpair_bwd_workspace_bytes(const dctr_fieldpair_bwd_args_t* args); /* host only; 0: none (or an argument error) */
+int dctr_fieldpair_bwd_supported(const dctr_fieldpair_bwd_args_t* args);          /* host only, reads shapes only */
+int dctr_fieldpair_bwd(const dctr_fieldpair_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ONN's field-aware embedding lookup + pair products — deepctr/models/onn.py:59-99 (no layer class in the reference)
  *     F >= 2 fields of one embedding_dim d.  Field j owns ONE fused table [vocab_j, F-1, d] (rows row_pitch floats apart): row r holds
