@@ -165,6 +165,13 @@ class bilinear(object):
                     ("workspace_bytes", c_sz)]
 
 
+# dctr_bilinear_bwd_args_t (tests/test_bilinear_bwd_oracle_cpu.py checks the layout)
+bilinear.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", bilinear.Args), ("d_out", c_vp), ("d_out_stride", c_i64), ("d_out_offset", c_i64), ("dx", c_vp), ("dx_stride", c_i64),
+    ("dx_offset", c_i64), ("accumulate", c_i32), ("max_blocks", c_i32), ("d_senet_w1", c_vp), ("d_senet_w2", c_vp),
+    ("d_senet_bilinear_w", c_vp), ("d_bilinear_w", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
+
+
 class fieldpair(object):
     """dctr_fieldpair_args_t, one level down for the same reason as interacting.Args (tests/test_fefm_cpu.py checks its layout)."""
     FEFM, FWFM = 0, 1
@@ -458,6 +465,9 @@ SYMBOLS = {
     "dctr_interacting_bwd": (ctypes.c_int, [ctypes.POINTER(interacting.BwdArgs), c_vp]),
     "dctr_bilinear_workspace_bytes": (c_sz, [ctypes.POINTER(bilinear.Args)]),
     "dctr_bilinear_fwd": (ctypes.c_int, [ctypes.POINTER(bilinear.Args), c_vp]),
+    "dctr_bilinear_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(bilinear.BwdArgs)]),
+    "dctr_bilinear_bwd_supported": (ctypes.c_int, [ctypes.POINTER(bilinear.BwdArgs)]),
+    "dctr_bilinear_bwd": (ctypes.c_int, [ctypes.POINTER(bilinear.BwdArgs), c_vp]),
     "dctr_fieldpair_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.Args)]),
     "dctr_fieldpair_fwd": (ctypes.c_int, [ctypes.POINTER(fieldpair.Args), c_vp]),
     "dctr_fieldpair_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(fieldpair.BwdArgs)]),

@@ -51,6 +51,7 @@ SOURCES = [
     "interacting_kernels.hip",
     "interacting_bwd_kernels.hip",
     "bilinear_kernels.hip",
+    "bilinear_bwd_kernels.hip",
     "fieldpair_kernels.hip",
     "fieldpair_bwd_kernels.hip",
     "ffm_kernels.hip",

@@ -5,7 +5,7 @@
 ``FGCNNLayer`` (:937-1064, fieldconv_kernels.hip).
 Same constructor kwargs, ``get_config`` and weight names/shapes; ``call`` launches the HIP kernels
 (deepctr_amd/csrc/interaction_kernels.hip, cin_kernels.hip, interacting_kernels.hip, bilinear_kernels.hip,
-fieldpair_kernels.hip).  The other six interaction layers of the reference are out of scope."""
+bilinear_bwd_kernels.hip, fieldpair_kernels.hip).  The other six interaction layers of the reference are out of scope."""
 import itertools
 
 import torch
@@ -215,8 +215,13 @@ class SENETLayer(Layer):
             raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs[0].dim()))
         x = _stack_fields(inputs)
         B, F, E = x.shape
-        y = ops.senet_bilinear(x, senet_w=self.weights_w12).reshape(B, F, E)
-        return list(torch.split(y, 1, dim=1))
+        w12 = self.weights_w12
+        if x.is_cuda and torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in w12)):
+            # differentiable: the same forward launch, dctr_bilinear_bwd behind it
+            y = ops.SenetBilinearFunction.apply(x.reshape(B, F * E), F, E, 0, "interaction", "senet", *w12)
+        else:
+            y = ops.senet_bilinear(x, senet_w=w12)
+        return list(torch.split(y.reshape(B, F, E), 1, dim=1))
 
     def compute_output_shape(self, input_shape):
         return input_shape
@@ -274,7 +279,12 @@ class BilinearInteraction(Layer):
             raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs[0].dim()))
         x = _stack_fields(inputs)
         B, F, E = x.shape
-        y = ops.senet_bilinear(x, bilinear_w=self.matrices, bilinear_type=self.bilinear_type)
+        ws = self.matrices
+        if x.is_cuda and torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in ws)):
+            # differentiable: the same forward launch, dctr_bilinear_bwd behind it
+            y = ops.SenetBilinearFunction.apply(x.reshape(B, F * E), F, E, 0, self.bilinear_type, "layer", *ws)
+        else:
+            y = ops.senet_bilinear(x, bilinear_w=ws, bilinear_type=self.bilinear_type)
         return y.reshape(B, F * (F - 1) // 2, E)
 
     def compute_output_shape(self, input_shape):

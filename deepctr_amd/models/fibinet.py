@@ -3,7 +3,10 @@
 
 Forward: fused gather (+ linear logit) -> dnn_in -> ``dctr_bilinear_fwd`` (SENET scalars, both bilinear layers and the dense tail in
 one launch, the fields' leading F*E columns of dnn_in read in place) into a DNN-input buffer -> the DNN kernel with dense/kernel as its
-head, adding the linear logit, the bias and the sigmoid."""
+head, adding the linear logit, the bias and the sigmoid.
+
+fit() runs the autograd step; from training.FIBINET_HIP_MIN_ROWS rows on its DNN input is one differentiable HIP op
+(training.senet_bilinear: ``dctr_bilinear_fwd`` forward, ``dctr_bilinear_bwd`` backward)."""
 import torch
 
 from .. import ops
@@ -75,12 +78,8 @@ class _FiBiNET(FeatureModel):
             ops.mlp(buf, [], [], "linear", **kw)
 
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # fibinet.py:50-63
-        F = self.n_fields
-        x = torch.stack(parts[:F], dim=1)                           # [B,F,E]
-        a2 = torch.relu(torch.relu(x.mean(-1) @ self.senet.w("W_1")) @ self.senet.w("W_2"))
-        # concat_func joins the two [B,P,E] outputs on the last axis (reference layers/utils.py:236), then Flatten
-        h = torch.cat([tops._bilinear(self.senet_bilinear, x * a2.unsqueeze(-1)), tops._bilinear(self.bilinear, x)], dim=-1)
-        h = torch.cat([h.reshape(x.shape[0], -1)] + parts[F:], dim=-1)
+        # the small cat [B, F*E + D]; training.senet_bilinear returns the whole DNN-input row from it
+        h = tops.senet_bilinear(self, torch.cat(parts, dim=-1))
         if self.dnn is not None:
             h = tops.dnn_forward(self.dnn, h, training)
         return (h @ self.dense.w("kernel")).reshape(-1)

@@ -847,6 +847,203 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
     return out
 
 
+_BILINEAR_MODES = {"model": _C.bilinear.MODE_MODEL, "senet": _C.bilinear.MODE_SENET, "layer": _C.bilinear.MODE_LAYER}
+
+
+def _bilinear_bwd_shape(batch, fields, dim, bilinear_type, mode, reduction_size, dense_cols=0):
+    if mode not in _BILINEAR_MODES:
+        raise ValueError("senet_bilinear_bwd: mode %r: expected 'model', 'senet' or 'layer'" % (mode,))
+    m = _BILINEAR_MODES[mode]
+    width = senet_bilinear_width(int(fields), int(dim), m, int(dense_cols))
+    b = _C.bilinear.BwdArgs(d_out_stride=width, dx_stride=int(fields) * int(dim) + int(dense_cols))
+    b.fwd = _bilinear_args(batch, fields, dim, int(fields) * int(dim) + int(dense_cols), bilinear_type, m, max(int(reduction_size), 1),
+                           dense_cols, width)
+    return b
+
+
+def senet_bilinear_bwd_supported(fields, dim, bilinear_type="interaction", mode="model", reduction_size=1):
+    """Does dctr_bilinear_bwd take these shapes (read from the library)?"""
+    return bool(_C.lib().dctr_bilinear_bwd_supported(ctypes.byref(_bilinear_bwd_shape(1, fields, dim, bilinear_type, mode,
+                                                                                      reduction_size))))
+
+
+def senet_bilinear_bwd_workspace_bytes(batch, fields, dim, bilinear_type="interaction", mode="model", reduction_size=1):
+    """Bytes of the workspace dctr_bilinear_bwd needs for these shapes (0 on the LDS route; read from the library)."""
+    return int(_C.lib().dctr_bilinear_bwd_workspace_bytes(ctypes.byref(_bilinear_bwd_shape(batch, fields, dim, bilinear_type, mode,
+                                                                                           reduction_size))))
+
+
+def senet_bilinear_bwd(x, d_out, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bilinear_type="interaction", fields=None,
+                       dim=None, dense_cols=0, d_out_offset=0, dx=None, dx_offset=0, accumulate=False, d_senet_w=None,
+                       d_senet_bilinear_w=None, d_bilinear_w=None, max_blocks=0, workspace=None):
+    """Backward of senet_bilinear(), one launch (include/dctr.h: dctr_bilinear_bwd); the forward saves nothing.  ``x`` / the weights /
+    ``bilinear_type`` / ``fields`` / ``dim`` / ``dense_cols`` as senet_bilinear(): which weights are given picks the mode.  ``d_out``: a
+    float32 2-D view whose row holds the gradient of the forward's output row from column ``d_out_offset``.  ``dx``: a 2-D view
+    [B, >= dx_offset + F*E + dense_cols] (or [B,F,E] contiguous) whose F*E embedding columns (and, in the FiBiNET form, the
+    ``dense_cols`` behind them) from ``dx_offset`` are written, or added to with ``accumulate`` — bit-identical from call to call.
+    ``d_senet_w`` = (dW_1 [F,r] or None, dW_2 [r,F] or None); ``d_senet_bilinear_w`` / ``d_bilinear_w``: ONE contiguous [nW,E,E] tensor
+    each.  All weight gradients are ACCUMULATED into; they leave through float atomics and may differ in the last bits from call to
+    call.  Any output may be None, but not all of them."""
+    op = "senet_bilinear_bwd"
+    x, B, F, E, x_stride, _ = _x_in_place(op, x, fields, dim)
+    if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
+        mode = _C.bilinear.MODE_MODEL
+    elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_SENET
+    elif senet_w is None and bilinear_w is not None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_LAYER
+    else:
+        raise ValueError("senet_bilinear_bwd: give senet_w + senet_bilinear_w + bilinear_w, senet_w alone, or bilinear_w alone")
+    if mode != _C.bilinear.MODE_MODEL and dense_cols:
+        raise ValueError("senet_bilinear_bwd: dense_cols exist in the three-weight (FiBiNET) form only")
+    if F < 2:
+        raise ValueError("senet_bilinear_bwd: %d field(s): the layers need at least 2" % F)
+    tensors = [x]
+    r = 0
+    w1 = w2 = None
+    if senet_w is not None:
+        w1, w2 = (_f32c(w, "senet_w") for w in senet_w)
+        r = w1.shape[1] if w1.dim() == 2 else -1
+        if r < 1 or tuple(w1.shape) != (F, r) or tuple(w2.shape) != (r, F):
+            raise ValueError("senet_bilinear_bwd: senet_w must be W_1 [%d, r] and W_2 [r, %d]" % (F, F))
+        tensors += [w1, w2]
+    nW = bilinear_weight_count(bilinear_type, F)
+    tables = []
+    for ws in (senet_bilinear_w, bilinear_w):
+        if ws is None:
+            tables.append(None)
+            continue
+        ws = [_f32c(w, "bilinear weight") for w in ws]
+        if len(ws) != nW or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("senet_bilinear_bwd: bilinear_type %r over %d fields takes %d matrices [%d, %d]"
+                             % (bilinear_type, F, nW, E, E))
+        tensors += ws
+        tables.append(bilinear_table(ws))
+    width = senet_bilinear_width(F, E, mode, dense_cols)
+    d_out_stride = _rows2d(op, "d_out", d_out, B, width, d_out_offset)
+    dx_stride = 0
+    if dx is not None:
+        if dx.dim() == 3 and dx_offset == 0 and not dense_cols and tuple(dx.shape) == (B, F, E) and dx.is_contiguous() \
+                and dx.dtype == torch.float32:
+            dx_stride = F * E
+        else:
+            dx_stride = _rows2d(op, "dx", dx, B, F * E + dense_cols, dx_offset)
+    dw1, dw2 = d_senet_w if d_senet_w is not None else (None, None)
+    if senet_w is None and (dw1 is not None or dw2 is not None):
+        raise ValueError("senet_bilinear_bwd: d_senet_w without senet_w")
+    if dw1 is not None:
+        _vec(op, "d_senet_w[0]", dw1, F * r)
+    if dw2 is not None:
+        _vec(op, "d_senet_w[1]", dw2, r * F)
+    for name, g, ws in (("d_senet_bilinear_w", d_senet_bilinear_w, senet_bilinear_w), ("d_bilinear_w", d_bilinear_w, bilinear_w)):
+        if g is not None:
+            if ws is None:
+                raise ValueError("senet_bilinear_bwd: %s without its weights" % name)
+            _vec(op, name, g, nW * E * E)
+    if dx is None and dw1 is None and dw2 is None and d_senet_bilinear_w is None and d_bilinear_w is None:
+        raise ValueError("senet_bilinear_bwd: no gradient asked for (dx and every d_* are None)")
+    for t in [d_out, dx, dw1, dw2, d_senet_bilinear_w, d_bilinear_w] + tensors:
+        if t is not None and t.device != x.device:
+            raise ValueError("senet_bilinear_bwd: operands on different devices (%s and %s)" % (x.device, t.device))
+    _dev_check(d_out, dx, dw1, dw2, d_senet_bilinear_w, d_bilinear_w, *tensors)
+    b = _C.bilinear.BwdArgs(d_out=d_out.data_ptr(), d_out_stride=d_out_stride, d_out_offset=int(d_out_offset), dx_stride=dx_stride,
+                            dx_offset=int(dx_offset), accumulate=int(bool(accumulate)), max_blocks=int(max_blocks))
+    b.fwd = _bilinear_args(B, F, E, x_stride, bilinear_type, mode, max(r, 1), dense_cols, width)
+    b.fwd.x = x.data_ptr()
+    if senet_w is not None:
+        b.fwd.senet_w1, b.fwd.senet_w2 = w1.data_ptr(), w2.data_ptr()
+    if tables[0] is not None:
+        b.fwd.senet_bilinear_w = tables[0].data_ptr()
+    if tables[1] is not None:
+        b.fwd.bilinear_w = tables[1].data_ptr()
+    for name, t in (("dx", dx), ("d_senet_w1", dw1), ("d_senet_w2", dw2), ("d_senet_bilinear_w", d_senet_bilinear_w),
+                    ("d_bilinear_w", d_bilinear_w)):
+        if t is not None:
+            setattr(b, name, t.data_ptr())
+    _workspace(op, b, int(_C.lib().dctr_bilinear_bwd_workspace_bytes(ctypes.byref(b))), workspace, x.device)
+    _C.check(_C.lib().dctr_bilinear_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_bilinear_bwd")
+
+
+class SenetBilinearFunction(torch.autograd.Function):
+    """SENETLayer / BilinearInteraction / FiBiNET's whole DNN-input row as one differentiable op: senet_bilinear() forward and
+    senet_bilinear_bwd() backward, one launch each.  ``apply(x2d, fields, dim, dense_cols, bilinear_type, mode, *weights)``: x2d
+    [B, F*E + dense_cols]; ``mode`` 'model' (weights = W_1, W_2, the nW SENET-side matrices, the nW raw-side matrices), 'senet' (W_1,
+    W_2) or 'layer' (the nW matrices).  Returns the forward's row [B, width].  Only x and the weights are saved: the backward loads x
+    again.  The per-matrix gradients are views of ONE zeroed buffer per layer.  Weight gradients leave the kernel through float atomics
+    and may differ in the last bits from call to call; dx does not."""
+
+    @staticmethod
+    def _split(mode, bilinear_type, fields, ws):
+        """(senet_w, senet_bilinear_w, bilinear_w) of the flat weight list."""
+        nW = bilinear_weight_count(bilinear_type, fields)
+        if mode == "model":
+            if len(ws) != 2 + 2 * nW:
+                raise ValueError("SenetBilinearFunction: mode 'model' takes W_1, W_2 and 2 x %d matrices" % nW)
+            return (ws[0], ws[1]), ws[2:2 + nW], ws[2 + nW:]
+        if mode == "senet":
+            if len(ws) != 2:
+                raise ValueError("SenetBilinearFunction: mode 'senet' takes W_1 and W_2")
+            return (ws[0], ws[1]), None, None
+        if mode == "layer":
+            if len(ws) != nW:
+                raise ValueError("SenetBilinearFunction: mode 'layer' takes %d matrices" % nW)
+            return None, None, ws
+        raise ValueError("SenetBilinearFunction: mode %r: expected 'model', 'senet' or 'layer'" % (mode,))
+
+    @staticmethod
+    def forward(ctx, x, fields, dim, dense_cols, bilinear_type, mode, *weights):
+        ctx.cfg = (int(fields), int(dim), int(dense_cols), bilinear_type, mode)
+        x = x.detach()
+        if x.dtype != torch.float32 or x.stride(-1) != 1:
+            x = x.float().contiguous()
+        ws = [w.detach() for w in weights]
+        sw, sbw, bw = SenetBilinearFunction._split(mode, bilinear_type, fields, ws)
+        out = senet_bilinear(x, senet_w=sw, senet_bilinear_w=sbw, bilinear_w=bw, bilinear_type=bilinear_type, fields=fields, dim=dim,
+                             dense_cols=dense_cols)
+        ctx.save_for_backward(x, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        saved = list(ctx.saved_tensors)
+        x, ws = saved[0], saved[1:]
+        F, E, D, bilinear_type, mode = ctx.cfg
+        sw, sbw, bw = SenetBilinearFunction._split(mode, bilinear_type, F, ws)
+        need = ctx.needs_input_grad
+        want_dx = need[0]
+        wneed = list(need[6:])
+        d_out = _grad_operand(d_out, True)
+        dx = torch.empty(x.shape[0], F * E + D, dtype=torch.float32, device=x.device) if want_dx else None
+        grads = [None] * len(ws)
+        at = 0
+        d_senet_w = None
+        if sw is not None:
+            # W_1 and W_2 are small: a zeroed tensor each
+            pair = [torch.zeros_like(ws[k], memory_format=torch.contiguous_format) if wneed[k] else None for k in (0, 1)]
+            grads[0], grads[1] = pair
+            d_senet_w = tuple(pair)
+            at = 2
+        flats = []
+        for layer in (sbw, bw):
+            if layer is None:
+                flats.append(None)
+                continue
+            n = len(layer)
+            flat = None
+            if any(wneed[at:at + n]):
+                # the op accumulates: the layer's per-matrix gradients are views of ONE zeroed buffer
+                flat = torch.zeros((n, E, E), dtype=torch.float32, device=x.device)
+                for k in range(n):
+                    if wneed[at + k]:
+                        grads[at + k] = flat[k]
+            flats.append(flat)
+            at += n
+        if want_dx or any(g is not None for g in grads):
+            senet_bilinear_bwd(x, d_out, senet_w=sw, senet_bilinear_w=sbw, bilinear_w=bw, bilinear_type=bilinear_type, fields=F, dim=E,
+                               dense_cols=D, dx=dx, d_senet_w=d_senet_w, d_senet_bilinear_w=flats[0], d_bilinear_w=flats[1])
+        return (dx, None, None, None, None, None) + tuple(grads)
+
+
 def _fieldpair_args(kind, B, F, E, x_stride, x_offset=0):
     return _C.fieldpair.Args(batch=int(B), x_stride=int(x_stride), x_offset=int(x_offset), fields=int(F), dim=int(E), kind=int(kind))
 

@@ -319,6 +319,14 @@ def interacting_stack(layers, x):
 FEFM_HIP_MIN_ROWS = 8192
 
 
+# Below this many rows FiBiNET's autograd step stays on the torch ops.  At 4,096 rows of the Criteo shape the HIP route lost (11.03
+# against 10.17 ms a step, 0.92x): dctr_bilinear_bwd walks its tiles five times for the 650 weight sums and then has 256 tiles for 256
+# workgroups, 1.08 ms a call, beside the host's handling of 650 weight tensors in both launches.  At 8,192 rows it won (7.51 against
+# 11.41 ms, 1.52x) and at 65,536 by 2.27x (profiles/fibinet_bilinear_bwd.txt); no size between 4,096 and 8,192 was measured, so the
+# threshold is the smallest size measured to win.
+FIBINET_HIP_MIN_ROWS = 8192
+
+
 def _fieldpair_on_hip(x, weights, kind, min_rows=0):
     """The gate of fefm_pairs / fwfm_logit: interacting_stack's, something must actually require grad, and FEFM's row threshold."""
     return (x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32 and x.shape[0] >= min_rows
@@ -348,6 +356,29 @@ def fwfm_logit(layer, x):
         return ops.FieldPairFunction.apply(x, "fwfm", False, True, r)[1]
     gram = torch.einsum("bie,bje->bij", x, x)
     return (gram * torch.triu(r, diagonal=1)).sum((1, 2))
+
+
+def senet_bilinear(model, xcat):
+    """FiBiNET's DNN input inside the autograd step.  ``model`` carries ``senet``, ``senet_bilinear``, ``bilinear`` (the three layers),
+    ``n_fields``, ``emb_dim`` and ``bilinear_type``; ``xcat`` [B, F*E + D] is the torch.cat of the F embedding parts and the dense
+    parts.  Returns the whole DNN-input row [B, 2*P*E + D]: per pair the bilinear over the SENET output and the bilinear over x, then
+    the dense values.  On the GPU, with gradients enabled and something requiring grad, it is ops.SenetBilinearFunction:
+    dctr_bilinear_fwd forward and dctr_bilinear_bwd backward, one launch each, no [B,P,E] tensor and no large cat in HBM
+    (profiles/fibinet_bilinear_bwd.txt).  Everything else — the CPU, torch.no_grad(), HIP_AUTOGRAD_OPS off, fewer than
+    FIBINET_HIP_MIN_ROWS rows, a shape the backward refuses — takes the torch ops of _bilinear."""
+    F, E = model.n_fields, model.emb_dim
+    B, D = xcat.shape[0], xcat.shape[1] - F * E
+    w12 = list(model.senet.weights_w12)
+    ws = w12 + model.senet_bilinear.matrices + model.bilinear.matrices
+    if (xcat.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and xcat.dtype == torch.float32 and B >= FIBINET_HIP_MIN_ROWS
+            and (xcat.requires_grad or any(w.requires_grad for w in ws))
+            and ops.senet_bilinear_bwd_supported(F, E, model.bilinear_type, "model", w12[0].shape[1])):
+        return ops.SenetBilinearFunction.apply(xcat, F, E, D, model.bilinear_type, "model", *ws)
+    x = xcat[:, :F * E].reshape(B, F, E)
+    a2 = torch.relu(torch.relu(x.mean(-1) @ w12[0]) @ w12[1])
+    # concat_func joins the two [B,P,E] outputs on the last axis (reference layers/utils.py:236), then Flatten
+    h = torch.cat([_bilinear(model.senet_bilinear, x * a2.unsqueeze(-1)), _bilinear(model.bilinear, x)], dim=-1)
+    return torch.cat([h.reshape(B, -1), xcat[:, F * E:]], dim=-1)
 
 
 def _layer_norm(ln, x):

@@ -494,6 +494,48 @@ typedef struct {
 size_t dctr_bilinear_workspace_bytes(const dctr_bilinear_args_t* args);
 int dctr_bilinear_fwd(const dctr_bilinear_args_t* args, void* stream);
 
+/* Backward of dctr_bilinear_fwd, one launch, every mode and bilinear_type; nothing is saved by the forward (the kernel loads the same
+ * X tile again and recomputes Z, A1, A2).  fwd: batch, x, x_stride, fields, dim, bilinear_type, mode, reduction_size, dense_cols and
+ * the weights are read as the forward reads them; out / out_stride / workspace are ignored.  d_out is the gradient of the forward's
+ * output row, read in place from a wider row.  Per pair (i, j), i < j, with g^s / g^r [dim] the gradients of its SENET-side / raw-side
+ * output, W^s / W^r the two layers' matrices of the pair and c = A2[i] A2[j]:
+ *   raw side:   dx_i += (g^r (.) x_j) W^T;  dx_j += g^r (.) (x_i W);  dW += x_i^T (g^r (.) x_j), summed over the samples;
+ *   SENET side: the same three with c g^s and W^s;  dA2[i] += A2[j] <g^s, s_ij>, dA2[j] += A2[i] <g^s, s_ij>, s_ij = (x_i W^s) (.) x_j;
+ *   SENET chain per sample: dA2 gated by A2 > 0 (relu'(0) = 0);  dW_2 += A1^T dA2;  dA1 = dA2 W_2^T gated by A1 > 0;  dW_1 += Z^T dA1;
+ *               dx_f[e] += (dA1 W_1^T)[f] / dim for every e.
+ *   mode SENET: dx_f = A2[f] g_f plus the chain with dA2[f] = <g_f, x_f>.  mode LAYER: the raw side alone, with bilinear_w.
+ * dx: the F*dim columns from dx_offset of a row of dx_stride floats are written (accumulate = 0) or added to (1); in mode MODEL with
+ * dense_cols > 0 the dense_cols columns behind them receive (or are added) d_out's tail: the exact transpose of the forward's in-place
+ * read of x.  The other columns stay untouched.  One owner per element and no atomics: dx is bit-identical from call to call.
+ * The four weight gradients are ACCUMULATED into (zero them first): summed per workgroup over all the tiles it walks, one float atomic
+ * per element and workgroup (dim > 16: per element and tile; EACH / ALL: per element, workgroup and chunk / walk of the pairs), so they may differ in the last bits from call to call.  dx and each
+ * d_* may be NULL (not wanted); all of the mode's outputs NULL is DCTR_E_NULL.  Arithmetic is fp32, the products on the f32 matrix
+ * cores as the forward.
+ * A tile too large for the LDS runs in `workspace` (dctr_bilinear_bwd_workspace_bytes; REQUIRED then: DCTR_E_NULL without, DCTR_E_ALIGN
+ * when not 16-B aligned, before anything is launched).  No shape the forward takes is refused, unless one tile's buffers pass 2^30
+ * floats: DCTR_E_UNSUPPORTED before anything is launched (dctr_bilinear_bwd_supported: 1 / 0).  Argument errors (DCTR_E_NULL / _DIM /
+ * _ENUM / _ALIGN: null pointers, F < 2, unknown type or mode, short strides) launch and write nothing. */
+typedef struct {
+    dctr_bilinear_args_t fwd;
+    const float* d_out;           /* row b at d_out + b * d_out_stride + d_out_offset, the forward's output width */
+    int64_t d_out_stride;         /* >= d_out_offset + width */
+    int64_t d_out_offset;         /* >= 0 */
+    float* dx;                    /* may be NULL: row b at dx + b * dx_stride + dx_offset, fields*dim (+ dense_cols) floats */
+    int64_t dx_stride;            /* >= dx_offset + fields*dim (+ dense_cols) */
+    int64_t dx_offset;            /* >= 0 */
+    int32_t accumulate;           /* 0 | 1: dx written | added to */
+    int32_t max_blocks;           /* 0: the library's grid (one workgroup per compute unit); > 0 caps it (each workgroup walks its tiles) */
+    float* d_senet_w1;            /* may be NULL; [F, r], ACCUMULATED into (modes MODEL, SENET) */
+    float* d_senet_w2;            /* may be NULL; [r, F] */
+    float* d_senet_bilinear_w;    /* may be NULL; ONE contiguous [nW, dim, dim] (mode MODEL) */
+    float* d_bilinear_w;          /* may be NULL; ONE contiguous [nW, dim, dim] (modes MODEL, LAYER) */
+    void* workspace;              /* NULL, or device scratch of dctr_bilinear_bwd_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_bilinear_bwd_args_t;
+size_t dctr_bilinear_bwd_workspace_bytes(const dctr_bilinear_bwd_args_t* args); /* host only; 0: none (or an argument error) */
+int dctr_bilinear_bwd_supported(const dctr_bilinear_bwd_args_t* args);          /* host only, reads shapes only */
+int dctr_bilinear_bwd(const dctr_bilinear_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FwFMLayer.call / FEFMLayer.call — deepctr/layers/interaction.py:1351-1499, wired as deepctr/models/fwfm.py and deepfefm.py
  *     x_f [dim] for f < F (F >= 2, one dim): the embeddings of ONE feature group.  Pairs (i, j), i < j, in itertools.combinations

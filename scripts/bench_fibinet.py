@@ -1,9 +1,11 @@
 """FiBiNET at the reference defaults on Criteo-shaped input (26 sparse fields of vocabulary 1e5, embedding_dim 16, 13 dense;
 bilinear_type 'interaction', reduction_ratio 3, DNN 256-128-64 over 2*325*16 + 13 = 10,413 columns): samples/s of the whole forward
 (staged ids -> probabilities: gather, bilinear kernel, DNN kernel) beside the same model's torch-ops forward (training.model_logits
-under no_grad), device-event timing after warm-up, then the bilinear kernel and the DNN kernel alone.  Prints one JSON line.
+under no_grad), device-event timing after warm-up, then the bilinear kernel and the DNN kernel alone.  ``--train`` adds one step of
+fit()'s autograd path with the DNN input in torch ops and on HIP (training.HIP_AUTOGRAD_OPS off / on, alternating in the same process)
+and dctr_bilinear_bwd alone beside its bound (profiles/fibinet_bilinear_bwd.txt).  Prints one JSON line.
 
-    python scripts/bench_fibinet.py [--rows 4096,65536] [--iters 20]"""
+    python scripts/bench_fibinet.py [--rows 4096,65536] [--iters 20] [--train]"""
 import argparse
 import json
 import os
@@ -18,6 +20,8 @@ if ROOT not in sys.path:
 
 F32_MFMA_PEAK_TF = 157.3
 STORE_TBPS = 6.0             # plain-store HBM rate the cost model uses
+F32_MFMA_TF = 155.0          # measured f32-MFMA rate the cost model uses
+READ_TBPS = 5.5              # gather / read rate the cost model uses
 
 
 def _time(fn, iters):
@@ -33,6 +37,82 @@ def _time(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def _median_spread(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2], xs[-1] - xs[0]
+
+
+def bilinear_bwd_flops(F, E):
+    """MFMA FLOP per sample of dctr_bilinear_bwd, 'interaction': per pair and layer x_i W, (g (.) x_j) W^T and the outer product
+    x_i^T (g (.) x_j) over the tile's samples, 2 E^2 each."""
+    return F * (F - 1) // 2 * 2 * 3 * 2 * E * E
+
+
+def train_leg(model, staged, n, iters, F, E, D, rounds=5):
+    """One step of fit()'s autograd path (model_logits(training=True), BCE, backward over every trainable weight; no optimizer) with
+    training.HIP_AUTOGRAD_OPS off (the torch ops: the baseline) and on, the two alternating in ``rounds`` windows of ``iters`` steps
+    each; and dctr_bilinear_bwd alone (dx and the four weight gradients) beside its bound: the larger of the HBM time of its d_out
+    read and the f32-MFMA time of its FLOP."""
+    from deepctr_amd import ops, training
+    device = model.device
+    P = F * (F - 1) // 2
+    y = (torch.rand(n, device=device) > 0.5).float()
+    frozen = training.frozen_weights(model)
+    params = [t for name, t in model.named_weights() if "moving_" not in name and t.data_ptr() not in frozen]
+
+    def step():
+        model._begin()
+        logit = training.model_logits(model, staged, 0, n, training=True)
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, y)
+        for t in params:
+            t.grad = None
+        loss.backward()
+        return loss
+
+    ms = {False: [], True: []}
+    losses = {}
+    min_rows = training.FIBINET_HIP_MIN_ROWS
+    try:
+        training.FIBINET_HIP_MIN_ROWS = 0       # the HIP route is timed at every row count: a threshold is read off this table
+        for t in params:
+            t.requires_grad_(True)
+        for _ in range(rounds):
+            for switch in (False, True):
+                training.HIP_AUTOGRAD_OPS = switch
+                ms[switch].append(_time(step, iters))
+                losses[switch] = float(step().detach())
+    finally:
+        training.HIP_AUTOGRAD_OPS = True
+        training.FIBINET_HIP_MIN_ROWS = min_rows
+        for t in params:
+            t.requires_grad_(False)
+            t.grad = None
+    off, off_spread = _median_spread(ms[False])
+    on, on_spread = _median_spread(ms[True])
+    ws = model.stage_plan.run(staged, 0, n)
+    width = 2 * P * E + D
+    d_out = torch.randn(n, width, device=device)
+    dx = torch.empty(n, F * E + D, device=device)
+    r = model.senet.weights_w12[0].shape[1]
+    g12 = (torch.zeros(F, r, device=device), torch.zeros(r, F, device=device))
+    gs, gr = torch.zeros(P, E, E, device=device), torch.zeros(P, E, E, device=device)
+
+    def bwd():
+        ops.senet_bilinear_bwd(ws["dnn_in"], d_out, senet_w=model.senet.weights_w12, senet_bilinear_w=model.senet_bilinear.matrices,
+                               bilinear_w=model.bilinear.matrices, bilinear_type="interaction", fields=F, dim=E, dense_cols=D, dx=dx,
+                               d_senet_w=g12, d_senet_bilinear_w=gs, d_bilinear_w=gr)
+    ms_bwd = _time(bwd, iters)
+    read_ms = 4 * width * n / (READ_TBPS * 1e12) * 1e3
+    mfma_ms = bilinear_bwd_flops(F, E) * n / (F32_MFMA_TF * 1e12) * 1e3
+    bound_ms = max(read_ms, mfma_ms)
+    return {"step_ms_switch_off": round(off, 4), "step_ms_switch_off_spread": round(off_spread, 4), "step_ms_switch_on": round(on, 4),
+            "step_ms_switch_on_spread": round(on_spread, 4), "step_speedup": round(off / on, 3), "windows": rounds, "steps_per_window": iters,
+            "loss_switch_off": losses[False], "loss_switch_on": losses[True], "bilinear_bwd_call_ms": round(ms_bwd, 4),
+            "bilinear_bwd_d_out_read_ms": round(read_ms, 4), "bilinear_bwd_mfma_ms": round(mfma_ms, 4),
+            "bilinear_bwd_flop_per_sample": bilinear_bwd_flops(F, E), "bilinear_bwd_bound_ms": round(bound_ms, 4),
+            "bilinear_bwd_share_of_bound": round(bound_ms / ms_bwd, 3)}
+
+
 def main():
     from deepctr_amd import engine, ops, training
     from deepctr_amd.feature_column import DenseFeat, SparseFeat
@@ -41,6 +121,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="4096,65536")
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--train", action="store_true", help="add the training-step leg (autograd step, DNN input off / on HIP)")
     args = ap.parse_args()
     device = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -92,6 +173,8 @@ def main():
                                "bilinear_hbm_bound_ms": round(bound_ms, 4), "bilinear_share_of_hbm_bound": round(bound_ms / ms_bil, 3),
                                "dnn_call_ms": round(ms_dnn, 4), "dnn_tflops": round(dnn_tf, 2),
                                "dnn_share_of_f32_mfma_peak": round(dnn_tf / F32_MFMA_PEAK_TF, 3)}
+        if args.train:
+            res["rows"][str(n)]["train"] = train_leg(model, staged, n, args.iters, F, E, D)
     print(json.dumps(res))
 
 
