@@ -29,6 +29,8 @@
 #include <stdint.h>
 #include "dctr_common.h"
 #include "mfma_tile.h"
+#include "pair_index.h"
+#include "tile_route.h"
 
 namespace {
 
@@ -38,9 +40,6 @@ constexpr int BB_S = 16;                        // samples per tile = the rows o
 constexpr int BB_CPW = 8;                       // chunks per walk
 constexpr int BB_RPC = 4;                       // rounds per chunk: a chunk holds up to BB_RPC * BB_WAVES pairs
 constexpr int BB_NACC = BB_CPW * BB_RPC * 2;    // 16x16 weight-gradient sums a wave keeps in registers (4 registers each)
-constexpr size_t BB_LDS_MAX = 160 * 1024;
-constexpr int BB_GLOBAL_WGS = 256;
-constexpr size_t BB_GLOBAL_MAX = (size_t)256 << 20;
 
 struct BbParams {
     const float* x;
@@ -106,8 +105,6 @@ __host__ __device__ inline BbLayout bb_layout(int F, int ldx, int senet, int nbl
     L.total = (o + 3) & ~(int64_t)3;
     return L;
 }
-
-__device__ __forceinline__ int64_t bb_row_start(int64_t i, int F) { return i * (2 * (int64_t)F - i - 1) / 2; }
 
 // The chunks in pair order, the same sequence for every tile and for the flush: (row i, first partner j0, n pairs); no chunk
 // crosses a row.
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(BB_THREADS) void bilinear_bwd_kernel(BbParams p) {
                         break;
                     }
                     const int i = c.i, n = c.n;
-                    const int64_t p0 = bb_row_start(i, F) + c.j0 - i - 1;
+                    const int64_t p0 = dctr::pair_row_start(i, F) + c.j0 - i - 1;
                     const int blen = n * nblk * E;
                     const float* xi = X + i * fs;
                     // the chunk's g: one contiguous run of d_out per sample (the barrier behind the previous chunk's pair phase, or
@@ -493,7 +490,7 @@ __global__ __launch_bounds__(BB_THREADS) void bilinear_bwd_kernel(BbParams p) {
             for (int cc = 0; cc < BB_CPW; ++cc) {
                 BbChunk c;
                 if (!bb_next(p, st, c)) break;
-                const int64_t p0 = bb_row_start(c.i, F) + c.j0 - c.i - 1;
+                const int64_t p0 = dctr::pair_row_start(c.i, F) + c.j0 - c.i - 1;
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     if (!(b < nblk && p.dw[b])) continue;
@@ -559,15 +556,10 @@ void bb_plan(const dctr_bilinear_args_t* a, BbPlan* pl) {
     pl->ldo = pl->nblk ? pl->nblk * pl->NP * E + 4 : 0;
     pl->tile_floats = bb_layout(F, pl->ldx, pl->senet, pl->nblk, pl->r, pl->ldo, pl->ldt).total;
     pl->ok = pl->tile_floats < 0x3fffffffLL;    // a tile's buffers are indexed in 32 bits
-    pl->global = false;
-    pl->grid_max = 0;
-    pl->route_bytes = 0;
-    const size_t tb = (size_t)pl->tile_floats * sizeof(float);
-    if (!pl->ok || tb <= BB_LDS_MAX) return;
-    pl->global = true;
-    const size_t gmax = BB_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(gmax < 1 ? 1 : gmax > BB_GLOBAL_WGS ? BB_GLOBAL_WGS : gmax);
-    pl->route_bytes = tb * pl->grid_max;
+    const dctr_tile_route r = pl->ok ? dctr_plan_tile_route((size_t)pl->tile_floats * sizeof(float)) : dctr_tile_route{false, 0, 0};
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 // the forward's size checks (bl_check of bilinear_kernels.hip; its output is not read) and the backward's own
@@ -633,11 +625,8 @@ extern "C" int dctr_bilinear_bwd(const dctr_bilinear_bwd_args_t* b, void* stream
     float* dws = pl.nblk == 2 ? b->d_senet_bilinear_w : nullptr;
     float* dwr = pl.nblk >= 1 ? b->d_bilinear_w : nullptr;
     DCTR_REQUIRE(b->dx || dw1 || dw2 || dws || dwr, DCTR_E_NULL, "bilinear_bwd: no gradient asked for (dx and every d_* are null)");
-    if (pl.route_bytes) {
-        DCTR_REQUIRE(b->workspace && b->workspace_bytes >= pl.route_bytes, DCTR_E_NULL,
-                     "bilinear_bwd: this shape needs a workspace of %zu bytes (dctr_bilinear_bwd_workspace_bytes)", pl.route_bytes);
-        DCTR_REQUIRE(dctr_aligned16(b->workspace), DCTR_E_ALIGN, "bilinear_bwd: workspace not 16-B aligned");
-    }
+    if (pl.route_bytes)
+        DCTR_REQUIRE_WORKSPACE("bilinear_bwd", "dctr_bilinear_bwd_workspace_bytes", b->workspace, b->workspace_bytes, pl.route_bytes);
     if (a->batch == 0) return DCTR_OK;
     BbParams p = {};
     p.x = a->x;

@@ -21,15 +21,14 @@
 #include <math.h>
 #include "dctr_common.h"
 #include "mfma_tile.h"
+#include "pair_index.h"
+#include "tile_route.h"
 
 namespace {
 
 constexpr int BL_THREADS = 512;                // 8 waves: one pair task per wave and chunk at the Criteo shape
 constexpr int BL_S = 16;                        // samples per tile = the rows of one MFMA tile
 constexpr int BL_CHUNK = 256;                   // output floats per sample and layer staged per chunk of pairs
-constexpr size_t BL_LDS_MAX = 160 * 1024;
-constexpr int BL_GLOBAL_WGS = 256;
-constexpr size_t BL_GLOBAL_MAX = (size_t)256 << 20;
 
 struct BlParams {
     const float* x;
@@ -75,20 +74,6 @@ __host__ __device__ inline BlLayout bl_layout(int F, int ldx, int nV, int r, int
     o = L.wp + 4 * (int64_t)NP;
     L.total = (o + 3) & ~(int64_t)3;
     return L;
-}
-
-// first pair index of row i in itertools.combinations(range(F), 2) order
-__device__ __forceinline__ int64_t bl_row_start(int64_t i, int F) { return i * (2 * (int64_t)F - i - 1) / 2; }
-
-__device__ void bl_pair(int64_t p, int F, int* pi, int* pj) {
-    const double b = 2.0 * F - 1.0;
-    int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
-    if (i < 0) i = 0;
-    if (i > F - 2) i = F - 2;
-    while (i > 0 && bl_row_start(i, F) > p) --i;
-    while (i < F - 2 && bl_row_start(i + 1, F) <= p) ++i;
-    *pi = (int)i;
-    *pj = (int)(p - bl_row_start(i, F) + i + 1);
 }
 
 // acc[q][b] += A_q [16 x E] W_qb [E x 16 columns], q, b < 2.  arow[q]: this lane's A row (sample lane & 15) at its k-slot
@@ -239,7 +224,7 @@ __global__ __launch_bounds__(BL_THREADS) void bilinear_kernel(BlParams p) {
             const int blen = np * nblk * E;
             // the chunk's pairs and (interaction) their weight pointers: one table load per pair and chunk, not per wave task
             for (int t = tid; t < np; t += BL_THREADS) {
-                bl_pair(q0 + t, F, &pij[2 * t], &pij[2 * t + 1]);
+                dctr::pair_at(q0 + t, F, &pij[2 * t], &pij[2 * t + 1]);
                 if (!via_v) {
                     wp[2 * t] = p.wt[0][q0 + t];
                     wp[2 * t + 1] = p.wt[nblk > 1 ? 1 : 0][q0 + t];
@@ -335,17 +320,10 @@ void bl_plan(const dctr_bilinear_args_t* a, BlPlan* pl) {
     pl->ldo = pl->nblk ? pl->nblk * pl->NP * E + 4 : 0;
     pl->nV = pl->nblk && a->bilinear_type != DCTR_BILINEAR_INTERACTION ? pl->nblk * (F - 1) : 0;
     pl->tile_floats = bl_layout(F, pl->ldx, pl->nV, pl->r, pl->ldo, pl->NP).total;
-    const size_t tb = (size_t)pl->tile_floats * sizeof(float);
-    if (tb <= BL_LDS_MAX) {
-        pl->global = false;
-        pl->grid_max = 0;
-        pl->route_bytes = 0;
-        return;
-    }
-    pl->global = true;
-    const size_t gmax = BL_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(gmax < 1 ? 1 : gmax > BL_GLOBAL_WGS ? BL_GLOBAL_WGS : gmax);
-    pl->route_bytes = tb * pl->grid_max;
+    const dctr_tile_route r = dctr_plan_tile_route((size_t)pl->tile_floats * sizeof(float));
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 int bl_check(const dctr_bilinear_args_t* a) {
@@ -391,11 +369,8 @@ extern "C" int dctr_bilinear_fwd(const dctr_bilinear_args_t* a, void* stream) {
     DCTR_REQUIRE(pl.nblk == 0 || a->bilinear_w, DCTR_E_NULL, "bilinear_fwd: null bilinear_w");
     DCTR_REQUIRE(pl.nblk < 2 || a->senet_bilinear_w, DCTR_E_NULL, "bilinear_fwd: null senet_bilinear_w");
     if (a->batch == 0) return DCTR_OK;
-    if (pl.route_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.route_bytes, DCTR_E_NULL,
-                     "bilinear_fwd: this shape needs a workspace of %zu bytes (dctr_bilinear_workspace_bytes)", pl.route_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "bilinear_fwd: workspace not 16-B aligned");
-    }
+    if (pl.route_bytes)
+        DCTR_REQUIRE_WORKSPACE("bilinear_fwd", "dctr_bilinear_workspace_bytes", a->workspace, a->workspace_bytes, pl.route_bytes);
     BlParams p = {};
     p.x = a->x;
     p.batch = a->batch;

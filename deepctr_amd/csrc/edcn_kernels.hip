@@ -24,6 +24,7 @@
 // other activations), which the host builds from the DNN / CrossNet / GEMM entry points.
 #include <math.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -32,7 +33,6 @@ constexpr int ED_THREADS = 512;
 constexpr int ED_WAVES = ED_THREADS / 64;
 constexpr int ED_MAX_ROUNDS = 32;                 // rounds per launch (kernel-argument space)
 constexpr size_t ED_LDS_TARGET = 80 * 1024;       // two workgroups per CU where the rows allow it
-constexpr size_t ED_LDS_MAX = 160 * 1024;
 constexpr int ED_EW_THREADS = 256;
 constexpr int ED_GATE_LDS_FIELDS = 8192;          // dctr_edcn_regulate keeps its gates in LDS up to this many fields
 
@@ -358,7 +358,7 @@ void edcn_plan(const dctr_edcn_args_t* a, EdPlan* pl) {
     const size_t gates = 2 * (size_t)a->fields;
     for (int R = 64; R >= 16; R >>= 1) {
         const size_t need = (4 * (size_t)R * pl->ld + gates) * sizeof(float);
-        if (need <= (R == 16 ? ED_LDS_MAX : ED_LDS_TARGET)) {
+        if (need <= (R == 16 ? DCTR_LDS_MAX : ED_LDS_TARGET)) {
             pl->fused = true;
             pl->R = R;
             pl->lds = need;

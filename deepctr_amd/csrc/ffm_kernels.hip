@@ -17,11 +17,11 @@
 #include <math.h>
 #include <stdint.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 
 namespace {
 
 constexpr int FFM_THREADS = 256;
-constexpr size_t FFM_LDS_MAX = 160 * 1024;       // one workgroup's LDS on gfx950
 constexpr size_t FFM_TILE_BUDGET = 40 * 1024;    // target bytes of a tile: >= 3 workgroups per CU
 constexpr int FFM_S_MAX = 32;
 constexpr int FFM_S_DIRECT = 8;
@@ -293,10 +293,10 @@ int ffm_check(const dctr_ffm_args_t* a) {
 void ffm_plan(const dctr_ffm_args_t* a, FfmPlan* pl) {
     const int F = a->n_fields, d = a->dim;
     const size_t per_sample = (size_t)F * (F - 1) * d * 4;
-    pl->direct = a->route == DCTR_FFM_ROUTE_DIRECT || ffm_layout(F, d, 1, false).total > FFM_LDS_MAX;
+    pl->direct = a->route == DCTR_FFM_ROUTE_DIRECT || ffm_layout(F, d, 1, false).total > DCTR_LDS_MAX;
     if (pl->direct) {
         int S = FFM_S_DIRECT;
-        while (S > 1 && ffm_layout(F, d, S, true).total > FFM_LDS_MAX / 4) S >>= 1;
+        while (S > 1 && ffm_layout(F, d, S, true).total > DCTR_LDS_MAX / 4) S >>= 1;
         pl->S = S;
         pl->lds = ffm_layout(F, d, S, true).total;
         return;
@@ -304,7 +304,7 @@ void ffm_plan(const dctr_ffm_args_t* a, FfmPlan* pl) {
     int64_t S = (int64_t)(FFM_TILE_BUDGET / per_sample);
     S = S < 1 ? 1 : S > FFM_S_MAX ? FFM_S_MAX : S;
     if (a->batch > 0 && S > a->batch) S = a->batch;
-    while (S > 1 && ffm_layout(F, d, (int)S, false).total > FFM_LDS_MAX) --S;
+    while (S > 1 && ffm_layout(F, d, (int)S, false).total > DCTR_LDS_MAX) --S;
     pl->S = (int)S;
     pl->lds = ffm_layout(F, d, (int)S, false).total;
 }
@@ -321,7 +321,7 @@ extern "C" int dctr_ffm_route(const dctr_ffm_args_t* args) {
     if (rc != DCTR_OK) return rc;
     FfmPlan pl;
     ffm_plan(args, &pl);
-    DCTR_REQUIRE(pl.lds <= FFM_LDS_MAX, DCTR_E_DIM, "ffm_fwd: %d fields: the row-address table alone exceeds the LDS", args->n_fields);
+    DCTR_REQUIRE(pl.lds <= DCTR_LDS_MAX, DCTR_E_DIM, "ffm_fwd: %d fields: the row-address table alone exceeds the LDS", args->n_fields);
     return pl.direct ? DCTR_FFM_ROUTE_DIRECT : DCTR_FFM_ROUTE_LDS;
 }
 
@@ -334,7 +334,7 @@ extern "C" int dctr_ffm_fwd(const dctr_ffm_args_t* a, void* stream) {
     DCTR_REQUIRE(!a->workspace || dctr_aligned16(a->workspace), DCTR_E_ALIGN, "ffm_fwd: workspace not 16-B aligned");
     FfmPlan pl;
     ffm_plan(a, &pl);
-    DCTR_REQUIRE(pl.lds <= FFM_LDS_MAX, DCTR_E_DIM, "ffm_fwd: %d fields: the row-address table alone exceeds the LDS", a->n_fields);
+    DCTR_REQUIRE(pl.lds <= DCTR_LDS_MAX, DCTR_E_DIM, "ffm_fwd: %d fields: the row-address table alone exceeds the LDS", a->n_fields);
     if (a->batch == 0) return DCTR_OK;
     const int64_t F = a->n_fields, d = a->dim, P = F * (F - 1) / 2;
     FfmParams p = {};
@@ -357,7 +357,7 @@ extern "C" int dctr_ffm_fwd(const dctr_ffm_args_t* a, void* stream) {
     p.status = a->status;
     p.n_tiles = dctr_ceil_div(a->batch, (int64_t)pl.S);
     const bool vec = d % 4 == 0;
-    size_t per_cu = FFM_LDS_MAX / (pl.lds > 1024 ? pl.lds : 1024);
+    size_t per_cu = DCTR_LDS_MAX / (pl.lds > 1024 ? pl.lds : 1024);
     per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
     const int64_t cap = (int64_t)dctr_n_cus() * (int64_t)per_cu;
     const int64_t grid = p.n_tiles < cap ? p.n_tiles : cap;

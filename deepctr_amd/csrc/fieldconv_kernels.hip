@@ -29,6 +29,7 @@
 // Cost model per sample: E x sum_stages rows w C_in C_out MACs.
 #include <math.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -36,11 +37,8 @@ namespace {
 constexpr int FC_THREADS = 256;
 constexpr int FC_WAVES = FC_THREADS / 64;
 constexpr int FC_MAX = DCTR_FIELDCONV_MAX_STAGES;
-constexpr size_t FC_LDS_MAX = 160 * 1024;
 constexpr size_t FC_LDS_TARGET = 64 * 1024;     // two workgroups per CU while the shapes allow
 constexpr int FC_GRID_MAX = 2048;
-constexpr int FC_GLOBAL_WGS = 256;
-constexpr size_t FC_GLOBAL_MAX = (size_t)256 << 20;
 constexpr int64_t FC_DIM_MAX = 1 << 20;
 constexpr int64_t FC_COL_MAX = (int64_t)1 << 26;        // floats of one column's maps: 32-bit offsets inside a tile
 
@@ -253,8 +251,8 @@ void fc_plan(const dctr_fieldconv_args_t* a, FcPlan* pl) {
     // AUTO keeps the kernels in LDS only while that costs no occupancy (maps and kernels within the two-workgroup budget): past it
     // a CU holds one resident workgroup, one wave per SIMD, against two or three streamed ones (the measured times: DESIGN.md 4.19)
     const size_t res_bytes = 16 * col_bytes + w_bytes;
-    pl->resident = may_res && res_bytes <= (a->route == DCTR_FIELDCONV_ROUTE_RESIDENT ? FC_LDS_MAX : FC_LDS_TARGET);
-    pl->global_tiles = !pl->resident && (16 * col_bytes > FC_LDS_MAX || a->route == DCTR_FIELDCONV_ROUTE_WORKSPACE);
+    pl->resident = may_res && res_bytes <= (a->route == DCTR_FIELDCONV_ROUTE_RESIDENT ? DCTR_LDS_MAX : FC_LDS_TARGET);
+    pl->global_tiles = !pl->resident && (16 * col_bytes > DCTR_LDS_MAX || a->route == DCTR_FIELDCONV_ROUTE_WORKSPACE);
     const size_t fixed = pl->resident ? w_bytes : 0;
     pl->G = 1;
     if (!pl->global_tiles)
@@ -269,9 +267,9 @@ void fc_plan(const dctr_fieldconv_args_t* a, FcPlan* pl) {
     pl->grid_max = FC_GRID_MAX;
     pl->ws_bytes = 0;
     if (pl->global_tiles) {
-        const size_t gmax = FC_GLOBAL_MAX / tiles_bytes;
-        pl->grid_max = (int)(gmax < 1 ? 1 : gmax > FC_GLOBAL_WGS ? FC_GLOBAL_WGS : gmax);
-        pl->ws_bytes = tiles_bytes * pl->grid_max;
+        const dctr_tile_route r = dctr_workspace_slices(tiles_bytes);
+        pl->grid_max = r.grid_max;
+        pl->ws_bytes = r.route_bytes;
     }
 }
 
@@ -332,11 +330,8 @@ extern "C" int dctr_fieldconv_fwd(const dctr_fieldconv_args_t* a, void* stream) 
         if (a->stage_outs[s])
             DCTR_REQUIRE(a->stage_out_strides && a->stage_out_strides[s] >= (int64_t)pl.rout[s] * a->dim * a->channels[s], DCTR_E_DIM,
                          "fieldconv_fwd: stage %d: stage_out stride smaller than its [%d, %d, %d] map", s, pl.rout[s], a->dim, a->channels[s]);
-    if (pl.ws_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.ws_bytes, DCTR_E_NULL,
-                     "fieldconv_fwd: this shape needs a workspace of %zu bytes (dctr_fieldconv_workspace_bytes)", pl.ws_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "fieldconv_fwd: workspace not 16-B aligned");
-    }
+    if (pl.ws_bytes)
+        DCTR_REQUIRE_WORKSPACE("fieldconv_fwd", "dctr_fieldconv_workspace_bytes", a->workspace, a->workspace_bytes, pl.ws_bytes);
     if (a->batch == 0) return DCTR_OK;
     FcParams p = {};
     p.x = a->x;
@@ -378,7 +373,7 @@ extern "C" int dctr_fieldconv_fwd(const dctr_fieldconv_args_t* a, void* stream) 
     unsigned grid = (unsigned)(n_tiles < pl.grid_max ? n_tiles : pl.grid_max);
     if (pl.resident) {
         // a workgroup copies every stage's kernel into LDS once and then walks its tiles: no more workgroups than the CUs hold at a time
-        const int64_t held = (int64_t)dctr_n_cus() * (int64_t)(FC_LDS_MAX / pl.lds_bytes);
+        const int64_t held = (int64_t)dctr_n_cus() * (int64_t)(DCTR_LDS_MAX / pl.lds_bytes);
         if (grid > held) grid = (unsigned)held;
         static thread_local size_t granted[DCTR_MAX_DEVICES] = {0};
         hipError_t e = dctr_grant_lds((const void*)fieldconv_kernel<true, false>, pl.lds_bytes, granted);

@@ -1,5 +1,6 @@
 // The backward of FEFMLayer.call / FwFMLayer.call (dctr_fieldpair_fwd, fieldpair_kernels.hip), one launch.  The forward saves
-// nothing: a workgroup loads the same X tile [F][16 M][ldx] with the forward's LDS layout and swizzle, and the gradients of its samples.
+// nothing: a workgroup loads the same X tile [F][16 M][ldx] with the forward's LDS layout and swizzle (fieldpair_device.h), and the
+// gradients of its samples.
 //
 // FEFM, with g_b,ij = d_pairs[b, ij] + d_logit[b] and S_ij = W_ij + W_ij^T (the matrix of the pair (min, max)):
 //   dx_i = sum_{j != i} g_ij S_ij x_j.  A wave task owns field i of the tile and chains every j != i into ONE accumulator per 16-sample
@@ -22,9 +23,17 @@
 #include <math.h>
 #include <stdint.h>
 #include "dctr_common.h"
+#include "fieldpair_device.h"
 #include "mfma_tile.h"
+#include "pair_index.h"
+#include "tile_route.h"
 
 namespace {
+
+using dctr::fp_gptr;
+using dctr::fp_xel;
+using dctr::fp_xoff;
+using dctr::pair_row_start;
 
 constexpr int FB_THREADS = 512;                 // 8 waves
 constexpr int FB_WAVES = FB_THREADS / 64;
@@ -37,9 +46,6 @@ constexpr int FB_LDG = FB_NP | 1;
 constexpr int FB_LDG_FULL = 329;
 constexpr int FB_TLD = 17;                      // row pitch of a wave's 16 x 16 transpose patch
 constexpr int FWB_THREADS = 256;                // FwFM: 16 samples x 16 e-lanes
-constexpr size_t FB_LDS_MAX = 160 * 1024;
-constexpr int FB_GLOBAL_WGS = 256;
-constexpr size_t FB_GLOBAL_MAX = (size_t)256 << 20;
 
 struct FbParams {
     const float* x;              // already advanced by x_offset
@@ -83,46 +89,10 @@ __host__ __device__ inline FbLayout fb_layout(int F, int S, int ldx, int ldg, in
     return L;
 }
 
-__device__ __forceinline__ int64_t fb_row_start(int64_t i, int F) { return i * (2 * (int64_t)F - i - 1) / 2; }
+using FbRaw = dctr::FpRaw<1>;
 
-__device__ void fb_pair(int64_t p, int F, int* pi, int* pj) {
-    const double b = 2.0 * F - 1.0;
-    int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
-    if (i < 0) i = 0;
-    if (i > F - 2) i = F - 2;
-    while (i > 0 && fb_row_start(i, F) > p) --i;
-    while (i < F - 2 && fb_row_start(i + 1, F) <= p) ++i;
-    *pi = (int)i;
-    *pj = (int)(p - fb_row_start(i, F) + i + 1);
-}
-
-// the forward's X layout: float offset of 16-B chunk `chunk` of sample row s inside one field (rows of ldx floats, ldx % 16 == 0)
-__device__ __forceinline__ int fb_xoff(int s, int chunk, int ldx) { return s * ldx + ((chunk ^ ((s >> 1) & 3)) << 2); }
-__device__ __forceinline__ int fb_xel(int s, int k, int ldx) { return fb_xoff(s, k >> 2, ldx) + (k & 3); }
-
-typedef const __attribute__((address_space(1))) float* fb_gptr;
-typedef const __attribute__((address_space(1))) dctr::f32x4* fb_gptr4;
-
-// the S operand of one pair at E <= 16, before the add: row[tt] = W[c][4g + tt], col[tt] = W[4g + tt][c] (indices clamped: the
-// product meets zero padding of X there)
-struct FbRaw {
-    float row[4], col[4];
-};
-
-__device__ __forceinline__ void fb_load_small(const float* wv, int E, bool vec, FbRaw& raw) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, c = min(lane & 15, E - 1);
-    const fb_gptr w = (fb_gptr)wv;
-    if (vec && ((uintptr_t)wv & 15) == 0) {
-        const dctr::f32x4 t = *(fb_gptr4)(w + c * E + min(4 * g, E - 4));
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) raw.row[tt] = t[tt];
-    } else {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) raw.row[tt] = w[c * E + min(4 * g + tt, E - 1)];
-    }
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) raw.col[tt] = w[min(4 * g + tt, E - 1) * E + c];
-}
+// the forward's weight fetch for one pair
+__device__ __forceinline__ void fb_load_small(const float* w, int E, bool vec, FbRaw& raw) { dctr::fp_load_small(&w, 0, 1, E, vec, raw); }
 
 // GFULL: the tile's g holds all P pairs (pitch FB_LDG_FULL), not one chunk (pitch FB_LDG)
 template <bool GLOBAL_WS, int M, bool GFULL>
@@ -152,7 +122,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
     for (int e = tid; e < F * S * padc; e += FB_THREADS) {
         const int row = e / padc, k = E + (e - row * padc);
         const int f = row / S, s = row - f * S;
-        X[f * fs + fb_xel(s, k, ldx)] = 0.f;
+        X[f * fs + fp_xel(s, k, ldx)] = 0.f;
     }
 
     for (int64_t q0 = 0; q0 < p.P; q0 += p.NP) {
@@ -162,7 +132,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
         // (the table runs to a multiple of 8 pairs, the tail repeating the last pair: every wave of the dW loop finds fields there)
         for (int t = tid; t < ((np + FB_WAVES - 1) & ~(FB_WAVES - 1)); t += FB_THREADS) {
             const int64_t pt = min(q0 + t, p.P - 1);
-            fb_pair(pt, F, &pij[2 * t], &pij[2 * t + 1]);
+            dctr::pair_at(pt, F, &pij[2 * t], &pij[2 * t + 1]);
             wp[t] = p.wt[pt];
         }
         dctr::f32x4 acc[FB_NPW];
@@ -179,7 +149,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
                 const float* xr = p.x + b * p.x_stride;
                 for (int e = lane; e < FE; e += 64) {
                     const int f = e / E, k = e - f * E;
-                    X[f * fs + fb_xel(s, k, ldx)] = on ? xr[e] : 0.f;
+                    X[f * fs + fp_xel(s, k, ldx)] = on ? xr[e] : 0.f;
                 }
                 const float gl = on && p.dl ? p.dl[b] : 0.f;
                 const float* dr = p.dp ? p.dp + b * p.dp_stride + (gfull ? 0 : q0) : nullptr;
@@ -198,13 +168,13 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
                         FbRaw cur = {}, nxt = {};
                         const int jfirst = i == 0 ? 1 : 0;
                         if (small) {
-                            const int64_t pf = i == 0 ? 0 : fb_row_start(0, F) + i - 1;
+                            const int64_t pf = i == 0 ? 0 : pair_row_start(0, F) + i - 1;
                             fb_load_small(one_chunk ? wp[pf] : p.wt[pf], E, vec, cur);
                         }
                         for (int j = jfirst; j < F; ++j) {
                             if (j == i) continue;
                             const int lo = min(i, j), hi = max(i, j);
-                            const int64_t pidx = fb_row_start(lo, F) + hi - lo - 1;
+                            const int64_t pidx = pair_row_start(lo, F) + hi - lo - 1;
                             float gv[M];
 #pragma unroll
                             for (int m = 0; m < M; ++m) {
@@ -221,15 +191,15 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
                                 if (jn == i) ++jn;
                                 if (jn < F) {
                                     const int ln = min(i, jn), hn = max(i, jn);
-                                    const int64_t pn = fb_row_start(ln, F) + hn - ln - 1;
+                                    const int64_t pn = pair_row_start(ln, F) + hn - ln - 1;
                                     fb_load_small(one_chunk ? wp[pn] : p.wt[pn], E, vec, nxt);
                                 }
                                 float a[4];
 #pragma unroll
-                                for (int tt = 0; tt < 4; ++tt) a[tt] = cur.row[tt] + cur.col[tt];
+                                for (int tt = 0; tt < 4; ++tt) a[tt] = cur.row[0][tt] + cur.col[0][tt];
                                 float4 xj[M];
 #pragma unroll
-                                for (int m = 0; m < M; ++m) xj[m] = *reinterpret_cast<const float4*>(X + j * fs + fb_xoff(m * 16 + jl, g, 16));
+                                for (int m = 0; m < M; ++m) xj[m] = *reinterpret_cast<const float4*>(X + j * fs + fp_xoff(m * 16 + jl, g, 16));
 #pragma unroll
                                 for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -239,7 +209,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
                                     }
                                 cur = nxt;
                             } else {
-                                const fb_gptr w = (fb_gptr)(one_chunk ? wp[pidx] : p.wt[pidx]);
+                                const fp_gptr w = (fp_gptr)(one_chunk ? wp[pidx] : p.wt[pidx]);
                                 const int64_t c = min(ct * 16 + jl, E - 1);
                                 for (int t0 = 0; t0 < KQ; t0 += 4) {
                                     float a[4];
@@ -251,7 +221,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
 #pragma unroll
                                     for (int m = 0; m < M; ++m) {
                                         const float4 xj =
-                                            *reinterpret_cast<const float4*>(X + j * fs + fb_xoff(m * 16 + jl, (g * KQ + t0) >> 2, ldx));
+                                            *reinterpret_cast<const float4*>(X + j * fs + fp_xoff(m * 16 + jl, (g * KQ + t0) >> 2, ldx));
                                         dacc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], xj.x * gv[m], dacc[m], 0, 0, 0);
                                         dacc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], xj.y * gv[m], dacc[m], 0, 0, 0);
                                         dacc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], xj.z * gv[m], dacc[m], 0, 0, 0);
@@ -297,7 +267,7 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
                         const float* xj = X + pw[2 * FB_WAVES * q + 1] * fs;
 #pragma unroll
                         for (int kk = 0; kk < 4 * M; ++kk) {
-                            const int o = fb_xel(4 * kk + g, jl, 16);
+                            const int o = fp_xel(4 * kk + g, jl, 16);
                             acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32((gw + 4 * kk * ldg)[FB_WAVES * q] * xi[o], xj[o], acc[q], 0, 0, 0);
                         }
                     }
@@ -312,8 +282,8 @@ __global__ __launch_bounds__(FB_THREADS) void fefm_bwd_kernel(FbParams p) {
 #pragma unroll
                                 for (int kk = 0; kk < 4 * M; ++kk) {
                                     const int s = 4 * kk + g;
-                                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(G[s * ldg + gq + pl] * xi[fb_xel(s, et * 16 + jl, ldx)],
-                                                                             xj[fb_xel(s, ct * 16 + jl, ldx)], a, 0, 0, 0);
+                                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(G[s * ldg + gq + pl] * xi[fp_xel(s, et * 16 + jl, ldx)],
+                                                                             xj[fp_xel(s, ct * 16 + jl, ldx)], a, 0, 0, 0);
                                 }
                                 const int c = ct * 16 + jl;
 #pragma unroll
@@ -449,23 +419,18 @@ void fb_plan(const dctr_fieldpair_args_t* a, FbPlan* pl) {
     for (;; M >>= 1) {
         pl->gfull = pl->P > pl->NP && pl->P < FB_LDG_FULL;
         pl->ldg = pl->gfull ? FB_LDG_FULL : FB_LDG;
-        if ((size_t)fb_tile_floats(a, pl, M) * sizeof(float) <= FB_LDS_MAX) break;
+        if ((size_t)fb_tile_floats(a, pl, M) * sizeof(float) <= DCTR_LDS_MAX) break;
         pl->gfull = false;
         pl->ldg = FB_LDG;
-        if ((size_t)fb_tile_floats(a, pl, M) * sizeof(float) <= FB_LDS_MAX || M == 1) break;
+        if ((size_t)fb_tile_floats(a, pl, M) * sizeof(float) <= DCTR_LDS_MAX || M == 1) break;
     }
     pl->M = M;
     pl->tile_floats = fb_tile_floats(a, pl, M);
     pl->ok = pl->tile_floats < 0x3fffffffLL;    // a tile's buffers are indexed in 32 bits
-    pl->global = false;
-    pl->grid_max = 0;
-    pl->route_bytes = 0;
-    const size_t tb = (size_t)pl->tile_floats * sizeof(float);
-    if (!pl->ok || tb <= FB_LDS_MAX) return;
-    pl->global = true;
-    const size_t gmax = FB_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(gmax < 1 ? 1 : gmax > FB_GLOBAL_WGS ? FB_GLOBAL_WGS : gmax);
-    pl->route_bytes = tb * pl->grid_max;
+    const dctr_tile_route r = pl->ok ? dctr_plan_tile_route((size_t)pl->tile_floats * sizeof(float)) : dctr_tile_route{false, 0, 0};
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 // the forward's size checks (fp_check of fieldpair_kernels.hip; its outputs are not read) and the backward's own
@@ -518,11 +483,8 @@ extern "C" int dctr_fieldpair_bwd(const dctr_fieldpair_bwd_args_t* b, void* stre
     const bool fwfm = a->kind == DCTR_FIELDPAIR_FWFM;
     DCTR_REQUIRE(a->x && a->weights, DCTR_E_NULL, "fieldpair_bwd: null x / weights");
     DCTR_REQUIRE(fwfm ? b->d_logit != nullptr : (b->d_pairs || b->d_logit), DCTR_E_NULL, "fieldpair_bwd: no gradient (d_pairs / d_logit)");
-    if (pl.route_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.route_bytes, DCTR_E_NULL,
-                     "fieldpair_bwd: this shape needs a workspace of %zu bytes (dctr_fieldpair_bwd_workspace_bytes)", pl.route_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "fieldpair_bwd: workspace not 16-B aligned");
-    }
+    if (pl.route_bytes)
+        DCTR_REQUIRE_WORKSPACE("fieldpair_bwd", "dctr_fieldpair_bwd_workspace_bytes", a->workspace, a->workspace_bytes, pl.route_bytes);
     if (a->batch == 0 || (!b->dx && !b->d_weights)) return DCTR_OK;
     FbParams p = {};
     p.x = a->x + a->x_offset;

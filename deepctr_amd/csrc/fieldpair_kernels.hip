@@ -25,18 +25,21 @@
 #include <math.h>
 #include <stdint.h>
 #include "dctr_common.h"
+#include "fieldpair_device.h"
 #include "mfma_tile.h"
+#include "pair_index.h"
+#include "tile_route.h"
 
 namespace {
+
+using dctr::fp_gptr;
+using dctr::fp_xoff;
 
 constexpr int FP_THREADS = 512;                // 8 waves
 constexpr int FP_WAVES = FP_THREADS / 64;
 constexpr int FP_Q = 2;                         // pairs per wave task: 2 x M independent accumulators, 10 weight loads in flight
 constexpr int FP_NP = 128;                      // pairs per chunk (staging buffer and pair table)
 constexpr int FW_THREADS = 256;                 // FwFM: 16 samples x 16 e-lanes
-constexpr size_t FP_LDS_MAX = 160 * 1024;
-constexpr int FP_GLOBAL_WGS = 256;
-constexpr size_t FP_GLOBAL_MAX = (size_t)256 << 20;
 
 struct FpParams {
     const float* x;              // already advanced by x_offset
@@ -76,55 +79,11 @@ __host__ __device__ inline FpLayout fp_layout(int F, int S, int ldx, int ldo, in
     return L;
 }
 
-// first pair index of row i in itertools.combinations(range(F), 2) order
-__device__ __forceinline__ int64_t fp_row_start(int64_t i, int F) { return i * (2 * (int64_t)F - i - 1) / 2; }
-
-__device__ void fp_pair(int64_t p, int F, int* pi, int* pj) {
-    const double b = 2.0 * F - 1.0;
-    int64_t i = (int64_t)((b - sqrt(b * b - 8.0 * (double)p)) * 0.5);
-    if (i < 0) i = 0;
-    if (i > F - 2) i = F - 2;
-    while (i > 0 && fp_row_start(i, F) > p) --i;
-    while (i < F - 2 && fp_row_start(i + 1, F) <= p) ++i;
-    *pi = (int)i;
-    *pj = (int)(p - fp_row_start(i, F) + i + 1);
-}
-
-// float offset of 16-B chunk `chunk` of sample row s inside one field of X (rows of ldx floats, ldx % 16 == 0)
-__device__ __forceinline__ int fp_xoff(int s, int chunk, int ldx) { return s * ldx + ((chunk ^ ((s >> 1) & 3)) << 2); }
-
 __device__ __forceinline__ float fp_dot4(const dctr::f32x4& a, const float4& b) {
     return fmaf(a[3], b.w, fmaf(a[2], b.z, fmaf(a[1], b.y, a[0] * b.x)));
 }
 
-// the S operand of one pair at E <= 16, before the add: row[tt] = W[c][4g + tt], col[tt] = W[4g + tt][c] (indices clamped: the
-// product meets zero padding of X there)
-struct FpRaw {
-    float row[FP_Q][4], col[FP_Q][4];
-};
-
-// the weight matrices are in global memory: a pointer read back from the LDS table is generic to the compiler, and a generic (flat)
-// load counts against the LDS counter as well, which would tie every ds_read wait to the L2 round trip
-typedef const __attribute__((address_space(1))) float* fp_gptr;
-typedef const __attribute__((address_space(1))) dctr::f32x4* fp_gptr4;
-
-__device__ __forceinline__ void fp_load_small(const float* const* wp, int q0, int np, int E, bool vec, FpRaw& raw) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, c = min(lane & 15, E - 1);
-#pragma unroll
-    for (int q = 0; q < FP_Q; ++q) {
-        const fp_gptr w = (fp_gptr)wp[min(q0 + q, np - 1)];
-        if (vec && ((uintptr_t)w & 15) == 0) {
-            const dctr::f32x4 t = *(fp_gptr4)(w + c * E + min(4 * g, E - 4));
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) raw.row[q][tt] = t[tt];
-        } else {
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) raw.row[q][tt] = w[c * E + min(4 * g + tt, E - 1)];
-        }
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) raw.col[q][tt] = w[min(4 * g + tt, E - 1) * E + c];
-    }
-}
+using FpRaw = dctr::FpRaw<FP_Q>;
 
 template <bool GLOBAL_WS, int M>
 __global__ __launch_bounds__(FP_THREADS) void fefm_kernel(FpParams p) {
@@ -155,7 +114,7 @@ __global__ __launch_bounds__(FP_THREADS) void fefm_kernel(FpParams p) {
     }
     if (one_chunk) {                            // the pair table does not depend on the tile
         for (int t = tid; t < (int)p.P; t += FP_THREADS) {
-            fp_pair(t, F, &pij[2 * t], &pij[2 * t + 1]);
+            dctr::pair_at(t, F, &pij[2 * t], &pij[2 * t + 1]);
             wp[t] = p.wt[t];
         }
     }
@@ -178,7 +137,7 @@ __global__ __launch_bounds__(FP_THREADS) void fefm_kernel(FpParams p) {
             const int np = (int)min((int64_t)p.NP, p.P - q0);
             if (!one_chunk) {
                 for (int t = tid; t < np; t += FP_THREADS) {
-                    fp_pair(q0 + t, F, &pij[2 * t], &pij[2 * t + 1]);
+                    dctr::pair_at(q0 + t, F, &pij[2 * t], &pij[2 * t + 1]);
                     wp[t] = p.wt[q0 + t];
                 }
             }
@@ -186,9 +145,9 @@ __global__ __launch_bounds__(FP_THREADS) void fefm_kernel(FpParams p) {
             const int ng = (np + FP_Q - 1) / FP_Q;
             if (small) {
                 FpRaw cur = {}, nxt = {};
-                if (wave < ng) fp_load_small(wp, wave * FP_Q, np, E, vec, cur);
+                if (wave < ng) dctr::fp_load_small(wp, wave * FP_Q, np, E, vec, cur);
                 for (int t = wave; t < ng; t += FP_WAVES) {
-                    if (t + FP_WAVES < ng) fp_load_small(wp, (t + FP_WAVES) * FP_Q, np, E, vec, nxt);
+                    if (t + FP_WAVES < ng) dctr::fp_load_small(wp, (t + FP_WAVES) * FP_Q, np, E, vec, nxt);
                     int pp[FP_Q], pi[FP_Q], pj[FP_Q];
                     dctr::f32x4 acc[FP_Q][M];
 #pragma unroll
@@ -375,20 +334,13 @@ void fp_plan(const dctr_fieldpair_args_t* a, FpPlan* pl) {
     // more samples per workgroup = fewer weight reads from L2, as long as the grid still fills the chip.  Measured at the Criteo shape,
     // 65,536 rows: M = 2 (two workgroups per CU) 0.24 ms, M = 4 (one per CU: its phases overlap with nothing) 0.29, M = 1 0.30
     int M = a->kind == DCTR_FIELDPAIR_FWFM ? 1 : a->batch >= 32 * 256 ? 2 : 1;
-    while (M > 1 && (size_t)fp_tile_floats(a, pl, M) * sizeof(float) > FP_LDS_MAX) M >>= 1;
+    while (M > 1 && (size_t)fp_tile_floats(a, pl, M) * sizeof(float) > DCTR_LDS_MAX) M >>= 1;
     pl->M = M;
     pl->tile_floats = fp_tile_floats(a, pl, M);
-    const size_t tb = (size_t)pl->tile_floats * sizeof(float);
-    if (tb <= FP_LDS_MAX) {
-        pl->global = false;
-        pl->grid_max = 0;
-        pl->route_bytes = 0;
-        return;
-    }
-    pl->global = true;
-    const size_t gmax = FP_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(gmax < 1 ? 1 : gmax > FP_GLOBAL_WGS ? FP_GLOBAL_WGS : gmax);
-    pl->route_bytes = tb * pl->grid_max;
+    const dctr_tile_route r = dctr_plan_tile_route((size_t)pl->tile_floats * sizeof(float));
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 int fp_check(const dctr_fieldpair_args_t* a) {
@@ -426,11 +378,8 @@ extern "C" int dctr_fieldpair_fwd(const dctr_fieldpair_args_t* a, void* stream) 
     DCTR_REQUIRE(a->x && a->weights, DCTR_E_NULL, "fieldpair_fwd: null x / weights");
     DCTR_REQUIRE(a->kind == DCTR_FIELDPAIR_FEFM ? (a->pairs_out || a->logit_out) : a->logit_out != nullptr, DCTR_E_NULL,
                  "fieldpair_fwd: no output (pairs_out / logit_out)");
-    if (pl.route_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.route_bytes, DCTR_E_NULL,
-                     "fieldpair_fwd: this shape needs a workspace of %zu bytes (dctr_fieldpair_workspace_bytes)", pl.route_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "fieldpair_fwd: workspace not 16-B aligned");
-    }
+    if (pl.route_bytes)
+        DCTR_REQUIRE_WORKSPACE("fieldpair_fwd", "dctr_fieldpair_workspace_bytes", a->workspace, a->workspace_bytes, pl.route_bytes);
     if (a->batch == 0) return DCTR_OK;
     FpParams p = {};
     p.x = a->x + a->x_offset;

@@ -26,6 +26,7 @@
 #include <math.h>
 #include <type_traits>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -35,10 +36,7 @@ constexpr int GRU_WAVES = GRU_THREADS / 64;
 constexpr int GRU_ROWS = 16;                    // samples of a tile
 constexpr int GRU_MAX_LAYERS = 2;
 constexpr int GRU_XREG = 4;                     // x_{t+1} elements a thread holds in registers across the gate phase (E <= 64 entirely)
-constexpr size_t GRU_LDS_MAX = 160 * 1024;
 constexpr int GRU_GRID_MAX = 2048;
-constexpr int GRU_GLOBAL_WGS = 256;
-constexpr size_t GRU_GLOBAL_MAX = (size_t)256 << 20;
 constexpr int GRU_NW = DCTR_GRU_LAYER_PTRS;     // gate kernel, gate bias, candidate kernel, candidate bias
 
 struct GruParams {
@@ -302,17 +300,16 @@ void gru_plan(const dctr_gru_args_t* a, GruPlan* pl) {
     const int64_t w_floats = (int64_t)L * (2 * (int64_t)E * pl->ldwg + 2 * (int64_t)E * pl->ldwc + 3 * (int64_t)E);
     const size_t tiles_bytes = (size_t)(GRU_ROWS + pl->tile_floats) * 4;
     const size_t res_bytes = tiles_bytes + (size_t)w_floats * 4;
-    const bool res_fits = res_bytes <= GRU_LDS_MAX;
+    const bool res_fits = res_bytes <= DCTR_LDS_MAX;
     pl->resident = res_fits && a->route != DCTR_GRU_ROUTE_STREAMED;
-    pl->global_tiles = !pl->resident && tiles_bytes > GRU_LDS_MAX;
+    pl->global_tiles = !pl->resident && tiles_bytes > DCTR_LDS_MAX;
     pl->lds_bytes = pl->resident ? res_bytes : pl->global_tiles ? (size_t)GRU_ROWS * 4 : tiles_bytes;
     pl->grid_max = GRU_GRID_MAX;
     pl->ws_bytes = 0;
     if (pl->global_tiles) {
-        const size_t tb = (size_t)pl->tile_floats * 4;
-        const size_t gmax = GRU_GLOBAL_MAX / tb;
-        pl->grid_max = (int)(gmax < 1 ? 1 : gmax > GRU_GLOBAL_WGS ? GRU_GLOBAL_WGS : gmax);
-        pl->ws_bytes = tb * pl->grid_max;
+        const dctr_tile_route r = dctr_workspace_slices((size_t)pl->tile_floats * 4);
+        pl->grid_max = r.grid_max;
+        pl->ws_bytes = r.route_bytes;
     }
 }
 
@@ -376,11 +373,7 @@ extern "C" int dctr_gru_fwd(const dctr_gru_args_t* a, void* stream) {
             DCTR_REQUIRE(a->layers[GRU_NW * l + m], DCTR_E_NULL, "gru_fwd: layer %d: null gate / candidate kernel or bias", l);
     GruPlan pl;
     gru_plan(a, &pl);
-    if (pl.ws_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.ws_bytes, DCTR_E_NULL,
-                     "gru_fwd: this shape needs a workspace of %zu bytes (dctr_gru_workspace_bytes)", pl.ws_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "gru_fwd: workspace not 16-B aligned");
-    }
+    if (pl.ws_bytes) DCTR_REQUIRE_WORKSPACE("gru_fwd", "dctr_gru_workspace_bytes", a->workspace, a->workspace_bytes, pl.ws_bytes);
     if (a->batch == 0) return DCTR_OK;
     GruParams p = {};
     p.x = a->x;

@@ -20,6 +20,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 
 namespace {
 
@@ -30,7 +31,6 @@ constexpr int IFM_ROWS = 16;                      // samples of a wave
 constexpr int IFM_WG_ROWS = 64;                   // samples of a workgroup
 constexpr int IFM_KC = 64;                        // source columns per LDS chunk
 constexpr int IFM_APITCH = IFM_KC + 4;            // bank = 4 * row + k-slot: the 64 operand reads of an MFMA hit 64 banks
-constexpr size_t IFM_LDS_MAX = 160 * 1024;
 constexpr int IFM_SMALL_WG_BELOW = 2;             // one-wave workgroups while four-wave ones would number fewer than this many per CU
 
 enum { IFM_FUSED = 0, IFM_PROJECT = 1, IFM_EPILOGUE = 2 };
@@ -249,7 +249,7 @@ void ifm_plan(const dctr_ifm_args_t* a, IfmPlan* pl) {
     const size_t Fpad = ((size_t)a->n_fields + 15) / 16 * 16;
     pl->lds_project = (size_t)4 * IFM_ROWS * IFM_APITCH * 4;
     pl->lds = a->n_src > 0 ? pl->lds_project + (size_t)4 * IFM_ROWS * (Fpad + 4) * 4 : 0;
-    pl->workspace = a->n_src > 0 && (a->route == DCTR_IFM_ROUTE_WORKSPACE || pl->lds > IFM_LDS_MAX);
+    pl->workspace = a->n_src > 0 && (a->route == DCTR_IFM_ROUTE_WORKSPACE || pl->lds > DCTR_LDS_MAX);
     pl->ws_bytes = pl->workspace ? ((size_t)a->batch * (size_t)a->n_fields * 4 + 15) & ~(size_t)15 : 0;
 }
 

@@ -22,6 +22,7 @@
 #include <math.h>
 #include "dctr_common.h"
 #include "mfma_tile.h"
+#include "tile_route.h"
 
 namespace {
 
@@ -31,9 +32,6 @@ constexpr int IB_WAVES = IB_THREADS / 64;
 constexpr int IB_DC = 16;                       // columns of one head a thread accumulates per pass over the other fields
 constexpr int IB_MAX_S = 16;
 constexpr size_t IB_LDS_TARGET = 80 * 1024;     // as the forward: two workgroups per CU where the samples allow it
-constexpr size_t IB_LDS_MAX = 160 * 1024;
-constexpr int IB_GLOBAL_WGS = 256;
-constexpr size_t IB_GLOBAL_MAX = (size_t)256 << 20;
 
 struct IbParams {
     const float* x;
@@ -365,12 +363,10 @@ void ib_plan(const dctr_interacting_args_t* a, IbPlan* pl) {
     while (S > 1 && (size_t)ib_tile_floats(S, a->fields, a->n_layers, a->head_num, pl->ldx, pl->ldq, pl->acc_floats) * 4 > IB_LDS_TARGET) --S;
     pl->tile_floats = ib_tile_floats(S, a->fields, a->n_layers, a->head_num, pl->ldx, pl->ldq, pl->acc_floats);
     pl->S = S;
-    if ((size_t)pl->tile_floats * 4 <= IB_LDS_MAX) return;
-    pl->global = true;
-    const size_t tb = (size_t)pl->tile_floats * 4;
-    size_t g = IB_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(g < 1 ? 1 : g > IB_GLOBAL_WGS ? IB_GLOBAL_WGS : g);
-    pl->route_bytes = tb * pl->grid_max;
+    const dctr_tile_route r = dctr_plan_tile_route((size_t)pl->tile_floats * 4);
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 // the forward's size checks (ia_check of interacting_kernels.hip; out / head_w / logit are not read) and the backward's own
@@ -418,11 +414,8 @@ extern "C" int dctr_interacting_bwd(const dctr_interacting_bwd_args_t* b, void* 
     for (int l = 0; l < a->n_layers; ++l)
         DCTR_REQUIRE(a->layers[4 * l] && a->layers[4 * l + 1] && a->layers[4 * l + 2] && (!a->use_res || a->layers[4 * l + 3]),
                      DCTR_E_NULL, "interacting_bwd: layer %d: null weight", l);
-    if (pl.route_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.route_bytes, DCTR_E_NULL,
-                     "interacting_bwd: this shape needs a workspace of %zu bytes (dctr_interacting_bwd_workspace_bytes)", pl.route_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "interacting_bwd: workspace not 16-B aligned");
-    }
+    if (pl.route_bytes)
+        DCTR_REQUIRE_WORKSPACE("interacting_bwd", "dctr_interacting_bwd_workspace_bytes", a->workspace, a->workspace_bytes, pl.route_bytes);
     if (a->batch == 0) return DCTR_OK;
     const int nb = a->use_res ? 4 : 3;
     IbParams p = {};

@@ -19,6 +19,7 @@
 #include <math.h>
 #include "dctr_common.h"
 #include "mfma_tile.h"
+#include "tile_route.h"
 
 namespace {
 
@@ -27,9 +28,6 @@ constexpr int IA_THREADS = 256;
 constexpr int IA_DC = 16;                       // output columns of one head a thread accumulates per pass over the keys
 constexpr int IA_MAX_S = 16;                    // samples per workgroup tile
 constexpr size_t IA_LDS_TARGET = 80 * 1024;     // two workgroups per CU where the samples allow it
-constexpr size_t IA_LDS_MAX = 160 * 1024;
-constexpr int IA_GLOBAL_WGS = 256;
-constexpr size_t IA_GLOBAL_MAX = (size_t)256 << 20;
 
 struct IaParams {
     const float* x;
@@ -197,21 +195,13 @@ void ia_plan(const dctr_interacting_args_t* a, IaPlan* pl) {
     pl->chain_bytes = 0;
     if (a->n_layers > IA_MAX_LAYERS && !a->out)
         pl->chain_bytes = (size_t)(a->batch > 0 ? a->batch : 0) * a->fields * dH * sizeof(float);
-    if ((size_t)ia_tile_floats(S, a->fields, pl->ldx, pl->ldq, nb) * 4 <= IA_LDS_MAX) {
-        pl->global = false;
-        pl->S = S;
-        pl->tile_floats = ia_tile_floats(S, a->fields, pl->ldx, pl->ldq, nb);
-        pl->grid_max = 0;
-        pl->route_bytes = 0;
-        return;
-    }
-    pl->global = true;
-    pl->S = 1;
-    pl->tile_floats = ia_tile_floats(1, a->fields, pl->ldx, pl->ldq, nb);
-    const size_t tb = (size_t)pl->tile_floats * 4;
-    size_t g = IA_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(g < 1 ? 1 : g > IA_GLOBAL_WGS ? IA_GLOBAL_WGS : g);
-    pl->route_bytes = tb * pl->grid_max;
+    // S > 1 left the loop under IA_LDS_TARGET: only a single sample's tile can exceed the LDS and take the general route
+    pl->S = S;
+    pl->tile_floats = ia_tile_floats(S, a->fields, pl->ldx, pl->ldq, nb);
+    const dctr_tile_route r = dctr_plan_tile_route((size_t)pl->tile_floats * 4);
+    pl->global = r.global;
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 int ia_check(const dctr_interacting_args_t* a) {
@@ -252,11 +242,7 @@ extern "C" int dctr_interacting_fwd(const dctr_interacting_args_t* a, void* stre
     IaPlan pl;
     ia_plan(a, &pl);
     const size_t need = pl.route_bytes + pl.chain_bytes;
-    if (need) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= need, DCTR_E_NULL,
-                     "interacting_fwd: this shape needs a workspace of %zu bytes (dctr_interacting_workspace_bytes)", need);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "interacting_fwd: workspace not 16-B aligned");
-    }
+    if (need) DCTR_REQUIRE_WORKSPACE("interacting_fwd", "dctr_interacting_workspace_bytes", a->workspace, a->workspace_bytes, need);
     const int dH = a->att_embedding_size * a->head_num;
     float* chain = a->out ? a->out : (pl.chain_bytes ? (float*)((char*)a->workspace + pl.route_bytes) : nullptr);
     const int64_t chain_stride = a->out ? a->out_stride : (int64_t)a->fields * dH;

@@ -26,6 +26,7 @@
 #include <math.h>
 #include <type_traits>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -34,10 +35,7 @@ constexpr int LSTM_THREADS = 256;
 constexpr int LSTM_WAVES = LSTM_THREADS / 64;
 constexpr int LSTM_ROWS = 16;                   // samples of a tile
 constexpr int LSTM_MAX_LAYERS = DCTR_LSTM_MAX_LAYERS;
-constexpr size_t LSTM_LDS_MAX = 160 * 1024;
 constexpr int LSTM_GRID_MAX = 2048;
-constexpr int LSTM_GLOBAL_WGS = 256;
-constexpr size_t LSTM_GLOBAL_MAX = (size_t)256 << 20;
 constexpr int LSTM_NW = DCTR_LSTM_LAYER_PTRS;   // fw kernel, fw recurrent kernel, fw bias, bw kernel, bw recurrent kernel, bw bias
 
 struct LstmParams {
@@ -240,16 +238,16 @@ void lstm_plan(const dctr_lstm_args_t* a, LstmPlan* pl) {
     const int64_t w_floats = 2 * (L > 1 && w1 > w0 ? w1 : w0);
     const size_t tiles_bytes = (size_t)pl->tile_floats * 4;
     const size_t res_bytes = tiles_bytes + (size_t)w_floats * 4;
-    const bool res_fits = res_bytes <= LSTM_LDS_MAX;
+    const bool res_fits = res_bytes <= DCTR_LDS_MAX;
     pl->resident = res_fits && (a->route == DCTR_LSTM_ROUTE_AUTO || a->route == DCTR_LSTM_ROUTE_RESIDENT);
-    pl->global_tiles = !pl->resident && (tiles_bytes > LSTM_LDS_MAX || a->route == DCTR_LSTM_ROUTE_WORKSPACE);
+    pl->global_tiles = !pl->resident && (tiles_bytes > DCTR_LDS_MAX || a->route == DCTR_LSTM_ROUTE_WORKSPACE);
     pl->lds_bytes = pl->resident ? res_bytes : pl->global_tiles ? 0 : tiles_bytes;
     pl->grid_max = LSTM_GRID_MAX;
     pl->ws_bytes = 0;
     if (pl->global_tiles) {
-        const size_t gmax = LSTM_GLOBAL_MAX / tiles_bytes;
-        pl->grid_max = (int)(gmax < 1 ? 1 : gmax > LSTM_GLOBAL_WGS ? LSTM_GLOBAL_WGS : gmax);
-        pl->ws_bytes = tiles_bytes * pl->grid_max;
+        const dctr_tile_route r = dctr_workspace_slices(tiles_bytes);
+        pl->grid_max = r.grid_max;
+        pl->ws_bytes = r.route_bytes;
     }
 }
 
@@ -334,11 +332,8 @@ extern "C" int dctr_bilstm_fwd(const dctr_lstm_args_t* a, void* stream) {
             for (int m = 0; m < LSTM_NW; ++m)
                 DCTR_REQUIRE(m % 3 == 2 || dctr_aligned16(a->layers[LSTM_NW * l + m]), DCTR_E_ALIGN,
                              "bilstm_fwd: layer %d: kernel / recurrent kernel not 16-B aligned", l);
-    if (pl.ws_bytes) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= pl.ws_bytes, DCTR_E_NULL,
-                     "bilstm_fwd: this shape needs a workspace of %zu bytes (dctr_bilstm_workspace_bytes)", pl.ws_bytes);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "bilstm_fwd: workspace not 16-B aligned");
-    }
+    if (pl.ws_bytes)
+        DCTR_REQUIRE_WORKSPACE("bilstm_fwd", "dctr_bilstm_workspace_bytes", a->workspace, a->workspace_bytes, pl.ws_bytes);
     if (a->batch == 0) return DCTR_OK;
     LstmParams p = {};
     p.x = a->x;

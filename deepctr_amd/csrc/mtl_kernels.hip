@@ -18,6 +18,7 @@
 // already lie in HBM (the host runs experts and gate DNNs through dctr_mlp_fwd).  One wave per row; any shape.
 #include <math.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -26,7 +27,6 @@ constexpr int MT_THREADS = 512;
 constexpr int MT_WAVES = MT_THREADS / 64;
 constexpr int MT_MAX_SLOTS = 8, MT_MAX_EXPERTS = 16, MT_MAX_ELAYERS = 32, MT_MAX_GATES = 8, MT_MAX_GLAYERS = 16, MT_MAX_MEMBERS = 64;
 constexpr int MT_MAX_DEPTH = 4;
-constexpr size_t MT_LDS_MAX = 160 * 1024;
 constexpr int MX_THREADS = 256;
 constexpr int MX_MAX_GATES = 8;               // gates per dctr_mtl_mix launch (kernel-argument space)
 
@@ -358,7 +358,7 @@ void mtl_plan(const dctr_mtl_args_t* a, int kind, MtPlan* pl) {
     for (int R = 64; R >= 16; R >>= 1) {
         if (a->tile_rows && R > a->tile_rows) continue;
         const int64_t need = per_row * R * (int64_t)sizeof(float);
-        if (need <= (int64_t)MT_LDS_MAX) {
+        if (need <= (int64_t)DCTR_LDS_MAX) {
             pl->fused = true;
             pl->R = R;
             pl->lds = (size_t)need;

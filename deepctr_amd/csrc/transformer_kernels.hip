@@ -32,6 +32,7 @@
 //   (37.7 KiB of the sample + 33 KiB of slabs); S 2 would be 104 KiB -> S = 1.
 #include <math.h>
 #include "dctr_common.h"
+#include "tile_route.h"
 #include "mfma_tile.h"
 
 namespace {
@@ -42,9 +43,6 @@ constexpr int TF_WAVES = TF_THREADS / 64;
 constexpr int TF_DC = 16;                       // output columns of one head a thread accumulates per pass over the keys
 constexpr int TF_MAX_S = 16;
 constexpr size_t TF_LDS_TARGET = 80 * 1024;
-constexpr size_t TF_LDS_MAX = 160 * 1024;
-constexpr int TF_GLOBAL_WGS = 256;
-constexpr size_t TF_GLOBAL_MAX = (size_t)256 << 20;
 constexpr int TF_NW = 9;                        // pointers per layer: query, key, value, fw1, fw2, ln_gamma, ln_beta, pe_q, pe_k
 
 struct TfParams {
@@ -332,22 +330,13 @@ void tf_plan(const dctr_transformer_args_t* a, TfPlan* pl) {
         pl->chain_bytes = (size_t)(a->batch > 0 ? a->batch : 0) * T * E * sizeof(float);
     int S = TF_MAX_S;
     while (S > 1 && (size_t)tf_tile_floats(S, T, pl->ldx, pl->ldq, pl->ldh) * 4 > TF_LDS_TARGET) --S;
-    const bool fits = (size_t)tf_tile_floats(S, T, pl->ldx, pl->ldq, pl->ldh) * 4 <= TF_LDS_MAX;
-    if (fits && a->route != DCTR_TRANSFORMER_ROUTE_GENERAL) {
-        pl->global = false;
-        pl->S = S;
-        pl->tile_floats = tf_tile_floats(S, T, pl->ldx, pl->ldq, pl->ldh);
-        pl->grid_max = 0;
-        pl->route_bytes = 0;
-        return;
-    }
-    pl->global = true;
-    pl->S = 1;
-    pl->tile_floats = tf_tile_floats(1, T, pl->ldx, pl->ldq, pl->ldh);
-    const size_t tb = (size_t)pl->tile_floats * 4;
-    size_t g = TF_GLOBAL_MAX / tb;
-    pl->grid_max = (int)(g < 1 ? 1 : g > TF_GLOBAL_WGS ? TF_GLOBAL_WGS : g);
-    pl->route_bytes = tb * pl->grid_max;
+    const bool fits = (size_t)tf_tile_floats(S, T, pl->ldx, pl->ldq, pl->ldh) * 4 <= DCTR_LDS_MAX;
+    pl->global = !fits || a->route == DCTR_TRANSFORMER_ROUTE_GENERAL;      // the general route takes one sample per tile
+    pl->S = pl->global ? 1 : S;
+    pl->tile_floats = tf_tile_floats(pl->S, T, pl->ldx, pl->ldq, pl->ldh);
+    const dctr_tile_route r = pl->global ? dctr_workspace_slices((size_t)pl->tile_floats * 4) : dctr_tile_route{false, 0, 0};
+    pl->grid_max = r.grid_max;
+    pl->route_bytes = r.route_bytes;
 }
 
 int tf_check(const dctr_transformer_args_t* a) {
@@ -415,11 +404,7 @@ extern "C" int dctr_transformer_fwd(const dctr_transformer_args_t* a, void* stre
     TfPlan pl;
     tf_plan(a, &pl);
     const size_t need = pl.route_bytes + pl.chain_bytes;
-    if (need) {
-        DCTR_REQUIRE(a->workspace && a->workspace_bytes >= need, DCTR_E_NULL,
-                     "transformer_fwd: this shape needs a workspace of %zu bytes (dctr_transformer_workspace_bytes)", need);
-        DCTR_REQUIRE(dctr_aligned16(a->workspace), DCTR_E_ALIGN, "transformer_fwd: workspace not 16-B aligned");
-    }
+    if (need) DCTR_REQUIRE_WORKSPACE("transformer_fwd", "dctr_transformer_workspace_bytes", a->workspace, a->workspace_bytes, need);
     if (a->batch == 0) return DCTR_OK;
     const int T = a->seq_len, E = a->dim;
     const bool pooled = a->output_type != DCTR_TRANSFORMER_OUT_NONE;

@@ -105,6 +105,97 @@ def _x_in_place(op, x, fields, dim, x_offset=0):
     return x, B, F, E, _rows2d(op, "x (with fields / dim)", x, B, F * E, x_offset), int(x_offset)
 
 
+def _dx_operand(op, dx, B, F, E, dx_offset, extra_cols=0):
+    """The input gradient a backward wrapper writes: a contiguous float32 [B,F,E] tensor (no offset, no extra columns), or a float32
+    2-D view that holds the F*E + ``extra_cols`` columns from ``dx_offset``.  Returns its row stride (0 for None)."""
+    if dx is None:
+        return 0
+    if dx.dim() == 3 and dx_offset == 0 and not extra_cols and tuple(dx.shape) == (B, F, E) and dx.is_contiguous() \
+            and dx.dtype == torch.float32:
+        return F * E
+    return _rows2d(op, "dx", dx, B, F * E + extra_cols, dx_offset)
+
+
+def _bilinear_operands(op, x, fields, dim, senet_w, senet_bilinear_w, bilinear_w, bilinear_type, dense_cols):
+    """What senet_bilinear() and senet_bilinear_bwd() read alike: x (_x_in_place), the mode the given weights pick, W_1 [F,r] and
+    W_2 [r,F], and the device tables of the two BilinearInteractions' matrices.  Returns (x, B, F, E, x_stride, mode, r, (w1, w2),
+    (senet_bilinear table, bilinear table), tensors) — None for what the mode has not, ``tensors`` for the device check."""
+    x, B, F, E, x_stride, _ = _x_in_place(op, x, fields, dim)
+    if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
+        mode = _C.bilinear.MODE_MODEL
+    elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_SENET
+    elif senet_w is None and bilinear_w is not None and senet_bilinear_w is None:
+        mode = _C.bilinear.MODE_LAYER
+    else:
+        raise ValueError("%s: give senet_w + senet_bilinear_w + bilinear_w, senet_w alone, or bilinear_w alone" % op)
+    if mode != _C.bilinear.MODE_MODEL and dense_cols:
+        raise ValueError("%s: dense_cols exist in the three-weight (FiBiNET) form only" % op)
+    if F < 2:
+        raise ValueError("%s: %d field(s): the layers need at least 2" % (op, F))
+    tensors = [x]
+    r = 0
+    w1 = w2 = None
+    if senet_w is not None:
+        w1, w2 = (_f32c(w, "senet_w") for w in senet_w)
+        r = w1.shape[1] if w1.dim() == 2 else -1
+        if r < 1 or tuple(w1.shape) != (F, r) or tuple(w2.shape) != (r, F):
+            raise ValueError("%s: senet_w must be W_1 [%d, r] and W_2 [r, %d]" % (op, F, F))
+        tensors += [w1, w2]
+    nW = bilinear_weight_count(bilinear_type, F)
+    tables = []
+    for ws in (senet_bilinear_w, bilinear_w):
+        if ws is None:
+            tables.append(None)
+            continue
+        ws = [_f32c(w, "bilinear weight") for w in ws]
+        if len(ws) != nW or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("%s: bilinear_type %r over %d fields takes %d matrices [%d, %d]" % (op, bilinear_type, F, nW, E, E))
+        tensors += ws
+        tables.append(bilinear_table(ws))
+    return x, B, F, E, x_stride, mode, r, (w1, w2), tables, tensors
+
+
+def _fieldpair_operands(op, x, weights, kind, fields, dim, x_offset):
+    """What fieldpair() and fieldpair_bwd() read alike: the kind, x (_x_in_place) over at least 2 fields, and the weights — FEFM's
+    P = F(F-1)/2 matrices [E,E] behind a device table of their addresses, or FwFM's field_pair_strengths [F,F].  Returns
+    (x, B, F, E, x_stride, x_offset, P, wptr, tensors): ``wptr`` is the tensor dctr_fieldpair_args_t.weights points to, ``tensors``
+    are for the device check."""
+    if kind not in _FIELDPAIR_KINDS:
+        raise ValueError("%s: kind %r: expected 'fefm' or 'fwfm'" % (op, kind))
+    x, B, F, E, x_stride, x_offset = _x_in_place(op, x, fields, dim, x_offset)
+    if F < 2:
+        raise ValueError("%s: %d field(s): a field pair needs at least 2" % (op, F))
+    P = F * (F - 1) // 2
+    if kind == "fefm":
+        ws = [_f32c(w, "field_embeddings") for w in weights]
+        if len(ws) != P or any(tuple(w.shape) != (E, E) for w in ws):
+            raise ValueError("%s: FEFM over %d fields takes %d matrices [%d, %d]" % (op, F, P, E, E))
+        return x, B, F, E, x_stride, x_offset, P, bilinear_table(ws), [x] + ws
+    r = _f32c(weights, "field_pair_strengths")
+    if tuple(r.shape) != (F, F):
+        raise ValueError("%s: FwFM over %d fields takes field_pair_strengths [%d, %d]" % (op, F, F, F))
+    return x, B, F, E, x_stride, x_offset, P, r, [x, r]
+
+
+def _zeroed_grads(weights, wanted, device):
+    """The backward ops ACCUMULATE into their weight gradients: ONE zeroed float32 buffer (one fill) with a slot per weight, in
+    order (a None weight takes none), and per weight its slot viewed in the weight's shape where ``wanted``, else None.  Returns
+    (flat, views); flat is None when nothing is wanted."""
+    views = [None] * len(weights)
+    if not any(wanted):
+        return None, views
+    flat = torch.zeros(sum(w.numel() for w in weights if w is not None), dtype=torch.float32, device=device)
+    at = 0
+    for i, w in enumerate(weights):
+        if w is None:
+            continue
+        if wanted[i]:
+            views[i] = flat[at:at + w.numel()].view(w.shape)
+        at += w.numel()
+    return flat, views
+
+
 def _workspace(op, a, need, workspace, device):
     """Hand the args struct ``a`` the ``need`` bytes the library asked for: the caller's tensor if it is large enough, else the
     per-stream scratch.  Returns the tensor (None when nothing is needed)."""
@@ -729,18 +820,10 @@ class InteractingFunction(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         x, it = saved[0], iter(saved[1:])
         ws = [next(it) if present else None for present in ctx.present]
-        if dy.dtype != torch.float32:
-            dy = dy.float()
-        if dy.stride(-1) != 1 or (dy.shape[0] > 1 and dy.stride(0) < dy.shape[1]):      # (the second: rows broadcast by expand())
-            dy = dy.contiguous()
+        dy = _grad_operand(dy, True)
         dx = torch.empty_like(x, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
-        # the op accumulates: the wanted weight gradients are views of ONE zeroed buffer (one fill for the whole stack)
         wanted = [w is not None and ctx.needs_input_grad[5 + i] and (i % 4 < 3 or use_res) for i, w in enumerate(ws)]
-        flat = torch.zeros(sum(w.numel() for w, on in zip(ws, wanted) if on), dtype=torch.float32, device=x.device)
-        grads, at = [], 0
-        for w, on in zip(ws, wanted):
-            grads.append(flat[at:at + w.numel()].view(w.shape) if on else None)
-            at += w.numel() if on else 0
+        _, grads = _zeroed_grads(ws, wanted, x.device)      # one fill for the whole stack
         interacting_bwd(x, [ws[i:i + 4] for i in range(0, len(ws), 4)], d, H, use_res, scaling, dy,
                         dx=None if dx is None else dx.view(dx.shape[0], -1),
                         d_weights=[grads[i:i + 4] for i in range(0, len(ws), 4)])
@@ -800,36 +883,8 @@ def senet_bilinear(x, senet_w=None, senet_bilinear_w=None, bilinear_w=None, bili
       * ``bilinear_w`` alone: out [B, >= P*E] = the bilinear interaction over x.
     ``out`` is a 2-D (possibly strided) view, allocated when not given; ``workspace``: a float32 tensor of
     >= senet_bilinear_workspace_bytes (default: the per-stream scratch).  Returns ``out``."""
-    x, B, F, E, x_stride, _ = _x_in_place("senet_bilinear", x, fields, dim)
-    if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
-        mode = _C.bilinear.MODE_MODEL
-    elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
-        mode = _C.bilinear.MODE_SENET
-    elif senet_w is None and bilinear_w is not None and senet_bilinear_w is None:
-        mode = _C.bilinear.MODE_LAYER
-    else:
-        raise ValueError("senet_bilinear: give senet_w + senet_bilinear_w + bilinear_w, senet_w alone, or bilinear_w alone")
-    if mode != _C.bilinear.MODE_MODEL and dense_cols:
-        raise ValueError("senet_bilinear: dense_cols are copied by the three-weight (FiBiNET) form only")
-    tensors = [x]
-    r = 0
-    if senet_w is not None:
-        w1, w2 = (_f32c(w, "senet_w") for w in senet_w)
-        r = w1.shape[1]
-        if tuple(w1.shape) != (F, r) or tuple(w2.shape) != (r, F):
-            raise ValueError("senet_bilinear: senet_w must be W_1 [%d, r] and W_2 [r, %d]" % (F, F))
-        tensors += [w1, w2]
-    tables = []
-    for ws in (senet_bilinear_w, bilinear_w):
-        if ws is None:
-            tables.append(None)
-            continue
-        ws = [_f32c(w, "bilinear weight") for w in ws]
-        if len(ws) != bilinear_weight_count(bilinear_type, F) or any(tuple(w.shape) != (E, E) for w in ws):
-            raise ValueError("senet_bilinear: bilinear_type %r over %d fields takes %d matrices [%d, %d]"
-                             % (bilinear_type, F, bilinear_weight_count(bilinear_type, F), E, E))
-        tensors += ws
-        tables.append(bilinear_table(ws))
+    x, B, F, E, x_stride, mode, r, (w1, w2), tables, tensors = _bilinear_operands(
+        "senet_bilinear", x, fields, dim, senet_w, senet_bilinear_w, bilinear_w, bilinear_type, dense_cols)
     _dev_check(out, *tensors)
     width = senet_bilinear_width(F, E, mode, dense_cols)
     if out is None:
@@ -885,49 +940,12 @@ def senet_bilinear_bwd(x, d_out, senet_w=None, senet_bilinear_w=None, bilinear_w
     each.  All weight gradients are ACCUMULATED into; they leave through float atomics and may differ in the last bits from call to
     call.  Any output may be None, but not all of them."""
     op = "senet_bilinear_bwd"
-    x, B, F, E, x_stride, _ = _x_in_place(op, x, fields, dim)
-    if senet_w is not None and bilinear_w is not None and senet_bilinear_w is not None:
-        mode = _C.bilinear.MODE_MODEL
-    elif senet_w is not None and bilinear_w is None and senet_bilinear_w is None:
-        mode = _C.bilinear.MODE_SENET
-    elif senet_w is None and bilinear_w is not None and senet_bilinear_w is None:
-        mode = _C.bilinear.MODE_LAYER
-    else:
-        raise ValueError("senet_bilinear_bwd: give senet_w + senet_bilinear_w + bilinear_w, senet_w alone, or bilinear_w alone")
-    if mode != _C.bilinear.MODE_MODEL and dense_cols:
-        raise ValueError("senet_bilinear_bwd: dense_cols exist in the three-weight (FiBiNET) form only")
-    if F < 2:
-        raise ValueError("senet_bilinear_bwd: %d field(s): the layers need at least 2" % F)
-    tensors = [x]
-    r = 0
-    w1 = w2 = None
-    if senet_w is not None:
-        w1, w2 = (_f32c(w, "senet_w") for w in senet_w)
-        r = w1.shape[1] if w1.dim() == 2 else -1
-        if r < 1 or tuple(w1.shape) != (F, r) or tuple(w2.shape) != (r, F):
-            raise ValueError("senet_bilinear_bwd: senet_w must be W_1 [%d, r] and W_2 [r, %d]" % (F, F))
-        tensors += [w1, w2]
+    x, B, F, E, x_stride, mode, r, (w1, w2), tables, tensors = _bilinear_operands(
+        op, x, fields, dim, senet_w, senet_bilinear_w, bilinear_w, bilinear_type, dense_cols)
     nW = bilinear_weight_count(bilinear_type, F)
-    tables = []
-    for ws in (senet_bilinear_w, bilinear_w):
-        if ws is None:
-            tables.append(None)
-            continue
-        ws = [_f32c(w, "bilinear weight") for w in ws]
-        if len(ws) != nW or any(tuple(w.shape) != (E, E) for w in ws):
-            raise ValueError("senet_bilinear_bwd: bilinear_type %r over %d fields takes %d matrices [%d, %d]"
-                             % (bilinear_type, F, nW, E, E))
-        tensors += ws
-        tables.append(bilinear_table(ws))
     width = senet_bilinear_width(F, E, mode, dense_cols)
     d_out_stride = _rows2d(op, "d_out", d_out, B, width, d_out_offset)
-    dx_stride = 0
-    if dx is not None:
-        if dx.dim() == 3 and dx_offset == 0 and not dense_cols and tuple(dx.shape) == (B, F, E) and dx.is_contiguous() \
-                and dx.dtype == torch.float32:
-            dx_stride = F * E
-        else:
-            dx_stride = _rows2d(op, "dx", dx, B, F * E + dense_cols, dx_offset)
+    dx_stride = _dx_operand(op, dx, B, F, E, dx_offset, dense_cols)
     dw1, dw2 = d_senet_w if d_senet_w is not None else (None, None)
     if senet_w is None and (dw1 is not None or dw2 is not None):
         raise ValueError("senet_bilinear_bwd: d_senet_w without senet_w")
@@ -1029,13 +1047,7 @@ class SenetBilinearFunction(torch.autograd.Function):
                 flats.append(None)
                 continue
             n = len(layer)
-            flat = None
-            if any(wneed[at:at + n]):
-                # the op accumulates: the layer's per-matrix gradients are views of ONE zeroed buffer
-                flat = torch.zeros((n, E, E), dtype=torch.float32, device=x.device)
-                for k in range(n):
-                    if wneed[at + k]:
-                        grads[at + k] = flat[k]
+            flat, grads[at:at + n] = _zeroed_grads(layer, wneed[at:at + n], x.device)     # [n,E,E] behind the per-matrix views
             flats.append(flat)
             at += n
         if want_dx or any(g is not None for g in grads):
@@ -1070,29 +1082,13 @@ def fieldpair(x, weights, kind="fefm", fields=None, dim=None, x_offset=0, pairs=
       * kind "fwfm": ``weights`` = field_pair_strengths [F,F] (only r[i][j], i < j is read); ``logit`` only (True by default).
     ``add`` [B] is added to the logit in the same launch.  ``workspace``: a float32 tensor of >= fieldpair_workspace_bytes (default:
     the per-stream scratch).  Returns (pairs, logit), None for an output not asked for."""
-    if kind not in _FIELDPAIR_KINDS:
-        raise ValueError("fieldpair: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
-    x, B, F, E, x_stride, x_offset = _x_in_place("fieldpair", x, fields, dim, x_offset)
-    if F < 2:
-        raise ValueError("fieldpair: %d field(s): a field pair needs at least 2" % F)
-    P = F * (F - 1) // 2
-    tensors = [x]
+    x, B, F, E, x_stride, x_offset, P, wptr, tensors = _fieldpair_operands("fieldpair", x, weights, kind, fields, dim, x_offset)
     if kind == "fefm":
-        ws = [_f32c(w, "field_embeddings") for w in weights]
-        if len(ws) != P or any(tuple(w.shape) != (E, E) for w in ws):
-            raise ValueError("fieldpair: FEFM over %d fields takes %d matrices [%d, %d]" % (F, P, E, E))
-        tensors += ws
-        wptr = bilinear_table(ws)
         if pairs is None and logit is None:
             pairs = True
     else:
-        r = _f32c(weights, "field_pair_strengths")
-        if tuple(r.shape) != (F, F):
-            raise ValueError("fieldpair: FwFM over %d fields takes field_pair_strengths [%d, %d]" % (F, F, F))
         if pairs is not None:
             raise ValueError("fieldpair: the FwFM kind has no pair outputs")
-        tensors.append(r)
-        wptr = r
         if logit is None:
             logit = True
     if pairs is True:
@@ -1149,40 +1145,19 @@ def fieldpair_bwd(x, weights, kind, d_pairs=None, d_pairs_offset=0, d_logit=None
     written, or added to with ``accumulate`` — bit-identical from call to call.  ``d_weights``: ACCUMULATED into; FEFM one contiguous
     [P,E,E] tensor, FwFM [F,F] of which only the strict upper triangle is touched.  Weight gradients leave through float atomics and
     may differ in the last bits from call to call."""
-    if kind not in _FIELDPAIR_KINDS:
-        raise ValueError("fieldpair_bwd: kind %r: expected 'fefm' or 'fwfm'" % (kind,))
-    x, B, F, E, x_stride, x_offset = _x_in_place("fieldpair_bwd", x, fields, dim, x_offset)
-    if F < 2:
-        raise ValueError("fieldpair_bwd: %d field(s): a field pair needs at least 2" % F)
-    P = F * (F - 1) // 2
-    tensors = [x]
+    x, B, F, E, x_stride, x_offset, P, wptr, tensors = _fieldpair_operands("fieldpair_bwd", x, weights, kind, fields, dim, x_offset)
     if kind == "fefm":
-        ws = [_f32c(w, "field_embeddings") for w in weights]
-        if len(ws) != P or any(tuple(w.shape) != (E, E) for w in ws):
-            raise ValueError("fieldpair_bwd: FEFM over %d fields takes %d matrices [%d, %d]" % (F, P, E, E))
-        tensors += ws
-        wptr = bilinear_table(ws)
         if d_pairs is None and d_logit is None:
             raise ValueError("fieldpair_bwd: FEFM needs d_pairs and / or d_logit")
     else:
-        r = _f32c(weights, "field_pair_strengths")
-        if tuple(r.shape) != (F, F):
-            raise ValueError("fieldpair_bwd: FwFM over %d fields takes field_pair_strengths [%d, %d]" % (F, F, F))
         if d_pairs is not None:
             raise ValueError("fieldpair_bwd: the FwFM kind has no pair gradients")
         if d_logit is None:
             raise ValueError("fieldpair_bwd: FwFM needs d_logit")
-        tensors.append(r)
-        wptr = r
     d_pairs_stride = 0 if d_pairs is None else _rows2d("fieldpair_bwd", "d_pairs", d_pairs, B, P, d_pairs_offset)
     if d_logit is not None:
         _vec("fieldpair_bwd", "d_logit", d_logit, B)
-    dx_stride = 0
-    if dx is not None:
-        if dx.dim() == 3 and dx_offset == 0 and tuple(dx.shape) == (B, F, E) and dx.is_contiguous() and dx.dtype == torch.float32:
-            dx_stride = F * E
-        else:
-            dx_stride = _rows2d("fieldpair_bwd", "dx", dx, B, F * E, dx_offset)
+    dx_stride = _dx_operand("fieldpair_bwd", dx, B, F, E, dx_offset)
     if d_weights is not None:
         _vec("fieldpair_bwd", "d_weights", d_weights, P * E * E if kind == "fefm" else F * F)
     _dev_check(d_pairs, d_logit, dx, d_weights, *tensors)
@@ -1239,23 +1214,13 @@ class FieldPairFunction(torch.autograd.Function):
         x, ws = saved[0], saved[1:]
         fefm = ctx.kind == "fefm"
         want_dx = ctx.needs_input_grad[0]
-        want_dw = any(ctx.needs_input_grad[4:])
         if d_pairs is None and d_logit is None:
             return (None,) * (4 + len(ws))
         d_pairs, d_logit = _grad_operand(d_pairs, True), _grad_operand(d_logit, False)
         dx = torch.empty_like(x, memory_format=torch.contiguous_format) if want_dx else None
-        # the op accumulates: the P FEFM weight gradients are views of ONE zeroed buffer
-        flat = None
-        if want_dw:
-            flat = torch.zeros((len(ws),) + tuple(ws[0].shape) if fefm else tuple(ws[0].shape), dtype=torch.float32, device=x.device)
-        if want_dx or want_dw:
+        flat, grads = _zeroed_grads(ws, ctx.needs_input_grad[4:], x.device)     # FEFM: [P,E,E] behind the per-pair views
+        if want_dx or flat is not None:
             fieldpair_bwd(x, ws if fefm else ws[0], ctx.kind, d_pairs=d_pairs, d_logit=d_logit, dx=dx, d_weights=flat)
-        if flat is None:
-            grads = [None] * len(ws)
-        elif fefm:
-            grads = [flat[i] if ctx.needs_input_grad[4 + i] else None for i in range(len(ws))]
-        else:
-            grads = [flat]
         return (dx, None, None, None) + tuple(grads)
 
 

@@ -1,5 +1,6 @@
 """CPU: the operand checks the interaction ops' wrappers are written with (ops._rows2d, _vec, _x_in_place, _workspace, _route_name,
-_id_stride), driven directly with CPU tensors: what they refuse, what they accept, and the strides they hand to the args structs."""
+_id_stride, and what a forward and its backward share: _bilinear_operands, _fieldpair_operands, _dx_operand, _zeroed_grads), driven
+directly with CPU tensors: what they refuse, what they accept, and the strides they hand to the args structs."""
 import pytest
 import torch
 
@@ -94,6 +95,140 @@ def test_x_in_place():
     for bad, off in ((buf, 8), (buf, -1), (buf.double(), 0), (torch.zeros(F * E + 7, B).t(), 0), (x3, 0), (torch.zeros(B, F * E - 1), 0)):
         with pytest.raises(ValueError, match="op: x .* must be a float32 .* view with unit column stride"):
             ops._x_in_place("op", bad, F, E, off)
+
+
+def _mats(n, E=4):
+    return [torch.zeros(E, E) for _ in range(n)]
+
+
+@pytest.mark.parametrize("rows", [1, B])
+def test_bilinear_operands_modes(rows):
+    from deepctr_amd import _C
+    F, E, r = 3, 4, 2
+    x3 = torch.zeros(rows, F, E)
+    sw = (torch.zeros(F, r), torch.zeros(r, F))
+    for bilinear_type, nW in (("all", 1), ("each", 2), ("interaction", 3)):
+        ws, wr = _mats(nW), _mats(nW)
+        # all three weights: the model mode, W_1 / W_2, two tables of nW addresses, every tensor named for the device check
+        x, *shape, mode, got_r, (w1, w2), tables, tensors = ops._bilinear_operands("op", x3, None, None, sw, ws, wr, bilinear_type, 0)
+        assert x is x3 and tuple(shape) == (rows, F, E, F * E) and mode == _C.bilinear.MODE_MODEL and got_r == r
+        assert w1 is sw[0] and w2 is sw[1] and len(tensors) == 3 + 2 * nW and all(a is b for a, b in zip(tensors, [x3, *sw, *ws, *wr]))
+        assert [t.tolist() for t in tables] == [[w.data_ptr() for w in ws], [w.data_ptr() for w in wr]]
+        # bilinear_w alone: one layer over x, no SENET operands
+        *_, mode, got_r, (w1, w2), tables, tensors = ops._bilinear_operands("op", x3, None, None, None, None, wr, bilinear_type, 0)
+        assert mode == _C.bilinear.MODE_LAYER and got_r == 0 and w1 is None and w2 is None and len(tensors) == 1 + nW
+        assert tables[0] is None and tables[1].tolist() == [w.data_ptr() for w in wr]
+    # senet_w alone
+    *_, mode, got_r, (w1, w2), tables, tensors = ops._bilinear_operands("op", x3, None, None, sw, None, None, "interaction", 0)
+    assert mode == _C.bilinear.MODE_SENET and got_r == r and tables == [None, None] and len(tensors) == 3
+    # x read in place behind dense columns: the model mode only
+    buf = torch.zeros(rows, F * E + 5)
+    x, *shape, mode, _, _, _, _ = ops._bilinear_operands("op", buf, F, E, sw, _mats(3), _mats(3), "interaction", 5)
+    assert x is buf and tuple(shape) == (rows, F, E, F * E + 5) and mode == _C.bilinear.MODE_MODEL
+
+
+@pytest.mark.parametrize("rows", [1, B])
+def test_bilinear_operands_refusals(rows):
+    F, E, r = 3, 4, 2
+    x3 = torch.zeros(rows, F, E)
+    sw = (torch.zeros(F, r), torch.zeros(r, F))
+
+    def refused(match, senet_w, senet_bilinear_w, bilinear_w, bilinear_type="interaction", dense_cols=0, x=x3, fields=None, dim=None):
+        with pytest.raises(ValueError, match=match):
+            ops._bilinear_operands("op", x, fields, dim, senet_w, senet_bilinear_w, bilinear_w, bilinear_type, dense_cols)
+
+    give = "op: give senet_w \\+ senet_bilinear_w \\+ bilinear_w, senet_w alone, or bilinear_w alone"
+    for two in ((sw, _mats(3), None), (sw, None, _mats(3)), (None, _mats(3), _mats(3)), (None, _mats(3), None), (None, None, None)):
+        refused(give, *two)
+    count = "op: bilinear_type 'each' over 3 fields takes 2 matrices \\[4, 4\\]"
+    for n in (1, 3):                                                                     # "each" takes F - 1
+        refused(count, None, None, _mats(n), "each")
+        refused(count, sw, _mats(n), _mats(2), "each")
+    refused(count, None, None, _mats(2, 5), "each")
+    refused("op: bilinear_type 'all' over 3 fields takes 1 matrices", None, None, _mats(2), "all")
+    senet = "op: senet_w must be W_1 \\[3, r\\] and W_2 \\[r, 3\\]"
+    refused(senet, (torch.zeros(F), torch.zeros(r, F)), None, None)                      # a 1-D W_1
+    refused(senet, (torch.zeros(F, 0), torch.zeros(0, F)), None, None)                   # r = 0
+    refused(senet, (torch.zeros(F + 1, r), torch.zeros(r, F)), None, None)
+    refused(senet, (torch.zeros(F, r), torch.zeros(r + 1, F)), None, None)
+    dense = "op: dense_cols exist in the three-weight \\(FiBiNET\\) form only"
+    buf = torch.zeros(rows, F * E + 5)
+    refused(dense, sw, None, None, dense_cols=5, x=buf, fields=F, dim=E)
+    refused(dense, None, None, _mats(3), dense_cols=5, x=buf, fields=F, dim=E)
+    refused("op: 1 field\\(s\\): the layers need at least 2", (torch.zeros(1, r), torch.zeros(r, 1)), None, None, x=torch.zeros(rows, 1, E))
+    with pytest.raises(NotImplementedError, match="bilinear_type 'some'"):
+        ops._bilinear_operands("op", x3, None, None, None, None, _mats(3), "some", 0)
+
+
+@pytest.mark.parametrize("rows", [1, B])
+@pytest.mark.parametrize("F", [2, 3])
+def test_fieldpair_operands(rows, F):
+    E, P = 4, F * (F - 1) // 2
+    x3 = torch.zeros(rows, F, E)
+    ws = _mats(P)
+    x, *rest, wptr, tensors = ops._fieldpair_operands("op", x3, ws, "fefm", None, None, 0)
+    assert x is x3 and tuple(rest) == (rows, F, E, F * E, 0, P)
+    assert wptr.dtype == torch.int64 and wptr.tolist() == [w.data_ptr() for w in ws]     # the table of the matrices' addresses
+    assert len(tensors) == 1 + P and all(a is b for a, b in zip(tensors, [x3] + ws))
+    r = torch.zeros(F, F)
+    x, *rest, wptr, tensors = ops._fieldpair_operands("op", x3, r, "fwfm", None, None, 0)
+    assert x is x3 and tuple(rest) == (rows, F, E, F * E, 0, P) and wptr is r and len(tensors) == 2 and tensors[1] is r
+    buf = torch.zeros(rows, F * E + 7)                                                   # one group's slice of a wider row
+    x, *rest, wptr, tensors = ops._fieldpair_operands("op", buf, r, "fwfm", F, E, 3)
+    assert x is buf and tuple(rest) == (rows, F, E, F * E + 7, 3, P)
+    with pytest.raises(ValueError, match="op: x .* must be a float32 .* view with unit column stride"):
+        ops._fieldpair_operands("op", buf, r, "fwfm", F, E, 8)
+    with pytest.raises(ValueError, match="op: kind 'fm': expected 'fefm' or 'fwfm'"):
+        ops._fieldpair_operands("op", x3, ws, "fm", None, None, 0)
+    fefm = "op: FEFM over %d fields takes %d matrices \\[4, 4\\]" % (F, P)
+    for bad in (_mats(P + 1), _mats(P - 1), _mats(P, 5), [torch.zeros(E * E)] * P):
+        with pytest.raises(ValueError, match=fefm):
+            ops._fieldpair_operands("op", x3, bad, "fefm", None, None, 0)
+    for bad in (torch.zeros(F, F + 1), torch.zeros(F * F), torch.zeros(F + 1, F + 1)):
+        with pytest.raises(ValueError, match="op: FwFM over %d fields takes field_pair_strengths \\[%d, %d\\]" % (F, F, F)):
+            ops._fieldpair_operands("op", x3, bad, "fwfm", None, None, 0)
+    with pytest.raises(TypeError):
+        ops._fieldpair_operands("op", x3, r.double(), "fwfm", None, None, 0)
+
+
+@pytest.mark.parametrize("rows", [1, B])
+def test_fieldpair_operands_refuse_one_field(rows):
+    for kind, weights in (("fefm", []), ("fwfm", torch.zeros(1, 1))):
+        with pytest.raises(ValueError, match="op: 1 field\\(s\\): a field pair needs at least 2"):
+            ops._fieldpair_operands("op", torch.zeros(rows, 1, 4), weights, kind, None, None, 0)
+        with pytest.raises(ValueError, match="op: 1 field\\(s\\): a field pair needs at least 2"):
+            ops._fieldpair_operands("op", torch.zeros(rows, 9), weights, kind, 1, 4, 2)
+
+
+@pytest.mark.parametrize("rows", [1, B])
+def test_dx_operand(rows):
+    F, E = 3, 4
+    assert ops._dx_operand("op", None, rows, F, E, 0) == 0
+    assert ops._dx_operand("op", torch.zeros(rows, F, E), rows, F, E, 0) == F * E
+    buf = torch.zeros(rows, 2 * F * E + 7)
+    view = buf[:, 2:F * E + 7]                                                           # a strided view: the buffer's pitch
+    assert ops._dx_operand("op", view, rows, F, E, 5) == 2 * F * E + 7                   # the last column is the view's last
+    assert ops._dx_operand("op", view, rows, F, E, 0) == 2 * F * E + 7
+    assert ops._dx_operand("op", view, rows, F, E, 2, extra_cols=3) == 2 * F * E + 7     # the dense columns behind the embeddings
+    assert ops._dx_operand("op", torch.zeros(rows, F * E), rows, F, E, 0) == F * E
+    refusals = [(view, 6, 0), (view, 3, 3), (view, -1, 0), (torch.zeros(rows, F * E - 1), 0, 0),     # too narrow / a bad offset
+                (torch.zeros(rows, F, E), 1, 0), (torch.zeros(rows, F, E), 0, 2),        # [B,F,E] has no offset and no extra columns
+                (torch.zeros(rows, E, F), 0, 0), (torch.zeros(rows, F, 2 * E)[:, :, :E], 0, 0),
+                (torch.zeros(rows, F, E, dtype=torch.float64), 0, 0), (buf.double(), 0, 0), (torch.zeros(rows + 1, F * E), 0, 0)]
+    for bad, off, extra in refusals:
+        with pytest.raises(ValueError, match=r"op: dx must be a float32 \[%d, >= %d\] view with unit column stride"
+                           % (rows, off + F * E + extra)):
+            ops._dx_operand("op", bad, rows, F, E, off, extra)
+
+
+def test_zeroed_grads():
+    ws = [torch.ones(2, 3), None, torch.ones(4), torch.ones(1, 5)]
+    flat, views = ops._zeroed_grads(ws, [True, False, False, True], torch.device("cpu"))
+    assert flat.dtype == torch.float32 and flat.numel() == 6 + 4 + 5 and not flat.any()  # a slot per weight, wanted or not
+    assert views[1] is None and views[2] is None and tuple(views[0].shape) == (2, 3) and tuple(views[3].shape) == (1, 5)
+    assert views[0].data_ptr() == flat.data_ptr() and views[3].data_ptr() == flat[10:].data_ptr()
+    flat, views = ops._zeroed_grads(ws, [False] * 4, torch.device("cpu"))
+    assert flat is None and views == [None] * 4
 
 
 class _Args:
