@@ -68,7 +68,10 @@ SOURCES = [
     "din_chain_kernels.hip",
     "gemm_kernels.hip",
     "mlp_bwd_kernels.hip",
-    "train_kernels.hip",
+    "loss_kernels.hip",
+    "embed_bwd_kernels.hip",
+    "dnn_train_kernels.hip",
+    "crossnet_bwd_kernels.hip",
     "opt_kernels.hip",
     "interaction_bwd_kernels.hip",
     "din_train_kernels.hip",

@@ -1,20 +1,169 @@
-// Optimizer objects (deepctr_amd/optimizers.py) on the HIP training step: every tf.keras rule and variant over all parameter
-// segments of a model in ONE launch, and the clipnorm / global_clipnorm pre-pass.
+// The optimizers of the HIP training step, all parameter segments of a model in ONE launch.
+//   dctr_opt_multi, dctr_opt_multi_l2, dctr_adam_step, dctr_adam_multi
+//                             tf.keras Adam / Adagrad / RMSprop / SGD (non-lazy: every row of a table moves every step, as TF's
+//                             _resource_apply_sparse does), the reference's l2 regulariser folded in
 //   dctr_opt_apply, dctr_grad_clip_scales, dctr_grad_clip_scales_workspace_bytes
-// The launch shape is opt_multi_kernel's (train_kernels.hip, measured in profiles/r03c_opt_lab.log): blockIdx.y = segment, two 16-B
-// groups per thread and trip with every load issued before the first use, non-temporal accesses, four groups per thread in the
-// largest segment.  The rules are stated in include/dctr.h and DESIGN.md §7.
+//                             optimizer objects (deepctr_amd/optimizers.py): every tf.keras rule and variant, and the clipnorm /
+//                             global_clipnorm pre-pass
+// opt_apply_kernel's launch shape is opt_multi_kernel's (below, measured in profiles/r03c_opt_lab.log): blockIdx.y = segment, two
+// 16-B groups per thread and trip with every load issued before the first use, non-temporal accesses, four groups per thread in the
+// largest segment.  The rules are stated in include/dctr.h and DESIGN.md §7.  The reference has no code of its own for any of this
+// (tf.keras.optimizers).
+#include <stdlib.h>
+
 #include "dctr_common.h"
 
 namespace {
 
-typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4(const float4* p) {
-    const f32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
+// ---------------------------------------------------------------------------------------------------
+// Adam (Keras): m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  w -= alpha * m / (sqrt(v) + eps),
+// alpha = lr * sqrt(1 - b2^t) / (1 - b1^t) computed by the caller;  g includes 2*l2*w;  the gradient buffer is cleared.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                                   float* __restrict__ g, int64_t n, float alpha, float b1, float b2, float eps,
+                                                   float l2, int zero_grad) {
+    const int64_t n4 = n / 4;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 wv = reinterpret_cast<float4*>(w)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        const float4 gv = reinterpret_cast<float4*>(g)[i];
+        float* wp = &wv.x; float* mp = &mv.x; float* vp = &vv.x; const float* gp = &gv.x;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float gg = fmaf(2.f * l2, wp[c], gp[c]);
+            mp[c] = fmaf(b1, mp[c], (1.f - b1) * gg);
+            vp[c] = fmaf(b2, vp[c], (1.f - b2) * gg * gg);
+            wp[c] -= alpha * mp[c] / (sqrtf(vp[c]) + eps);
+        }
+        reinterpret_cast<float4*>(w)[i] = wv;
+        reinterpret_cast<float4*>(m)[i] = mv;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const float gg = fmaf(2.f * l2, w[i], g[i]);
+        m[i] = fmaf(b1, m[i], (1.f - b1) * gg);
+        v[i] = fmaf(b2, v[i], (1.f - b2) * gg * gg);
+        w[i] -= alpha * m[i] / (sqrtf(v[i]) + eps);
+        if (zero_grad) g[i] = 0.f;
+    }
 }
+
+// one optimizer update of a single element (tf.keras formulas, optimizer_v2/{adam,adagrad,rmsprop,gradient_descent}.py)
+template <int KIND>
+__device__ __forceinline__ void opt_update(float& w, float& m, float& v, float g, float lr, float b1, float b2, float eps) {
+    if constexpr (KIND == DCTR_OPT_ADAM) {            // lr = lr0 * sqrt(1 - b2^t) / (1 - b1^t) from the caller
+        m = fmaf(b1, m, (1.f - b1) * g);
+        v = fmaf(b2, v, (1.f - b2) * g * g);
+        w -= lr * m / (sqrtf(v) + eps);
+    } else if constexpr (KIND == DCTR_OPT_ADAGRAD) {  // v = accumulator (initial_accumulator_value set by the caller)
+        v = fmaf(g, g, v);
+        w -= lr * g / (sqrtf(v) + eps);
+    } else if constexpr (KIND == DCTR_OPT_RMSPROP) {  // b2 = rho; no momentum, not centered
+        v = fmaf(b2, v, (1.f - b2) * g * g);
+        w -= lr * g / (sqrtf(v) + eps);
+    } else {                                          // SGD without momentum
+        w -= lr * g;
+    }
+}
+
+// all parameters of a model in ONE launch: blockIdx.y = segment, blockIdx.x walks the segment (blocks past its end exit).
+// sg.touched (embedding tables): one byte per 16-B group of the gradient table, set by the backward kernels where they added
+// something — groups with a clear byte have a ZERO gradient, which is then neither read nor cleared (a 4096-row batch touches
+// < 4 % of a 1e5-row table: 24 instead of 32 bytes of traffic per element; the update itself stays non-lazy, every element moves).
+// Two 16-B groups per thread and trip, all their loads issued before the first use.
+typedef float f32x4_nt __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ float4 ld4(const float4* p) {
+    if constexpr (NT) {
+        const f32x4_nt t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt*>(p));
+        return make_float4(t.x, t.y, t.z, t.w);
+    } else {
+        return *p;
+    }
+}
+template <bool NT>
 __device__ __forceinline__ void st4(float4* p, const float4& v) {
-    __builtin_nontemporal_store(f32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_nt*>(p));
+    if constexpr (NT) __builtin_nontemporal_store(f32x4_nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_nt*>(p));
+    else *p = v;
+}
+
+// PEN: also adds  pen_scale * sum_segments l2 * sum(w^2)  of the weights BEFORE the update to *pen — the l2 penalties tf.keras adds to
+// that batch's loss (regularizers: inputs.py:22, layers/core.py:170, interaction.py:100,258,387); the weights pass through registers anyway
+template <int KIND, int U = 2, bool NT = false, bool PEN = false>
+__global__ __launch_bounds__(256) void opt_multi_kernel(const dctr_adam_seg_t* __restrict__ segs, float lr, float b1, float b2,
+                                                        float eps, int zero_grad, double* __restrict__ pen, float pen_scale) {
+    const dctr_adam_seg_t sg = segs[blockIdx.y];
+    float4* __restrict__ w = reinterpret_cast<float4*>(sg.w);
+    float4* __restrict__ m = reinterpret_cast<float4*>(sg.m);
+    float4* __restrict__ v = reinterpret_cast<float4*>(sg.v);
+    float4* __restrict__ g = reinterpret_cast<float4*>(sg.g);
+    uint8_t* __restrict__ tch = sg.touched;
+    const float l2 = sg.l2;
+    const int64_t n = sg.n, n4 = n / 4;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    constexpr bool USE_M = KIND == DCTR_OPT_ADAM, USE_V = KIND != DCTR_OPT_SGD;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float psum = 0.f;                  // (PEN: this thread's share of sum(w^2): a few hundred terms at most)
+    for (int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += U * stride) {
+        bool in[U], has[U];
+        float4 wv[U], mv[U], vv[U], gv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = i0 + u * stride;
+            in[u] = i < n4;
+            has[u] = in[u] && (tch == nullptr || tch[i] != 0);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = in[u] ? i0 + u * stride : i0;
+            wv[u] = ld4<NT>(w + i);
+            mv[u] = USE_M ? ld4<NT>(m + i) : z4;
+            vv[u] = USE_V ? ld4<NT>(v + i) : z4;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) gv[u] = has[u] ? g[i0 + u * stride] : z4;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!in[u]) continue;
+            const int64_t i = i0 + u * stride;
+            float* wp = &wv[u].x; float* mp = &mv[u].x; float* vp = &vv[u].x; const float* gp = &gv[u].x;
+            if constexpr (PEN) psum += (wp[0] * wp[0] + wp[1] * wp[1]) + (wp[2] * wp[2] + wp[3] * wp[3]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) opt_update<KIND>(wp[c], mp[c], vp[c], fmaf(2.f * l2, wp[c], gp[c]), lr, b1, b2, eps);
+            st4<NT>(w + i, wv[u]);
+            if (USE_M) st4<NT>(m + i, mv[u]);
+            if (USE_V) st4<NT>(v + i, vv[u]);
+            if (zero_grad && has[u]) {
+                g[i] = z4;
+                if (tch != nullptr) tch[i] = 0;
+            }
+        }
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t i = 4 * n4 + threadIdx.x; i < n; i += 256) {
+            float mm = USE_M ? sg.m[i] : 0.f, vv = USE_V ? sg.v[i] : 0.f;
+            if constexpr (PEN) psum = fmaf(sg.w[i], sg.w[i], psum);
+            opt_update<KIND>(sg.w[i], mm, vv, fmaf(2.f * l2, sg.w[i], sg.g[i]), lr, b1, b2, eps);
+            if (USE_M) sg.m[i] = mm;
+            if (USE_V) sg.v[i] = vv;
+            if (zero_grad) sg.g[i] = 0.f;
+        }
+    }
+    if constexpr (PEN) {
+        if (l2 != 0.f) {               // (uniform per workgroup: a segment's l2)
+            __shared__ double pw[4];
+            double d = (double)psum;
+#pragma unroll
+            for (int mk = 32; mk >= 1; mk >>= 1) d += __shfl_xor(d, mk, 64);
+            if ((threadIdx.x & 63) == 0) pw[threadIdx.x >> 6] = d;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const double t = (pw[0] + pw[1]) + (pw[2] + pw[3]);
+                if (t != 0.0) unsafeAtomicAdd(pen, t * (double)l2 * (double)pen_scale);
+            }
+        }
+    }
 }
 
 // the launch scalars (dctr_opt_args_t without its pointers)
@@ -135,10 +284,10 @@ __global__ __launch_bounds__(256) void opt_apply_kernel(const dctr_opt_seg_t* __
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int64_t i = in[u] ? i0 + u * stride : i0;
-            wv[u] = ld4(w + i);
-            v0[u] = NS >= 1 ? ld4(a0 + i) : z4;
-            v1[u] = NS >= 2 ? ld4(a1 + i) : z4;
-            v2[u] = NS >= 3 ? ld4(a2 + i) : z4;
+            wv[u] = ld4<true>(w + i);
+            v0[u] = NS >= 1 ? ld4<true>(a0 + i) : z4;
+            v1[u] = NS >= 2 ? ld4<true>(a1 + i) : z4;
+            v2[u] = NS >= 3 ? ld4<true>(a2 + i) : z4;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) gv[u] = has[u] ? g[i0 + u * stride] : z4;
@@ -150,10 +299,10 @@ __global__ __launch_bounds__(256) void opt_apply_kernel(const dctr_opt_seg_t* __
             if constexpr (PEN) psum += (wp[0] * wp[0] + wp[1] * wp[1]) + (wp[2] * wp[2] + wp[3] * wp[3]);
 #pragma unroll
             for (int c = 0; c < 4; ++c) opt_elem<KIND, NS>(wp[c], p0[c], p1[c], p2[c], clipped(gp[c], wp[c], l2x2, scale, scaled, cv), P);
-            st4(w + i, wv[u]);
-            if (NS >= 1) st4(a0 + i, v0[u]);
-            if (NS >= 2) st4(a1 + i, v1[u]);
-            if (NS >= 3) st4(a2 + i, v2[u]);
+            st4<true>(w + i, wv[u]);
+            if (NS >= 1) st4<true>(a0 + i, v0[u]);
+            if (NS >= 2) st4<true>(a1 + i, v1[u]);
+            if (NS >= 3) st4<true>(a2 + i, v2[u]);
             if (zero_grad && has[u]) {
                 g[i] = z4;
                 if (tch != nullptr) tch[i] = 0;
@@ -344,4 +493,70 @@ extern "C" int dctr_grad_clip_scales(const dctr_opt_seg_t* segs, int32_t n_segs,
                        clip_scale);
     if (mode == DCTR_CLIP_GLOBAL) hipLaunchKernelGGL(clip_global_kernel, dim3(1), dim3(256), 0, st, sumsq, (int)n_segs, clip, clip_scale);
     return dctr_launch_status("dctr_grad_clip_scales");
+}
+
+extern "C" int dctr_adam_step(float* w, float* m, float* v, float* g, int64_t n, float alpha, float beta1, float beta2,
+                              float eps, float l2, int32_t zero_grad, void* stream) {
+    DCTR_REQUIRE(n >= 0, DCTR_E_DIM, "adam_step: n < 0");
+    if (n == 0) return DCTR_OK;
+    DCTR_REQUIRE(w && m && v && g, DCTR_E_NULL, "adam_step: null pointer");
+    DCTR_REQUIRE(dctr_aligned16(w) && dctr_aligned16(m) && dctr_aligned16(v) && dctr_aligned16(g), DCTR_E_ALIGN,
+                 "adam_step: buffers must be 16-B aligned");
+    int64_t blocks = dctr_ceil_div(n / 4 + 1, (int64_t)256);
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, m, v, g, n, alpha, beta1, beta2,
+                       eps, l2, (int)zero_grad);
+    return dctr_launch_status("dctr_adam_step");
+}
+
+extern "C" int dctr_opt_multi(int32_t kind, const dctr_adam_seg_t* segs, int32_t n_segs, int64_t max_n, float lr, float beta1,
+                              float beta2, float eps, int32_t zero_grad, void* stream) {
+    return dctr_opt_multi_l2(kind, segs, n_segs, max_n, lr, beta1, beta2, eps, zero_grad, nullptr, 0.f, stream);
+}
+
+// ABI 13 — the same step; with l2_penalty != NULL the launch also adds penalty_scale * sum over the segments of l2 * sum(w^2), taken on the
+// weights BEFORE the update, to *l2_penalty (a DEVICE double): what tf.keras adds to that batch's reported loss
+extern "C" int dctr_opt_multi_l2(int32_t kind, const dctr_adam_seg_t* segs, int32_t n_segs, int64_t max_n, float lr, float beta1,
+                                 float beta2, float eps, int32_t zero_grad, double* l2_penalty, float penalty_scale, void* stream) {
+    DCTR_REQUIRE(kind >= DCTR_OPT_ADAM && kind <= DCTR_OPT_SGD, DCTR_E_ENUM, "opt_multi: optimizer kind %d", kind);
+    DCTR_REQUIRE(n_segs >= 0 && n_segs <= 65535 && max_n >= 0, DCTR_E_DIM, "opt_multi: bad n_segs / max_n");
+    if (n_segs == 0 || max_n == 0) return DCTR_OK;
+    DCTR_REQUIRE(segs != nullptr, DCTR_E_NULL, "opt_multi: null segment array");
+    // Two 16-B groups per trip, non-temporal loads / stores, four groups per thread in the largest segment: 175 us for the C2 DeepFM
+    // parameter set with touched bytes (6.15 TB/s) against 215 us with default-policy accesses and 205 us with four groups per trip
+    // (profiles/r03c_opt_lab.log).  DCTR_OPT_VARIANT / DCTR_OPT_F4 re-run that lab (scripts/opt_lab.py).
+    static const int f4 = [] { const char* e = dctr_lab_env("DCTR_OPT_F4"); return e != nullptr && atoi(e) >= 1 ? atoi(e) : 4; }();
+    static const int variant = [] { const char* e = dctr_lab_env("DCTR_OPT_VARIANT"); return e != nullptr ? atoi(e) : 2; }();
+    int64_t bx = dctr_ceil_div(max_n / 4 + 1, (int64_t)(256 * f4));
+    if (bx > 4096) bx = 4096;
+    const dim3 grid((unsigned)bx, (unsigned)n_segs);
+    hipStream_t st = (hipStream_t)stream;
+#define DCTR_OPT_LAUNCH(K)                                                                                                                     \
+    do {                                                                                                                                       \
+        if (pen != nullptr) hipLaunchKernelGGL((opt_multi_kernel<K, 2, true, true>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, penalty_scale); \
+        else if (variant == 0) hipLaunchKernelGGL((opt_multi_kernel<K, 2, false>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, 0.f);      \
+        else if (variant == 1) hipLaunchKernelGGL((opt_multi_kernel<K, 4, false>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, 0.f); \
+        else if (variant == 3) hipLaunchKernelGGL((opt_multi_kernel<K, 4, true>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, 0.f);  \
+        else hipLaunchKernelGGL((opt_multi_kernel<K, 2, true>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, 0.f);                    \
+    } while (0)
+#define DCTR_OPT_LAUNCH2(K)                                                                                                                    \
+    do {                                                                                                                                       \
+        if (pen != nullptr) hipLaunchKernelGGL((opt_multi_kernel<K, 2, true, true>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, penalty_scale); \
+        else hipLaunchKernelGGL((opt_multi_kernel<K, 2, true>), grid, dim3(256), 0, st, segs, lr, beta1, beta2, eps, (int)zero_grad, pen, 0.f);  \
+    } while (0)
+    double* pen = l2_penalty;
+    switch (kind) {
+        case DCTR_OPT_ADAM: DCTR_OPT_LAUNCH(DCTR_OPT_ADAM); break;
+        case DCTR_OPT_ADAGRAD: DCTR_OPT_LAUNCH2(DCTR_OPT_ADAGRAD); break;
+        case DCTR_OPT_RMSPROP: DCTR_OPT_LAUNCH2(DCTR_OPT_RMSPROP); break;
+        default: DCTR_OPT_LAUNCH2(DCTR_OPT_SGD); break;
+    }
+#undef DCTR_OPT_LAUNCH
+#undef DCTR_OPT_LAUNCH2
+    return dctr_launch_status("dctr_opt_multi");
+}
+
+extern "C" int dctr_adam_multi(const dctr_adam_seg_t* segs, int32_t n_segs, int64_t max_n, float alpha, float beta1, float beta2,
+                               float eps, int32_t zero_grad, void* stream) {
+    return dctr_opt_multi(DCTR_OPT_ADAM, segs, n_segs, max_n, alpha, beta1, beta2, eps, zero_grad, stream);
 }

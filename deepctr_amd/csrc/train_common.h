@@ -1,5 +1,5 @@
-// What the units of the training step share (train_kernels.hip and the units split from it: cin_layered_kernels.hip,
-// din_train_kernels.hip; mlp_bwd_kernels.hip): the grid sizing of the column-sum passes, the activation helpers of the elementwise
+// What the units of the training step share (dnn_train_kernels.hip, crossnet_bwd_kernels.hip, cin_layered_kernels.hip,
+// din_train_kernels.hip, mlp_bwd_kernels.hip): the grid sizing of the column-sum passes, the activation helpers of the elementwise
 // kernels, and the declarations of every host launcher that one unit defines and another calls.  No kernel is defined here: the
 // objects are built without relocatable device code, so a __global__ function lives in ONE unit and the other units reach it
 // through the launcher next to it.
@@ -89,7 +89,7 @@ __device__ __forceinline__ float act_deriv(float y, int act) {
     return dctr_act::deriv_from_z(act, y);      // DCTR_ACT_ELU .. DCTR_ACT_GELU; anything else: 1
 }
 
-namespace dctr_train {   // defined in train_kernels.hip, next to their kernels
+namespace dctr_train {   // defined in dnn_train_kernels.hip, next to their kernels
 // in place: dh[b, n] *= act'(h[b, n]);  db[n] += sum_b dh[b, n]   (h == NULL: only the column sums)
 void launch_act_bwd_colsum(hipStream_t st, float* dh, const float* h, int64_t batch, int N, int act, float* db);
 // dz[b, n] = dlogit[b] * head_w[n] * act'(h[b, n]);  d_head_w[n] += sum_b dlogit[b] * h[b, n]

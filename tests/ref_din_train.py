@@ -1,8 +1,9 @@
 """What tests/test_gpu_din_train_oracle.py and tests/test_din_train_oracle_cpu.py share:
   1. float64 NumPy oracles, closed form and without autograd, of the kernels only the DIN training step uses and of the loss of every
      single-task step: dctr_din_att_in_fwd / _bwd, dctr_din_wsum_fwd / _bwd, dctr_din_softmax_fwd / _bwd
-     (deepctr_amd/csrc/din_train_kernels.hip), dctr_embed_lookup_bwd, dctr_dice_train_fwd, the Dice branch of dctr_mlp_bwd and
-     dctr_bce_grad / dctr_bce_grad_w (deepctr_amd/csrc/train_kernels.hip);
+     (deepctr_amd/csrc/din_train_kernels.hip), dctr_embed_lookup_bwd (deepctr_amd/csrc/embed_bwd_kernels.hip), dctr_dice_train_fwd and
+     the Dice branch of dctr_mlp_bwd (deepctr_amd/csrc/dnn_train_kernels.hip) and dctr_bce_grad / dctr_bce_grad_w
+     (deepctr_amd/csrc/loss_kernels.hip);
   2. a restatement of the host arithmetic that picks each kernel's form and sizes its grid;
   3. the tables of cases the GPU test runs, each with the route it is there for.
 The CPU test pins 1 against torch double autograd and 2 and 3 against each other.
@@ -133,7 +134,7 @@ def dice_train_fwd(z, bias, alpha, moving_mean, moving_var, eps=1e-9, momentum=0
 
 
 def dice_bwd_stored(z, dy, alpha, mean, var, eps=1e-9, zmag=None):
-    """Dice with given (stored) statistics, the comment block above dice_bwd_kernel (train_kernels.hip:957-960):
+    """Dice with given (stored) statistics, the comment block above dice_bwd_kernel (dnn_train_kernels.hip):
         dz = dy (alpha + (1 - alpha) p + z (1 - alpha) p (1 - p) rs);   d_alpha = sum_rows dy z (1 - p)
     z [R, N] with the bias in it, ``zmag`` the magnitude z was summed at (default |z|)."""
     z, dy, al = _f64(z), _f64(dy), _f64(alpha)
@@ -148,7 +149,7 @@ def dice_bwd_stored(z, dy, alpha, mean, var, eps=1e-9, zmag=None):
 
 def dice_bwd_batch(z, dy, alpha, mean, var, eps=1e-9, zmag=None):
     """Dice under training=True, ``mean`` / ``var`` this batch's statistics, the gradient flows through them (the comment block above
-    dice_colstat_kernel, train_kernels.hip:985-990):
+    dice_colstat_kernel, dnn_train_kernels.hip):
         xn = (z - mean) rs;  dxn = dy z (1 - alpha) p (1 - p);  d_alpha = sum_rows dy z (1 - p)
         dz = dy (alpha + (1 - alpha) p) + rs (dxn - mean_rows(dxn) - xn mean_rows(dxn xn))"""
     z, dy, al = _f64(z), _f64(dy), _f64(alpha)
@@ -213,7 +214,7 @@ def bce_grad(pred, y, task="binary", weight=None):
 DIN_CAP = 16384             # din_train_kernels.hip: workgroups of every launcher there
 COLSUM_MAX_WG = 64          # train_common.h
 BWD_ROWS = 16               # train_common.h: rows per trip of the one-thread-per-column Dice passes
-LB_TILE = 1024              # train_kernels.hip: positions a workgroup of lookup_bwd_tile_kernel sorts
+LB_TILE = 1024              # embed_bwd_kernels.hip: positions a workgroup of lookup_bwd_tile_kernel sorts
 LOOKUP_PLAIN_CAP, MARK_ROWS_CAP, DICE_APPLY_CAP = 16384, 4096, 4096
 
 

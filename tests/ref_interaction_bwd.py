@@ -1,7 +1,7 @@
 """What tests/test_gpu_interaction_bwd.py and tests/test_interaction_bwd_oracle_cpu.py share:
   1. float64 NumPy oracles, closed form and without autograd, of the backward ops between dctr_mlp_bwd and the embedding scatter of NFM,
      PNN, AFM, DCN and DCNMix: dctr_bi_interaction_bwd, dctr_inner_product_bwd, dctr_afm_bwd (deepctr_amd/csrc/interaction_bwd_kernels.hip),
-     dctr_crossnet_bwd (vector and matrix) and dctr_crossnet_mix_bwd (deepctr_amd/csrc/train_kernels.hip);
+     dctr_crossnet_bwd (vector and matrix) and dctr_crossnet_mix_bwd (deepctr_amd/csrc/crossnet_bwd_kernels.hip);
   2. a restatement of the host arithmetic that picks each op's route and sizes its workspace;
   3. the table of cases the GPU test runs, each with the route it is there for.
 The CPU test pins 1 against torch double autograd and 2 and 3 against the library's host-only calls.
@@ -128,7 +128,8 @@ def crossnet_forward(x, kernels, bias, mode):
 
 
 def crossnet_bwd(x, kernels, bias, mode, dy, corrupt=None):
-    """CrossNet backward (train_kernels.hip:773-777, 941; reference layers/interaction.py:405-424), g = dy, l = L - 1 .. 0:
+    """CrossNet backward (crossnet_bwd_kernels.hip: the "CrossNet backward" comment block above cross_vector_bwd_kernel and the comment of
+    cross_matrix_bwd_elem_kernel; reference layers/interaction.py:405-424), g = dy, l = L - 1 .. 0:
       vector: ds = g . x0;  d b_l += sum_b g;  d w_l += sum_b ds x_l;  d x0 += g s_l;  g += ds w_l
       matrix: du = g .* x0;  d x0 += g .* (u_l + b_l);  d b_l += sum_b du;  d W_l[n, k] += sum_b du[b, n] x_l[b, k];  g += du W_l
     and d x0 += g at the end (x_0 is the first x_l too).  x [B, d], kernels [L, d] or [L, d, d], bias [L, d], dy [B, d].
@@ -187,7 +188,8 @@ def mix_forward(x, U, V, C, G, bias):
 
 
 def crossnet_mix_bwd(x, U, V, C, G, bias, dy, corrupt=None):
-    """CrossNetMix backward (train_kernels.hip:2143-2153; reference layers/interaction.py:511-549).  Per layer l and expert e, with
+    """CrossNetMix backward (crossnet_bwd_kernels.hip: the "CrossNetMix backward" comment block above mix_copy_rows_kernel; reference
+    layers/interaction.py:511-549).  Per layer l and expert e, with
     v1 = tanh(x_l V_e), v2 = tanh(v1 C_e^T), uv_e = v2 U_e^T, out_e = x_0 .* (uv_e + b_l), p = softmax_e(x_l . g_e), g the gradient of x_{l+1}:
         dp_e = g . out_e;  ds_e = p_e (dp_e - sum_e' p_e' dp_e');  t_e = p_e g .* x_0
         d b_l += sum_b g .* x_0;  d U_e += t_e^T v2;  d v2 = t_e U_e;  a2 = d v2 .* (1 - v2^2);  d C_e += a2^T v1

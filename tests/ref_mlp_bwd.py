@@ -1,5 +1,5 @@
 """Three things that tests/test_gpu_mlp_bwd.py and tests/test_mlp_bwd_oracle_cpu.py share, which is why they live in one module:
-  1. the float64 NumPy oracle of dctr_mlp_bwd (deepctr_amd/csrc/train_kernels.hip, deepctr_amd/csrc/mlp_bwd_kernels.hip) for relu /
+  1. the float64 NumPy oracle of dctr_mlp_bwd (deepctr_amd/csrc/dnn_train_kernels.hip, deepctr_amd/csrc/mlp_bwd_kernels.hip) for relu /
      sigmoid / tanh / linear;
   2. a restatement of the host arithmetic that decides which of the op's two forms a shape takes and how large its workspace is;
   3. the table of cases the GPU test runs, each with the form it must take.
@@ -93,8 +93,8 @@ def mlp_bwd(x, kernels, acts, act, head_w=None, dlogit=None, d_out=None):
 
 
 # ---------------------------------------------------------------------------------------------------
-# host arithmetic of the two forms (deepctr_amd/csrc/train_kernels.hip: mlp_bwd_chained, mlp_bwd_chain_floats, mlp_dw_parts,
-# mlp_bwd_main_floats; deepctr_amd/csrc/gemm_kernels.hip: k_slices; deepctr_amd/csrc/mlp_bwd_kernels.hip: chain_lda, bwd_chain_fits), restated
+# host arithmetic of the two forms (deepctr_amd/csrc/dnn_train_kernels.hip: mlp_bwd_chained, mlp_bwd_chain_floats, mlp_bwd_main_floats;
+# deepctr_amd/csrc/train_common.h: mlp_dw_parts; deepctr_amd/csrc/gemm_kernels.hip: k_slices; deepctr_amd/csrc/mlp_bwd_kernels.hip: chain_lda, bwd_chain_fits), restated
 # ---------------------------------------------------------------------------------------------------
 MAX_LAYERS = 8
 CHAIN_DW_ROWS = 256

@@ -1,7 +1,8 @@
 """GPU parity tests, op level, of the kernels only the DIN training step uses and of the loss of every single-task step —
 dctr_din_att_in_fwd / _bwd, dctr_din_wsum_fwd / _bwd, dctr_din_softmax_fwd / _bwd (deepctr_amd/csrc/din_train_kernels.hip),
-dctr_embed_lookup_bwd on both routes, dctr_dice_train_fwd and the Dice branch of dctr_mlp_bwd in both forms, dctr_bce_grad /
-dctr_bce_grad_w (deepctr_amd/csrc/train_kernels.hip) — against the float64 oracles of tests/ref_din_train.py, on every case of the
+dctr_embed_lookup_bwd on both routes (deepctr_amd/csrc/embed_bwd_kernels.hip), dctr_dice_train_fwd and the Dice branch of dctr_mlp_bwd in
+both forms (deepctr_amd/csrc/dnn_train_kernels.hip), dctr_bce_grad / dctr_bce_grad_w (deepctr_amd/csrc/loss_kernels.hip) — against
+the float64 oracles of tests/ref_din_train.py, on every case of the
 tables there.  The oracles, the routes and the room the bar leaves are pinned without a GPU by tests/test_din_train_oracle_cpu.py; here
 every case is resolved again and one that no longer reaches its route FAILS.
 

@@ -1,6 +1,6 @@
 """GPU parity tests, op level, of the two scatter kernels every HIP training step ends in — dctr_embed_gather_fm_bwd and
-dctr_embed_pool_bwd (csrc/train_kernels.hip) — and of dctr_fm_bwd (csrc/interaction_bwd_kernels.hip), dctr_dense1_bwd,
-dctr_din_softmax_fwd/_bwd (csrc/din_train_kernels.hip) and dctr_seq_weight_fwd,
+dctr_embed_pool_bwd (csrc/embed_bwd_kernels.hip) — and of dctr_fm_bwd (csrc/interaction_bwd_kernels.hip), dctr_dense1_bwd
+(csrc/dnn_train_kernels.hip), dctr_din_softmax_fwd/_bwd (csrc/din_train_kernels.hip) and dctr_seq_weight_fwd,
 against the float64 oracle of tests/ref_embed_bwd.py (pinned without a GPU by tests/test_embed_bwd_oracle_cpu.py).
 
 Bar: tests.util.assert_close_terms' defaults — 1e-4 of the result plus 2e-6 of the summed magnitude.  The kernels ACCUMULATE, so every

@@ -1,6 +1,6 @@
 """GPU parity tests, op level, of the backward ops between dctr_mlp_bwd and the embedding scatter in NFM, PNN, AFM, DCN and DCNMix —
 dctr_bi_interaction_bwd, dctr_inner_product_bwd, dctr_afm_bwd (deepctr_amd/csrc/interaction_bwd_kernels.hip), dctr_crossnet_bwd in its
-three forms and dctr_crossnet_mix_bwd (deepctr_amd/csrc/train_kernels.hip) — against the float64 oracles of
+three forms and dctr_crossnet_mix_bwd (deepctr_amd/csrc/crossnet_bwd_kernels.hip) — against the float64 oracles of
 tests/ref_interaction_bwd.py, on every route of the table there.  The oracles, the routes and the room the bar leaves are pinned
 without a GPU by tests/test_interaction_bwd_oracle_cpu.py; here every case is resolved again and one that no longer reaches its route
 FAILS.

@@ -1,4 +1,4 @@
-"""GPU parity tests, op level, of dctr_mlp_bwd (deepctr_amd/csrc/train_kernels.hip, deepctr_amd/csrc/mlp_bwd_kernels.hip, the grouped
+"""GPU parity tests, op level, of dctr_mlp_bwd (deepctr_amd/csrc/dnn_train_kernels.hip, deepctr_amd/csrc/mlp_bwd_kernels.hip, the grouped
 GEMM of deepctr_amd/csrc/gemm_kernels.hip) on both of its forms — chained (widest layer <= 1216) and layered (wider, and Dice) — against
 the float64 oracle of tests/ref_mlp_bwd.py, which restates the op's contract (act' from the SAVED outputs) and is pinned without a GPU
 by tests/test_mlp_bwd_oracle_cpu.py together with the form every case of the table takes.

@@ -90,7 +90,8 @@ def _library_bytes(batch, widths, act="relu"):
 
 
 def test_width_1216_is_chained_and_1217_is_layered():
-    """The threshold between the two forms, from the layouts in the comments of deepctr_amd/csrc/train_kernels.hip: chained = per layer
+    """The threshold between the two forms, from the layouts in the comments of mlp_bwd_chain_floats and mlp_bwd_main_floats
+    (deepctr_amd/csrc/dnn_train_kernels.hip): chained = per layer
     dZ [B, N] + W^T [K N] + slices x (K + 1) N, each 4-float aligned; layered = two buffers [B, widest] + the largest sliced dW."""
     B = 37                                                   # one slice, one part
     for k0, chained in ((1216, True), (1217, False)):
