@@ -293,6 +293,13 @@ class gru(object):
                     ("out_stride", c_i64), ("out_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_gru_bwd_args_t (tests/test_gru_bwd_oracle_cpu.py checks the layout)
+gru.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", gru.Args), ("h_seq", c_vp), ("h_stride", c_i64), ("h_row_stride", c_i64), ("d_out", c_vp), ("d_out_stride", c_i64),
+    ("d_out_row_stride", c_i64), ("dx", c_vp), ("dx_stride", c_i64), ("dx_row_stride", c_i64), ("d_att", c_vp), ("d_att_stride", c_i64),
+    ("d_layers", c_vp), ("accumulate", c_i32), ("max_blocks", c_i32)]})
+
+
 class lstm(object):
     """dctr_lstm_args_t, one level down for the same reason as interacting.Args (tests/test_dsin_cpu.py checks the layout)."""
     MERGES = {"fw": 0, "bw": 1, "sum": 2, "mul": 3, "ave": 4, "concat": 5, None: 6}
@@ -492,6 +499,9 @@ SYMBOLS = {
     "dctr_gru_workspace_bytes": (c_sz, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_route": (ctypes.c_int, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_fwd": (ctypes.c_int, [ctypes.POINTER(gru.Args), c_vp]),
+    "dctr_gru_bwd_supported": (ctypes.c_int, [ctypes.POINTER(gru.BwdArgs)]),
+    "dctr_gru_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(gru.BwdArgs)]),
+    "dctr_gru_bwd": (ctypes.c_int, [ctypes.POINTER(gru.BwdArgs), c_vp]),
     "dctr_bilstm_workspace_bytes": (c_sz, [ctypes.POINTER(lstm.Args)]),
     "dctr_bilstm_route": (ctypes.c_int, [ctypes.POINTER(lstm.Args)]),
     "dctr_bilstm_fwd": (ctypes.c_int, [ctypes.POINTER(lstm.Args), c_vp]),

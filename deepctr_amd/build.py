@@ -62,6 +62,7 @@ SOURCES = [
     "mtl_bwd_kernels.hip",
     "transformer_kernels.hip",
     "gru_kernels.hip",
+    "gru_bwd_kernels.hip",
     "lstm_kernels.hip",
     "fieldconv_kernels.hip",
     "din_kernels.hip",

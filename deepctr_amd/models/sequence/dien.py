@@ -8,8 +8,8 @@ dien.py:166-173), then per ``gru_type``:
                         ``dctr_din_attn_pool_fwd`` with the length mask into its slot of the DNN input;
   AIGRU / AGRU / AUGRU  gru1 (sequence), the attention scores (``dctr_din_attn_pool_fwd`` with return_score), gru2 — plain with its input
                         scaled by the scores, or the attention-gated cell — whose final state goes straight into the DNN slot;
-and ``dctr_mlp_fwd`` (DNN + Dense(1) + sigmoid).  fit() takes the autograd step over the torch restatement below (no HIP backward for
-the recurrence); with ``use_negsampling`` it adds ``alpha`` times the auxiliary loss of dien.py:22-63 over the ``neg_hist_*`` columns,
+and ``dctr_mlp_fwd`` (DNN + Dense(1) + sigmoid).  fit() takes the autograd step over the torch restatement below, in which every GRU
+layer is one differentiable HIP op (``dctr_gru_fwd`` / ``dctr_gru_bwd``, training.dynamic_gru); with ``use_negsampling`` it adds ``alpha`` times the auxiliary loss of dien.py:22-63 over the ``neg_hist_*`` columns,
 which predict() ignores."""
 import torch
 
@@ -124,22 +124,22 @@ class _DIEN(_DIN):
         k = self._embed(self.history_cols, staged, lo, hi)
         lens = staged.length["seq_length"][lo:hi].reshape(-1)
         km = torch.arange(k.shape[1], device=k.device)[None, :] < lens[:, None]
-        h1 = tops._gru(k, lens, [self.gru1.operands()])
+        h1 = tops.dynamic_gru(k, lens, [self.gru1.operands()])
         self._added = None
         if self.use_negsampling and k.shape[1] > 1 and all(fc.name in staged.seq for fc in self.neg_cols):
             neg = self._embed(self.neg_cols, staged, lo, hi)
             self._added = self.alpha * self.auxiliary_loss(h1[:, :-1], k[:, 1:], neg[:, 1:], lens - 1, training)
         if self.gru_type == "GRU":
-            h2 = tops._gru(h1, lens, [self.gru2.operands()])
+            h2 = tops.dynamic_gru(h1, lens, [self.gru2.operands()])
             parts[extra["hist"]] = (self._scores(q, h2, km, training).unsqueeze(1) @ h2).squeeze(1)
         else:
             score = self._scores(q, h1, km, training)
-            parts[extra["hist"]] = tops._gru(h1, lens, [self.gru2.operands()], cell=self.gru2.cell, att_scores=score,
+            parts[extra["hist"]] = tops.dynamic_gru(h1, lens, [self.gru2.operands()], cell=self.gru2.cell, att_scores=score,
                                              scale_input=self.gru_type == "AIGRU", return_sequence=False)
         return super(_DIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
     def _hip_supported(self):
-        return False                # no HIP backward for the recurrence: fit() takes the autograd step
+        return False                # fit() takes the autograd step; its GRUs run on dctr_gru_fwd / dctr_gru_bwd
 
 
 def DIEN(dnn_feature_columns, history_feature_list, gru_type="GRU", use_negsampling=False, alpha=1.0, use_bn=False,

@@ -2536,7 +2536,132 @@ def dynamic_gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=Fal
     return out
 
 
-LSTM_WEIGHTS = ("fw_kernel", "fw_recurrent_kernel", "fw_bias", "bw_kernel", "bw_recurrent_kernel", "bw_bias")
+def gru_bwd_macs(T, E):
+    """Multiply-adds per sample of one layer's backward: per step the forward's 6 E^2 recomputed + 12 E^2 for the four gradient
+    products (dz W^T and A^T dz through the gate and the candidate kernel)."""
+    return int(T) * 18 * int(E) * int(E)
+
+
+def _gru_bwd_shape(batch, seq_len, dim, cell, scale_input, return_sequence, route=None, n_layers=1):
+    T, E = int(seq_len), int(dim)
+    b = _C.gru.BwdArgs(h_stride=T * E, h_row_stride=E, d_out_stride=T * E if return_sequence else E, d_out_row_stride=E,
+                       dx_stride=T * E, dx_row_stride=E, d_att_stride=T)
+    b.fwd = _gru_args(batch, T, E, n_layers, cell, scale_input, return_sequence, route)
+    return b
+
+
+def gru_bwd_supported(seq_len, dim, cell="GRU", scale_input=False, return_sequence=True, route=None, n_layers=1):
+    """Does dctr_gru_bwd take these shapes and options (read from the library)?"""
+    b = _gru_bwd_shape(1, seq_len, dim, cell, scale_input, return_sequence, route, n_layers)
+    return bool(_C.lib().dctr_gru_bwd_supported(ctypes.byref(b)))
+
+
+def gru_bwd_workspace_bytes(batch, seq_len, dim, cell="GRU", scale_input=False, return_sequence=True, route=None):
+    """Bytes of the workspace dctr_gru_bwd needs for these shapes (read from the library; every supported shape runs out of the LDS)."""
+    b = _gru_bwd_shape(batch, seq_len, dim, cell, scale_input, return_sequence, route)
+    return int(_C.lib().dctr_gru_bwd_workspace_bytes(ctypes.byref(b)))
+
+
+def gru_bwd(x, lengths, layer, h_seq, d_out, cell="GRU", att_scores=None, scale_input=False, return_sequence=True, dx=None,
+            accumulate=False, d_att=None, d_weights=None, max_blocks=0, route=None, workspace=None):
+    """Backward of dynamic_gru() over ONE layer, all T steps in one launch (include/dctr.h: dctr_gru_bwd).  ``x``, ``lengths``,
+    ``att_scores``, ``cell``, ``scale_input`` as dynamic_gru(); ``layer``: its four weights (or a dict of GRU_WEIGHTS); ``h_seq``: the
+    forward's return_sequence=True output of the layer, a [B, T, E] view; ``d_out``: the gradient of the forward's output, a [B, T, E]
+    view with ``return_sequence``, else a [B, >= E] view (the final state's).  ``dx`` [B, T, E] view: written, or added to with
+    ``accumulate``; ``d_att`` [B, >= T] view: written; ``d_weights``: four contiguous tensors of the weights' shapes, ACCUMULATED
+    into.  Each output, and any entry of ``d_weights``, may be None."""
+    op = "gru_bwd"
+    if x.dim() != 3:
+        raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
+    B, T, E = (int(v) for v in x.shape)
+    b = _gru_bwd_shape(B, T, E, cell, scale_input, return_sequence, route)
+    a = b.fwd
+    a.x_stride, a.x_row_stride = _seq3d(op, "x", x, B, T, E)
+    b.h_stride, b.h_row_stride = _seq3d(op, "h_seq", h_seq, B, T, E)
+    if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("gru_bwd: lengths must be a contiguous int32 tensor of %d elements" % B)
+    need_att = cell != "GRU" or bool(scale_input)
+    if need_att:
+        if att_scores is None:
+            raise ValueError("gru_bwd: cell %r%s needs att_scores" % (cell, " with scale_input" if scale_input else ""))
+        _vec(op, "att_scores", att_scores, B * T)
+        if d_att is not None:
+            b.d_att_stride = _rows2d(op, "d_att", d_att, B, T)
+    else:
+        att_scores = d_att = None
+    if isinstance(layer, dict):
+        layer = [layer.get(name) for name in GRU_WEIGHTS]
+    if len(layer) != len(GRU_WEIGHTS) or any(w is None for w in layer):
+        raise ValueError("gru_bwd: the layer needs %s" % ", ".join(GRU_WEIGHTS))
+    sizes = (4 * E * E, 2 * E, 2 * E * E, E)
+    for name, w, n in zip(GRU_WEIGHTS, layer, sizes):
+        _vec(op, name, w, n)
+    d_weights = [None] * 4 if d_weights is None else list(d_weights)
+    if len(d_weights) != 4:
+        raise ValueError("gru_bwd: d_weights must hold four entries (%s)" % ", ".join(GRU_WEIGHTS))
+    for name, g, n in zip(GRU_WEIGHTS, d_weights, sizes):
+        if g is not None:
+            _vec(op, "d_weights %s" % name, g, n)
+    if return_sequence:
+        b.d_out_stride, b.d_out_row_stride = _seq3d(op, "d_out", d_out, B, T, E)
+    else:
+        b.d_out_stride = _rows2d(op, "d_out", d_out, B, E)
+    if dx is not None:
+        b.dx_stride, b.dx_row_stride = _seq3d(op, "dx", dx, B, T, E)
+    _dev_check(x, lengths, att_scores, h_seq, d_out, dx, d_att, *(list(layer) + d_weights))
+    lp, dp = _ptr_array(list(layer)), _ptr_array(d_weights)
+    a.layers = ctypes.cast(lp, ctypes.c_void_p)
+    a.x, a.lengths, a.att_scores = x.data_ptr(), lengths.data_ptr(), _ptr(att_scores)
+    b.h_seq, b.d_out, b.dx, b.d_att = h_seq.data_ptr(), d_out.data_ptr(), _ptr(dx), _ptr(d_att)
+    if any(g is not None for g in d_weights):
+        b.d_layers = ctypes.cast(dp, ctypes.c_void_p)
+    b.accumulate, b.max_blocks = int(bool(accumulate)), int(max_blocks)
+    _workspace(op, a, int(_C.lib().dctr_gru_bwd_workspace_bytes(ctypes.byref(b))), workspace, x.device)
+    _C.check(_C.lib().dctr_gru_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_gru_bwd")
+    del lp, dp
+
+
+class DynamicGRUFunction(torch.autograd.Function):
+    """One DynamicGRU layer as a differentiable op: dynamic_gru() forward (always with return_sequence: the backward reads h_{t-1}
+    from it) and gru_bwd() backward, one launch each.  ``apply(x, lengths, att_scores, cell, scale_input, return_sequence, gate_kernel,
+    gate_bias, candidate_kernel, candidate_bias)``: x [B,T,E], lengths int32 [B], att_scores [B,T] or None.  Returns [B,T,E], or the
+    final state [B,E]: the row at length - 1 of the sequence, zeros for length <= 0."""
+
+    @staticmethod
+    def forward(ctx, x, lengths, att_scores, cell, scale_input, return_sequence, *weights):
+        ctx.cfg = (cell, bool(scale_input), bool(return_sequence))
+        x = x.detach()
+        x = x if x.stride(2) == 1 or x.shape[2] == 1 else x.contiguous()
+        B, T, E = x.shape
+        lengths = lengths.reshape(-1).to(torch.int32).contiguous()
+        need_att = cell != "GRU" or bool(scale_input)
+        att = att_scores.detach().reshape(B, T).contiguous() if need_att else None
+        ws = [w.detach().contiguous() for w in weights]
+        seq = dynamic_gru(x, lengths, [ws], cell=cell, att_scores=att, scale_input=scale_input, return_sequence=True)
+        ctx.has_att = att is not None
+        ctx.save_for_backward(x, lengths, seq, *(ws + ([att] if att is not None else [])))
+        if return_sequence:
+            return seq
+        last = (lengths.clamp(1, T) - 1).to(torch.int64)
+        final = seq[torch.arange(B, device=x.device), last]
+        return final * (lengths > 0).to(final.dtype).unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        cell, scale_input, return_sequence = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        x, lengths, seq, ws = saved[0], saved[1], saved[2], saved[3:7]
+        att = saved[7] if ctx.has_att else None
+        d_out = _grad_operand(d_out, not return_sequence)
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
+        d_att = torch.empty_like(att) if att is not None and ctx.needs_input_grad[2] else None
+        _, grads = _zeroed_grads(ws, [ctx.needs_input_grad[6 + i] for i in range(4)], x.device)     # one fill for the four
+        gru_bwd(x, lengths, ws, seq, d_out, cell=cell, att_scores=att, scale_input=scale_input, return_sequence=return_sequence, dx=dx,
+                d_att=d_att, d_weights=grads)
+        return (dx, None, d_att, None, None, None) + tuple(grads)
+
+
+LSTM_WEIGHTS =("fw_kernel", "fw_recurrent_kernel", "fw_bias", "bw_kernel", "bw_recurrent_kernel", "bw_bias")
 
 
 def bilstm_macs(T, Din, u, n_layers=1):

@@ -464,6 +464,28 @@ def _gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, ret
     return x if return_sequence else h
 
 
+def dynamic_gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, return_sequence=True):
+    """DynamicGRU inside the autograd step, the arguments of _gru.  On the GPU, with gradients enabled and something requiring grad,
+    every layer is ops.DynamicGRUFunction: dctr_gru_fwd forward and dctr_gru_bwd backward, one launch each where _gru runs T steps of
+    some fifteen torch ops and autograd replays them (profiles/dien_gru_bwd.txt: faster at every size measured, so no row threshold).
+    A stack of plain layers is one application per layer (a stack with scores is nothing DynamicGRU builds and goes to _gru whole).
+    Everything else — the CPU, torch.no_grad(), HIP_AUTOGRAD_OPS off, another dtype, a shape the backward refuses — takes _gru, per
+    layer."""
+    layers = list(layers)
+    if len(layers) != 1 and (cell != "GRU" or scale_input or not layers):       # nothing DynamicGRU builds: a stack is plain
+        return _gru(x, lengths, layers, cell, att_scores, scale_input, return_sequence)
+    on_hip = x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32
+    need_att = cell != "GRU" or bool(scale_input)
+    for i, layer in enumerate(layers):
+        seq = bool(return_sequence) or i < len(layers) - 1
+        if (on_hip and (x.requires_grad or any(w.requires_grad for w in layer) or (need_att and att_scores.requires_grad))
+                and ops.gru_bwd_supported(x.shape[1], x.shape[2], cell, scale_input, seq)):
+            x = ops.DynamicGRUFunction.apply(x, lengths, att_scores if need_att else None, cell, bool(scale_input), seq, *layer)
+        else:
+            x = _gru(x, lengths, [layer], cell, att_scores, scale_input, seq)
+    return x
+
+
 def _bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", dropout_rate=0.0, training=False):
     """BiLSTM.call (reference sequence.py:375-409) over keras' LSTM in torch ops.  x [B,T,Din]; layers [(fw kernel [D,4u], fw recurrent
     kernel [u,4u], fw bias [4u], bw kernel, bw recurrent kernel, bw bias)], gate order i | f | c~ | o; every step runs (no mask).  The

@@ -1165,6 +1165,52 @@ size_t dctr_gru_workspace_bytes(const dctr_gru_args_t* args);
 int dctr_gru_route(const dctr_gru_args_t* args);
 int dctr_gru_fwd(const dctr_gru_args_t* args, void* stream);
 
+/* Backward of ONE DynamicGRU layer over all T steps, one launch (backpropagation through time).  fwd: batch, x (+ strides), lengths,
+ * att_scores (+ stride), seq_len, dim, cell, scale_input, return_sequence, route and layers[0..3] are read; n_layers must be 1 (a
+ * stack is one call per layer, last to first), out / out strides / workspace are ignored.  h_seq is the forward's return_sequence = 1
+ * output of this layer: row t holds h_t for t < length, h_{t-1} is read from it (h_{-1} = 0) and rows at t >= length are never read.
+ * d_out: the gradient of the forward's output, [B, T, E] at d_out_stride / d_out_row_stride with fwd.return_sequence, else the
+ * gradient of the final state [B, E] at d_out_stride (injected at t = length - 1).  lengths are clamped to [0, T] as the forward does.
+ * Per live step, last to first, with dh the gradient reaching h_t (from step t + 1, plus d_out):
+ *     [r | u] and c recomputed from x_t and h_{t-1} with the forward's arithmetic;
+ *     GRU / AUGRU (u' = u, or (1 - a) u):  dc = dh (1 - u');  du' = dh (h_{t-1} - c);  dh_prev = dh u'
+ *                 AUGRU:  du = du' (1 - a);  da_t += -sum_e du' u                  GRU: du = du'
+ *     AGRU:       dc = dh a;  dh_prev = dh (1 - a);  da_t += sum_e dh (c - h_{t-1});  du = 0
+ *     dzc = dc (1 - c^2);   [dx_c | d(rh)] = dzc Wc^T;   dWc += [x_t | r h_{t-1}]^T dzc;   dbc += sum_rows dzc
+ *     dr = d(rh) h_{t-1};   dh_prev += d(rh) r
+ *     dzg = [dr r (1 - r) | du u (1 - u)];   [dx_g | dh_g] = dzg Wg^T;   dWg += [x_t | h_{t-1}]^T dzg;   dbg += sum_rows dzg
+ *     dx_t = dx_c + dx_g;   dh_prev += dh_g;       scale_input:  da_t += sum_e dx_t x_raw,t;  dx_raw,t = a_t dx_t
+ * A row at t >= length passes dh through and contributes nothing else; rows of length <= 0 contribute nothing.
+ * Outputs, each may be NULL: dx [B, T, E] at its strides, written (exact zeros at t >= length) or, with accumulate, added to;
+ * d_att [B, T] at d_att_stride, written (zeros at t >= length; NULL or a plain GRU without scale_input: not touched);
+ * d_layers: HOST array of 4 DEVICE pointers of the weights' shapes, ACCUMULATED into (the array or any entry may be NULL) — summed
+ * on chip per workgroup over all steps and tiles, one atomic per workgroup and element.  dx, d_att and the dh chain use no atomics:
+ * the same bits on every call.  All products are exact fp32 on v_mfma_f32_16x16x4_f32.  The weights stay in LDS next to the
+ * weight-gradient sums and the tiles while all fit the 160 KiB (E <= 48), else they are read from global / L2 each step (route
+ * STREAMED forces that); from E = 66 the sums and the tiles alone exceed the LDS: DCTR_E_UNSUPPORTED, as two layers and scale_input
+ * with an attention-gated cell (dctr_gru_bwd_supported: 1 / 0, sizes and flags only).  No workspace is needed
+ * (dctr_gru_bwd_workspace_bytes answers 0).  Argument errors as dctr_gru_fwd; nothing is launched or written then. */
+typedef struct {
+    dctr_gru_args_t fwd;
+    const float* h_seq;              /* [B, T, E] */
+    int64_t h_stride;                /* elements between samples */
+    int64_t h_row_stride;            /* elements between steps, >= dim */
+    const float* d_out;              /* [B, T, E] (fwd.return_sequence) or [B, E] */
+    int64_t d_out_stride;
+    int64_t d_out_row_stride;        /* fwd.return_sequence only */
+    float* dx;                       /* NULL, or [B, T, E] */
+    int64_t dx_stride;
+    int64_t dx_row_stride;
+    float* d_att;                    /* NULL, or [B, T] */
+    int64_t d_att_stride;            /* >= seq_len */
+    float* const* d_layers;          /* NULL, or HOST array [4] of DEVICE pointers, shapes of fwd.layers; each may be NULL */
+    int32_t accumulate;              /* 0 | 1: dx written | added to */
+    int32_t max_blocks;              /* 0 = 2 per compute unit, else the most workgroups to launch (each walks its tiles) */
+} dctr_gru_bwd_args_t;
+int dctr_gru_bwd_supported(const dctr_gru_bwd_args_t* args);          /* host only */
+size_t dctr_gru_bwd_workspace_bytes(const dctr_gru_bwd_args_t* args); /* host only; 0: none */
+int dctr_gru_bwd(const dctr_gru_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * BiLSTM.call — deepctr/layers/sequence.py:318-428 over tf.keras.layers.LSTM as documented: two independent stacks of n_layers LSTMs,
  * the whole of both in one launch (DSIN's session-interest interaction, models/sequence/dsin.py:121-122)

@@ -3,10 +3,14 @@ whole forward (staged ids -> probabilities: fused gather, key lookups, dctr_gru_
 torch-ops forward (training.model_logits under no_grad, the same device), and dctr_gru_fwd alone on the model's own key buffer: the
 default route, the streamed route forced, and for the plain stack the two-layer launch beside two one-layer launches.  The bound beside
 the kernel's time is arithmetic, not a measurement: T x 6 E^2 multiply-adds per sample and layer (ops.gru_macs) at the f32 MFMA rate.
+With --train-rows: the backward as well.  dctr_gru_bwd alone for the evolution layer's cell (default route and streamed) beside its
+bound, the forward's 6 E^2 multiply-adds recomputed + 12 E^2 for the four gradient products per step and sample (ops.gru_bwd_macs),
+and the autograd step (model_logits in training mode, the loss, torch.autograd.grad over every trainable weight) at each of the
+given row counts with training.HIP_AUTOGRAD_OPS on and off: the table of profiles/dien_gru_bwd.txt.
 Medians of device-event timings over repeated windows, after warm-up of every shape.  Prints one JSON line and exits 1 when a speed
 condition fails (the default route slower than the torch-ops forward; the two-layer launch slower than two one-layer launches).
 
-    python scripts/bench_dien.py [--rows 4096] [--iters 20] [--windows 7]"""
+    python scripts/bench_dien.py [--rows 4096] [--iters 20] [--windows 7] [--train-rows 256,1024,4096]"""
 import argparse
 import json
 import os
@@ -40,6 +44,53 @@ def _time(fn, iters, windows):
     return float(np.median(out))
 
 
+def _train(r, model, staged, feed, keys, lt, att, gru_type, lens, E, T, args):
+    """dctr_gru_bwd alone on the evolution layer, and the autograd step with the switch on and off per row count."""
+    from deepctr_amd import ops, training
+    n = keys.shape[0]
+    plain = gru_type == "GRU"
+    kw = dict(cell=model.gru2.cell, att_scores=None if plain else att, scale_input=gru_type == "AIGRU", return_sequence=plain)
+    l2 = model.gru2.operands()
+    h = ops.dynamic_gru(keys, lt, [l2], cell=kw["cell"], att_scores=kw["att_scores"], scale_input=kw["scale_input"])
+    d_out = torch.randn((n, T, E) if plain else (n, E), device=keys.device)
+    dx, d_att = torch.empty_like(keys), torch.empty_like(att)
+    gw = [torch.zeros_like(w) for w in l2]
+
+    def bwd(route=None):
+        ops.gru_bwd(keys, lt, l2, h, d_out, dx=dx, d_att=None if plain else d_att, d_weights=gw, route=route, **kw)
+    ms_b = _time(bwd, args.iters, args.windows)
+    ms_bs = _time(lambda: bwd("streamed"), args.iters, args.windows)
+    bound = 2 * float(np.minimum(lens, T).sum()) * 18 * E * E / (MFMA_F32_TFLOPS * 1e12) * 1e3
+    r.update(gru_bwd_ms=round(ms_b, 4), gru_bwd_streamed_ms=round(ms_bs, 4), gru_bwd_bound_ms=round(bound, 5),
+             gru_bwd_share_of_bound=round(bound / ms_b, 4), gru_bwd_macs_per_sample_full_length=ops.gru_bwd_macs(T, E))
+    frozen = training.frozen_weights(model)
+    params = [t for k, t in model.named_weights() if "moving_" not in k and t.data_ptr() not in frozen]
+    y = torch.randint(0, 2, (n,), device=keys.device).float()
+    steps = r["autograd_step_ms"] = {}
+    try:
+        for t in params:
+            t.requires_grad_(True)
+        for rows in [int(v) for v in args.train_rows.split(",")]:
+            rows = min(rows, n)
+
+            def step():
+                model._begin()
+                logit = training.model_logits(model, staged, 0, rows, training=True)
+                loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, y[:rows])
+                torch.autograd.grad(loss, params, allow_unused=True)
+            cell = steps[str(rows)] = {}
+            for switch in (True, False, True, False):            # alternately: drift shows as a difference between the two passes
+                training.HIP_AUTOGRAD_OPS = switch
+                ms = _time(step, max(2, args.iters // 5), max(3, args.windows // 2))
+                cell.setdefault("hip_ms" if switch else "torch_ms", []).append(round(ms, 3))
+            training.HIP_AUTOGRAD_OPS = True
+            cell["speedup"] = round(min(cell["torch_ms"]) / max(cell["hip_ms"]), 2)
+    finally:
+        training.HIP_AUTOGRAD_OPS = True
+        for t in params:
+            t.requires_grad_(False)
+
+
 def main():
     from deepctr_amd import engine, models, ops, training
     from deepctr_amd.feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
@@ -50,6 +101,7 @@ def main():
     ap.add_argument("--seq-len", type=int, default=50)
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--no-torch", action="store_true", help="skip the torch-ops forward")
+    ap.add_argument("--train-rows", default="", help="comma-separated row counts of the autograd step, switch on / off (empty: forward only)")
     args = ap.parse_args()
     device = torch.device("cuda:0")
     T, V, n = args.seq_len, 100000, args.rows
@@ -126,6 +178,8 @@ def main():
         if ms_two is not None:
             r.update(two_one_layer_launches_ms=round(ms_two, 4), two_layer_launch_speedup=round(ms_two / ms_k, 2))
             ok = ok and ms_k <= ms_two
+        if args.train_rows:
+            _train(r, model, staged, feed, keys, lt, att, gru_type, lens, E, T, args)
         del model
         torch.cuda.empty_cache()
     res["conditions_hold"] = bool(ok)
