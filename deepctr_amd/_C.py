@@ -316,6 +316,14 @@ class lstm(object):
                     ("out_bw_stride", c_i64), ("out_bw_row_stride", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_lstm_train_args_t (tests/test_bilstm_bwd_oracle_cpu.py checks the layout)
+lstm.TrainArgs = type("TrainArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", lstm.Args), ("masks", c_vp), ("tape", c_vp), ("tape_bytes", c_sz), ("d_out", c_vp), ("d_out_stride", c_i64),
+    ("d_out_row_stride", c_i64), ("d_out_bw", c_vp), ("d_out_bw_stride", c_i64), ("d_out_bw_row_stride", c_i64), ("dx", c_vp),
+    ("dx_stride", c_i64), ("dx_row_stride", c_i64), ("d_layers", c_vp), ("accumulate", c_i32), ("max_blocks", c_i32), ("workspace", c_vp),
+    ("workspace_bytes", c_sz)]})
+
+
 class fieldconv(object):
     """dctr_fieldconv_args_t, one level down for the same reason as interacting.Args (tests/test_ccpm_fgcnn_cpu.py checks the layout)."""
     POOL_KMAX, POOL_MAX = 0, 1
@@ -505,6 +513,11 @@ SYMBOLS = {
     "dctr_bilstm_workspace_bytes": (c_sz, [ctypes.POINTER(lstm.Args)]),
     "dctr_bilstm_route": (ctypes.c_int, [ctypes.POINTER(lstm.Args)]),
     "dctr_bilstm_fwd": (ctypes.c_int, [ctypes.POINTER(lstm.Args), c_vp]),
+    "dctr_bilstm_tape_bytes": (c_sz, [ctypes.POINTER(lstm.Args)]),
+    "dctr_bilstm_train_fwd": (ctypes.c_int, [ctypes.POINTER(lstm.TrainArgs), c_vp]),
+    "dctr_bilstm_bwd_supported": (ctypes.c_int, [ctypes.POINTER(lstm.TrainArgs)]),
+    "dctr_bilstm_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(lstm.TrainArgs)]),
+    "dctr_bilstm_bwd": (ctypes.c_int, [ctypes.POINTER(lstm.TrainArgs), c_vp]),
     "dctr_bias_encoding_fwd": (ctypes.c_int, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "dctr_fieldconv_workspace_bytes": (c_sz, [ctypes.POINTER(fieldconv.Args)]),
     "dctr_fieldconv_route": (ctypes.c_int, [ctypes.POINTER(fieldconv.Args)]),

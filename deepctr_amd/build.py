@@ -64,6 +64,7 @@ SOURCES = [
     "gru_kernels.hip",
     "gru_bwd_kernels.hip",
     "lstm_kernels.hip",
+    "lstm_bwd_kernels.hip",
     "fieldconv_kernels.hip",
     "din_kernels.hip",
     "din_chain_kernels.hip",

@@ -28,6 +28,7 @@
 #include "dctr_common.h"
 #include "tile_route.h"
 #include "mfma_tile.h"
+#include "lstm_device.h"
 
 namespace {
 
@@ -52,39 +53,19 @@ struct LstmParams {
     float* ws;               // tiles of the streamed route when they exceed the LDS
 };
 
-// acc[q][16 x 16] += A[16 x K] W[0:K, q u + cols] for the four gates q: mfma_tile.h's operand layout (k-slot g of a lane walks
-// k = g KQ + t, A zero-padded to 4 KQ columns), W [K, 4u] with its own row pitch; the four accumulators are independent, so
-// consecutive MFMAs never wait for each other
-template <typename IDX>
-__device__ __forceinline__ void lstm_gemm4(const float* A, int lda, int K, int KQ, const float* W, int ldw, int u, int col,
-                                           dctr::f32x4 (&acc)[4]) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
-    const float* arow = A + j * lda + g * KQ;
-    const float* wp = W + col;
-    for (int t0 = 0; t0 < KQ; t0 += 4) {
-        const float4 a4 = *reinterpret_cast<const float4*>(arow + t0);
-        const float av[4] = {a4.x, a4.y, a4.z, a4.w};
-        float b[4][4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            const float* wr = wp + (IDX)min(g * KQ + t0 + tt, K - 1) * ldw;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[tt][q] = wr[q * u];
-        }
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[tt], b[tt][q], acc[q], 0, 0, 0);
-        }
-    }
-}
+// the training forward (dctr_bilstm_train_fwd): the input-dropout masks [B, D_l] of every LSTM and the tape of h_t and c_t
+struct LstmTrainParams : LstmParams {
+    const float* mask[LSTM_MAX_LAYERS][2];
+    float* tape;
+};
 
-__device__ __forceinline__ float lstm_gate(float z, int hard) {
-    return hard ? fminf(fmaxf(fmaf(0.2f, z, 0.5f), 0.f), 1.f) : dctr::sigmoidf_(z);
-}
+using dctr::lstm_gate;
+using dctr::lstm_gemm4;
 
-template <bool RESIDENT, bool GLOBAL_TILES>
-__global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(LstmParams p) {
+// TRAIN: the forward of a training step (never with GLOBAL_TILES): every LSTM's input is multiplied by its dropout mask where it
+// enters x_t W (the residual adds the unmasked input), and h_t, c_t of every (layer, direction, step, sample) go to the tape
+template <bool RESIDENT, bool GLOBAL_TILES, bool TRAIN = false>
+__global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(typename std::conditional<TRAIN, LstmTrainParams, LstmParams>::type p) {
     extern __shared__ __attribute__((aligned(16))) float lstm_lds[];
     typedef typename std::conditional<RESIDENT, int, int64_t>::type IDX;
     float* tiles = GLOBAL_TILES ? p.ws + (int64_t)blockIdx.x * p.tile_floats : lstm_lds;
@@ -97,6 +78,9 @@ __global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(LstmParams p) {
     float* SEQ = X0 + T * xt;
     float* H = SEQ + (L > 1 ? 4 : 2) * T * st;
     float* C = H + 4 * st;
+    // TRAIN: the two directions' mask tiles of the current layer, in the layout of its input tile (ones without a mask)
+    const int64_t mkt = (int64_t)LSTM_ROWS * max(ldx, ld);
+    float* MK = C + 2 * LSTM_ROWS * ldc;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int CT = (u + 15) >> 4;
     // a direction the merge never reads is not computed
@@ -140,6 +124,15 @@ __global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(LstmParams p) {
                     for (int e = tid; e < 4 * u; e += LSTM_THREADS) dst[e] = sb[e];
                 }
             }
+            if constexpr (TRAIN) {
+                for (int d = d0; d < d0 + nd; ++d) {
+                    const float* mk = p.mask[l][d];
+                    for (int e = tid; e < LSTM_ROWS * D; e += LSTM_THREADS) {
+                        const int row = e / D, c = e - row * D;
+                        MK[d * mkt + row * lda + c] = !mk ? 1.f : row < nvalid ? mk[(b0 + row) * D + c] : 0.f;
+                    }
+                }
+            }
             __syncthreads();                // x / the previous layer's sequences / the weights are in place
             for (int t = 0; t < T; ++t) {
                 for (int item = wave; item < nd * CT; item += LSTM_WAVES) {
@@ -159,7 +152,10 @@ __global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(LstmParams p) {
                         const float b = bv[q * u + colc];
                         acc[q] = dctr::f32x4{b, b, b, b};
                     }
-                    lstm_gemm4<IDX>(in, lda, D, KQa, Wx, ldwx, u, colc, acc);
+                    if constexpr (TRAIN)
+                        lstm_gemm4<IDX, true>(in, lda, D, KQa, Wx, ldwx, u, colc, acc, MK + d * mkt);
+                    else
+                        lstm_gemm4<IDX>(in, lda, D, KQa, Wx, ldwx, u, colc, acc);
                     if (t) lstm_gemm4<IDX>(Hc, ld, u, p.KQh, Wh, ldwh, u, colc, acc);      // h_0 = 0
                     if (col < u) {
 #pragma unroll
@@ -173,6 +169,13 @@ __global__ __launch_bounds__(LSTM_THREADS) void bilstm_kernel(LstmParams p) {
                             const float h = og * dctr::tanh_fast(c);
                             Hn[row * ld + col] = h;
                             outp[row * ld + col] = res ? h + in[row * lda + col] : h;
+                            if constexpr (TRAIN) {
+                                if (row < nvalid) {
+                                    float* tp = p.tape + ((((int64_t)l * 2 + d) * T + td) * 2 * p.batch + b0 + row) * u + col;
+                                    tp[0] = h;
+                                    tp[p.batch * u] = c;
+                                }
+                            }
                         }
                     }
                 }
@@ -213,26 +216,21 @@ struct LstmPlan {
     size_t ws_bytes;
 };
 
-// row pitch >= n of a weight matrix in LDS: the k-slot groups g and g + 1 of a B-operand read (one ds_read_b32 serves 32 lanes = two
-// groups, KQ rows apart) land 16 banks apart when KQ * pitch = 16 (mod 32)
-int lstm_pitch(int n, int KQ) {
-    for (int p = n; p < n + 32; ++p)
-        if (((int64_t)KQ * p) % 32 == 16) return p;
-    return n;
-}
-
-void lstm_plan(const dctr_lstm_args_t* a, LstmPlan* pl) {
+void lstm_plan(const dctr_lstm_args_t* a, LstmPlan* pl, bool train = false) {
     const int64_t T = a->seq_len, Din = a->in_dim, u = a->units, L = a->n_layers;
-    const int padx = (int)((Din + 15) & ~(int64_t)15), padu = (int)((u + 15) & ~(int64_t)15);
-    pl->ldx = padx + 4;
-    pl->ld = padu + 4;
-    pl->ldc = (int)u | 1;
-    pl->KQx = padx >> 2;
-    pl->KQh = padu >> 2;
-    pl->ldw0 = lstm_pitch((int)(4 * u), pl->KQx);
-    pl->ldw = pl->ldwh = lstm_pitch((int)(4 * u), pl->KQh);
+    const dctr::LstmPitch lp = dctr::lstm_pitches(Din, u);
+    pl->ldx = lp.ldx;
+    pl->ld = lp.ld;
+    pl->ldc = lp.ldc;
+    pl->KQx = lp.KQx;
+    pl->KQh = lp.KQh;
+    pl->ldw0 = lp.ldw0;
+    pl->ldw = lp.ldw;
+    pl->ldwh = lp.ldwh;
     const int64_t xt = (int64_t)LSTM_ROWS * pl->ldx, st = (int64_t)LSTM_ROWS * pl->ld;
-    pl->tile_floats = (T * xt + (L > 1 ? 4 : 2) * T * st + 4 * st + 2 * (int64_t)LSTM_ROWS * pl->ldc + 3) & ~(int64_t)3;
+    // (the training forward's two mask tiles behind the cell states)
+    pl->tile_floats = (T * xt + (L > 1 ? 4 : 2) * T * st + 4 * st + 2 * (int64_t)LSTM_ROWS * pl->ldc + (train ? 2 * (xt > st ? xt : st) : 0) + 3) &
+                      ~(int64_t)3;
     // the widest layer's W, U and b of both directions
     const int64_t w0 = Din * pl->ldw0 + u * pl->ldwh + 4 * u, w1 = u * pl->ldw + u * pl->ldwh + 4 * u;
     const int64_t w_floats = 2 * (L > 1 && w1 > w0 ? w1 : w0);
@@ -287,6 +285,38 @@ int lstm_check(const dctr_lstm_args_t* a) {
     return DCTR_OK;
 }
 
+void lstm_fill(const dctr_lstm_args_t* a, const LstmPlan& pl, LstmParams* p) {
+    p->x = a->x;
+    p->batch = a->batch;
+    p->x_stride = a->x_stride;
+    p->x_row_stride = a->x_row_stride;
+    p->T = a->seq_len;
+    p->Din = a->in_dim;
+    p->u = a->units;
+    p->n_layers = a->n_layers;
+    p->res_layers = a->res_layers < a->n_layers ? a->res_layers : a->n_layers;
+    p->merge = a->merge_mode;
+    p->hard_sigmoid = a->recurrent_activation;
+    p->ldx = pl.ldx;
+    p->ld = pl.ld;
+    p->ldc = pl.ldc;
+    p->KQx = pl.KQx;
+    p->KQh = pl.KQh;
+    p->ldw0 = pl.ldw0;
+    p->ldw = pl.ldw;
+    p->ldwh = pl.ldwh;
+    p->tile_floats = pl.tile_floats;
+    for (int l = 0; l < a->n_layers; ++l)
+        for (int m = 0; m < LSTM_NW; ++m) p->W[l][m] = a->layers[LSTM_NW * l + m];
+    p->out = a->out;
+    p->out_stride = a->out_stride;
+    p->out_row_stride = a->out_row_stride;
+    p->out_bw = a->out_bw;
+    p->out_bw_stride = a->out_bw_stride;
+    p->out_bw_row_stride = a->out_bw_row_stride;
+    p->ws = pl.global_tiles ? (float*)a->workspace : nullptr;
+}
+
 __global__ void bias_encoding_kernel(float* x, int64_t n, int32_t S, int32_t T, int32_t E, int64_t sb, int64_t ss, int64_t st, const float* sess,
                                      const float* seq, const float* item) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -336,35 +366,7 @@ extern "C" int dctr_bilstm_fwd(const dctr_lstm_args_t* a, void* stream) {
         DCTR_REQUIRE_WORKSPACE("bilstm_fwd", "dctr_bilstm_workspace_bytes", a->workspace, a->workspace_bytes, pl.ws_bytes);
     if (a->batch == 0) return DCTR_OK;
     LstmParams p = {};
-    p.x = a->x;
-    p.batch = a->batch;
-    p.x_stride = a->x_stride;
-    p.x_row_stride = a->x_row_stride;
-    p.T = a->seq_len;
-    p.Din = a->in_dim;
-    p.u = a->units;
-    p.n_layers = a->n_layers;
-    p.res_layers = a->res_layers < a->n_layers ? a->res_layers : a->n_layers;
-    p.merge = a->merge_mode;
-    p.hard_sigmoid = a->recurrent_activation;
-    p.ldx = pl.ldx;
-    p.ld = pl.ld;
-    p.ldc = pl.ldc;
-    p.KQx = pl.KQx;
-    p.KQh = pl.KQh;
-    p.ldw0 = pl.ldw0;
-    p.ldw = pl.ldw;
-    p.ldwh = pl.ldwh;
-    p.tile_floats = pl.tile_floats;
-    for (int l = 0; l < a->n_layers; ++l)
-        for (int m = 0; m < LSTM_NW; ++m) p.W[l][m] = a->layers[LSTM_NW * l + m];
-    p.out = a->out;
-    p.out_stride = a->out_stride;
-    p.out_row_stride = a->out_row_stride;
-    p.out_bw = a->out_bw;
-    p.out_bw_stride = a->out_bw_stride;
-    p.out_bw_row_stride = a->out_bw_row_stride;
-    p.ws = pl.global_tiles ? (float*)a->workspace : nullptr;
+    lstm_fill(a, pl, &p);
     const int64_t n_tiles = dctr_ceil_div(a->batch, LSTM_ROWS);
     const unsigned grid = (unsigned)(n_tiles < pl.grid_max ? n_tiles : pl.grid_max);
     if (pl.resident) {
@@ -381,6 +383,68 @@ extern "C" int dctr_bilstm_fwd(const dctr_lstm_args_t* a, void* stream) {
         DCTR_LAUNCH((bilstm_kernel<false, true>), dim3(grid), dim3(LSTM_THREADS), pl.lds_bytes, (hipStream_t)stream, p);
     }
     return dctr_launch_status("dctr_bilstm_fwd");
+}
+
+extern "C" size_t dctr_bilstm_tape_bytes(const dctr_lstm_args_t* a) {
+    if (lstm_check(a) != DCTR_OK) return 0;
+    return (size_t)a->n_layers * 2 * (size_t)a->seq_len * 2 * (size_t)a->batch * (size_t)a->units * sizeof(float);
+}
+
+// (lstm_bwd_kernels.hip: the backward's arguments pass the forward's checks first, and it asks whether the training forward takes a
+// shape before it does: it reads the tape only that forward writes)
+int dctr_lstm_check_args(const dctr_lstm_args_t* a) { return lstm_check(a); }
+
+bool dctr_lstm_train_fwd_fits(const dctr_lstm_args_t* a) {
+    if (a->route == DCTR_LSTM_ROUTE_WORKSPACE) return false;
+    LstmPlan pl;
+    lstm_plan(a, &pl, true);
+    return !pl.global_tiles;
+}
+
+extern "C" int dctr_bilstm_train_fwd(const dctr_lstm_train_args_t* t, void* stream) {
+    DCTR_REQUIRE(t, DCTR_E_NULL, "bilstm_train_fwd: null args");
+    const dctr_lstm_args_t* a = &t->fwd;
+    int rc = lstm_check(a);
+    if (rc != DCTR_OK) return rc;
+    DCTR_REQUIRE(dctr_lstm_train_fwd_fits(a), DCTR_E_UNSUPPORTED,
+                 "bilstm_train_fwd: the tiles of %d units over %d steps and %d layer(s) do not fit the LDS (no workspace route)", a->units,
+                 a->seq_len, a->n_layers);
+    DCTR_REQUIRE(a->x && a->layers && a->out, DCTR_E_NULL, "bilstm_train_fwd: null x / layers / out");
+    DCTR_REQUIRE(a->merge_mode != DCTR_LSTM_MERGE_NONE || a->out_bw, DCTR_E_NULL, "bilstm_train_fwd: merge_mode none needs out_bw");
+    for (int l = 0; l < a->n_layers; ++l)
+        for (int m = 0; m < LSTM_NW; ++m)
+            DCTR_REQUIRE(a->layers[LSTM_NW * l + m], DCTR_E_NULL, "bilstm_train_fwd: layer %d: null kernel / recurrent kernel / bias", l);
+    LstmPlan pl;
+    lstm_plan(a, &pl, true);
+    DCTR_REQUIRE(a->route != DCTR_LSTM_ROUTE_RESIDENT || pl.resident, DCTR_E_UNSUPPORTED,
+                 "bilstm_train_fwd: a layer's kernels of %d units over %d steps do not fit the resident route's LDS", a->units, a->seq_len);
+    if (pl.resident)
+        for (int l = 0; l < a->n_layers; ++l)
+            for (int m = 0; m < LSTM_NW; ++m)
+                DCTR_REQUIRE(m % 3 == 2 || dctr_aligned16(a->layers[LSTM_NW * l + m]), DCTR_E_ALIGN,
+                             "bilstm_train_fwd: layer %d: kernel / recurrent kernel not 16-B aligned", l);
+    DCTR_REQUIRE(a->batch == 0 || (t->tape && t->tape_bytes >= dctr_bilstm_tape_bytes(a)), DCTR_E_NULL,
+                 "bilstm_train_fwd: needs a tape of dctr_bilstm_tape_bytes() bytes");
+    if (a->batch == 0) return DCTR_OK;
+    LstmTrainParams p = {};
+    lstm_fill(a, pl, &p);
+    for (int l = 0; l < a->n_layers; ++l)
+        for (int d = 0; d < 2; ++d) p.mask[l][d] = t->masks ? t->masks[2 * l + d] : nullptr;
+    p.tape = (float*)t->tape;
+    const int64_t n_tiles = dctr_ceil_div(a->batch, LSTM_ROWS);
+    const unsigned grid = (unsigned)(n_tiles < pl.grid_max ? n_tiles : pl.grid_max);
+    if (pl.resident) {
+        static thread_local size_t granted[DCTR_MAX_DEVICES] = {0};
+        hipError_t e = dctr_grant_lds((const void*)bilstm_kernel<true, false, true>, pl.lds_bytes, granted);
+        DCTR_REQUIRE(e == hipSuccess, (int)e, "bilstm_train_fwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));
+        DCTR_LAUNCH((bilstm_kernel<true, false, true>), dim3(grid), dim3(LSTM_THREADS), pl.lds_bytes, (hipStream_t)stream, p);
+    } else {
+        static thread_local size_t granted[DCTR_MAX_DEVICES] = {0};
+        hipError_t e = dctr_grant_lds((const void*)bilstm_kernel<false, false, true>, pl.lds_bytes, granted);
+        DCTR_REQUIRE(e == hipSuccess, (int)e, "bilstm_train_fwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));
+        DCTR_LAUNCH((bilstm_kernel<false, false, true>), dim3(grid), dim3(LSTM_THREADS), pl.lds_bytes, (hipStream_t)stream, p);
+    }
+    return dctr_launch_status("dctr_bilstm_train_fwd");
 }
 
 extern "C" int dctr_bias_encoding_fwd(float* x, int64_t batch, int32_t sess, int32_t seq_len, int32_t dim, int64_t x_stride, int64_t sess_stride,

@@ -424,8 +424,9 @@ class _LSTMWeights(Layer):
 
 class BiLSTM(Layer):
     """A multiple layer bidirectional residual LSTM (reference sequence.py:318-428): one launch of ``dctr_bilstm_fwd`` for both stacks.
-    ``dropout_rate`` is the LSTMs' input dropout: inactive at inference, applied by the torch restatement under fit()
-    (training._bilstm).  keras' masked-step rule (a masked step copies the state through) is outside this build: a mask raises
+    ``dropout_rate`` is the LSTMs' input dropout: inactive at inference; under fit() training.bilstm draws one mask per LSTM and
+    runs both stacks as one differentiable HIP op (``dctr_bilstm_train_fwd`` / ``dctr_bilstm_bwd``), or the torch restatement
+    training._bilstm where that op does not apply (the CPU, no_grad, float64, a refused shape).  keras' masked-step rule (a masked step copies the state through) is outside this build: a mask raises
     NotImplementedError; in DSIN none reaches the layer (Transformer.compute_mask returns None)."""
 
     def __init__(self, units, layers=2, res_layers=0, dropout_rate=0.2, merge_mode='ave', **kwargs):

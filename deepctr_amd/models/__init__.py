@@ -7,7 +7,7 @@ the HIP step; EDCN the fused Deep & Cross tower with bridge and regulation modul
 SharedBottom, ESMM, MMOE and PLE — deepctr.models.multitask — the fused expert / gate level and tower kernels;
 BST — deepctr.models.sequence.bst — DIN's wiring with the fused Transformer sequence-block kernel;
 DIEN — deepctr.models.sequence.dien — DIN's wiring with the fused recurrent GRU / AGRU / AUGRU kernel, forward and (fit) backward;
-DSIN — deepctr.models.sequence.dsin — sessions through the Transformer kernel, then the fused bidirectional LSTM kernel;
+DSIN — deepctr.models.sequence.dsin — sessions through the Transformer kernel, then the fused bidirectional LSTM kernel, forward and (fit) backward;
 CCPM and FGCNN the fused field-axis conv / pooling kernel).  The other 1 model constructor of the reference, MLR, is not built."""
 from .afm import AFM
 from .autoint import AutoInt

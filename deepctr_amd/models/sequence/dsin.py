@@ -8,7 +8,8 @@ which also writes the position mask: every feature's id non-zero, keras' ``Conca
 place when ``bias_encoding``, ONE ``dctr_transformer_fwd`` launch over the [B S, T, E] view whose mean output is the session
 interests [B, S, E], ``dctr_din_attn_pool_fwd`` over them, ``dctr_bilstm_fwd`` and a second ``dctr_din_attn_pool_fwd`` over its
 output, both under ``sequence_mask(sess_length, S)`` and each into its slot of the DNN input, and ``dctr_mlp_fwd`` (DNN + Dense(1) +
-sigmoid).  fit() takes the autograd step over the torch restatement below (no HIP backward for the recurrence)."""
+sigmoid).  fit() takes the autograd step over the torch restatement below, in which the BiLSTM is one differentiable HIP op
+(``dctr_bilstm_train_fwd`` / ``dctr_bilstm_bwd``, training.bilstm); the Transformer block and the poolings stay torch ops."""
 from collections import OrderedDict
 
 import numpy as np
@@ -174,13 +175,14 @@ class _DSIN(FeatureModel):
         sess_fea = tops._transformer(self.transformer, k, k, m, m, training).reshape(B, S, E)
         sm = torch.arange(S, device=k.device)[None, :] < staged.length["sess_length"][lo:hi].reshape(-1, 1)
         parts[extra["sess"]] = self._pool(self.sess_attention, q, sess_fea, sm, training)
-        lstm = tops._bilstm(sess_fea, self.bilstm.operands(), self.bilstm.res_layers, self.bilstm.merge_mode,
-                            self.bilstm.recurrent_activation, self.bilstm.dropout_rate, training)
+        lstm = tops.bilstm(sess_fea, self.bilstm.operands(), self.bilstm.res_layers, self.bilstm.merge_mode,
+                           self.bilstm.recurrent_activation, self.bilstm.dropout_rate, training)
         parts[extra["lstm"]] = self._pool(self.lstm_attention, q, lstm, sm, training)
         return super(_DSIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
     def _hip_supported(self):
-        return False                # no HIP backward for the Transformer block and the recurrence: fit() takes the autograd step
+        return False                # no HIP backward for the Transformer block: fit() takes the autograd step; its BiLSTM runs on
+                                    # dctr_bilstm_train_fwd / dctr_bilstm_bwd
 
 
 def DSIN(dnn_feature_columns, sess_feature_list, sess_max_count=5, bias_encoding=False, att_embedding_size=1, att_head_num=8,

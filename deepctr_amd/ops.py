@@ -2701,26 +2701,20 @@ def bilstm_route(T, Din, u, n_layers, res_layers=0, merge_mode="ave", route=None
     return _route_name("dctr_bilstm_route", _C.lib().dctr_bilstm_route(ctypes.byref(a)), (None, "resident", "streamed"))
 
 
-def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", out=None, route=None, workspace=None):
-    """BiLSTM.call (reference sequence.py:375-409) over keras' LSTM: both stacks of len(layers) layers in one launch.
-
-    ``x`` [B, T, Din] float32 view (any sample / step strides, unit stride on the last axis).  ``layers``: per layer (fw kernel [D, 4u],
-    fw recurrent kernel [u, 4u], fw bias [4u], then the same three of the backward stack), or a dict of LSTM_WEIGHTS; D = Din for
-    layer 0 and u after it, gate order i | f | c~ | o.  The last ``res_layers`` layers add their input to their output.  ``merge_mode``:
-    'fw', 'bw', 'sum', 'mul', 'ave' -> [B, T, u], 'concat' -> [B, T, 2u], None -> the pair (fw, bw).  ``out``: a view of that shape (a
-    pair for None), allocated when None.  Returns ``out``."""
-    op = "bilstm"
+def _bilstm_operands(op, x, layers, res_layers, merge_mode, recurrent_activation, route):
+    """The checks of x and the layers' weights that bilstm(), bilstm_train() and bilstm_bwd() share.  Returns (args struct with the
+    sizes and x's strides, the 6 * n_layers weights in the library's order)."""
     if x.dim() != 3:
         raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % x.dim())
     B, T, Din = (int(v) for v in x.shape)
     if not layers:
-        raise ValueError("bilstm: at least one layer")
+        raise ValueError("%s: at least one layer" % op)
     rows = []
     for li, layer in enumerate(layers):
         if isinstance(layer, dict):
             layer = [layer.get(name) for name in LSTM_WEIGHTS]
         if len(layer) != len(LSTM_WEIGHTS) or any(w is None for w in layer):
-            raise ValueError("bilstm: layer %d: needs %s" % (li, ", ".join(LSTM_WEIGHTS)))
+            raise ValueError("%s: layer %d: needs %s" % (op, li, ", ".join(LSTM_WEIGHTS)))
         rows.append(layer)
     u = int(rows[0][1].shape[0])
     a = _bilstm_args(B, T, Din, u, len(rows), res_layers, merge_mode, recurrent_activation, route)
@@ -2736,20 +2730,40 @@ def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigm
             else:
                 r, c = shapes[name[3:]]
                 if _rows2d(op, what, w, r, c) != c and r > 1:
-                    raise ValueError("bilstm: %s must be contiguous" % what)
+                    raise ValueError("%s: %s must be contiguous" % (op, what))
             flat.append(w)
+    return a, flat
+
+
+def _bilstm_out(op, a, out, merge_mode, device):
+    """``out`` of bilstm() / bilstm_train(): the given views, or new tensors; their strides go into ``a``.  Returns (out_fw, out_bw)."""
+    B, T, u = int(a.batch), int(a.seq_len), int(a.units)
     wout = 2 * u if merge_mode == "concat" else u
     if merge_mode is None:
         out_fw, out_bw = out if out is not None else (None, None)
     else:
         out_fw, out_bw = out, None
     if out_fw is None:
-        out_fw = torch.empty((B, T, wout), dtype=torch.float32, device=x.device)
+        out_fw = torch.empty((B, T, wout), dtype=torch.float32, device=device)
     a.out_stride, a.out_row_stride = _seq3d(op, "out", out_fw, B, T, wout)
     if merge_mode is None:
         if out_bw is None:
-            out_bw = torch.empty((B, T, u), dtype=torch.float32, device=x.device)
+            out_bw = torch.empty((B, T, u), dtype=torch.float32, device=device)
         a.out_bw_stride, a.out_bw_row_stride = _seq3d(op, "out (backward)", out_bw, B, T, u)
+    return out_fw, out_bw
+
+
+def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", out=None, route=None, workspace=None):
+    """BiLSTM.call (reference sequence.py:375-409) over keras' LSTM: both stacks of len(layers) layers in one launch.
+
+    ``x`` [B, T, Din] float32 view (any sample / step strides, unit stride on the last axis).  ``layers``: per layer (fw kernel [D, 4u],
+    fw recurrent kernel [u, 4u], fw bias [4u], then the same three of the backward stack), or a dict of LSTM_WEIGHTS; D = Din for
+    layer 0 and u after it, gate order i | f | c~ | o.  The last ``res_layers`` layers add their input to their output.  ``merge_mode``:
+    'fw', 'bw', 'sum', 'mul', 'ave' -> [B, T, u], 'concat' -> [B, T, 2u], None -> the pair (fw, bw).  ``out``: a view of that shape (a
+    pair for None), allocated when None.  Returns ``out``."""
+    op = "bilstm"
+    a, flat = _bilstm_operands(op, x, layers, res_layers, merge_mode, recurrent_activation, route)
+    out_fw, out_bw = _bilstm_out(op, a, out, merge_mode, x.device)
     _dev_check(x, out_fw, out_bw, *flat)
     lp = _ptr_array(flat)
     a.layers = ctypes.cast(lp, ctypes.c_void_p)
@@ -2758,6 +2772,151 @@ def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigm
     _C.check(_C.lib().dctr_bilstm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_bilstm_fwd")
     del lp
     return (out_fw, out_bw) if merge_mode is None else out_fw
+
+
+def bilstm_bwd_macs(T, Din, u, n_layers=1):
+    """Multiply-adds per sample of dctr_bilstm_bwd: the forward's products recomputed, as many for dz [W; U]^T and as many for the
+    weight gradients [in | h_prev]^T dz — three times bilstm_macs()."""
+    return 3 * bilstm_macs(T, Din, u, n_layers)
+
+
+def _bilstm_train_shape(B, T, Din, u, n_layers, res_layers, merge_mode, recurrent_activation, route):
+    t = _C.lstm.TrainArgs()
+    t.fwd = _bilstm_args(B, T, Din, u, n_layers, res_layers, merge_mode, recurrent_activation, route)
+    t.d_out_stride, t.d_out_row_stride = t.fwd.out_stride, t.fwd.out_row_stride
+    t.d_out_bw_stride, t.d_out_bw_row_stride = t.fwd.out_bw_stride, t.fwd.out_bw_row_stride
+    t.dx_stride, t.dx_row_stride = int(T) * int(Din), int(Din)
+    return t
+
+
+def bilstm_bwd_supported(T, Din, u, n_layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", route=None):
+    """Does dctr_bilstm_bwd (and the training forward whose tape it reads) take these shapes and options (read from the library)?"""
+    if int(n_layers) > _C.lstm.MAX_LAYERS:
+        return False
+    t = _bilstm_train_shape(1, T, Din, u, n_layers, res_layers, merge_mode, recurrent_activation, route)
+    return bool(_C.lib().dctr_bilstm_bwd_supported(ctypes.byref(t)))
+
+
+def bilstm_bwd_workspace_bytes(batch, T, Din, u, n_layers, res_layers=0, merge_mode="ave", route=None):
+    """Bytes of the workspace dctr_bilstm_bwd needs for these shapes (read from the library; 0 for a shape it refuses)."""
+    t = _bilstm_train_shape(batch, T, Din, u, n_layers, res_layers, merge_mode, "sigmoid", route)
+    return int(_C.lib().dctr_bilstm_bwd_workspace_bytes(ctypes.byref(t)))
+
+
+def _bilstm_train_operands(op, x, layers, masks, tape, res_layers, merge_mode, recurrent_activation, route):
+    """x, the weights, the masks and the tape of bilstm_train() / bilstm_bwd().  Returns (train args, weights, masks, keep-alive)."""
+    a, flat = _bilstm_operands(op, x, layers, res_layers, merge_mode, recurrent_activation, route)
+    B, Din, u, L = int(a.batch), int(a.in_dim), int(a.units), int(a.n_layers)
+    t = _C.lstm.TrainArgs()
+    t.fwd = a
+    masks = [None] * (2 * L) if masks is None else list(masks)
+    if len(masks) != 2 * L:
+        raise ValueError("%s: masks must hold 2 x %d entries (fw, bw per layer), got %d" % (op, L, len(masks)))
+    for i, m in enumerate(masks):
+        if m is not None:
+            _vec(op, "mask %d" % i, m, B * (Din if i < 2 else u))
+    need = int(_C.lib().dctr_bilstm_tape_bytes(ctypes.byref(a)))
+    if tape is None or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() * 4 < need:
+        raise ValueError("%s: tape must be a contiguous float32 tensor of >= %d bytes (bilstm_train allocates it)" % (op, need))
+    lp, mp = _ptr_array(flat), _ptr_array(masks)
+    t.fwd.layers = ctypes.cast(lp, ctypes.c_void_p)
+    if any(m is not None for m in masks):
+        t.masks = ctypes.cast(mp, ctypes.c_void_p)
+    t.fwd.x, t.tape, t.tape_bytes = x.data_ptr(), tape.data_ptr(), tape.numel() * 4
+    return t, flat, masks, (lp, mp)
+
+
+def bilstm_train(x, layers, masks=None, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", out=None, tape=None,
+                 route=None):
+    """bilstm() as the forward of a training step (dctr_bilstm_train_fwd): the same kernel, so the same bits without masks.
+    ``masks``: None, or 2 x len(layers) entries in the order fw layer 0, bw layer 0, fw layer 1, ...; each None or a contiguous
+    float32 [B, D_l] (or [B, 1, D_l]) tensor that holds 0 or 1 / (1 - rate): the input dropout of that LSTM, the same for every step.
+    Returns (out, tape): ``out`` as bilstm(), ``tape`` the h_t and c_t of every (layer, direction, step, sample) for bilstm_bwd()
+    (include/dctr.h has the layout), allocated when None."""
+    op = "bilstm_train"
+    if tape is None:
+        L = len(layers)
+        u = int((layers[0]["fw_recurrent_kernel"] if isinstance(layers[0], dict) else layers[0][1]).shape[0]) if L else 0
+        tape = torch.empty(max(1, L * 2 * int(x.shape[1]) * 2 * int(x.shape[0]) * u), dtype=torch.float32, device=x.device)
+    t, flat, masks, keep = _bilstm_train_operands(op, x, layers, masks, tape, res_layers, merge_mode, recurrent_activation, route)
+    out_fw, out_bw = _bilstm_out(op, t.fwd, out, merge_mode, x.device)
+    _dev_check(x, out_fw, out_bw, tape, *(flat + masks))
+    t.fwd.out, t.fwd.out_bw = out_fw.data_ptr(), _ptr(out_bw)
+    _C.check(_C.lib().dctr_bilstm_train_fwd(ctypes.byref(t), _C.stream_ptr()), "dctr_bilstm_train_fwd")
+    del keep
+    return ((out_fw, out_bw) if merge_mode is None else out_fw), tape
+
+
+def bilstm_bwd(x, layers, tape, d_out, masks=None, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", dx=None,
+               accumulate=False, d_weights=None, max_blocks=0, route=None, workspace=None):
+    """Backward of bilstm_train(): both stacks, all layers and all steps (include/dctr.h: dctr_bilstm_bwd).  ``x``, ``layers``,
+    ``masks`` and the options as bilstm_train(), ``tape`` what it returned.  ``d_out``: the gradient of its output, a float32 view
+    of the output's shape (the pair (d_fw, d_bw) for merge_mode None).  ``dx`` [B, T, Din] view: written, or added to with
+    ``accumulate``; ``d_weights``: 6 x len(layers) contiguous tensors of the weights' shapes in the layers' order, ACCUMULATED into.
+    ``dx`` and any entry of ``d_weights`` may be None.  No atomics: the same bits on every call."""
+    op = "bilstm_bwd"
+    t, flat, masks, keep = _bilstm_train_operands(op, x, layers, masks, tape, res_layers, merge_mode, recurrent_activation, route)
+    a = t.fwd
+    B, T, Din, u = int(a.batch), int(a.seq_len), int(a.in_dim), int(a.units)
+    d_fw, d_bw = d_out if merge_mode is None else (d_out, None)
+    t.d_out_stride, t.d_out_row_stride = _seq3d(op, "d_out", d_fw, B, T, 2 * u if merge_mode == "concat" else u)
+    if merge_mode is None:
+        t.d_out_bw_stride, t.d_out_bw_row_stride = _seq3d(op, "d_out (backward)", d_bw, B, T, u)
+    if dx is not None:
+        t.dx_stride, t.dx_row_stride = _seq3d(op, "dx", dx, B, T, Din)
+    d_weights = [None] * len(flat) if d_weights is None else list(d_weights)
+    if len(d_weights) != len(flat):
+        raise ValueError("bilstm_bwd: d_weights must hold %d entries (%s per layer)" % (len(flat), ", ".join(LSTM_WEIGHTS)))
+    for i, (w, g) in enumerate(zip(flat, d_weights)):
+        if g is not None:
+            _vec(op, "d_weights layer %d %s" % (i // 6, LSTM_WEIGHTS[i % 6]), g, w.numel())
+    _dev_check(x, tape, d_fw, d_bw, dx, *(flat + masks + d_weights))
+    dp = _ptr_array(d_weights)
+    if any(g is not None for g in d_weights):
+        t.d_layers = ctypes.cast(dp, ctypes.c_void_p)
+    t.d_out, t.d_out_bw, t.dx = d_fw.data_ptr(), _ptr(d_bw), _ptr(dx)
+    t.accumulate, t.max_blocks = int(bool(accumulate)), int(max_blocks)
+    _workspace(op, t, int(_C.lib().dctr_bilstm_bwd_workspace_bytes(ctypes.byref(t))), workspace, x.device)
+    _C.check(_C.lib().dctr_bilstm_bwd(ctypes.byref(t), _C.stream_ptr()), "dctr_bilstm_bwd")
+    del keep, dp
+
+
+class BiLSTMFunction(torch.autograd.Function):
+    """BiLSTM as one differentiable op: bilstm_train() forward (masks applied, tape kept) and bilstm_bwd() backward.
+    ``apply(x, masks, res_layers, merge_mode, recurrent_activation, *weights)``: x [B,T,Din]; ``masks`` None or the 2 x n_layers
+    dropout masks of bilstm_train() (no gradient); ``weights`` the 6 x n_layers tensors layer by layer in LSTM_WEIGHTS' order.
+    Returns what bilstm() returns, a pair for merge_mode None.  Gradients for x and the weights."""
+
+    @staticmethod
+    def forward(ctx, x, masks, res_layers, merge_mode, recurrent_activation, *weights):
+        ctx.set_materialize_grads(False)
+        x = x.detach()
+        x = x if x.stride(2) == 1 or x.shape[2] == 1 else x.contiguous()
+        B = x.shape[0]
+        ws = [w.detach().contiguous() for w in weights]
+        layers = [ws[i:i + 6] for i in range(0, len(ws), 6)]
+        masks = None if masks is None else [None if m is None else m.detach().reshape(B, -1).contiguous() for m in masks]
+        out, tape = bilstm_train(x, layers, masks, res_layers, merge_mode, recurrent_activation)
+        ctx.cfg = (int(res_layers), merge_mode, recurrent_activation, masks)
+        ctx.save_for_backward(x, tape, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, *d_out):
+        res_layers, merge_mode, recurrent_activation, masks = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        x, tape, ws = saved[0], saved[1], saved[2:]
+        B, T, _ = x.shape
+        u = ws[1].shape[0]
+        if merge_mode is None:      # a branch nothing consumed has no gradient
+            d = tuple(torch.zeros((B, T, u), dtype=torch.float32, device=x.device) if g is None else _grad_operand(g, False) for g in d_out)
+        else:
+            d = _grad_operand(d_out[0], False)
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
+        _, grads = _zeroed_grads(ws, [ctx.needs_input_grad[5 + i] for i in range(len(ws))], x.device)       # one fill for all
+        layers = [ws[i:i + 6] for i in range(0, len(ws), 6)]
+        bilstm_bwd(x, layers, tape, d, masks, res_layers, merge_mode, recurrent_activation, dx=dx, d_weights=grads)
+        return (dx, None, None, None, None) + tuple(grads)
 
 
 def bias_encoding(x, sess_bias, seq_bias, item_bias):

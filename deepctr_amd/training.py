@@ -535,6 +535,33 @@ def _bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sig
     raise ValueError('Invalid merge mode. Merge mode should be one of {"fw","bw","sum", "mul", "ave", "concat", None}')
 
 
+# Below this many rows BiLSTM's autograd step would stay on the torch ops of _bilstm.  0: on one MI355X the HIP route won at every
+# size measured (256, 1,024 and 4,096 rows, E 32 and 64: profiles/dsin_bilstm_bwd.txt).
+BILSTM_HIP_MIN_ROWS = 0
+
+
+def bilstm(x, layers, res_layers=0, merge_mode="ave", recurrent_activation="sigmoid", dropout_rate=0.0, training=False):
+    """BiLSTM inside the autograd step, the arguments of _bilstm.  On the GPU, with gradients enabled and something requiring grad,
+    both stacks, all layers and all steps are ONE ops.BiLSTMFunction: dctr_bilstm_train_fwd forward (input dropout and a tape of h_t,
+    c_t) and dctr_bilstm_bwd backward, where _bilstm runs 2 x layers x T cells of a dozen torch ops and autograd replays them.  The
+    dropout masks are drawn by the same calls in the same order as _bilstm draws them (fw then bw, layer by layer), so a seeded step
+    sees the same masks on both routes.  Everything else — the CPU, torch.no_grad(), HIP_AUTOGRAD_OPS off, another dtype, fewer than
+    BILSTM_HIP_MIN_ROWS rows, hard_sigmoid or a shape the backward refuses — takes _bilstm."""
+    layers = [tuple(layer) for layer in layers]
+    if not (layers and x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32
+            and x.shape[0] >= BILSTM_HIP_MIN_ROWS and recurrent_activation in ("sigmoid", "hard_sigmoid")
+            and (x.requires_grad or any(w.requires_grad for layer in layers for w in layer))
+            and ops.bilstm_bwd_supported(x.shape[1], x.shape[2], layers[0][1].shape[0], len(layers), res_layers, merge_mode,
+                                         recurrent_activation)):
+        return _bilstm(x, layers, res_layers, merge_mode, recurrent_activation, dropout_rate, training)
+    masks = None
+    if training and dropout_rate:
+        B, u = x.shape[0], layers[0][1].shape[0]
+        masks = [_dropout(torch.ones(B, 1, x.shape[2] if li == 0 else u, dtype=x.dtype, device=x.device), dropout_rate, True)
+                 for li in range(len(layers)) for _ in range(2)]
+    return ops.BiLSTMFunction.apply(x, masks, int(res_layers), merge_mode, recurrent_activation, *[w for layer in layers for w in layer])
+
+
 def _bilinear(layer, x):
     """BilinearInteraction.call (reference interaction.py:1190-1209) in torch ops: x [B,F,E] -> [B,P,E], pairs i < j in
     itertools.combinations order."""

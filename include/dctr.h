@@ -1268,6 +1268,63 @@ size_t dctr_bilstm_workspace_bytes(const dctr_lstm_args_t* args);
 /* The route these arguments take (DCTR_LSTM_ROUTE_RESIDENT, or _STREAMED with or without a workspace), or the DCTR_E_* the checks answer. */
 int dctr_bilstm_route(const dctr_lstm_args_t* args);
 int dctr_bilstm_fwd(const dctr_lstm_args_t* args, void* stream);
+/* The BiLSTM of a training step: dctr_bilstm_train_fwd is dctr_bilstm_fwd (the same kernel, the same bits without masks) with the
+ * input dropout of every LSTM and a tape, dctr_bilstm_bwd backpropagation through time of both stacks, all layers and all steps.
+ * fwd: as dctr_bilstm_fwd (x, layers, sizes, flags, route; out / out_bw are written by the forward and ignored by the backward;
+ * fwd.workspace is not used by either).
+ * masks: NULL, or a HOST array [2 * n_layers] of DEVICE pointers in the order fw layer 0, bw layer 0, fw layer 1, ...; each NULL (no
+ *   dropout for that LSTM) or [B, D_l] contiguous floats that already hold 0 or 1 / (1 - rate) (D_0 = in_dim, units after it).  A mask
+ *   multiplies its LSTM's input where it enters x_t W, the same for every step; the residual adds the unmasked input.
+ * tape: caller-allocated, dctr_bilstm_tape_bytes(&fwd) bytes, written by the forward and read by the backward:
+ *   float [n_layers][2 directions][T][2][B][units]: for layer l, direction d (0 fw, 1 bw) and TIME position t, [0] is h_t and [1] is
+ *   c_t, the bits the forward produced (h before the residual is added).  A direction the merge_mode never reads is not written.
+ * The backward.  d_out: the gradient of out ([B, T, u], [B, T, 2u] for CONCAT) at its strides; d_out_bw: that of out_bw (NONE only).
+ *   Merge: AVE d_fw = d_bw = d_out / 2;  SUM d_out;  MUL d_fw = d_out y_bw, d_bw = d_out y_fw (the stacks' outputs rebuilt from the
+ *   tape);  CONCAT the two halves;  FW / BW that stack alone (the other is neither walked nor given gradients);  NONE d_out, d_out_bw.
+ *   Per stack, layer (last to first) and step (the reverse of the direction's walk), dh the gradient reaching h_t:
+ *     i, f, g, o recomputed from [in_t * m | h_prev] [W; U] + b with the forward's arithmetic;  c_prev, c_t from the tape
+ *     tc = tanh(c_t);  do = dh tc;  dc = dc_next + dh o (1 - tc^2);  di = dc g;  df = dc c_prev;  dg = dc i;  dc_prev = dc f
+ *     dz = [di i (1 - i) | df f (1 - f) | dg (1 - g^2) | do o (1 - o)];   [d(in * m)_t | dh_prev] = dz [W; U]^T
+ *     dW += (in_t * m)^T dz;  dU += h_prev^T dz;  db += sum_rows dz;   d_in_t = d(in * m)_t * m (+ d_y_t when the layer is residual)
+ *   One recurrent launch: a workgroup owns (16 samples, direction) with the layer's gradient and input sequences in LDS; exact fp32
+ *   on v_mfma_f32_16x16x4_f32, the dz [W; U]^T products read the forward's weight copy (resident in LDS while it fits next to the
+ *   tiles, else streamed from global / L2; fwd.route forces either for the backward, whatever route the forward took).  It stores dz and the rows [in * m | h_prev] to the workspace,
+ *   one grouped GEMM launch forms every [dW; dU; db] in stored k-slices, and a last launch sums the slices into d_layers and the
+ *   two directions' input gradients into dx: no atomics anywhere, the same bits on every call.
+ * dx: NULL, or [B, T, in_dim] at its strides, written, or added to with accumulate.  d_layers: NULL, or a HOST array [6 * n_layers]
+ *   of DEVICE pointers of the weights' shapes in fwd.layers' order, ACCUMULATED into; any entry may be NULL.
+ * max_blocks: 0, or the most workgroups of the recurrent launch (each walks its tiles).
+ * workspace: dctr_bilstm_bwd_workspace_bytes() bytes, 16-B aligned (the backward's; DCTR_E_NULL without, nothing launched).
+ * dctr_bilstm_bwd_supported answers 1 or 0 from sizes and flags only: sigmoid recurrent activation (hard_sigmoid has kinks and no
+ *   model here trains under it), n_layers <= 4 (the grouped GEMM's eight groups), every merge_mode and res_layers, in_dim != units,
+ *   every units and seq_len whose per-workgroup tiles fit the 160 KiB in both kernels; everything else answers
+ *   DCTR_E_UNSUPPORTED from dctr_bilstm_bwd with nothing written (dctr_bilstm_train_fwd refuses only the tiles that do not fit).
+ * Argument errors answer the codes of dctr_bilstm_fwd; nothing is launched or written then. */
+typedef struct {
+    dctr_lstm_args_t fwd;
+    const float* const* masks;       /* NULL, or HOST array [2 * n_layers] of DEVICE pointers, each NULL or [B, D_l] */
+    void* tape;                      /* dctr_bilstm_tape_bytes() bytes */
+    size_t tape_bytes;
+    const float* d_out;              /* [B, T, u] ([B, T, 2u] for CONCAT) */
+    int64_t d_out_stride;
+    int64_t d_out_row_stride;
+    const float* d_out_bw;           /* DCTR_LSTM_MERGE_NONE only */
+    int64_t d_out_bw_stride;
+    int64_t d_out_bw_row_stride;
+    float* dx;                       /* NULL, or [B, T, in_dim] */
+    int64_t dx_stride;
+    int64_t dx_row_stride;
+    float* const* d_layers;          /* NULL, or HOST array [n_layers * 6] of DEVICE pointers; each may be NULL */
+    int32_t accumulate;              /* 0 | 1: dx written | added to */
+    int32_t max_blocks;
+    void* workspace;                 /* the backward's: dctr_bilstm_bwd_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_lstm_train_args_t;
+size_t dctr_bilstm_tape_bytes(const dctr_lstm_args_t* args);                 /* host only; 0 for arguments the checks refuse */
+int dctr_bilstm_train_fwd(const dctr_lstm_train_args_t* args, void* stream);
+int dctr_bilstm_bwd_supported(const dctr_lstm_train_args_t* args);           /* host only */
+size_t dctr_bilstm_bwd_workspace_bytes(const dctr_lstm_train_args_t* args);  /* host only */
+int dctr_bilstm_bwd(const dctr_lstm_train_args_t* args, void* stream);
 /* BiasEncoding.call — deepctr/layers/sequence.py:735-744, in place over a [B, S, T, E] view (sample / session / step strides in
  * elements, unit stride on the last axis): x[b, s, t, e] += item_bias[e] + seq_bias[t] + sess_bias[s]. */
 int dctr_bias_encoding_fwd(float* x, int64_t batch, int32_t sess, int32_t seq_len, int32_t dim, int64_t x_stride, int64_t sess_stride,

@@ -3,11 +3,15 @@ forward (staged ids -> probabilities: fused gather, session lookups, dctr_transf
 dctr_bilstm_fwd, DNN) beside the same model's torch-ops forward (training.model_logits under no_grad, the same device), and
 dctr_bilstm_fwd alone on the model's own session interests beside training._bilstm in torch ops: the default route and the streamed
 route forced.  The bound beside the kernel's time is arithmetic, not a measurement: S x 2 x 4u (D + u) multiply-adds per sample and
-layer (ops.bilstm_macs) at the f32 MFMA rate.  Medians of device-event timings over repeated windows, after warm-up of every shape;
+layer (ops.bilstm_macs) at the f32 MFMA rate.
+With --train-rows: the backward as well.  dctr_bilstm_train_fwd and dctr_bilstm_bwd alone (all six weight gradients and dx, dropout
+masks on; default route and streamed) beside the backward's bound, three times the forward's multiply-adds (ops.bilstm_bwd_macs), and
+the autograd step (model_logits in training mode, the loss, torch.autograd.grad over every trainable weight) at each of the given row
+counts with training.HIP_AUTOGRAD_OPS off and on, alternating window by window: the table of profiles/dsin_bilstm_bwd.txt.  Medians of device-event timings over repeated windows, after warm-up of every shape;
 the two sides of a comparison alternate window by window.  Prints one JSON line and exits 1 when a speed condition fails (a HIP path
 slower than its torch-ops counterpart).
 
-    python scripts/bench_dsin.py [--rows 4096] [--iters 20] [--windows 7]"""
+    python scripts/bench_dsin.py [--rows 4096] [--iters 20] [--windows 7] [--train-rows 256,1024,4096]"""
 import argparse
 import json
 import os
@@ -46,6 +50,59 @@ def _time_pair(fa, fb, iters_a, iters_b, windows):
     return float(np.median(ta)), float(np.median(tb))
 
 
+def _train(r, model, staged, x, S, E, args):
+    """dctr_bilstm_train_fwd / dctr_bilstm_bwd alone on the session interests, and the autograd step with the switch off and on per
+    row count."""
+    from deepctr_amd import ops, training
+    n = x.shape[0]
+    layers = model.bilstm.operands()
+    masks = [(torch.rand(n, E, device=x.device) >= 0.2).float() / 0.8 for _ in range(4)]
+    out, tape = ops.bilstm_train(x, layers, masks)
+    d_out, dx = torch.randn_like(out), torch.empty_like(x)
+    gw = [torch.zeros_like(w) for layer in layers for w in layer]
+
+    def fwd():
+        ops.bilstm_train(x, layers, masks, out=out, tape=tape)
+
+    def bwd(route=None):
+        ops.bilstm_bwd(x, layers, tape, d_out, masks, dx=dx, d_weights=gw, route=route)
+    ms_f, ms_b = _time_pair(fwd, bwd, args.iters, args.iters, args.windows)
+    ms_bs, _ = _time_pair(lambda: bwd("streamed"), bwd, args.iters, args.iters, args.windows)
+    bound = 2 * float(n) * ops.bilstm_bwd_macs(S, E, E, 2) / (MFMA_F32_TFLOPS * 1e12) * 1e3
+    r.update(bilstm_train_fwd_ms=round(ms_f, 4), bilstm_bwd_ms=round(ms_b, 4), bilstm_bwd_streamed_ms=round(ms_bs, 4),
+             bilstm_bwd_bound_ms=round(bound, 5), bilstm_bwd_share_of_bound=round(bound / ms_b, 4),
+             bilstm_bwd_macs_per_sample=ops.bilstm_bwd_macs(S, E, E, 2),
+             bilstm_bwd_route="resident" if ops.bilstm_bwd_supported(S, E, E, 2, route="resident") else "streamed")
+    frozen = training.frozen_weights(model)
+    params = [t for k, t in model.named_weights() if "moving_" not in k and t.data_ptr() not in frozen]
+    y = torch.randint(0, 2, (n,), device=x.device).float()
+    steps = r["autograd_step_ms"] = {}
+    try:
+        for t in params:
+            t.requires_grad_(True)
+        for rows in [int(v) for v in args.train_rows.split(",")]:
+            rows = min(rows, n)
+
+            def step():
+                model._begin()
+                logit = training.model_logits(model, staged, 0, rows, training=True)
+                loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, y[:rows])
+                torch.autograd.grad(loss, params, allow_unused=True)
+
+            def switched(on):
+                def run():
+                    training.HIP_AUTOGRAD_OPS = on
+                    step()
+                return run
+            iters = max(2, args.iters // 5)
+            ms_off, ms_on = _time_pair(switched(False), switched(True), iters, iters, args.windows)
+            steps[str(rows)] = {"torch_ms": round(ms_off, 3), "hip_ms": round(ms_on, 3), "speedup": round(ms_off / ms_on, 2)}
+    finally:
+        training.HIP_AUTOGRAD_OPS = True
+        for t in params:
+            t.requires_grad_(False)
+
+
 def main():
     from deepctr_amd import engine, models, ops, training
     from deepctr_amd.feature_column import DenseFeat, SparseFeat, VarLenSparseFeat
@@ -56,6 +113,7 @@ def main():
     ap.add_argument("--sessions", type=int, default=5)
     ap.add_argument("--seq-len", type=int, default=10)
     ap.add_argument("--dims", type=int, nargs="+", default=[16, 32], help="embedding_dim of each of the two session features")
+    ap.add_argument("--train-rows", default="", help="comma-separated row counts of the autograd step, switch off / on (empty: forward only)")
     args = ap.parse_args()
     device = torch.device("cuda:0")
     S, T, V, n = args.sessions, args.seq_len, 100000, args.rows
@@ -125,6 +183,8 @@ def main():
                  bilstm_us_per_step_and_layer=round(ms_k * 1e3 / (S * 2), 3), bilstm_macs_per_sample=ops.bilstm_macs(S, E, E, 2),
                  bilstm_max_abs_diff_vs_torch_ops=err)
         ok = ok and ms_k <= ms_t
+        if args.train_rows:
+            _train(r, model, staged, x, S, E, args)
         del model
         torch.cuda.empty_cache()
     res["conditions_hold"] = bool(ok)
