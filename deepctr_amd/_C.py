@@ -278,6 +278,14 @@ class transformer(object):
                     ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_transformer_train_args_t (tests/test_transformer_bwd_oracle_cpu.py checks the layout)
+transformer.BWD_MAX_LAYERS = 8
+transformer.TrainArgs = type("TrainArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", transformer.Args), ("tape", c_vp), ("tape_bytes", c_sz), ("d_out", c_vp), ("d_out_stride", c_i64), ("d_out_row_stride", c_i64),
+    ("dx", c_vp), ("dx_stride", c_i64), ("dx_row_stride", c_i64), ("d_layers", c_vp), ("accumulate", c_i32), ("max_blocks", c_i32),
+    ("workspace", c_vp), ("workspace_bytes", c_sz)]})
+
+
 class gru(object):
     """dctr_gru_args_t, one level down for the same reason as interacting.Args (tests/test_dien_cpu.py checks the layout)."""
     CELL_GRU, CELL_AGRU, CELL_AUGRU = 0, 1, 2
@@ -504,6 +512,11 @@ SYMBOLS = {
     "dctr_transformer_workspace_bytes": (c_sz, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_route": (ctypes.c_int, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_fwd": (ctypes.c_int, [ctypes.POINTER(transformer.Args), c_vp]),
+    "dctr_transformer_tape_bytes": (c_sz, [ctypes.POINTER(transformer.Args)]),
+    "dctr_transformer_train_fwd": (ctypes.c_int, [ctypes.POINTER(transformer.TrainArgs), c_vp]),
+    "dctr_transformer_bwd_supported": (ctypes.c_int, [ctypes.POINTER(transformer.TrainArgs)]),
+    "dctr_transformer_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(transformer.TrainArgs)]),
+    "dctr_transformer_bwd": (ctypes.c_int, [ctypes.POINTER(transformer.TrainArgs), c_vp]),
     "dctr_gru_workspace_bytes": (c_sz, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_route": (ctypes.c_int, [ctypes.POINTER(gru.Args)]),
     "dctr_gru_fwd": (ctypes.c_int, [ctypes.POINTER(gru.Args), c_vp]),

@@ -61,6 +61,7 @@ SOURCES = [
     "mtl_kernels.hip",
     "mtl_bwd_kernels.hip",
     "transformer_kernels.hip",
+    "transformer_bwd_kernels.hip",
     "gru_kernels.hip",
     "gru_bwd_kernels.hip",
     "lstm_kernels.hip",

@@ -34,16 +34,11 @@
 #include "dctr_common.h"
 #include "tile_route.h"
 #include "mfma_tile.h"
+#include "transformer_device.h"
 
 namespace {
 
 constexpr int TF_MAX_LAYERS = 16;               // layers per launch (more: launches chained through out / the workspace)
-constexpr int TF_THREADS = 256;
-constexpr int TF_WAVES = TF_THREADS / 64;
-constexpr int TF_DC = 16;                       // output columns of one head a thread accumulates per pass over the keys
-constexpr int TF_MAX_S = 16;
-constexpr size_t TF_LDS_TARGET = 80 * 1024;
-constexpr int TF_NW = 9;                        // pointers per layer: query, key, value, fw1, fw2, ln_gamma, ln_beta, pe_q, pe_k
 
 struct TfParams {
     const float* x;
@@ -64,36 +59,8 @@ struct TfParams {
     int64_t out_stride, out_row_stride;
     uint8_t* mask_out;
     float* ws;               // general route only
+    float* tape;             // training forward only: the inputs of layers >= 1, [n_layers - 1][B][T][E]
 };
-
-__device__ __forceinline__ float tf_dot(const float* a, const float* b, int n) {
-    float s = 0.f;
-    for (int c = 0; c < n; ++c) s = fmaf(a[c], b[c], s);
-    return s;
-}
-
-// LayerNormalization over the E columns of every row of A: one wave per row
-__device__ __forceinline__ void tf_layer_norm(float* A, int rows, int ldx, int E, const float* __restrict__ gamma,
-                                              const float* __restrict__ beta, float eps) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int r = wave; r < rows; r += TF_WAVES) {
-        float* row = A + r * ldx;
-        float s = 0.f;
-        for (int c = lane; c < E; c += 64) s += row[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        const float mean = s / (float)E;
-        float v = 0.f;
-        for (int c = lane; c < E; c += 64) {
-            const float t = row[c] - mean;
-            v = fmaf(t, t, v);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        const float sd = sqrtf(v / (float)E + eps);
-        for (int c = lane; c < E; c += 64) row[c] = (row[c] - mean) / sd * gamma[c] + beta[c];
-    }
-}
 
 // LayerNormalization.call alone: one wave per row of x [rows, dim] (gamma / beta may be null: scale / center off)
 __global__ __launch_bounds__(TF_THREADS) void layer_norm_kernel(const float* __restrict__ x, int64_t rows, int dim, int64_t x_stride,
@@ -124,7 +91,8 @@ __global__ __launch_bounds__(TF_THREADS) void layer_norm_kernel(const float* __r
     }
 }
 
-template <bool GLOBAL_WS>
+// TAPE: the training forward, which also writes the input of every layer past the first to p.tape
+template <bool GLOBAL_WS, bool TAPE>
 __global__ __launch_bounds__(TF_THREADS) void transformer_kernel(TfParams p) {
     extern __shared__ __attribute__((aligned(16))) float tf_lds[];
     float* A = GLOBAL_WS ? p.ws + (int64_t)blockIdx.x * p.tile_floats : tf_lds;
@@ -140,7 +108,6 @@ __global__ __launch_bounds__(TF_THREADS) void transformer_kernel(TfParams p) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int RT = rows_pad >> 4, CT = (E + 15) >> 4, E4 = 4 * E, CTH = (E4 + 15) >> 4;
     const int KQ = ((E + 15) & ~15) >> 2, KQH = ((E4 + 15) & ~15) >> 2;
-    const float NEG = -4294967295.f;        // -2^32 + 1 (rounds to -2^32 in fp32, as the reference's constant does)
     const int64_t n_tiles = (p.batch + S - 1) / S;
 
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -178,6 +145,10 @@ __global__ __launch_bounds__(TF_THREADS) void transformer_kernel(TfParams p) {
             for (int e = tid; e < ST * ldx; e += TF_THREADS) {
                 const int r = e / ldx, c = e - r * ldx;
                 const float xv = A[e];
+                if constexpr (TAPE) {
+                    if (l > 0 && c < E && r / T < nvalid)
+                        p.tape[(((int64_t)(l - 1) * p.batch + b0 + r / T) * T + r % T) * E + c] = xv;
+                }
                 float kv = own_keys ? Bk[e] : xv;
                 float qv = xv;
                 if (p.use_pe && c < E) {
@@ -189,62 +160,9 @@ __global__ __launch_bounds__(TF_THREADS) void transformer_kernel(TfParams p) {
                 Bk[e] = kv;
             }
             __syncthreads();
-            // Q = Xq Wq, K = Xk Wk, V = Xk Wv: one 16 x 16 output tile per wave task
-            for (int t = wave; t < RT * CT * 3; t += TF_WAVES) {
-                const int m = t % 3, rest = t / 3, ct = rest % CT, rt = rest / CT;
-                dctr::f32x4 acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-                dctr::tile_gemm_kn<1>((m == 0 ? A : Bk) + rt * 16 * ldx, ldx, E, KQ, W[m], E, ct * 16, acc);
-                float* dst = m == 0 ? Qb : m == 1 ? Kb : Vb;
-                const int col = ct * 16 + (lane & 15), row0 = rt * 16 + 4 * (lane >> 4);
-                if (col < E) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (row0 + r < ST) dst[(row0 + r) * ldq + col] = acc[0][r];
-                }
-            }
+            tf_project_qkv(A, Bk, Qb, Kb, Vb, W, RT, CT, ST, E, KQ, ldx, ldq);
             __syncthreads();
-            // attention + query mask + residual, written over Xq (the projections are done with it)
-            for (int it = tid; it < nvalid * T * H; it += TF_THREADS) {
-                const int h = it % H, row = it / H, s = row / T, tq = row - s * T;
-                const float* q = Qb + row * ldq + h * d;
-                const float* kb = Kb + s * T * ldq + h * d;
-                const float* vb = Vb + s * T * ldq + h * d;
-                const float* kmask = km + s * T;
-                const int blind = p.blinding ? tq : -1;
-                float mx = -INFINITY;
-                for (int j = 0; j < T; ++j) {
-                    float sc = tf_dot(q, kb + j * ldq, d) / p.sqrt_d;
-                    if (kmask[j] == 0.f || j == blind) sc = NEG;
-                    mx = fmaxf(mx, sc);
-                }
-                const float qmask = qm[row];
-                for (int c0 = 0; c0 < d; c0 += TF_DC) {
-                    float acc[TF_DC];
-#pragma unroll
-                    for (int c = 0; c < TF_DC; ++c) acc[c] = 0.f;
-                    float sum = 0.f;
-                    for (int j = 0; j < T; ++j) {
-                        float sc = tf_dot(q, kb + j * ldq, d) / p.sqrt_d;
-                        if (kmask[j] == 0.f || j == blind) sc = NEG;
-                        const float e = __expf(sc - mx);
-                        sum += e;
-                        const float* vj = vb + j * ldq + c0;
-#pragma unroll
-                        for (int c = 0; c < TF_DC; ++c)
-                            if (c0 + c < d) acc[c] = fmaf(e, vj[c], acc[c]);
-                    }
-                    const float inv = qmask / sum;
-                    float* xo = A + row * ldx + h * d + c0;
-#pragma unroll
-                    for (int c = 0; c < TF_DC; ++c) {
-                        if (c0 + c < d) {
-                            float o = acc[c] * inv;
-                            if (p.use_res) o += xo[c];
-                            xo[c] = o;
-                        }
-                    }
-                }
-            }
+            tf_attention<false>(A, Qb, Kb, Vb, qm, km, nvalid, T, H, d, ldx, ldq, p.blinding, p.use_res, p.sqrt_d, nullptr);
             __syncthreads();
             if (p.use_ln) {
                 tf_layer_norm(A, ST, ldx, E, W[5], W[6], p.eps);
@@ -390,9 +308,12 @@ extern "C" int dctr_transformer_route(const dctr_transformer_args_t* args) {
     return pl.global ? DCTR_TRANSFORMER_ROUTE_GENERAL : DCTR_TRANSFORMER_ROUTE_FUSED;
 }
 
-extern "C" int dctr_transformer_fwd(const dctr_transformer_args_t* a, void* stream) {
-    int rc = tf_check(a);
-    if (rc != DCTR_OK) return rc;
+namespace {
+
+// dctr_transformer_fwd (tape == nullptr) and dctr_transformer_train_fwd (the same kernel under its TAPE flag)
+template <bool TAPE>
+int tf_forward(const dctr_transformer_args_t* a, float* tape, void* stream) {
+    int rc = DCTR_OK;
     DCTR_REQUIRE(a->queries && a->layers && a->out, DCTR_E_NULL, "transformer_fwd: null queries / layers / out");
     for (int l = 0; l < a->n_layers; ++l) {
         const float* const* w = a->layers + TF_NW * l;
@@ -415,7 +336,7 @@ extern "C" int dctr_transformer_fwd(const dctr_transformer_args_t* a, void* stre
     const size_t lds = pl.global ? 0 : (size_t)pl.tile_floats * sizeof(float);
     if (!pl.global) {
         static thread_local size_t granted[DCTR_MAX_DEVICES] = {0};
-        hipError_t e = dctr_grant_lds((const void*)transformer_kernel<false>, lds, granted);
+        hipError_t e = dctr_grant_lds((const void*)transformer_kernel<false, TAPE>, lds, granted);
         DCTR_REQUIRE(e == hipSuccess, (int)e, "transformer_fwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));
     }
     const int64_t grid = pl.global ? (n_tiles < pl.grid_max ? n_tiles : pl.grid_max) : (n_tiles < (1 << 24) ? n_tiles : (1 << 24));
@@ -459,14 +380,41 @@ extern "C" int dctr_transformer_fwd(const dctr_transformer_args_t* a, void* stre
         p.out_row_stride = last ? a->out_row_stride : chain_row;
         p.mask_out = first ? a->key_mask_out : nullptr;
         p.ws = pl.global ? (float*)a->workspace : nullptr;
+        p.tape = tape;
         if (pl.global)
-            DCTR_LAUNCH(transformer_kernel<true>, dim3((unsigned)grid), dim3(TF_THREADS), 0, (hipStream_t)stream, p);
+            DCTR_LAUNCH((transformer_kernel<true, TAPE>), dim3((unsigned)grid), dim3(TF_THREADS), 0, (hipStream_t)stream, p);
         else
-            DCTR_LAUNCH(transformer_kernel<false>, dim3((unsigned)grid), dim3(TF_THREADS), lds, (hipStream_t)stream, p);
-        rc = dctr_launch_status("dctr_transformer_fwd");
+            DCTR_LAUNCH((transformer_kernel<false, TAPE>), dim3((unsigned)grid), dim3(TF_THREADS), lds, (hipStream_t)stream, p);
+        rc = dctr_launch_status(TAPE ? "dctr_transformer_train_fwd" : "dctr_transformer_fwd");
         if (rc != DCTR_OK) return rc;
     }
     return DCTR_OK;
+}
+
+}  // namespace
+
+extern "C" int dctr_transformer_fwd(const dctr_transformer_args_t* a, void* stream) {
+    int rc = tf_check(a);
+    if (rc != DCTR_OK) return rc;
+    return tf_forward<false>(a, nullptr, stream);
+}
+
+extern "C" size_t dctr_transformer_tape_bytes(const dctr_transformer_args_t* a) {
+    if (tf_check(a) != DCTR_OK || a->n_layers > DCTR_TRANSFORMER_BWD_MAX_LAYERS) return 0;
+    return (size_t)(a->n_layers - 1) * (size_t)a->batch * a->seq_len * a->dim * sizeof(float);
+}
+
+extern "C" int dctr_transformer_train_fwd(const dctr_transformer_train_args_t* t, void* stream) {
+    DCTR_REQUIRE(t, DCTR_E_NULL, "transformer_train_fwd: null args");
+    const dctr_transformer_args_t* a = &t->fwd;
+    int rc = tf_check(a);
+    if (rc != DCTR_OK) return rc;
+    DCTR_REQUIRE(a->n_layers <= DCTR_TRANSFORMER_BWD_MAX_LAYERS, DCTR_E_UNSUPPORTED,
+                 "transformer_train_fwd: %d layers, the tape and the backward take at most %d", a->n_layers, DCTR_TRANSFORMER_BWD_MAX_LAYERS);
+    const size_t need = dctr_transformer_tape_bytes(a);
+    DCTR_REQUIRE(!need || (t->tape && t->tape_bytes >= need), DCTR_E_NULL,
+                 "transformer_train_fwd: the tape needs %zu bytes (dctr_transformer_tape_bytes)", need);
+    return tf_forward<true>(a, (float*)t->tape, stream);
 }
 
 extern "C" int dctr_layer_norm_fwd(const float* x, int64_t rows, int32_t dim, int64_t x_stride, const float* gamma, const float* beta,

@@ -178,7 +178,9 @@ class AttentionSequencePoolingLayer(Layer):
 class Transformer(Layer):
     """Multi-head self-attention block with positional encodings, residual, LayerNormalization and feed-forward (reference
     sequence.py:431-651): every flag, both input forms, ``attention_type='scaled_dot_product'``.  One launch of
-    ``dctr_transformer_fwd``; BST stacks its layers into a single launch through ``operands``."""
+    ``dctr_transformer_fwd``; BST stacks its layers into a single launch through ``operands``.  In a training step a stack over
+    self-attention without an active dropout is one differentiable op, ``dctr_transformer_train_fwd`` / ``dctr_transformer_bwd``
+    (training.transformer); everything else trains on the torch ops of training._transformer."""
 
     def __init__(self, att_embedding_size=1, head_num=8, dropout_rate=0.0, use_positional_encoding=True, use_res=True,
                  use_feed_forward=True, use_layer_norm=False, blinding=True, seed=1024, supports_masking=False,

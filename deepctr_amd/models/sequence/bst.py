@@ -5,7 +5,8 @@ Per batch: DIN's staging (pooled non-history sequences + fused gather of every S
 lookups (``dctr_embed_lookup_multi``; BST hashes them without mask_zero, bst.py:68-71), ``dctr_transformer_fwd`` over the [B, T, E] key
 buffer IN PLACE for all layers in one launch — it also emits the ``sequence_mask(seq_length, T)`` key mask the pooling needs —
 ``dctr_din_attn_pool_fwd`` (AttentionSequencePoolingLayer((64, 16), 'sigmoid', weight_normalization=True)) into its slot of the DNN
-input, and ``dctr_mlp_fwd`` (DNN + Dense(1) + sigmoid).  fit() takes the autograd step over the torch restatement below."""
+input, and ``dctr_mlp_fwd`` (DNN + Dense(1) + sigmoid).  fit() takes the autograd step over the torch restatement below, in which the
+Transformer stack is one differentiable HIP op (``dctr_transformer_train_fwd`` / ``dctr_transformer_bwd``, training.transformer)."""
 import torch
 
 from ... import ops
@@ -69,8 +70,8 @@ class _BST(_DIN):
                        for fc in self.history_cols], dim=-1)
         lens = staged.length["seq_length"][lo:hi].reshape(-1, 1)
         km = torch.arange(k.shape[1], device=k.device)[None, :] < lens
-        for layer in self.transformers:
-            k = tops._transformer(layer, k, k, km, km, training)
+        # every layer as one differentiable HIP op (dctr_transformer_train_fwd / dctr_transformer_bwd), lengths form
+        k = tops.transformer(self.transformers, k, km, km, training, lengths=staged.length["seq_length"][lo:hi])
         la = self.attention.local_att
         qq = q.unsqueeze(1).expand(-1, k.shape[1], -1)
         att = tops.dnn_forward(la.dnn, torch.cat([qq, k, qq - k, qq * k], dim=-1), training)
@@ -80,7 +81,8 @@ class _BST(_DIN):
         return super(_DIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
     def _hip_supported(self):
-        return False                # no HIP backward for the Transformer block: fit() takes the autograd step
+        return False                # fit() takes the autograd step (DIN's pooling over the Transformer output has no HIP step); in it
+                                    # the Transformer stack runs on dctr_transformer_train_fwd / dctr_transformer_bwd
 
 
 def BST(dnn_feature_columns, history_feature_list, transformer_num=1, att_head_num=8, use_bn=False, dnn_hidden_units=(256, 128, 64),

@@ -9,7 +9,8 @@ place when ``bias_encoding``, ONE ``dctr_transformer_fwd`` launch over the [B S,
 interests [B, S, E], ``dctr_din_attn_pool_fwd`` over them, ``dctr_bilstm_fwd`` and a second ``dctr_din_attn_pool_fwd`` over its
 output, both under ``sequence_mask(sess_length, S)`` and each into its slot of the DNN input, and ``dctr_mlp_fwd`` (DNN + Dense(1) +
 sigmoid).  fit() takes the autograd step over the torch restatement below, in which the BiLSTM is one differentiable HIP op
-(``dctr_bilstm_train_fwd`` / ``dctr_bilstm_bwd``, training.bilstm); the Transformer block and the poolings stay torch ops."""
+(``dctr_bilstm_train_fwd`` / ``dctr_bilstm_bwd``, training.bilstm) and so is the Transformer over all sessions
+(``dctr_transformer_train_fwd`` / ``dctr_transformer_bwd``, training.transformer); the poolings stay torch ops."""
 from collections import OrderedDict
 
 import numpy as np
@@ -172,7 +173,7 @@ class _DSIN(FeatureModel):
             be = self.bias_enc
             k = k + be.w("item_bias_embedding") + be.w("seq_bias_embedding") + be.w("sess_bias_embedding").reshape(1, S, 1, 1)
         k, m = k.reshape(B * S, T, E), m.reshape(B * S, T)
-        sess_fea = tops._transformer(self.transformer, k, k, m, m, training).reshape(B, S, E)
+        sess_fea = tops.transformer([self.transformer], k, m, m, training).reshape(B, S, E)      # mask form, output mean
         sm = torch.arange(S, device=k.device)[None, :] < staged.length["sess_length"][lo:hi].reshape(-1, 1)
         parts[extra["sess"]] = self._pool(self.sess_attention, q, sess_fea, sm, training)
         lstm = tops.bilstm(sess_fea, self.bilstm.operands(), self.bilstm.res_layers, self.bilstm.merge_mode,
@@ -181,8 +182,9 @@ class _DSIN(FeatureModel):
         return super(_DSIN, self)._autograd_logit(staged, lo, hi, parts, extra, training)
 
     def _hip_supported(self):
-        return False                # no HIP backward for the Transformer block: fit() takes the autograd step; its BiLSTM runs on
-                                    # dctr_bilstm_train_fwd / dctr_bilstm_bwd
+        return False                # fit() takes the autograd step (the poolings have no HIP step); in it the Transformer runs on
+                                    # dctr_transformer_train_fwd / dctr_transformer_bwd and the BiLSTM on dctr_bilstm_train_fwd /
+                                    # dctr_bilstm_bwd
 
 
 def DSIN(dnn_feature_columns, sess_feature_list, sess_max_count=5, bias_encoding=False, att_embedding_size=1, att_head_num=8,

@@ -2358,18 +2358,10 @@ def _transformer_mask(op, name, lengths, mask, B, T):
     return lengths, mask
 
 
-def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None,
-                use_positional_encoding=True, use_res=True, use_feed_forward=True, use_layer_norm=False, blinding=True,
-                output_type=None, out=None, key_mask_out=None, route=None, workspace=None, ln_eps=1e-9):
-    """Transformer.call (reference sequence.py:523-635) stacked over len(layers) layers (bst.py:84-92), one launch.
-
-    ``queries`` [B, T, E] float32 view (any sample / position strides, unit stride on the last axis); ``keys`` the same shape or None
-    (the queries).  ``layers``: per layer a dict (or a sequence in this order) of query, key, value [E, E], fw1 [E, 4E], fw2 [4E, E],
-    ln_gamma, ln_beta [E], pe_q, pe_k [T, E] — the positional tables ALREADY multiplied by float32(sqrt(E)); weights a flag switches
-    off may be None.  Masks: int32 lengths [B] or a uint8 / bool [B, T] mask per side, None = every position counts.
-    ``out``: a [B, T, E] view (``output_type`` None; may be ``queries`` itself: in place) or [B, E] ('mean' / 'sum'), allocated when
-    None.  ``key_mask_out``: a uint8 [B, T] tensor that receives the key mask.  Returns ``out``."""
-    op = "transformer"
+def _transformer_operands(op, queries, layers, head_num, keys, query_lengths, key_lengths, query_mask, key_mask,
+                          use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding, output_type, route, ln_eps):
+    """The checked operands transformer(), transformer_train() and transformer_bwd() share: the args struct with sizes, flags and
+    the queries' / keys' strides, the flat weight list (None where a flag switches a weight off) and the four mask operands."""
     if queries.dim() != 3:
         raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % queries.dim())
     B, T, E = (int(v) for v in queries.shape)
@@ -2379,7 +2371,7 @@ def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_le
     if keys is not None:
         a.k_stride, a.k_row_stride = _seq3d(op, "keys", keys, B, T, E)
     if not layers:
-        raise ValueError("transformer: at least one layer")
+        raise ValueError("%s: at least one layer" % op)
     shapes = {"query": (E, E), "key": (E, E), "value": (E, E), "fw1": (E, 4 * E), "fw2": (4 * E, E), "ln_gamma": (1, E), "ln_beta": (1, E),
               "pe_q": (T, E), "pe_k": (T, E)}
     needed = {"query": True, "key": True, "value": True, "fw1": bool(use_feed_forward and use_res), "fw2": bool(use_feed_forward and use_res),
@@ -2393,17 +2385,36 @@ def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_le
             w = layer.get(name)
             if w is None or not needed[name]:
                 if needed[name]:
-                    raise ValueError("transformer: layer %d: %s is missing" % (li, name))
+                    raise ValueError("%s: layer %d: %s is missing" % (op, li, name))
                 flat.append(None)
                 continue
             rows, cols = shapes[name]
             if name.startswith("ln_"):
                 _vec(op, "layer %d %s" % (li, name), w, cols)
             elif _rows2d(op, "layer %d %s" % (li, name), w, rows, cols) != cols and rows > 1:
-                raise ValueError("transformer: layer %d: %s must be contiguous" % (li, name))
+                raise ValueError("%s: layer %d: %s must be contiguous" % (op, li, name))
             flat.append(w)
     query_lengths, query_mask = _transformer_mask(op, "query", query_lengths, query_mask, B, T)
     key_lengths, key_mask = _transformer_mask(op, "key", key_lengths, key_mask, B, T)
+    return a, flat, (query_lengths, key_lengths, query_mask, key_mask)
+
+
+def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None,
+                use_positional_encoding=True, use_res=True, use_feed_forward=True, use_layer_norm=False, blinding=True,
+                output_type=None, out=None, key_mask_out=None, route=None, workspace=None, ln_eps=1e-9):
+    """Transformer.call (reference sequence.py:523-635) stacked over len(layers) layers (bst.py:84-92), one launch.
+
+    ``queries`` [B, T, E] float32 view (any sample / position strides, unit stride on the last axis); ``keys`` the same shape or None
+    (the queries).  ``layers``: per layer a dict (or a sequence in this order) of query, key, value [E, E], fw1 [E, 4E], fw2 [4E, E],
+    ln_gamma, ln_beta [E], pe_q, pe_k [T, E] — the positional tables ALREADY multiplied by float32(sqrt(E)); weights a flag switches
+    off may be None.  Masks: int32 lengths [B] or a uint8 / bool [B, T] mask per side, None = every position counts.
+    ``out``: a [B, T, E] view (``output_type`` None; may be ``queries`` itself: in place) or [B, E] ('mean' / 'sum'), allocated when
+    None.  ``key_mask_out``: a uint8 [B, T] tensor that receives the key mask.  Returns ``out``."""
+    op = "transformer"
+    a, flat, (query_lengths, key_lengths, query_mask, key_mask) = _transformer_operands(
+        op, queries, layers, head_num, keys, query_lengths, key_lengths, query_mask, key_mask, use_positional_encoding, use_res,
+        use_feed_forward, use_layer_norm, blinding, output_type, route, ln_eps)
+    B, T, E = int(a.batch), int(a.seq_len), int(a.dim)
     if out is None:
         out = torch.empty((B, T, E) if output_type is None else (B, E), dtype=torch.float32, device=queries.device)
     if output_type is None:
@@ -2425,6 +2436,172 @@ def transformer(queries, layers, head_num, keys=None, query_lengths=None, key_le
     _C.check(_C.lib().dctr_transformer_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_transformer_fwd")
     del lp
     return out
+
+
+def transformer_bwd_flops(T, E, n_layers=1, use_feed_forward=True):
+    """FLOP per sample of dctr_transformer_bwd without its recompute of the forward: Y W^T and X^T dY for every projection (twice the
+    forward's matrix FLOP) and the two attention walks, 12 T^2 E (csrc/transformer_bwd_kernels.hip has the model)."""
+    return int(n_layers) * (12 * T * E * E + 12 * T * T * E + (32 * T * E * E if use_feed_forward else 0))
+
+
+def _transformer_train_shape(B, T, E, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding,
+                             output_type, route, max_blocks=0):
+    t = _C.transformer.TrainArgs()
+    t.fwd = _transformer_args(B, T, E, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding,
+                              output_type, route)
+    t.d_out_stride, t.d_out_row_stride = (int(T) * int(E), int(E)) if output_type is None else (int(E), 0)
+    t.dx_stride, t.dx_row_stride = int(T) * int(E), int(E)
+    t.max_blocks = int(max_blocks)
+    return t
+
+
+def transformer_tape_bytes(batch, seq_len, dim, head_num, n_layers=1):
+    """Bytes of the tape dctr_transformer_train_fwd writes: the inputs of the layers past the first (read from the library)."""
+    a = _transformer_args(batch, seq_len, dim, head_num, n_layers, True, True, True, False, True, None, None)
+    return int(_C.lib().dctr_transformer_tape_bytes(ctypes.byref(a)))
+
+
+def transformer_bwd_supported(seq_len, dim, head_num, n_layers=1, use_positional_encoding=True, use_res=True, use_feed_forward=True,
+                              use_layer_norm=False, blinding=True, output_type=None, route=None):
+    """Does dctr_transformer_bwd (and the training forward whose tape it reads) take these shapes and options (read from the
+    library)?  Self-attention is understood: separate keys are never supported."""
+    t = _transformer_train_shape(1, seq_len, dim, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward, use_layer_norm,
+                                 blinding, output_type, route)
+    return bool(_C.lib().dctr_transformer_bwd_supported(ctypes.byref(t)))
+
+
+def transformer_bwd_workspace_bytes(batch, seq_len, dim, head_num, n_layers=1, use_positional_encoding=True, use_res=True,
+                                    use_feed_forward=True, use_layer_norm=False, blinding=True, output_type=None, route=None,
+                                    max_blocks=0):
+    """Bytes of the workspace dctr_transformer_bwd needs for these shapes (read from the library; 0 for a shape it refuses)."""
+    t = _transformer_train_shape(batch, seq_len, dim, head_num, n_layers, use_positional_encoding, use_res, use_feed_forward,
+                                 use_layer_norm, blinding, output_type, route, max_blocks)
+    return int(_C.lib().dctr_transformer_bwd_workspace_bytes(ctypes.byref(t)))
+
+
+def _transformer_train_operands(op, x, layers, head_num, keys, tape, query_lengths, key_lengths, query_mask, key_mask,
+                                use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding, output_type, route, ln_eps):
+    """x, the weights, the masks and the tape of transformer_train() / transformer_bwd().  Returns (train args, weights, masks,
+    keep-alive)."""
+    a, flat, masks = _transformer_operands(op, x, layers, head_num, keys, query_lengths, key_lengths, query_mask, key_mask,
+                                           use_positional_encoding, use_res, use_feed_forward, use_layer_norm, blinding, output_type,
+                                           route, ln_eps)
+    t = _C.transformer.TrainArgs()
+    t.fwd = a
+    need = (len(layers) - 1) * int(a.batch) * int(a.seq_len) * int(a.dim) * 4
+    if need and (tape is None or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() * 4 < need):
+        raise ValueError("%s: tape must be a contiguous float32 tensor of >= %d bytes (transformer_train allocates it)" % (op, need))
+    lp = _ptr_array(flat)
+    t.fwd.layers = ctypes.cast(lp, ctypes.c_void_p)
+    t.fwd.queries = x.data_ptr()
+    t.fwd.keys = None if keys is None else keys.data_ptr()
+    t.fwd.query_lengths, t.fwd.key_lengths, t.fwd.query_mask, t.fwd.key_mask = (_ptr(m) for m in masks)
+    if tape is not None:
+        t.tape, t.tape_bytes = tape.data_ptr(), tape.numel() * 4
+    return t, flat, masks, lp
+
+
+def transformer_train(x, layers, head_num, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None,
+                      use_positional_encoding=True, use_res=True, use_feed_forward=True, use_layer_norm=False, blinding=True,
+                      output_type=None, out=None, tape=None, route=None, workspace=None, ln_eps=1e-9):
+    """transformer() over self-attention as the forward of a training step (dctr_transformer_train_fwd): the same kernel, so the
+    same bits in ``out``, plus a tape.  Returns (out, tape): ``tape`` float32 [len(layers) - 1, B, T, E], the input of every layer
+    past the first for transformer_bwd(), allocated when None."""
+    op = "transformer_train"
+    if tape is None:
+        tape = torch.empty((max(0, len(layers) - 1),) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    t, flat, masks, keep = _transformer_train_operands(op, x, layers, head_num, None, tape, query_lengths, key_lengths, query_mask,
+                                                       key_mask, use_positional_encoding, use_res, use_feed_forward, use_layer_norm,
+                                                       blinding, output_type, route, ln_eps)
+    a = t.fwd
+    B, T, E = int(a.batch), int(a.seq_len), int(a.dim)
+    if out is None:
+        out = torch.empty((B, T, E) if output_type is None else (B, E), dtype=torch.float32, device=x.device)
+    if output_type is None:
+        t.fwd.out_stride, t.fwd.out_row_stride = _seq3d(op, "out", out, B, T, E)
+    else:
+        t.fwd.out_stride = _rows2d(op, "out", out, B, E)
+    _dev_check(x, out, tape, *(list(masks) + flat))
+    t.fwd.out = out.data_ptr()
+    _workspace(op, t.fwd, int(_C.lib().dctr_transformer_workspace_bytes(ctypes.byref(t.fwd))), workspace, x.device)
+    _C.check(_C.lib().dctr_transformer_train_fwd(ctypes.byref(t), _C.stream_ptr()), "dctr_transformer_train_fwd")
+    del keep
+    return out, tape
+
+
+def transformer_bwd(x, layers, head_num, tape, d_out, query_lengths=None, key_lengths=None, query_mask=None, key_mask=None,
+                    use_positional_encoding=True, use_res=True, use_feed_forward=True, use_layer_norm=False, blinding=True,
+                    output_type=None, dx=None, accumulate=False, d_weights=None, max_blocks=0, route=None, workspace=None, ln_eps=1e-9,
+                    keys=None):
+    """Backward of transformer_train(): the whole stack in one call (include/dctr.h: dctr_transformer_bwd).  ``x``, ``layers``, the
+    masks and the options as transformer_train(), ``tape`` what it returned.  ``d_out``: the gradient of its output, a float32
+    [B, T, E] view (``output_type`` None) or [B, E] ('mean' / 'sum').  ``dx`` [B, T, E] view: written, or added to with
+    ``accumulate``; ``d_weights``: 9 x len(layers) contiguous tensors of the weights' shapes in the layers' order (None where not
+    wanted), ACCUMULATED into; the gradients of pe_q / pe_k are those of the pre-scaled tables.  ``keys``: only to hear the library
+    refuse separate keys.  No atomics: the same bits on every call."""
+    op = "transformer_bwd"
+    t, flat, masks, keep = _transformer_train_operands(op, x, layers, head_num, keys, tape, query_lengths, key_lengths, query_mask,
+                                                       key_mask, use_positional_encoding, use_res, use_feed_forward, use_layer_norm,
+                                                       blinding, output_type, route, ln_eps)
+    a = t.fwd
+    B, T, E = int(a.batch), int(a.seq_len), int(a.dim)
+    if output_type is None:
+        t.d_out_stride, t.d_out_row_stride = _seq3d(op, "d_out", d_out, B, T, E)
+    else:
+        t.d_out_stride = _rows2d(op, "d_out", d_out, B, E)
+    if dx is not None:
+        t.dx_stride, t.dx_row_stride = _seq3d(op, "dx", dx, B, T, E)
+    d_weights = [None] * len(flat) if d_weights is None else list(d_weights)
+    if len(d_weights) != len(flat):
+        raise ValueError("transformer_bwd: d_weights must hold %d entries (%s per layer)" % (len(flat), ", ".join(TRANSFORMER_WEIGHTS)))
+    for i, (w, g) in enumerate(zip(flat, d_weights)):
+        if g is not None:
+            if w is None:
+                raise ValueError("transformer_bwd: d_weights layer %d %s: the flags switch this weight off" % (i // 9, TRANSFORMER_WEIGHTS[i % 9]))
+            _vec(op, "d_weights layer %d %s" % (i // 9, TRANSFORMER_WEIGHTS[i % 9]), g, w.numel())
+    _dev_check(x, keys, tape, d_out, dx, *(list(masks) + flat + d_weights))
+    dp = _ptr_array(d_weights)
+    if any(g is not None for g in d_weights):
+        t.d_layers = ctypes.cast(dp, ctypes.c_void_p)
+    t.d_out, t.dx = d_out.data_ptr(), _ptr(dx)
+    t.accumulate, t.max_blocks = int(bool(accumulate)), int(max_blocks)
+    _workspace(op, t, int(_C.lib().dctr_transformer_bwd_workspace_bytes(ctypes.byref(t))), workspace, x.device)
+    _C.check(_C.lib().dctr_transformer_bwd(ctypes.byref(t), _C.stream_ptr()), "dctr_transformer_bwd")
+    del keep, dp
+
+
+class TransformerFunction(torch.autograd.Function):
+    """A stack of Transformer layers over self-attention as one differentiable op: transformer_train() forward (tape kept) and
+    transformer_bwd() backward.  ``apply(x, query_lengths, key_lengths, query_mask, key_mask, head_num, flags, output_type,
+    *weights)``: x [B,T,E]; the masks as transformer() takes them (no gradient); ``flags`` the dict of Transformer.flags();
+    ``weights`` the 9 x n_layers tensors layer by layer in TRANSFORMER_WEIGHTS' order, None where a flag switches one off, the
+    positional tables pre-scaled.  Returns [B,T,E], or [B,E] for 'mean' / 'sum'.  Gradients for x and the weights."""
+
+    @staticmethod
+    def forward(ctx, x, query_lengths, key_lengths, query_mask, key_mask, head_num, flags, output_type, *weights):
+        x = x.detach()
+        x = x if x.stride(2) == 1 or x.shape[2] == 1 else x.contiguous()
+        ws = [None if w is None else w.detach().contiguous() for w in weights]
+        layers = [ws[i:i + 9] for i in range(0, len(ws), 9)]
+        masks = dict(query_lengths=query_lengths, key_lengths=key_lengths, query_mask=query_mask, key_mask=key_mask)
+        out, tape = transformer_train(x, layers, head_num, output_type=output_type, **masks, **flags)
+        ctx.cfg = (int(head_num), dict(flags), output_type, masks, [w is not None for w in ws])
+        ctx.save_for_backward(x, tape, *[w for w in ws if w is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        head_num, flags, output_type, masks, present = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        x, tape, rest = saved[0], saved[1], saved[2:]
+        ws = [rest.pop(0) if here else None for here in present]
+        d = _grad_operand(d_out, output_type is not None)
+        dx = torch.empty_like(x, memory_format=torch.contiguous_format) if ctx.needs_input_grad[0] else None
+        wanted = [w is not None and ctx.needs_input_grad[8 + i] for i, w in enumerate(ws)]
+        _, grads = _zeroed_grads(ws, wanted, x.device)      # one fill for all
+        layers = [ws[i:i + 9] for i in range(0, len(ws), 9)]
+        transformer_bwd(x, layers, head_num, tape, d, output_type=output_type, dx=dx, d_weights=grads, **masks, **flags)
+        return (dx,) + (None,) * 7 + tuple(grads)
 
 
 def layer_norm(x, gamma=None, beta=None, eps=1e-9, out=None):

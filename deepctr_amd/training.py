@@ -431,6 +431,46 @@ def _transformer(layer, queries, keys, query_mask, key_mask, training=False):
     return r
 
 
+# Below this many rows (samples of the [B, T, E] input) the Transformer's autograd step would stay on the torch ops of _transformer.
+# 0: on one MI355X the HIP route won by more than the 3 % boxes differ by at every size measured — 256, 1,024 and 4,096 rows a step,
+# BST with one and two layers (T 50, E 32) by 3.9 .. 15 %, DSIN (T 10, 5 sessions) at E 32 by 6.9 .. 8.7 % and at E 64 by 3.3 .. 5.8 %
+# (profiles/transformer_bwd.txt).
+TRANSFORMER_HIP_MIN_ROWS = 0
+
+
+def transformer(layers, x, query_mask, key_mask, training=False, lengths=None, keys=None):
+    """A stack of Transformer layers over x [B,T,E] inside the autograd step; bool masks [B,T] as _transformer takes them, or with
+    ``lengths`` (int32 [B], both masks then being t < length) the lengths form.  On the GPU, with gradients enabled and something
+    requiring grad, the whole stack is ONE ops.TransformerFunction: dctr_transformer_train_fwd forward (a tape of the layers' inputs)
+    and dctr_transformer_bwd backward, where _transformer runs some twenty-five torch ops per layer and autograd replays them.
+    Everything else — the CPU, torch.no_grad(), HIP_AUTOGRAD_OPS off, another dtype, an active dropout, separate ``keys``, layers that
+    differ in their options or pool before the last one, fewer than TRANSFORMER_HIP_MIN_ROWS rows, a shape the backward refuses — takes _transformer, layer by
+    layer (the keys of a layer past the first are its queries)."""
+    layers = list(layers)
+    own_keys = keys is not None and keys is not x
+    if (layers and not own_keys and x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32
+            and x.shape[0] >= TRANSFORMER_HIP_MIN_ROWS and not (training and any(l.dropout_rate for l in layers))):
+        first = layers[0]
+        flags, H, out_type = first.flags(), first.head_num, layers[-1].output_type
+        same = all((l.flags(), l.head_num) == (flags, H) for l in layers) and all(l.output_type is None for l in layers[:-1])
+        ws = [l.operands().get(name) for l in layers for name in ops.TRANSFORMER_WEIGHTS]
+        if not (flags["use_feed_forward"] and flags["use_res"]):        # the reference computes the feed-forward and drops it
+            ws = [None if i % 9 in (3, 4) else w for i, w in enumerate(ws)]
+        opts = {k: v for k, v in flags.items() if k != "ln_eps"}
+        if (same and (x.requires_grad or any(w is not None and w.requires_grad for w in ws))
+                and ops.transformer_bwd_supported(x.shape[1], x.shape[2], H, len(layers), output_type=out_type, **opts)):
+            if lengths is not None:
+                lens = lengths.reshape(-1).to(torch.int32)
+                masks = (lens, lens, None, None)
+            else:
+                masks = (None, None, query_mask.contiguous(), key_mask.contiguous())
+            y = ops.TransformerFunction.apply(x, masks[0], masks[1], masks[2], masks[3], H, flags, out_type, *ws)
+            return y if out_type is None else y.unsqueeze(1)
+    for i, layer in enumerate(layers):
+        x = _transformer(layer, x, keys if own_keys and i == 0 else x, query_mask, key_mask, training)
+    return x
+
+
 def _gru(x, lengths, layers, cell="GRU", att_scores=None, scale_input=False, return_sequence=True):
     """DynamicGRU.call (reference sequence.py:786-803) in torch ops: tf's GRUCell / the AGRU and AUGRU cells of contrib/utils.py
     (:208-261, :327-378) under dynamic_rnn's sequence_length rule (contrib/rnn_v2.py:1324-1401) — at t >= length the state is copied

@@ -1101,6 +1101,69 @@ size_t dctr_transformer_workspace_bytes(const dctr_transformer_args_t* args);
 /* The route these arguments take (DCTR_TRANSFORMER_ROUTE_FUSED / _GENERAL), or the DCTR_E_* the checks answer. */
 int dctr_transformer_route(const dctr_transformer_args_t* args);
 int dctr_transformer_fwd(const dctr_transformer_args_t* args, void* stream);
+/* The Transformer stack of a training step: dctr_transformer_train_fwd is dctr_transformer_fwd (the same kernel under one more
+ * template flag, the same bits in out) that also writes a tape; dctr_transformer_bwd is the backward of the whole stack in one call.
+ * fwd: as dctr_transformer_fwd (queries = x, layers, masks in either form, sizes, flags, route; out is written by the forward and
+ *   ignored by the backward; fwd.workspace is the forward's alone).
+ * tape: caller-allocated, dctr_transformer_tape_bytes(&fwd) bytes, written by the forward and read by the backward:
+ *   float [n_layers - 1][B][T][E] contiguous: entry l - 1 is the input of layer l >= 1 (= the output of layer l - 1), the bits the
+ *   forward produced.  Layer 0 reads x.  One layer: 0 bytes, the pointer may be NULL.  Everything else is recomputed in the backward
+ *   with the forward's own arithmetic (the same device functions), so the recomputed activations are the forward's bits.
+ * The backward.  d_out: the gradient of out: [B, T, E] at d_out_stride / d_out_row_stride for output NONE, [B, E] at d_out_stride for
+ *   MEAN / SUM, which spread it over ALL T rows (d_out / T for MEAN).  Per layer, last to first, dy the gradient of its output:
+ *     df = LNbwd(dy) (use_feed_forward and use_layer_norm), else dy
+ *     use_feed_forward and use_res: h = relu(r fw1);  dh = (df fw2^T) [h > 0];  d_fw2 += h^T df;  d_fw1 += r^T dh;  dr = df + dh fw1^T
+ *     da = LNbwd(dr) (use_layer_norm), else dr.   LNbwd(g) at the row x it normalised, xh = (x - mean) / sd, sd = sqrt(var + ln_eps):
+ *       d_ln_gamma += sum_rows g xh;  d_ln_beta += sum_rows g;  gh = g gamma;  dx = (gh - mean(gh) - xh mean(gh xh)) / sd.
+ *       Both LayerNorm applications share gamma / beta, so d_ln_gamma / d_ln_beta are the sum of both.  An all-zero row (use_res = 0
+ *       and a masked query) has xh = 0 and sd = sqrt(ln_eps): its dx is finite.
+ *     attention, per head, p~ = p * query mask (the mask multiplies p AFTER the softmax):  dV_j = sum_i p~_ij da_i;  dP_ij = da_i . V_j;
+ *       ds_ij = p~_ij (dP_ij - sum_k p~_ik dP_ik) / sqrt(d) at keys that count, and 0 at a masked key and on the blinded diagonal
+ *       (where(mask, s, -2^32+1) passes no gradient there).  A row whose keys are all masked has a uniform softmax: every ds is 0,
+ *       dV still receives p~ da.   dQ_i = sum_j ds_ij K_j;  dK_j = sum_i ds_ij Q_i.
+ *     dXq = dQ Wq^T (+ da with use_res);  dXk = dK Wk^T + dV Wv^T;  d_query += Xq^T dQ;  d_key += Xk^T dK;  d_value += Xk^T dV
+ *     d_pe_q += sum over samples of dXq, d_pe_k of dXk ([T, E], in the units of the PRE-SCALED tables the op reads: the caller
+ *       multiplies by float32(sqrt(E)) for the lookup tables);  the layer's dx = dXq + dXk is the dy of the layer before.
+ *   One persistent launch: a workgroup owns a tile of samples; the layer's recomputed activations, the gradient rows and the three
+ *   numbers per (row, head) of the attention (max, query mask / sum, sum p~ dP) live in LDS, or in a per-workgroup workspace slice when
+ *   a sample does not fit 160 KiB or fwd.route is GENERAL.  Every matrix product is exact fp32 on v_mfma_f32_16x16x4_f32; the
+ *   attention backward is a thread per (row, head), one walk for dQ and one for dK / dV, no [T, T] matrix anywhere.  Each workgroup
+ *   adds its weight-gradient partials tile after tile into its own workspace slice and a second launch sums the slices in workgroup
+ *   order: no atomics, dx and every weight gradient repeat bit for bit from call to call.
+ * dx: NULL, or [B, T, E] at its strides, written, or added to with accumulate.  d_layers: NULL, or a HOST array [9 * n_layers] of
+ *   DEVICE pointers of the weights' shapes in fwd.layers' order (d_pe_q / d_pe_k [T, E]), ACCUMULATED into; any entry may be NULL,
+ *   and an entry whose weight the flags switch off is left untouched.
+ * max_blocks: 0, or the most workgroups of the persistent launch (at most 256 either way; each walks its tiles).
+ * workspace: dctr_transformer_bwd_workspace_bytes() bytes, 16-B aligned (DCTR_E_NULL without, nothing launched); it depends on batch
+ *   and max_blocks.
+ * dctr_transformer_bwd_supported answers 1 or 0 from sizes and flags only: self-attention (fwd.keys NULL or the queries), n_layers
+ *   <= DCTR_TRANSFORMER_BWD_MAX_LAYERS; every seq_len, dim, head_num, flag set, output type and mask form the forward takes.
+ *   Separate keys and more layers answer DCTR_E_UNSUPPORTED from dctr_transformer_bwd with nothing launched.  Dropout has no operand:
+ *   a step with an active dropout does not use this op.
+ * Argument errors answer the codes of dctr_transformer_fwd (plus DCTR_E_NULL for a missing x, d_out or tape, DCTR_E_DIM for d_out / dx
+ *   strides smaller than their blocks, DCTR_E_ENUM for accumulate not 0 / 1 or max_blocks < 0); nothing is launched or written then. */
+#define DCTR_TRANSFORMER_BWD_MAX_LAYERS 8
+typedef struct {
+    dctr_transformer_args_t fwd;
+    void* tape;                      /* dctr_transformer_tape_bytes() bytes (NULL when that is 0) */
+    size_t tape_bytes;
+    const float* d_out;              /* [B, T, E] (output NONE) or [B, E] (MEAN / SUM) */
+    int64_t d_out_stride;
+    int64_t d_out_row_stride;        /* output NONE only */
+    float* dx;                       /* NULL, or [B, T, E] */
+    int64_t dx_stride;
+    int64_t dx_row_stride;
+    float* const* d_layers;          /* NULL, or HOST array [n_layers * 9] of DEVICE pointers; each may be NULL */
+    int32_t accumulate;              /* 0 | 1: dx written | added to */
+    int32_t max_blocks;
+    void* workspace;                 /* the backward's: dctr_transformer_bwd_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_transformer_train_args_t;
+size_t dctr_transformer_tape_bytes(const dctr_transformer_args_t* args);                    /* host only; 0 for refused arguments */
+int dctr_transformer_train_fwd(const dctr_transformer_train_args_t* args, void* stream);
+int dctr_transformer_bwd_supported(const dctr_transformer_train_args_t* args);              /* host only */
+size_t dctr_transformer_bwd_workspace_bytes(const dctr_transformer_train_args_t* args);     /* host only */
+int dctr_transformer_bwd(const dctr_transformer_train_args_t* args, void* stream);
 /* LayerNormalization.call alone (layers/normalization.py:34-43) over the rows of x [rows, dim]: (x - mean) / sqrt(var + eps) * gamma +
  * beta with the biased variance; gamma / beta NULL = scale / center off.  out may be x. */
 int dctr_layer_norm_fwd(const float* x, int64_t rows, int32_t dim, int64_t x_stride, const float* gamma, const float* beta, float eps,

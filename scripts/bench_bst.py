@@ -3,9 +3,11 @@ samples/s of the whole forward (staged ids -> probabilities: fused gather, key l
 DNN) beside the same model's torch-ops forward (training.model_logits under no_grad), and dctr_transformer_fwd alone on the model's own
 key buffer (the fused route and, forced, the general route) beside its f32-MFMA bound.  The bound is arithmetic, not a measurement:
 6 T E^2 + 4 T^2 E + 16 T E^2 FLOP per sample and layer (ops.transformer_flops) at 157.3 TFLOP/s.  Device-event timing after warm-up.
-Prints one JSON line.
+With --train-rows: dctr_transformer_train_fwd and dctr_transformer_bwd alone on the key buffer beside the backward's bound
+(ops.transformer_bwd_flops), and the autograd step at each of the given row counts with the HIP Transformer off (the torch ops of
+training._transformer) and on, alternating window by window: the table of profiles/transformer_bwd.txt.  Prints one JSON line.
 
-    python scripts/bench_bst.py [--rows 4096] [--iters 20]"""
+    python scripts/bench_bst.py [--rows 4096] [--iters 20] [--train-rows 256,1024,4096]"""
 import argparse
 import json
 import os
@@ -45,6 +47,8 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--layers", default="1,2")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch-ops forward")
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--train-rows", default="", help="comma-separated row counts of the autograd step, HIP Transformer off / on")
     args = ap.parse_args()
     device = torch.device("cuda:0")
     T, V = args.seq_len, 100000
@@ -104,6 +108,12 @@ def main():
             bound = n * ops.transformer_flops(T, E, L) / (MFMA_F32_TFLOPS * 1e12) * 1e3
             r.update(block_ms=round(ms_fused, 4), block_general_ms=round(ms_general, 4), block_bound_ms=round(bound, 4),
                      block_share_of_bound=round(bound / ms_fused, 3), block_gflops=round(n * ops.transformer_flops(T, E, L) / ms_fused * 1e-6, 1))
+            if args.train_rows:
+                import transformer_bwd_timing as tbt
+                tbt.kernels(r, model.transformers, args.heads, keys, dict(query_lengths=lt, key_lengths=lt), None, args.iters, args.windows)
+                tbt.steps(r, model, staged, n, [int(v) for v in args.train_rows.split(",")],
+                          [("transformer_torch", {"TRANSFORMER_HIP_MIN_ROWS": 1 << 62}), ("transformer_hip", {"TRANSFORMER_HIP_MIN_ROWS": 0})],
+                          args.iters, args.windows)
             del model
             torch.cuda.empty_cache()
     print(json.dumps(res))

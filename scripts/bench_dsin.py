@@ -7,7 +7,10 @@ layer (ops.bilstm_macs) at the f32 MFMA rate.
 With --train-rows: the backward as well.  dctr_bilstm_train_fwd and dctr_bilstm_bwd alone (all six weight gradients and dx, dropout
 masks on; default route and streamed) beside the backward's bound, three times the forward's multiply-adds (ops.bilstm_bwd_macs), and
 the autograd step (model_logits in training mode, the loss, torch.autograd.grad over every trainable weight) at each of the given row
-counts with training.HIP_AUTOGRAD_OPS off and on, alternating window by window: the table of profiles/dsin_bilstm_bwd.txt.  Medians of device-event timings over repeated windows, after warm-up of every shape;
+counts with training.HIP_AUTOGRAD_OPS off and on, alternating window by window: the table of profiles/dsin_bilstm_bwd.txt; then
+dctr_transformer_train_fwd and dctr_transformer_bwd alone over [rows x sessions, T, E] beside the backward's bound, and the step
+with every HIP op off, with the BiLSTM alone on HIP (the Transformer on the torch ops of training._transformer) and with both on HIP:
+the table of profiles/transformer_bwd.txt.  Medians of device-event timings over repeated windows, after warm-up of every shape;
 the two sides of a comparison alternate window by window.  Prints one JSON line and exits 1 when a speed condition fails (a HIP path
 slower than its torch-ops counterpart).
 
@@ -101,6 +104,18 @@ def _train(r, model, staged, x, S, E, args):
         training.HIP_AUTOGRAD_OPS = True
         for t in params:
             t.requires_grad_(False)
+    # ---- the Transformer over all sessions: the two launches alone, and the step with it off (BiLSTM on HIP) and on ----------------
+    import transformer_bwd_timing as tbt
+    T = args.seq_len
+    xs = torch.randn(n * S, T, E, device=x.device)
+    m = torch.rand(n * S, T, device=x.device) < 0.7
+    tbt.kernels(r, [model.transformer], model.transformer.head_num, xs, dict(query_mask=m, key_mask=m), "mean", args.iters, args.windows)
+    keep = dict(steps)
+    tbt.steps(r, model, staged, n, [int(v) for v in args.train_rows.split(",")],
+              [("torch", {"HIP_AUTOGRAD_OPS": False}), ("bilstm_hip", {"TRANSFORMER_HIP_MIN_ROWS": 1 << 62}),
+               ("bilstm_and_transformer_hip", {"TRANSFORMER_HIP_MIN_ROWS": 0})], args.iters, args.windows)
+    r["transformer_autograd_step_ms"] = r.pop("autograd_step_ms")
+    r["autograd_step_ms"] = keep
 
 
 def main():
