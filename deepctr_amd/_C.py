@@ -203,6 +203,15 @@ class ffm(object):
                     ("out_offset", c_i64), ("status", c_vp), ("route", c_i32), ("reserved", c_i32), ("workspace", c_vp),
                     ("workspace_bytes", c_sz)]
 
+    class Grad(ctypes.Structure):
+        _fields_ = [("grad", c_vp), ("row_stride", c_i64)]
+
+
+# dctr_ffm_bwd_args_t (tests/test_ffm_bwd_oracle_cpu.py checks the layout)
+ffm.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", ffm.Args), ("d_out", c_vp), ("d_out_stride", c_i64), ("d_out_offset", c_i64), ("grads", c_vp), ("max_blocks", c_i32),
+    ("reserved", c_i32), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
+
 
 class ifm(object):
     """dctr_ifm_src_t / dctr_ifm_lin_t / dctr_ifm_args_t, one level down for the same reason as interacting.Args (tests/test_ifm_cpu.py
@@ -499,6 +508,9 @@ SYMBOLS = {
     "dctr_ffm_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_route": (ctypes.c_int, [ctypes.POINTER(ffm.Args)]),
     "dctr_ffm_fwd": (ctypes.c_int, [ctypes.POINTER(ffm.Args), c_vp]),
+    "dctr_ffm_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.BwdArgs)]),
+    "dctr_ffm_bwd_route": (ctypes.c_int, [ctypes.POINTER(ffm.BwdArgs)]),
+    "dctr_ffm_bwd": (ctypes.c_int, [ctypes.POINTER(ffm.BwdArgs), c_vp]),
     "dctr_ifm_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_route": (ctypes.c_int, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_fwd": (ctypes.c_int, [ctypes.POINTER(ifm.Args), c_vp]),

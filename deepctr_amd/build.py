@@ -55,6 +55,7 @@ SOURCES = [
     "fieldpair_kernels.hip",
     "fieldpair_bwd_kernels.hip",
     "ffm_kernels.hip",
+    "ffm_bwd_kernels.hip",
     "ifm_kernels.hip",
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",

@@ -212,13 +212,42 @@ class _ONN(FeatureModel):
             embs.append(row)
         return embs
 
+    def _pooled_rows(self, staged, lo, hi, j):
+        """torch ops: sequence feature j's [B, (F-1)*d] fused row, its F-1 per-name views pooled as field_aware_rows pools them and
+        laid side by side in slot order — what ops.FieldAwareFunction takes for a field that arrives pooled."""
+        fc_j = self.deep_cols[j]
+        seq = staged.extra.get("ffm_seq:" + fc_j.name)
+        rows = (staged.seq[fc_j.name] if seq is None else seq)[lo:hi].to(torch.int64)
+        mask = rows != 0
+        return torch.cat([tops._pool(self.tables["%s_%s" % (fc_j.embedding_name, fc_i.embedding_name)].embeddings[rows], fc_j, mask,
+                                     None, None).reshape(hi - lo, -1) for i, fc_i in enumerate(self.deep_cols) if i != j], dim=-1)
+
+    def _pairs_on_hip(self, staged, lo, hi):
+        """The pair columns [B, P*d] ([B, P]) as ONE differentiable HIP op (ops.FieldAwareFunction), or None: the torch ops."""
+        masters, views = [], []
+        for j, (fc_j, master) in enumerate(zip(self.deep_cols, self.masters)):
+            if isinstance(fc_j, VarLenSparseFeat):
+                masters.append(None)
+                views.append(lambda j=j: self._pooled_rows(staged, lo, hi, j))
+            else:
+                masters.append(master)
+                views.append([self.tables["%s_%s" % (fc_j.embedding_name, fc_i.embedding_name)].embeddings
+                              for i, fc_i in enumerate(self.deep_cols) if i != j])
+        inputs = tops._ffm_on_hip(masters, views, hi - lo, tops.ONN_HIP_MIN_ROWS)
+        if inputs is None or not any(t.requires_grad for t in inputs):
+            return None
+        return ops.FieldAwareFunction.apply(staged.extra["ffm_ids"][lo:hi].t(), masters, self.emb_dim, self.reduce_sum,
+                                            self.stage_plan.status(), *inputs)
+
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # onn.py:59-105
-        embs = self.field_aware_rows(staged, lo, hi)
-        prods = []
-        for i, j in zip(*tops._pair_indices(self.n_fields)):
-            pr = embs[i][j] * embs[j][i]
-            prods.append(pr.sum(-1, keepdim=True) if self.reduce_sum else pr)
-        x = torch.cat(prods, dim=-1)
+        x = self._pairs_on_hip(staged, lo, hi)
+        if x is None:
+            embs = self.field_aware_rows(staged, lo, hi)
+            prods = []
+            for i, j in zip(*tops._pair_indices(self.n_fields)):
+                pr = embs[i][j] * embs[j][i]
+                prods.append(pr.sum(-1, keepdim=True) if self.reduce_sum else pr)
+            x = torch.cat(prods, dim=-1)
         if self.bn is not None:
             x = tops._batch_norm(self.bn, x, training)
         return (tops.dnn_forward(self.dnn, torch.cat([x] + parts, dim=-1), training) @ self.dense.w("kernel")).reshape(-1)

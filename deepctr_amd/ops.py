@@ -1269,6 +1269,46 @@ def make_ffm_fields(fields, device):
     return _upload(arr, device)
 
 
+def _ffm_operands(op, ids, masters, dim, desc, batch):
+    """What ffm() and ffm_bwd() read alike: the ids [F, B] and per field the fused table or the pre-pooled (buffer,) 1-tuple, behind a
+    dctr_ffm_field_t array — or a ready ``desc`` with ``dim`` and ``batch``.  Returns (F, dim, B, desc, the 2-D tables to keep alive)."""
+    F = len(masters)
+    if F < 2:
+        raise ValueError("%s: %d field(s): a field pair needs at least 2" % (op, F))
+    keep = []
+    if desc is None:
+        B = int(ids.shape[1]) if batch is None else int(batch)
+        if ids.dim() != 2 or ids.shape[0] != F or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s: ids must be an int32 / int64 [%d, B] matrix" % (op, F))
+        fields = []
+        for j, m in enumerate(masters):
+            pooled = isinstance(m, tuple)
+            m = m[0] if pooled else m
+            if m.dtype != torch.float32:
+                raise TypeError("%s: tables must be float32, got %s" % (op, m.dtype))
+            if m.dim() == 3:
+                if dim is None:
+                    dim = int(m.shape[2])
+                if m.shape[1] != F - 1 or m.shape[2] != dim or not m.is_contiguous():
+                    raise ValueError("%s: field %d: expected a contiguous [V, %d, %d] table, got %s" % (op, j, F - 1, dim, tuple(m.shape)))
+                m = m.view(m.shape[0], -1)
+            if dim is None:
+                raise ValueError("%s: dim is required with 2-D tables" % op)
+            if m.dim() != 2 or m.stride(1) != 1 or m.shape[1] < (F - 1) * dim:
+                raise ValueError("%s: field %d: expected [rows, >= %d] with unit column stride" % (op, j, (F - 1) * dim))
+            if pooled and m.shape[0] < B:
+                raise ValueError("%s: pre-pooled field %d holds %d rows for a batch of %d" % (op, j, m.shape[0], B))
+            keep.append(m)
+            fields.append(dict(rows=m, ids=None if pooled else ids[j]))
+        _dev_check(ids, *keep)
+        desc = make_ffm_fields(fields, ids.device)
+    else:
+        if dim is None or batch is None:
+            raise ValueError("%s: desc needs dim and batch" % op)
+        B = int(batch)
+    return F, int(dim), B, desc, keep
+
+
 def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None, reduce_sum=False, out=None, out_offset=0,
         status=None, route=None, desc=None, batch=None):
     """ONN's field-aware lookup + pair products (reference models/onn.py:59-99), one launch: ids [F, B] (int32 / int64; row j unused
@@ -1278,41 +1318,7 @@ def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None
     copied behind them.  ``out``: a float32 2-D view with unit column stride and a row stride that is a multiple of 4, written from
     column ``out_offset``; other columns are not touched.  ``route='direct'`` forces the direct route.  ``desc``: a descriptor tensor
     from make_ffm_fields (then ``ids`` / ``masters`` are not looked at; ``dim`` and ``batch`` are required)."""
-    F = len(masters)
-    if F < 2:
-        raise ValueError("ffm: %d field(s): a field pair needs at least 2" % F)
-    keep = []
-    if desc is None:
-        B = int(ids.shape[1]) if batch is None else int(batch)
-        if ids.dim() != 2 or ids.shape[0] != F or ids.dtype not in (torch.int32, torch.int64):
-            raise ValueError("ffm: ids must be an int32 / int64 [%d, B] matrix" % F)
-        fields = []
-        for j, m in enumerate(masters):
-            pooled = isinstance(m, tuple)
-            m = m[0] if pooled else m
-            if m.dtype != torch.float32:
-                raise TypeError("ffm: tables must be float32, got %s" % m.dtype)
-            if m.dim() == 3:
-                if dim is None:
-                    dim = int(m.shape[2])
-                if m.shape[1] != F - 1 or m.shape[2] != dim or not m.is_contiguous():
-                    raise ValueError("ffm: field %d: expected a contiguous [V, %d, %d] table, got %s" % (j, F - 1, dim, tuple(m.shape)))
-                m = m.view(m.shape[0], -1)
-            if dim is None:
-                raise ValueError("ffm: dim is required with 2-D tables")
-            if m.dim() != 2 or m.stride(1) != 1 or m.shape[1] < (F - 1) * dim:
-                raise ValueError("ffm: field %d: expected [rows, >= %d] with unit column stride" % (j, (F - 1) * dim))
-            if pooled and m.shape[0] < B:
-                raise ValueError("ffm: pre-pooled field %d holds %d rows for a batch of %d" % (j, m.shape[0], B))
-            keep.append(m)
-            fields.append(dict(rows=m, ids=None if pooled else ids[j]))
-        _dev_check(ids, *keep)
-        desc = make_ffm_fields(fields, ids.device)
-    else:
-        if dim is None or batch is None:
-            raise ValueError("ffm: desc needs dim and batch")
-        B = int(batch)
-    dim = int(dim)
+    F, dim, B, desc, keep = _ffm_operands("ffm", ids, masters, dim, desc, batch)
     P = F * (F - 1) // 2
     W = P if reduce_sum else P * dim
     if dense is not None:
@@ -1342,6 +1348,161 @@ def ffm(ids, masters, dim=None, scale=None, shift=None, dense=None, n_dense=None
     _C.check(_C.lib().dctr_ffm_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_ffm_fwd")
     del keep
     return out
+
+
+_FFM_ROUTE_NAMES = {_C.ffm.ROUTE_LDS: "lds", _C.ffm.ROUTE_DIRECT: "direct"}
+
+
+def _ffm_bwd_args(batch, fields, dim, reduce_sum=False, route=None, d_out_stride=None, d_out_offset=0, max_blocks=0):
+    F, d = int(fields), int(dim)
+    P = F * (F - 1) // 2
+    if d_out_stride is None:
+        d_out_stride = int(d_out_offset) + (P if reduce_sum else P * d)
+    b = _C.ffm.BwdArgs(d_out_stride=int(d_out_stride), d_out_offset=int(d_out_offset), max_blocks=int(max_blocks))
+    b.fwd = _ffm_args(batch, F, d, reduce_sum, route=route)
+    return b
+
+
+def ffm_bwd_workspace_bytes(batch, fields, dim, reduce_sum=False, route=None):
+    """Bytes of workspace dctr_ffm_bwd needs for these shapes (read from the library: 0, both routes keep their state on chip)."""
+    return int(_C.lib().dctr_ffm_bwd_workspace_bytes(ctypes.byref(_ffm_bwd_args(batch, fields, dim, reduce_sum, route))))
+
+
+def ffm_bwd_route(batch, fields, dim, reduce_sum=False, route=None):
+    """'lds' or 'direct': the route dctr_ffm_bwd takes for these shapes (the library's answer, dctr_ffm_bwd_route)."""
+    b = _ffm_bwd_args(batch, fields, dim, reduce_sum, route)
+    return _route_name("dctr_ffm_bwd_route", _C.lib().dctr_ffm_bwd_route(ctypes.byref(b)), _FFM_ROUTE_NAMES)
+
+
+def make_ffm_grads(grads, device):
+    """grads: per field a float32 2-D view with unit column stride (a table's dense gradient, a pre-pooled field's d_rows), or None for
+    a field that gets no gradient -> uint8 device tensor holding the dctr_ffm_grad_t array (kept alive by the caller)."""
+    arr = (_C.ffm.Grad * max(1, len(grads)))()
+    for j, g in enumerate(grads):
+        if g is not None:
+            arr[j].grad = g.data_ptr()
+            arr[j].row_stride = row_stride(g)
+    return _upload(arr, device)
+
+
+def ffm_bwd(ids, masters, d_out, grads, dim=None, reduce_sum=False, d_out_offset=0, status=None, route=None, max_blocks=0, desc=None,
+            batch=None):
+    """Backward of ffm()'s pair products, one launch (include/dctr.h: dctr_ffm_bwd); the forward saves nothing.  ``ids`` / ``masters`` /
+    ``dim`` / ``reduce_sum`` / ``route`` / ``desc`` / ``batch`` as ffm() (no scale / shift, no dense columns: their backward stays with
+    the caller).  ``d_out``: a float32 2-D view whose row holds the gradient of the P*d (P) pair columns from column ``d_out_offset``.
+    ``grads``: per field where its gradient goes — a table field: the dense gradient [V_j, F-1, d] (or a [V_j, >= (F-1)*d] view),
+    ACCUMULATED into with float atomics (zero it first; last bits may differ from call to call); a pre-pooled field: d_rows
+    [>= B, >= (F-1)*d], whose first (F-1)*d columns are written (bit-identical from call to call, the others untouched); None: a frozen
+    field, skipped.  An id out of range raises ``status``, gets no gradient and gives its partners zeros."""
+    F, dim, B, desc, keep = _ffm_operands("ffm_bwd", ids, masters, dim, desc, batch)
+    R = (F - 1) * dim
+    W = F * (F - 1) // 2 * (1 if reduce_sum else dim)
+    d_out_stride = _rows2d("ffm_bwd", "d_out", d_out, B, W, d_out_offset, at_least_rows=True)
+    if len(grads) != F:
+        raise ValueError("ffm_bwd: grads must hold one entry (a tensor or None) per field, got %d for %d fields" % (len(grads), F))
+    gs = []
+    for j, g in enumerate(grads):
+        if g is None:
+            gs.append(None)
+            continue
+        pooled = isinstance(masters[j], tuple)
+        if g.dim() == 3 and g.is_contiguous() and tuple(g.shape[1:]) == (F - 1, dim):
+            g = g.view(g.shape[0], R)
+        rows = B if pooled else (keep[j].shape[0] if keep else g.shape[0] if g.dim() == 2 else 0)
+        _rows2d("ffm_bwd", "grads[%d]" % j, g, rows, R, at_least_rows=pooled)
+        gs.append(g)
+    _dev_check(desc, d_out, status, *gs)
+    gdesc = make_ffm_grads(gs, desc.device)
+    b = _ffm_bwd_args(B, F, dim, reduce_sum, route, d_out_stride, d_out_offset, max_blocks)
+    b.fwd.fields, b.d_out, b.grads = desc.data_ptr(), d_out.data_ptr(), gdesc.data_ptr()
+    if status is not None:
+        b.fwd.status = status.data_ptr()
+    _C.check(_C.lib().dctr_ffm_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_ffm_bwd")
+    del keep
+
+
+class FieldAwareFunction(torch.autograd.Function):
+    """ONN's field-aware lookup + pair products as one differentiable op: ffm() forward and ffm_bwd() backward, one launch each.
+    ``apply(ids, masters, dim, reduce_sum, status, *inputs)``: ids [F, B]; ``masters`` per field the fused table [V_j, F-1, d], or None for
+    a field that arrives pooled; ``inputs`` in field order — a table field's F-1 per-name views ``master[:, k, :]`` (``inputs_of`` checks
+    that they are), a pooled field's [B, (F-1)*d] rows.  Returns the pair columns [B, P*d] ([B, P] with reduce_sum).  The backward zeroes
+    one [V_j, F-1, d] gradient per field that wants one and hands each view its slot ``grad[:, k, :]``, a pooled field its d_rows; table
+    gradients leave the kernel through float atomics and may differ in the last bits from call to call."""
+
+    @staticmethod
+    def inputs_of(masters, views):
+        """The gate: ``views[j]`` = field j's F-1 per-name tensors in slot order (``masters[j]`` its fused table), or its pooled
+        [B, (F-1)*d] rows (``masters[j]`` None; a callable is called for them once every table view has passed).  Returns ``inputs``
+        for apply(), or None when a view is not the slot of its table (pointer, strides, shape) — the op reads the tables, so anything
+        else must stay on the torch ops."""
+        F = len(masters)
+        flat = []
+        for m, vs in zip(masters, views):
+            if m is None:
+                flat.append(vs)
+                continue
+            if not m.is_cuda:
+                return None
+            if m.dim() != 3 or m.shape[1] != F - 1 or not m.is_contiguous() or m.dtype != torch.float32 or len(vs) != F - 1:
+                return None
+            V, _, d = m.shape
+            base = m.data_ptr()
+            for k, v in enumerate(vs):
+                if (v.data_ptr() != base + k * d * 4 or tuple(v.shape) != (V, d) or v.dtype != torch.float32 or v.device != m.device
+                        or (V > 1 and v.stride(0) != (F - 1) * d) or (d > 1 and v.stride(1) != 1)):
+                    return None
+            flat.extend(vs)
+        return [v() if callable(v) else v for v in flat]
+
+    @staticmethod
+    def forward(ctx, ids, masters, dim, reduce_sum, status, *inputs):
+        ctx.set_materialize_grads(False)
+        F = len(masters)
+        ms, at = [], 0
+        for m in masters:
+            if m is None:
+                ms.append((_f32c(inputs[at].detach(), "pooled rows"),))
+                at += 1
+            else:
+                ms.append(m.detach())
+                at += F - 1
+        ctx.dim, ctx.reduce_sum, ctx.status = int(dim), bool(reduce_sum), status
+        ctx.pooled = [m is None for m in masters]
+        out = ffm(ids, ms, dim=dim, reduce_sum=reduce_sum, status=status)
+        ctx.save_for_backward(ids, *[m[0] if isinstance(m, tuple) else m for m in ms])
+        return out[:, :F * (F - 1) // 2 * (1 if reduce_sum else int(dim))]
+
+    @staticmethod
+    def backward(ctx, d_out):
+        saved = list(ctx.saved_tensors)
+        ids, rows = saved[0], saved[1:]
+        F, R = len(rows), (len(rows) - 1) * ctx.dim
+        needs = ctx.needs_input_grad[5:]
+        none = (None,) * (5 + len(needs))
+        if d_out is None:
+            return none
+        wanted, at = [], 0
+        for pooled in ctx.pooled:
+            n = 1 if pooled else F - 1
+            wanted.append(any(needs[at:at + n]))
+            at += n
+        if not any(wanted):
+            return none
+        d_out = _grad_operand(d_out, True)
+        _, tables = _zeroed_grads([None if p or not w else r for p, w, r in zip(ctx.pooled, wanted, rows)], wanted, ids.device)
+        grads = [torch.empty(ids.shape[1], R, dtype=torch.float32, device=ids.device) if p and w else t
+                 for p, w, t in zip(ctx.pooled, wanted, tables)]
+        ffm_bwd(ids, [(r,) if p else r for p, r in zip(ctx.pooled, rows)], d_out, grads, dim=ctx.dim, reduce_sum=ctx.reduce_sum,
+                status=ctx.status)
+        ret, at = [None] * 5, 0
+        for p, g in zip(ctx.pooled, grads):
+            if p:
+                ret.append(g if needs[at] else None)
+                at += 1
+            else:
+                ret.extend(g[:, k, :] if g is not None and needs[at + k] else None for k in range(F - 1))
+                at += F - 1
+        return tuple(ret)
 
 
 _IFM_ROUTES = {None: _C.ifm.ROUTE_AUTO, "auto": _C.ifm.ROUTE_AUTO, "workspace": _C.ifm.ROUTE_WORKSPACE}

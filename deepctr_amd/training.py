@@ -358,6 +358,25 @@ def fwfm_logit(layer, x):
     return (gram * torch.triu(r, diagonal=1)).sum((1, 2))
 
 
+# ONN's pair products have no row threshold: at the Criteo shape the autograd step with ops.FieldAwareFunction took 0.25x (d = 4) and
+# 0.27x (d = 16) of the torch ops' time at 4,096 rows and 0.20x / 0.32x at 65,536, and with half of every column on one id 0.03x down to
+# 0.004x (profiles/onn_ffm_bwd.txt).  The name stays so that a measurement at another shape has somewhere to put its answer.
+ONN_HIP_MIN_ROWS = 0
+
+
+def _ffm_on_hip(masters, views, rows, min_rows=0):
+    """The gate of ONN's pair products inside the autograd step (models/onn.py).  ``masters`` per field the fused table [V_j, F-1, d] or
+    None for a sequence field, ``views`` per field its F-1 per-name weights (or a callable giving a sequence field's pooled rows).  On
+    the GPU, with gradients enabled, HIP_AUTOGRAD_OPS on, float32 tables, at least ``min_rows`` rows and every view the slot of its
+    table, returns the inputs of ops.FieldAwareFunction — dctr_ffm_fwd forward and dctr_ffm_bwd backward, one launch each in place of
+    F(F-1) gathers and index-put backwards (profiles/onn_ffm_bwd.txt) — else None: the torch ops."""
+    tables = [m for m in masters if m is not None]
+    if not (tables and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and rows >= min_rows
+            and all(m.is_cuda and m.dtype == torch.float32 for m in tables)):
+        return None
+    return ops.FieldAwareFunction.inputs_of(masters, views)
+
+
 def senet_bilinear(model, xcat):
     """FiBiNET's DNN input inside the autograd step.  ``model`` carries ``senet``, ``senet_bilinear``, ``bilinear`` (the three layers),
     ``n_fields``, ``emb_dim`` and ``bilinear_type``; ``xcat`` [B, F*E + D] is the torch.cat of the F embedding parts and the dense

@@ -662,6 +662,45 @@ size_t dctr_ffm_workspace_bytes(const dctr_ffm_args_t* args);
 int dctr_ffm_route(const dctr_ffm_args_t* args);
 int dctr_ffm_fwd(const dctr_ffm_args_t* args, void* stream);
 
+/* Backward of dctr_ffm_fwd's pair products, one launch; the forward saves nothing (the kernel loads the ids and the rows again: they
+ * are unchanged until the optimizer runs).  fwd: fields, batch, n_fields, dim, reduce_sum, status and route are read as the forward
+ * reads them; scale / shift must be NULL and n_dense 0 (in training BatchNormalization uses batch statistics: it and the dense concat
+ * stay with the caller), out / out_stride / out_offset / dense are ignored.  With g = d_out row b (P*d floats, P with reduce_sum,
+ * from column d_out_offset of a row of d_out_stride floats), for every pair p = (i, j), i < j:
+ *     d row_i[slot of j][e] += g[p*d + e] * row_j[slot of i][e]        d row_j[slot of i][e] += g[p*d + e] * row_i[slot of j][e]
+ *     (reduce_sum: g[p] in place of g[p*d + e])
+ * Where the gradient of field f goes is grads[f]:
+ *   a table field: ACCUMULATED into the dense gradient table [vocab_f, row_stride] (zero it first) at the row of the sample's id, with
+ *     float atomics — one (sample, field) row is one contiguous run of (F-1)*d floats, one dword per lane — so it may differ in the last
+ *     bits from call to call;
+ *   a pre-pooled (identity) field: plain stores into the first (F-1)*d floats of row b of a [batch, row_stride] buffer, one owner per
+ *     element: bit-identical from call to call, columns behind (F-1)*d untouched;
+ *   grad = NULL (a frozen field): skipped, nothing of it is touched.
+ * An id outside [0, vocab) raises DCTR_STATUS_INDEX_OOR, receives no gradient and enters its partners' gradients as a row of zeros,
+ * exactly as the forward treats it; nothing outside the tables is read or written.
+ * Routes as the forward: tiles of samples gathered whole into LDS, or — rows beyond the LDS, or fwd.route = DCTR_FFM_ROUTE_DIRECT —
+ * the partner rows read from global memory.  Same arithmetic on both.  No shape the forward takes is refused and neither route needs a
+ * workspace (dctr_ffm_bwd_workspace_bytes() = 0; the two members are reserved).  Argument errors launch and write nothing. */
+typedef struct {
+    float* grad;                  /* table field: [vocab, row_stride], ACCUMULATED into; identity field: [batch, row_stride], written; NULL: skipped */
+    int64_t row_stride;           /* floats between rows, >= (F-1)*d */
+} dctr_ffm_grad_t;
+typedef struct {
+    dctr_ffm_args_t fwd;
+    const float* d_out;           /* row b at d_out + b * d_out_stride + d_out_offset: P*d (or P) floats */
+    int64_t d_out_stride;         /* >= d_out_offset + width */
+    int64_t d_out_offset;         /* >= 0 */
+    const dctr_ffm_grad_t* grads; /* DEVICE array [n_fields], in field order */
+    int32_t max_blocks;           /* 0: the library's choice; > 0 caps the grid (one workgroup then walks every tile) */
+    int32_t reserved;             /* 0 */
+    void* workspace;              /* reserved: NULL, or 16-B aligned */
+    size_t workspace_bytes;
+} dctr_ffm_bwd_args_t;
+size_t dctr_ffm_bwd_workspace_bytes(const dctr_ffm_bwd_args_t* args);   /* host only: 0 */
+/* The route dctr_ffm_bwd takes (DCTR_FFM_ROUTE_LDS / DCTR_FFM_ROUTE_DIRECT), or the DCTR_E_* of its size checks; no pointer is read. */
+int dctr_ffm_bwd_route(const dctr_ffm_bwd_args_t* args);
+int dctr_ffm_bwd(const dctr_ffm_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * IFM / DIFM: the input-aware factor, the refined FM and linear terms, the prediction — deepctr/models/ifm.py:55-72, difm.py:59-80
  *     F >= 1 fields of one embedding_dim d, read in place from the leading F*d columns of x (e.g. dnn_in) at x_stride.  Per sample b:
