@@ -38,6 +38,22 @@
 // activation, a head, optional BatchNormalization scale / shift (inference form), no saved activations, and at least 64 rows
 // per CU (or tile_rows 128 / 256).  Everything else takes stream_kernel / mlp_kernel.
 // Same arithmetic as those: v_mfma_f32_16x16x4_f32 = exact fp32; only the summation order over k differs.
+//
+// Vector-instruction budget.  fp32 MFMAs and vector-ALU instructions exclude each other on a SIMD, so what a pass
+// carries beside its 4,736 MFMAs per wave is counted (tests/test_chain_valu_budget.py, on the assembly of the benchmark's
+// instantiation <2, 8, 1, false, 4, 2, 1, true>, between the phase markers of chain_kernel).  Static vector instructions / of them
+// v_max_f32 / v_readlane + v_writelane:   main phase 2353 / 449 / 429 -> 1214 / 224 / 0,   tail phase 2042 / 225 / 511 -> 889 / 112 / 0;
+// scalar registers parked in VGPR lanes 316 -> 0; executed vector instructions per MFMA (SQ_INSTS_VALU less SQ_INSTS_MFMA, over
+// SQ_INSTS_MFMA) 0.50 -> 0.38 at K = 256 and 0.69 -> 0.50 at K = 20.  What went:
+//   * ReLU was two v_max_f32 per value (act_block);
+//   * the weight chunks' address pairs, the chunk-kind comparisons and ~30 launch parameters a pass reads once were held in scalar
+//     registers across the pass loop, more than there are: hipcc parked them in VGPR lanes and fetched them back in every step
+//     (dma_l0 / dma_ln / dma_chunk: opaque bases and comparisons; cold(): once-per-pass parameters re-read from the kernel arguments);
+//   * the DMA lane offsets were rebuilt from an opaque lane copy in every step (KEEP_DMA);
+//   * the biases lay in LDS in feature order and every accumulator set was transposed into place with register moves (bias_slot);
+//   * wave-uniform predicates kept as lane masks were negated through v_cndmask / v_cmp pairs (dma_half, consume_x's in_fm).
+// What is left beside the MFMAs is the layer-0 request work (~100 vector instructions per field pair: ids, range checks, row and
+// linear-entry addresses, FM sums), one v_max_f32 per activated value, the head's 64 fmas.
 #pragma once
 #include "mlp_device.h"
 
@@ -204,13 +220,21 @@ __device__ __forceinline__ void act_block(int act, f32x4 (&acc)[NM][RT]) {
             }
         return;
     }
-    const float floor_ = act == DCTR_ACT_RELU ? 0.f : -__builtin_inff();
+    // ReLU is ONE v_max_f32 per value against the inline constant 0, a linear DNN branches around the block (wave-uniform).  As
+    // fmaxf(acc, floor) with a run-time floor it was two: hipcc cannot see that an MFMA result is canonical and puts v_max_f32 t, x, x
+    // in front of the v_max_f32 proper, with the floor in a VGPR.  Same bits: the kernel runs with fp32 denormals on (denormals pass
+    // through either form), max(-0, +0) = +0 in hardware, a quiet NaN gives 0 (an MFMA never hands out a signalling one)
+    if (act != DCTR_ACT_RELU) return;
 #pragma unroll
     for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int nt = 0; nt < RT; ++nt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][nt][r] = fmaxf(acc[m][nt][r], floor_);
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[m][nt][r];
+                asm volatile("v_max_f32 %0, 0, %0" : "+v"(v));      // (volatile: stays behind mfma_drain())
+                acc[m][nt][r] = v;
+            }
 }
 
 // BatchNormalization (inference form) of a whole accumulator set in place, between bias_add and the activation (reference
@@ -256,6 +280,11 @@ struct ChainOff {
     static constexpr int END = BN_T + 64 * (M0 + M1 + M2);
 };
 
+// Where bias i of a layer lies in LDS: in ACCUMULATOR order.  Register r of M-tile mt of M-group mg holds feature 64 mg + 16 g + 4 r + mt
+// (lane group g); with the (r, mt) digits swapped, the quad of an M-tile is four consecutive floats — one ds_read_b128 initialises an
+// accumulator.  In feature order every pass transposed 4 x 4 blocks with register moves: ~230 v_mov per pass and wave
+__device__ __forceinline__ constexpr int bias_slot(int i) { return (i & ~15) | ((i & 3) << 2) | ((i >> 2) & 3); }
+
 // The passes [first, first + stride, ...) < n_pass of one phase: pass q covers rows row_base + q * (16 RT NW) ... of the launch
 // (absolute row numbers; rows >= row_end do not exist).  Called by all NW waves of the phase, with the launch parameters in LDS.
 // FPB > 1 (embedding_dim 16 / FPB = 8 or 4, the reference's default is 4): SEVERAL fields share a 16-wide k-block — lane group g
@@ -275,7 +304,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
     typedef XBlkT<RT> XBlk;
     constexpr int S1 = M0 * M1, S2 = M1 * M2;      // chunks (= steps) of layers 1 and 2
     constexpr int SL = S1 + S2;
-    static_assert(SL >= 2, "the next pass's gather prologue needs two steps behind layer 0");
+    static_assert(SL >= 2 && S1 >= 2, "the next pass's gather prologue needs two steps behind layer 0; the last two layer-0 steps ask for layer 1's first chunks");
     static_assert(FPB == 1 || (EB == 1 && (FPB == 2 || FPB == 4) && !CROSS), "several fields per k-block: E = 8 / 4, plain fp32 kernels");
     static_assert(!REC || (EB == 1 && FPB == 1 && !CROSS && !EXPACT), "record-form tables: embedding_dim 16, plain fp32 kernels");
     static_assert(!POOL || (EB == 1 && FPB == 1 && !CROSS && !EXPACT && !REC && M0 == 4), "in-pass sequence pooling: embedding_dim 16, plain fp32 kernels, units[0] = 256");
@@ -297,6 +326,17 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         asm volatile("" : "+v"(ln));
         return ln;
     };
+    // COLD launch parameters — what a pass touches once, outside its step loops: the output and logit pointers, add[], the dense matrix,
+    // the BatchNormalization and activation switches — are re-read from the kernel-argument segment (ChainParams is chain_kernel's only
+    // argument: offset 0) with scalar loads where they are used.  Read through `p` they are loaded at the kernel's start and held across
+    // the pass loop: ~30 scalar registers more than the allocator has, which it made up for by parking the step loops' own scalars in
+    // lanes of a VGPR (v_readlane_b32 beside the MFMAs).  The pointer is opaque, or the loads would be hoisted back to the start
+    typedef const __attribute__((address_space(4))) ChainParams* cold_t;
+    auto cold = [&]() -> cold_t {
+        uint64_t a = reinterpret_cast<uint64_t>(__builtin_amdgcn_kernarg_segment_ptr());
+        asm volatile("" : "+s"(a));
+        return reinterpret_cast<cold_t>(a);
+    };
 
     const int NBE = FPB > 1 ? (p.n_fields + FPB - 1) / FPB : p.n_fields * EB;         // embedding k-blocks
     const int NB = FPB > 1 ? NBE + ((p.n_dense + 15) >> 4) : (p.in_dim + 15) >> 4;     // k-blocks of the DNN input (= steps of layer 0)
@@ -306,8 +346,12 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
     const int NSF = POOL ? p.n_fields - p.n_pool : p.n_fields;
     const int NBS = POOL ? NSF * EB : NBE;
     const int emb_rows = p.n_fields * E;           // rows of W0 the embedding part takes (FPB > 1: not necessarily whole k-blocks)
-    const int STEPS = NB + SL;
     const int k_last = p.in_dim - 1;
+    auto has_dense = [&]() -> bool {                  // (decided where it is asked: see dma_chunk)
+        int n = NDB;
+        asm volatile("" : "+s"(n));
+        return n > 0;
+    };
     float* dreg = smem + DENSE_OFF + (WROWS * wave) * (16 * NDB);     // this wave's rows of the dense staging area
     // Layer 1 starts with 128 + 64 accumulator registers live (all of layer 0's outputs, its own) and uses layer 0's M-groups
     // one after the other: the LAST M-group of layer 0 waits in LDS until the first ones are dead (8 x 1 KiB per wave, written
@@ -319,26 +363,46 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
     auto dlacc_ptr = [&]() -> float* { return smem + DENSE_OFF + PROWS * 16 * NDB + wave * (RT * 64) + opaque_lane(); };   // [nt * 64]
 
     // ---- weight chunks.  Chunk ci of a pass: ci < NB: rows 16*ci .. + 15 of W0 (all 64*M0 columns); then the 64 x 64
-    // sub-blocks (mg, mg1) of W1, mg-major; then those of W2; ci >= STEPS wraps to the next pass.  A chunk image is
+    // sub-blocks (mg, mg1) of W1, mg-major; then those of W2; a chunk past the last wraps to the next pass.  A chunk image is
     // 16 pieces of 1 KiB (fewer for M0 < 4); wave w moves pieces w, w + 8: lane l's 16 bytes land at piece + 16 l.
     // The DMA instruction is issued through inline asm on purpose: hipcc orders every later ds_read behind an LDS-DMA it
     // can see with s_waitcnt vmcnt(0) (it cannot prove the chunk being filled is not the chunk being read), which would
     // stall each step on the loads it has just requested.  Unseen, the DMA only makes hipcc's own vmcnt bookkeeping for
     // the register loads conservative (more operations in the queue than it counts: it can over-wait, never under-wait).
-    // Addresses are a scalar base + one per-lane 32-bit offset (the lane index is made opaque per call: otherwise the
-    // offsets of all ten layer >= 1 chunks are hoisted out of the persistent loop — live VGPRs across the pass, i.e. spills)
+    // Addresses are a scalar base + one per-lane 32-bit offset: three offsets in all (layer 0, one per row pitch of layers 1 / 2),
+    // persistent where the instantiation has the registers (KEEP_DMA below), else rebuilt per call from an opaque lane copy
     auto dma16 = [&](const void* sbase, uint32_t voff, float* dst) {
         const uint32_t lds_addr = (uint32_t)(size_t)(lds_ptr_t)dst;
         asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
     };
-    auto dma_l0 = [&](int b, float* dst) {
-        constexpr int ROW_B = 256 * M0;
+    // The lane's byte inside piece `wave` of a chunk image (o) and its offsets into a weight matrix of layer 1 / 2 (one per row pitch) are
+    // PERSISTENT where the instantiation has the registers (KEEP_DMA; as issue_x1's KEEP_LC below): three registers against the five to six
+    // vector instructions per step that rebuilt them from an opaque lane copy.  The SCALAR bases go the other way: a weight pointer is
+    // made opaque where a step uses it, so that the step derives its pieces' addresses with scalar adds.  Visible as invariants of
+    // the pass loop, hipcc computed the address pair of every piece of every layer >= 1 chunk ahead of the loop (40 scalars in the main
+    // phase, 80 in the tail), ran out of scalar registers, parked them in lanes of a VGPR and fetched them back with v_readlane_b32 in
+    // every step: 4 per step and wave in the main phase, 8 in the tail (fp32 MFMAs and vector instructions share the SIMD's issue slots)
+    constexpr bool KEEP_DMA = !CROSS && !POOL;
+    const uint32_t dma_o_ = (uint32_t)(1024 * wave + 16 * lane);
+    const uint32_t dma_voff1_ = (dma_o_ >> 8) * (uint32_t)(64 * M1 * 4) + (dma_o_ & 255u);
+    const uint32_t dma_voff2_ = (dma_o_ >> 8) * (uint32_t)(64 * (M2 > 0 ? M2 : M1) * 4) + (dma_o_ & 255u);
+    auto dma_o = [&]() -> uint32_t {
+        if constexpr (KEEP_DMA) return dma_o_;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const uint32_t o = (uint32_t)(1024 * wave + 16 * ln);                  // this lane's byte inside piece `wave`
+        return (uint32_t)(1024 * wave + 16 * ln);
+    };
+    auto opaque_base = [&](const float* W) -> const char* {
+        uint64_t b = reinterpret_cast<uint64_t>(W);
+        asm volatile("" : "+s"(b));
+        return reinterpret_cast<const char*>(b);
+    };
+    auto dma_l0 = [&](int b, float* dst) {
+        constexpr int ROW_B = 256 * M0;
+        const uint32_t o = dma_o();                                            // this lane's byte inside piece `wave`
         const int row0 = (FPB > 1 && b >= NBE) ? emb_rows + 16 * (b - NBE) : 16 * b;     // first W0 row of the block
         if (row0 + 16 <= p.in_dim) {                                           // a whole block: 16 KiB (M0 = 4) as they lie
-            const char* base = reinterpret_cast<const char*>(p.W[0]) + (size_t)row0 * ROW_B;
+            const char* base = opaque_base(p.W[0]) + (size_t)row0 * ROW_B;
 #pragma unroll
             for (int pc0 = 0; pc0 < 4 * M0; pc0 += NW)
                 if (pc0 + wave < 4 * M0) dma16(base + pc0 * 1024, o, dst + (pc0 + wave) * 256);
@@ -352,27 +416,39 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                 }
         }
     };
-    auto dma_ln = [&](const float* W, int N, int mg, int mg1, float* dst) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const uint32_t o = (uint32_t)(1024 * wave + 16 * ln);
-        const uint32_t voff = (o >> 8) * (uint32_t)(N * 4) + (o & 255u);       // image row o / 256 <-> weight row, 256 B of it
-        const char* base = reinterpret_cast<const char*>(W) + ((size_t)(64 * mg) * N + 64 * mg1) * 4;   // scalar
+    auto dma_ln = [&](const float* W, int L, int N, int mg, int mg1, float* dst) {
+        uint32_t voff;                                                         // image row o / 256 <-> weight row, 256 B of it
+        if constexpr (KEEP_DMA) {
+            voff = L == 1 ? dma_voff1_ : dma_voff2_;
+        } else {
+            const uint32_t o = dma_o();
+            voff = (o >> 8) * (uint32_t)(N * 4) + (o & 255u);
+        }
+        const char* base = opaque_base(W) + ((size_t)(64 * mg) * N + 64 * mg1) * 4;   // scalar
 #pragma unroll
         for (int pc0 = 0; pc0 < 16; pc0 += NW) dma16(base + (size_t)(4 * pc0) * N * 4, voff, dst + (pc0 + wave) * 256);
     };
-    auto dma_chunk = [&](int ci, float* dst) {
-        if (ci >= STEPS) ci -= STEPS;
-        if (ci < NB) {
+    // which chunk a step asks for is decided where it asks, on opaque scalar copies of NB: as invariants of the pass loop the outcomes
+    // of these comparisons were kept as lane masks, parked like the bases above and fetched back in every step that used them
+    auto dma_chunk = [&](int ci, float* dst) {         // (a layer-0 step: ci = its k-block + 2 <= NB + 1, never wraps)
+        int nb = NB;
+        asm volatile("" : "+s"(nb));
+        if (ci < nb) {
             dma_l0(ci, dst);
         } else {
-            int c = ci - NB;
-            if (c < S1) {
-                dma_ln(p.W[1], 64 * M1, c / M1, c % M1, dst);
-            } else if constexpr (M2 > 0) {
-                c -= S1;
-                dma_ln(p.W[2], 64 * M2, c / M2, c % M2, dst);
-            }
+            const int c = ci - nb;                     // 0 or 1: S1 >= 2
+            dma_ln(p.W[1], 1, 64 * M1, c / M1, c % M1, dst);
+        }
+    };
+    // the chunk two steps behind step sidx of layers >= 1 (sidx is a compile-time number once the layer loops are unrolled)
+    auto dma_chunk_n = [&](int sidx, float* dst) {
+        const int c = sidx + 2;
+        if (c < S1) {
+            dma_ln(p.W[1], 1, 64 * M1, c / M1, c % M1, dst);
+        } else if (c < SL) {
+            if constexpr (M2 > 0) dma_ln(p.W[2], 2, 64 * M2, (c - S1) / M2, (c - S1) % M2, dst);
+        } else {
+            dma_chunk(c - SL, dst);                    // wraps into the next pass: chunk 0 or 1
         }
     };
 
@@ -435,7 +511,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         const uint2 l = *reinterpret_cast<const uint2*>(fdesc + 12 * fi + 2);          // (per lane: its field's linear table)
         const uint64_t base = ((uint64_t)l.y << 32) | l.x;
         has = base != 0 && 2 * pr + q < NSF;
-        const float* t = has ? reinterpret_cast<const float*>(base) : reinterpret_cast<const float*>(p.fields);
+        const float* t = has ? reinterpret_cast<const float*>(base) : p.W[0];      // (any readable float: the entry is not used)
         return (gbl_f_t)(t + (has ? (REC ? idc << 5 : idc) : 0u));            // (REC: linear entries lie 32 floats apart, as the rows)
     };
     // issue the row loads of embedding k-block cb: its ids are half `half` of the folded pair ids `idc`
@@ -506,16 +582,16 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
     // k-blocks of layer 0 read their B operand from there, so the hot loop has ONE kind of global load.  Lane (g, j) moves
     // columns 4g .. 4g + 3 of dense k-block c for its two rows; the lane's share of dense . dense_lin_w comes out on the way
     auto dense_request = [&](int c, int pass, float (&td)[RT][4]) {
-        const int d0 = 16 * c + 4 * g;
+        const int d0 = 16 * c + 4 * g, n_dense = cold()->n_dense;
 #pragma unroll
         for (int nt = 0; nt < RT; ++nt) {
-            gbl_f_t src = (gbl_f_t)(p.dense + (int64_t)brow_of(pass, nt) * p.dense_stride);
+            gbl_f_t src = (gbl_f_t)(cold()->dense + (int64_t)brow_of(pass, nt) * cold()->dense_stride);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) td[nt][e] = src[min(d0 + e, p.n_dense - 1)];
+            for (int e = 0; e < 4; ++e) td[nt][e] = src[min(d0 + e, n_dense - 1)];
         }
     };
     auto dense_store = [&](int c, const float (&td)[RT][4]) {
-        const int d0 = 16 * c + 4 * g;
+        const int d0 = 16 * c + 4 * g, n_dense = cold()->n_dense;
         float* dlacc = dlacc_ptr();
 #pragma unroll
         for (int nt = 0; nt < RT; ++nt) {
@@ -523,7 +599,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             float dl = c == 0 ? 0.f : dlacc[nt * 64];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                v[e] = d0 + e < p.n_dense ? td[nt][e] : 0.f;
+                v[e] = d0 + e < n_dense ? td[nt][e] : 0.f;
                 dl = fmaf(v[e], dlw[min(d0 + e, 255)], dl);
             }
             *reinterpret_cast<f32x4*>(dreg + (16 * nt + j) * (16 * NDB) + d0) = v;
@@ -616,7 +692,14 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
     // sits behind micro-step 0 for waves 0-3 and behind micro-step CHAIN_DMA_LATE for waves 4-7, so that the CU's vector-
     // memory address path does not get all eight waves' requests in one burst (it has no register results, so placing it
     // twice costs nothing; the gather part placed twice merges in-flight registers of the two placements and spills).
-    const bool dma_early = wave < NW / 2;
+    // (which half the wave is in: an opaque 0 / 1 in a scalar register, tested with s_cmp where it is used.  As a bool hipcc kept it
+    // as a lane mask and rebuilt its negation with a v_cndmask / v_cmp pair at the end of every step)
+    const int dma_half_ = __builtin_amdgcn_readfirstlane(wave < NW / 2 ? 0 : 1);
+    auto dma_half = [&]() -> int {                    // (opaque at every use: the comparison is an invariant too, and would be hoisted)
+        int h = dma_half_;
+        asm volatile("" : "+s"(h));
+        return h;
+    };
     constexpr int DMA_LATE0 = CHAIN_DMA_LATE < 4 * M0 ? CHAIN_DMA_LATE : 2 * M0;     // layer 0 has 4 M0 micro-steps per step (even index)
     static_assert(DMA_LATE0 % 2 == 0 && DMA_LATE0 < 4 * M0 && CHAIN_DMA_LATE % 2 == 0 && CHAIN_DMA_LATE < 16, "late DMA slot outside the step");
     for (int it = 0, pass = first; pass < n_pass; ++it, pass += stride) {
@@ -625,19 +708,17 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         const int pass_n = min(pass + stride, n_pass - 1);               // rows the gather prologue at the pass's end is for
         // ================= layer 0: acc0[4 mg + mt][nt] = C tile of output features 64 mg + 4 i + mt
         f32x4 acc0[4 * M0][RT];
+        // (the biases lie in LDS in ACCUMULATOR order — bias_slot, chain_kernel: a quad is one ds_read_b128, no register moves)
+        // (each N tile reads for itself, through an offset hipcc cannot see through: it would read once and copy 64 registers)
 #pragma unroll
-        for (int mg = 0; mg < M0; ++mg) {
-            float bv[16];
+        for (int nt = 0; nt < RT; ++nt) {
+            int boff = 16 * g;
+            asm volatile("" : "+v"(boff));
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const float4 t = *reinterpret_cast<const float4*>(cpar + 64 * mg + 16 * g + 4 * qq);
-                bv[4 * qq] = t.x; bv[4 * qq + 1] = t.y; bv[4 * qq + 2] = t.z; bv[4 * qq + 3] = t.w;
-            }
+            for (int mg = 0; mg < M0; ++mg)
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < RT; ++nt)
-                    acc0[4 * mg + mt][nt] = f32x4{bv[mt], bv[4 + mt], bv[8 + mt], bv[12 + mt]};
+                for (int mt = 0; mt < 4; ++mt)
+                    acc0[4 * mg + mt][nt] = *reinterpret_cast<const f32x4*>(cpar + boff + 64 * mg + 4 * mt);
         }
         f32x4 sum[EB][RT];
         float sq[RT];
@@ -863,7 +944,9 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                 return;
             }
             const int f = b / EB, h = b % EB;
-            if ((fm_mask >> f) & 1ull) {
+            int in_fm = (int)((uint32_t)(fm_mask >> f) & 1u);       // (an opaque scalar, tested with s_cmp: see dma_half)
+            asm volatile("" : "+s"(in_fm));
+            if (in_fm) {
 #pragma unroll
                 for (int nt = 0; nt < RT; ++nt) {
 #pragma unroll
@@ -882,7 +965,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         // their range check (s = PAIR - 1).  A dense k-block takes its operand from the staging rows in LDS instead
 #define CHAIN_PHASE0(XC, XN)                                                                                     \
         {                                                                                                        \
-            if (dma_early) dma_chunk(b_ + 2, slot_ptr(2));                                                       \
+            if (dma_half() == 0) dma_chunk(b_ + 2, slot_ptr(2));                                                 \
             {                                                                                  \
                 /* every request is issued unconditionally (past the last field / pair: a clamped, redundant one):   \
                    a conditionally written register keeps its old value alive — through layers 1.. where 192 of the   \
@@ -916,7 +999,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             constexpr int i_ = (I);                                                                              \
             const int prn_ = min(pr_ + 1, (NBS - 1) / PAIR);                                                     \
             if (i_ == 0) {                                                                                       \
-                if (dma_early) dma_chunk(b_ + 2, slot_ptr(2));                                                   \
+                if (dma_half() == 0) dma_chunk(b_ + 2, slot_ptr(2));                                             \
                 if (s_ == 1) linacc += (lvn_has && b_ - 1 < NBS) ? lvn : 0.f;                    \
                 if (s_ == PAIR - 1) idcn = fold_pair_ids(prn_, pass, idr_lo, idr_hi);            \
             }                                                                                                    \
@@ -976,7 +1059,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                     if (u_ == 6) CHAIN_PIECE0(3, XC, XN)                                                         \
                     if (u_ == 4 * M0 - 2 && u_ > 6) CHAIN_PIECE0(2 * M0 - 1, XC, XN)                             \
                 } else if (u_ == PH) CHAIN_PHASE0(XC, XN)                                                        \
-                if (u_ == DMA_LATE0 && !dma_early) dma_chunk(b_ + 2, slot_ptr(2));                               \
+                if (u_ == DMA_LATE0 && dma_half() != 0) dma_chunk(b_ + 2, slot_ptr(2));                          \
                 if (!DEEP) {                                                                                     \
                     if (u_ + 2 < 4 * M0) c0 = read_l0(sb_, u_ + 2);                                              \
                     else if (b_ + 1 < NB) c0 = read_l0(slot_ptr(1), 0);                                          \
@@ -1002,7 +1085,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         {                                                                                                        \
             constexpr int i_ = (I);                                                                              \
             if (i_ == 0) {                                                                                       \
-                if (dma_early) dma_chunk(b_ + 2, slot_ptr(2));                                                   \
+                if (dma_half() == 0) dma_chunk(b_ + 2, slot_ptr(2));                                             \
                 {                                                                              \
                     idcn = fold_pair_ids(PPB * (b_ + 1), pass, idr_lo, idr_hi);                                  \
                     if constexpr (PPB > 1) idcnB = fold_pair_ids(PPB * (b_ + 1) + 1, pass, idrB_lo, idrB_hi);    \
@@ -1055,7 +1138,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                 if (u_ == 4) CHAIN_PIECEQ(2, XC, XN)                                                             \
                 if (u_ == 6) CHAIN_PIECEQ(3, XC, XN)                                                             \
                 if (u_ == 4 * M0 - 2 && u_ > 6) CHAIN_PIECEQ(2 * M0 - 1, XC, XN)                                 \
-                if (u_ == DMA_LATE0 && !dma_early) dma_chunk(b_ + 2, slot_ptr(2));                               \
+                if (u_ == DMA_LATE0 && dma_half() != 0) dma_chunk(b_ + 2, slot_ptr(2));                          \
                 if (!DEEP) {                                                                                     \
                     if (u_ + 2 < 4 * M0) c0 = read_l0(sb_, u_ + 2);                                              \
                     else if (b_ + 1 < NB) c0 = read_l0(slot_ptr(1), 0);                                          \
@@ -1076,6 +1159,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             idcB = idcnB;                                                                                        \
         }
         if constexpr (FPB > 1) {
+#pragma nounroll
             for (int b0_ = 0; b0_ < NB; b0_ += 2) {
                 {
                     const int b_ = b0_;
@@ -1091,6 +1175,9 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             linacc += (lvn_has && NB - 1 < NBE) ? lvn : 0.f;
             if constexpr (PPB > 1) linacc += (lvnB_has && NB - 1 < NBE) ? lvnB : 0.f;
         } else {
+        // (nounroll: no peeling either — a peeled first pair doubles the step's code, and the peeled copies' loop conditions, invariants
+        // of the pass loop, are kept as lane masks in scalar register pairs the step loops do not have)
+#pragma nounroll
         for (int pr_ = 0; pr_ * PAIR < NB; ++pr_) {
             CHAIN_STEP0(0, XA, XB);
             if (pr_ * PAIR + 1 < NB) CHAIN_STEP0(1, XB, XA);
@@ -1152,11 +1239,11 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                 fm += __shfl_xor(fm, 16, 64);
                 fm += __shfl_xor(fm, 32, 64);
                 fm *= 0.5f;
-                float dl = NDB > 0 ? dlacc_ptr()[nt * 64] : 0.f;
+                float dl = has_dense() ? dlacc_ptr()[nt * 64] : 0.f;
                 dl += __shfl_xor(dl, 16, 64);
                 dl += __shfl_xor(dl, 32, 64);
                 const float lin_all = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * nt + j), __builtin_bit_cast(int, lin_rows))) + dl;
-                extras[nt] = (p.fm_used ? fm : 0.f) + (p.lin_used ? lin_all : 0.f);
+                extras[nt] = (cold()->fm_used ? fm : 0.f) + (cold()->lin_used ? lin_all : 0.f);
                 if constexpr (CROSS) {
                     const float* cq = smem + p.xv_off + CROSS_NV * 16 * NB;
                     float dots[CROSS_NV], cst[CROSS_NV];
@@ -1172,14 +1259,14 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                 }
                 const int r = row_of(pass, nt);
                 if (g == 0 && r < row_end) {
-                    if (p.fm_logit != nullptr) p.fm_logit[r] = fm;
-                    if (p.lin_logit != nullptr) p.lin_logit[r] = lin_all;
+                    if (cold()->fm_logit != nullptr) cold()->fm_logit[r] = fm;
+                    if (cold()->lin_logit != nullptr) cold()->lin_logit[r] = lin_all;
                 }
             }
         }
         // (BatchNormalization scale / shift,) activation in place: acc0 is now the B operand of layer 1
-        if (p.bn_scale[0] != nullptr) bn_block<4 * M0, RT>(cpar + Off::BN_S, cpar + Off::BN_T, g, acc0);
-        act_block<4 * M0, RT, EXPACT>(p.activation, acc0);
+        if (cold()->bn_scale[0] != nullptr) bn_block<4 * M0, RT>(cpar + Off::BN_S, cpar + Off::BN_T, g, acc0);
+        act_block<4 * M0, RT, EXPACT>(cold()->activation, acc0);
         if constexpr (M0 > 1) {
             f32x4* park = park_ptr();
 #pragma unroll
@@ -1198,18 +1285,13 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         auto init_acc = [&](auto& acc, int boff, auto MG) {
             constexpr int MGc = decltype(MG)::value;
 #pragma unroll
-            for (int mg = 0; mg < MGc; ++mg) {
-                float bv[16];
+            for (int mg = 0; mg < MGc; ++mg)
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    const float4 t = *reinterpret_cast<const float4*>(cpar + boff + 64 * mg + 16 * g + 4 * qq);
-                    bv[4 * qq] = t.x; bv[4 * qq + 1] = t.y; bv[4 * qq + 2] = t.z; bv[4 * qq + 3] = t.w;
+                for (int mt = 0; mt < 4; ++mt) {
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(cpar + boff + 64 * mg + 16 * g + 4 * mt);     // (accumulator order: bias_slot)
+#pragma unroll
+                    for (int nt = 0; nt < RT; ++nt) acc[4 * mg + mt][nt] = b;
                 }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < RT; ++nt) acc[4 * mg + mt][nt] = f32x4{bv[mt], bv[4 + mt], bv[8 + mt], bv[12 + mt]};
-            }
         };
         // (the generic lambda is instantiated per layer; MI / MO = M-groups of its input / output)
         auto dense_layer = [&](auto& accin, auto& accout, auto MIc, auto MOc, auto PARKc) {
@@ -1224,7 +1306,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                     if (last) CHAIN_TOP_ID();                      // the ids requested in the step before
                     else CHAIN_TOP();
                     const float* sb = slot_ptr(0);
-                    if (last && NDB > 0) {                         // the next pass's dense values have landed
+                    if (last && has_dense()) {                         // the next pass's dense values have landed
                         dense_store(0, td);
                         dense_rest(pass_n);
                     }
@@ -1251,11 +1333,11 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                         DCTR_SB;
                         if (ks == PH) {
                             // the chunk after next, and at the pass's end the next pass's gather prologue
-                            if (dma_early) dma_chunk(NB + sidx + 2, slot_ptr(2));
+                            if (dma_half() == 0) dma_chunk_n(sidx, slot_ptr(2));
                             if (sidx == SL - 2) {
                                 request_pair_ids(0, pass_n, idr_lo, idr_hi);
                                 if constexpr (FPB > 1 && PPB > 1) request_pair_ids(1, pass_n, idrB_lo, idrB_hi);
-                                if (NDB > 0) dense_request(0, pass_n, td);
+                                if (has_dense()) dense_request(0, pass_n, td);
                             }
                             if (last) {
                                 idc = fold_pair_ids(0, pass_n, idr_lo, idr_hi);
@@ -1269,7 +1351,7 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
                                 }
                             }
                         }
-                        if (ks == CHAIN_DMA_LATE && !dma_early) dma_chunk(NB + sidx + 2, slot_ptr(2));
+                        if (ks == CHAIN_DMA_LATE && dma_half() != 0) dma_chunk_n(sidx, slot_ptr(2));
                         if (!DEEP) {
                             if (ks + 2 < 16) c0 = read_an(sb, ks + 2);
                             else if (!last) c0 = read_an(slot_ptr(1), 0);
@@ -1302,8 +1384,8 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
         // head of the last layer: act(acc) . head_w over this lane's 16 features per M-group, then over g
         auto head = [&](auto& acc, auto MGc, int layer, int bn_off) {
             constexpr int MG = decltype(MGc)::value;
-            if (p.bn_scale[layer] != nullptr) bn_block<4 * MG, RT>(cpar + Off::BN_S + bn_off, cpar + Off::BN_T + bn_off, g, acc);
-            act_block<4 * MG, RT, EXPACT>(p.activation, acc);
+            if (cold()->bn_scale[layer] != nullptr) bn_block<4 * MG, RT>(cpar + Off::BN_S + bn_off, cpar + Off::BN_T + bn_off, g, acc);
+            act_block<4 * MG, RT, EXPACT>(cold()->activation, acc);
 #pragma unroll
             for (int nt = 0; nt < RT; ++nt) hs[nt] = 0.f;
 #pragma unroll
@@ -1324,8 +1406,8 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             }
         };
         if constexpr (M2 > 0) {
-            if (p.bn_scale[1] != nullptr) bn_block<4 * M1, RT>(cpar + Off::BN_S + 64 * M0, cpar + Off::BN_T + 64 * M0, g, acc1);
-            act_block<4 * M1, RT, EXPACT>(p.activation, acc1);
+            if (cold()->bn_scale[1] != nullptr) bn_block<4 * M1, RT>(cpar + Off::BN_S + 64 * M0, cpar + Off::BN_T + 64 * M0, g, acc1);
+            act_block<4 * M1, RT, EXPACT>(cold()->activation, acc1);
             f32x4 acc2[4 * (M2 > 0 ? M2 : 1)][RT];
             init_acc(acc2, B2_OFF, std::integral_constant<int, M2>{});
             dense_layer(acc1, acc2, std::integral_constant<int, M1>{}, std::integral_constant<int, M2>{}, std::false_type{});
@@ -1345,10 +1427,10 @@ __device__ __forceinline__ void chain_passes(const ChainParams& p, float* smem, 
             if (g == 0 && r < row_end) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (p.add[i] != nullptr) v += p.add[i][r];
+                    if (cold()->add[i] != nullptr) v += cold()->add[i][r];
                 v += cpar[GB_OFF];
-                if (p.sigmoid_out) v = dctr::sigmoidf_(v);
-                p.y[r] = v;
+                if (cold()->sigmoid_out) v = dctr::sigmoidf_(v);
+                cold()->y[r] = v;
             }
         }
     }
@@ -1375,10 +1457,10 @@ __global__ __launch_bounds__(64 * NW, 1) void chain_kernel(ChainParams p) {
     // ---- once per launch: descriptors, biases, head weights, BatchNormalization scale / shift, dense linear weights -> LDS
     for (int i = threadIdx.x; i < 12 * p.n_fields; i += NT)
         reinterpret_cast<uint32_t*>(fdesc)[i] = reinterpret_cast<const uint32_t*>(p.fields)[i];
-    for (int i = threadIdx.x; i < 64 * M0; i += NT) cpar[i] = p.bias[0] != nullptr ? p.bias[0][i] : 0.f;
-    for (int i = threadIdx.x; i < 64 * M1; i += NT) cpar[Off::B1 + i] = p.bias[1] != nullptr ? p.bias[1][i] : 0.f;
+    for (int i = threadIdx.x; i < 64 * M0; i += NT) cpar[bias_slot(i)] = p.bias[0] != nullptr ? p.bias[0][i] : 0.f;
+    for (int i = threadIdx.x; i < 64 * M1; i += NT) cpar[Off::B1 + bias_slot(i)] = p.bias[1] != nullptr ? p.bias[1][i] : 0.f;
     if constexpr (M2 > 0)
-        for (int i = threadIdx.x; i < 64 * M2; i += NT) cpar[Off::B2 + i] = p.bias[2] != nullptr ? p.bias[2][i] : 0.f;
+        for (int i = threadIdx.x; i < 64 * M2; i += NT) cpar[Off::B2 + bias_slot(i)] = p.bias[2] != nullptr ? p.bias[2][i] : 0.f;
     for (int i = threadIdx.x; i < 64 * Off::ML; i += NT) cpar[Off::HW + i] = p.head_w[i];
     if (threadIdx.x == 0) cpar[Off::GB] = p.global_bias != nullptr ? p.global_bias[0] : 0.f;
     {
@@ -1421,17 +1503,21 @@ __global__ __launch_bounds__(64 * NW, 1) void chain_kernel(ChainParams p) {
     __syncthreads();                                   // LDS parameters written
     int oor = 0;
     const int main_end = (int)(TAIL ? p.main_rows : p.batch);
+    // (comment lines in the assembly, no instruction: tests/test_chain_valu_budget.py counts each phase's vector instructions between them)
+    asm volatile("; dctr_chain phase: main");
     chain_passes<RT, NW, EB, I64, M0, M1, M2, CROSS, FPB, EXPACT, REC, POOL>(p, smem, wave, lane, 0, main_end, (int)blockIdx.x, (int)gridDim.x, p.n_pass, oor);
     if constexpr (TAIL) {
         if (p.n_tail > 0) {
             // every wave is through with the ring and the staging areas of the main phase; waves 4.. leave (s_barrier waits for
             // the surviving waves of a workgroup only), waves 0-3 take the workgroup's 64-row units
             __syncthreads();
+            asm volatile("; dctr_chain phase: tail");
             if (wave < 4)
                 chain_passes<1, 4, EB, I64, M0, M1, M2, CROSS, FPB, EXPACT, REC, POOL>(p, smem, wave, lane, main_end, (int)p.batch, (int)blockIdx.x,
                                                                          (int)gridDim.x, p.n_tail, oor);
         }
     }
+    asm volatile("; dctr_chain phase: end");
     if (p.status != nullptr && oor && lane == 0) atomicOr(p.status, (int)DCTR_STATUS_INDEX_OOR);
     if (p.probe != nullptr && lane == 0) atomicMax(p.probe + 1, (unsigned long long)wall_clock64());
 }
