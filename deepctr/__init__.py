@@ -9,8 +9,8 @@ scripts (``examples/run_classification_criteo.py``, ``run_din.py`` ...) run unmo
 
 Differences from the reference package, on purpose: importing it performs no HTTP version check
 (reference ``deepctr/__init__.py:1-4`` -> ``utils.check_version`` starts a thread that queries PyPI), and only the §8
-scope exists: the other 1 model constructor (MLR), the Estimator API and ``deepctr.contrib`` raise ``ImportError`` /
-``AttributeError`` by absence.
+scope exists: every one of the 27 model constructors is built (MLR the last), the Estimator API and ``deepctr.contrib`` raise
+``ImportError`` / ``AttributeError`` by absence.
 """
 import importlib
 import sys
@@ -21,7 +21,7 @@ _ALIASES = (
     "feature_column", "inputs",
     "layers", "layers.activation", "layers.core", "layers.interaction", "layers.normalization", "layers.sequence", "layers.utils",
     "models", "models.afm", "models.autoint", "models.ccpm", "models.dcn", "models.dcnmix", "models.deepfefm", "models.deepfm", "models.difm", "models.edcn", "models.fgcnn", "models.fibinet",
-    "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.nfm", "models.onn", "models.pnn",
+    "models.flen", "models.fnn", "models.fwfm", "models.ifm", "models.mlr", "models.nfm", "models.onn", "models.pnn",
     "models.wdl", "models.xdeepfm", "models.sequence", "models.sequence.bst", "models.sequence.dien", "models.sequence.din", "models.sequence.dsin",
     "models.multitask", "models.multitask.esmm", "models.multitask.mmoe", "models.multitask.ple", "models.multitask.sharedbottom",
 )

@@ -213,6 +213,30 @@ ffm.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
     ("reserved", c_i32), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
 
 
+class mlr(object):
+    """dctr_mlr_field_t / dctr_mlr_args_t / dctr_mlr_grad_t / dctr_mlr_bwd_args_t, one level down for the same reason as
+    interacting.Args (tests/test_mlr_cpu.py checks the layout)."""
+    LEARNER_SIGMOID, LEARNER_LINEAR = 0, 1
+    MAX_COLUMNS = 64
+
+    class Field(ctypes.Structure):
+        _fields_ = [("rows", c_vp), ("ids", c_vp), ("vocab", c_i64), ("row_pitch", c_i64), ("ids_stride", c_i64), ("ids_is_i64", c_i32),
+                    ("identity", c_i32), ("col0", c_i32), ("width", c_i32)]
+
+    class Args(ctypes.Structure):
+        _fields_ = [("fields", c_vp), ("batch", c_i64), ("n_fields", c_i32), ("region_num", c_i32), ("has_bias", c_i32),
+                    ("learner_act", c_i32), ("n_dense", c_i32), ("reserved", c_i32), ("dense", c_vp), ("dense_stride", c_i64),
+                    ("dense_w", c_vp), ("out", c_vp), ("out_stride", c_i64), ("z", c_vp), ("z_stride", c_i64), ("z_offset", c_i64),
+                    ("status", c_vp)]
+
+    class Grad(ctypes.Structure):
+        _fields_ = [("grad", c_vp), ("row_stride", c_i64)]
+
+
+mlr.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", mlr.Args), ("d_out", c_vp), ("d_out_stride", c_i64), ("dz", c_vp), ("dz_stride", c_i64), ("grads", c_vp)]})
+
+
 class ifm(object):
     """dctr_ifm_src_t / dctr_ifm_lin_t / dctr_ifm_args_t, one level down for the same reason as interacting.Args (tests/test_ifm_cpu.py
     checks the layout)."""
@@ -511,6 +535,9 @@ SYMBOLS = {
     "dctr_ffm_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(ffm.BwdArgs)]),
     "dctr_ffm_bwd_route": (ctypes.c_int, [ctypes.POINTER(ffm.BwdArgs)]),
     "dctr_ffm_bwd": (ctypes.c_int, [ctypes.POINTER(ffm.BwdArgs), c_vp]),
+    "dctr_mlr_supported": (ctypes.c_int, [ctypes.POINTER(mlr.Args)]),
+    "dctr_mlr_fwd": (ctypes.c_int, [ctypes.POINTER(mlr.Args), c_vp]),
+    "dctr_mlr_bwd": (ctypes.c_int, [ctypes.POINTER(mlr.BwdArgs), c_vp]),
     "dctr_ifm_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_route": (ctypes.c_int, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_fwd": (ctypes.c_int, [ctypes.POINTER(ifm.Args), c_vp]),

@@ -56,6 +56,8 @@ SOURCES = [
     "fieldpair_bwd_kernels.hip",
     "ffm_kernels.hip",
     "ffm_bwd_kernels.hip",
+    "mlr_kernels.hip",
+    "mlr_bwd_kernels.hip",
     "ifm_kernels.hip",
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",

@@ -28,6 +28,10 @@ def linear_columns(feature_columns):
 class FeatureModel(Model):
     """linear part + embedding stage + DNN + head: the skeleton DeepFM / DCN / xDeepFM share."""
 
+    # what autograd_logits returns: "logit" (the value PredictionLayer receives) or "prediction" (the model's output itself: MLR, whose
+    # output is no sigmoid of a logit) — training._fit_torch forms the loss accordingly
+    output_kind = "logit"
+
     def __init__(self, *args, **kwargs):
         super(FeatureModel, self).__init__(*args, **kwargs)
         self._buf = {}              # batch size -> the model's own per-batch buffers (_per_batch)

@@ -1505,6 +1505,271 @@ class FieldAwareFunction(torch.autograd.Function):
         return tuple(ret)
 
 
+_MLR_LEARNERS = {"binary": _C.mlr.LEARNER_SIGMOID, "regression": _C.mlr.LEARNER_LINEAR}
+
+
+def _mlr_args(batch, n_fields, region_num, bias, task):
+    if task not in _MLR_LEARNERS:
+        raise ValueError("mlr: task %r: expected 'binary' or 'regression'" % (task,))
+    return _C.mlr.Args(batch=int(batch), n_fields=int(n_fields), region_num=int(region_num), has_bias=int(bool(bias)),
+                       learner_act=_MLR_LEARNERS[task], out_stride=1)
+
+
+def mlr_supported(region_num, bias=False):
+    """Does dctr_mlr_fwd / dctr_mlr_bwd take K = 2 region_num (+ 1) logit columns (K <= 64)?  The library's answer, host only."""
+    return bool(_C.lib().dctr_mlr_supported(ctypes.byref(_mlr_args(0, 0, region_num, bias, "binary"))))
+
+
+def make_mlr_fields(fields, device):
+    """fields: list of dicts(rows = float32 2-D view with unit column stride whose first ``width`` columns the field adds to the logit
+    columns ``col0`` .. ``col0 + width - 1``; ids = 1-D int32 / int64 view, or None: a pre-pooled field whose row is the sample index)
+    -> uint8 device tensor holding the dctr_mlr_field_t array (kept alive by the caller, with the tensors it points at)."""
+    arr = (_C.mlr.Field * max(1, len(fields)))()
+    for j, f in enumerate(fields):
+        rows, ids = f["rows"], f.get("ids")
+        arr[j].rows = rows.data_ptr()
+        arr[j].vocab = int(rows.shape[0])
+        arr[j].row_pitch = row_stride(rows)
+        arr[j].col0, arr[j].width = int(f["col0"]), int(f["width"])
+        if ids is None:
+            arr[j].identity = 1
+        else:
+            arr[j].ids = ids.data_ptr()
+            arr[j].ids_stride = _id_stride(ids)
+            arr[j].ids_is_i64 = int(ids.dtype == torch.int64)
+    return _upload(arr, device)
+
+
+def _mlr_operands(op, fields, region_num, bias, desc, batch, n_fields):
+    """What mlr() and mlr_bwd() read alike: the field list behind a dctr_mlr_field_t array, or a ready ``desc`` with ``n_fields`` and
+    ``batch``.  Returns (K, B, n_fields, desc, the tensors to keep alive)."""
+    K = 2 * int(region_num) + int(bool(bias))
+    keep = []
+    if desc is None:
+        if batch is None:
+            raise ValueError("%s: batch is required" % op)
+        B = int(batch)
+        fields = list(fields or [])           # (no sparse or sequence feature at all is legal: the dense part alone, n_fields = 0)
+        for j, f in enumerate(fields):
+            rows, ids = f["rows"], f.get("ids")
+            col0, width = int(f["col0"]), int(f["width"])
+            if not (0 <= col0 and 1 <= width and col0 + width <= K):
+                raise ValueError("%s: field %d: columns [%d, %d) outside the %d logit columns" % (op, j, col0, col0 + width, K))
+            _rows2d(op, "fields[%d].rows" % j, rows, B if ids is None else 0, width, at_least_rows=True)
+            if ids is not None:
+                if ids.dim() != 1 or ids.shape[0] != B or ids.dtype not in (torch.int32, torch.int64):
+                    raise ValueError("%s: field %d: ids must be an int32 / int64 vector of %d elements" % (op, j, B))
+                keep.append(ids)
+            keep.append(rows)
+        _dev_check(*keep)
+        n_fields = len(fields)
+        desc = make_mlr_fields(fields, keep[0].device) if fields else None
+    else:
+        if n_fields is None or batch is None:
+            raise ValueError("%s: desc needs n_fields and batch" % op)
+        B = int(batch)
+    return K, B, int(n_fields), desc, keep
+
+
+def mlr(fields, region_num, bias=False, task="binary", dense=None, dense_w=None, out=None, z=None, z_offset=0, status=None, desc=None,
+        batch=None, n_fields=None, device=None):
+    """MLR's forward (reference models/mlr.py:17-74), one launch: ``fields`` as make_mlr_fields takes them (or a ready ``desc`` with
+    ``n_fields``), ``batch`` samples, K = 2 region_num (+ 1 with ``bias``) logit columns in the order region, learner, bias.
+    ``dense`` [B, >= n_dense] with ``dense_w`` [n_dense, K] (contiguous) adds dense @ dense_w.  ``out``: a float32 vector of B
+    elements (any stride), allocated when None.  ``z``: True for a fresh [B, K], or a float32 2-D view written from column ``z_offset``
+    (other columns untouched), or None: z is not written.  Returns (out, z).  K > 64 raises DctrError with rc = E_UNSUPPORTED and
+    writes nothing."""
+    K, B, F, desc, keep = _mlr_operands("mlr", fields, region_num, bias, desc, batch, n_fields)
+    dev = device or (desc.device if desc is not None else keep[0].device if keep else dense.device if dense is not None else out.device)
+    a = _mlr_args(B, F, region_num, bias, task)
+    if dense is not None:
+        n_dense = int(dense_w.shape[0])
+        a.dense_stride = _rows2d("mlr", "dense", dense, B, n_dense, at_least_rows=True)
+        if tuple(dense_w.shape) != (n_dense, K):
+            raise ValueError("mlr: dense_w must be [n_dense, %d], got %s" % (K, tuple(dense_w.shape)))
+        _vec("mlr", "dense_w", dense_w, n_dense * K)
+        a.n_dense, a.dense, a.dense_w = n_dense, dense.data_ptr(), dense_w.data_ptr()
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    if out.dim() != 1 or out.shape[0] != B or out.dtype != torch.float32:
+        raise ValueError("mlr: out must be a float32 vector of %d elements" % B)
+    a.out, a.out_stride = out.data_ptr(), _id_stride(out)
+    if z is True:
+        z = torch.empty(B, K, dtype=torch.float32, device=dev)
+    if z is not None:
+        a.z_stride = _rows2d("mlr", "z", z, B, K, z_offset, at_least_rows=True)
+        a.z, a.z_offset = z.data_ptr(), int(z_offset)
+    _dev_check(desc, dense, dense_w, out, z, status)
+    if desc is not None:
+        a.fields = desc.data_ptr()
+    if status is not None:
+        a.status = status.data_ptr()
+    _C.check(_C.lib().dctr_mlr_fwd(ctypes.byref(a), _C.stream_ptr()), "dctr_mlr_fwd")
+    del keep
+    return out, z
+
+
+def make_mlr_grads(grads, device):
+    """grads: per field a float32 2-D view with unit column stride (a table field's dense gradient, advanced to the field's first
+    column; a pre-pooled field's d_rows), or None for a field that gets no gradient -> uint8 device tensor holding the dctr_mlr_grad_t
+    array (kept alive by the caller)."""
+    arr = (_C.mlr.Grad * max(1, len(grads)))()
+    for j, g in enumerate(grads):
+        if g is not None:
+            arr[j].grad = g.data_ptr()
+            arr[j].row_stride = row_stride(g)
+    return _upload(arr, device)
+
+
+def mlr_bwd(fields, region_num, z, d_out, bias=False, task="binary", grads=None, dz=None, z_offset=0, status=None, desc=None,
+            batch=None, n_fields=None):
+    """Backward of mlr(), one launch (include/dctr.h: dctr_mlr_bwd).  ``z``: what the forward saved (read from column ``z_offset``);
+    ``d_out``: a float32 vector of B elements.  ``grads``: None, or per field where its slice of dz goes — a table field: a
+    [vocab, >= width] view of the dense gradient master (advanced to the field's first column), ACCUMULATED into with float atomics (zero
+    it first; last bits may differ from call to call); a pre-pooled field: d_rows [>= B, >= width], its first ``width`` columns written;
+    None: a frozen field, skipped.  Returns dz [B, K] (``dz``: a float32 2-D view to write instead)."""
+    K, B, F, desc, keep = _mlr_operands("mlr_bwd", fields, region_num, bias, desc, batch, n_fields)
+    b = _C.mlr.BwdArgs()
+    b.fwd = _mlr_args(B, F, region_num, bias, task)
+    b.fwd.z_stride = _rows2d("mlr_bwd", "z", z, B, K, z_offset, at_least_rows=True)
+    b.fwd.z, b.fwd.z_offset = z.data_ptr(), int(z_offset)
+    if d_out.dim() != 1 or d_out.shape[0] != B or d_out.dtype != torch.float32:
+        raise ValueError("mlr_bwd: d_out must be a float32 vector of %d elements" % B)
+    b.d_out, b.d_out_stride = d_out.data_ptr(), _id_stride(d_out)
+    if dz is None:
+        dz = torch.empty(B, K, dtype=torch.float32, device=z.device)
+    b.dz_stride = _rows2d("mlr_bwd", "dz", dz, B, K, at_least_rows=True)
+    b.dz = dz.data_ptr()
+    gdesc = None
+    if grads is not None:
+        if len(grads) != F:
+            raise ValueError("mlr_bwd: grads must hold one entry (a tensor or None) per field, got %d for %d fields" % (len(grads), F))
+        if fields is not None:
+            for j, (f, g) in enumerate(zip(fields, grads)):
+                if g is not None:
+                    pooled = f.get("ids") is None
+                    _rows2d("mlr_bwd", "grads[%d]" % j, g, B if pooled else int(f["rows"].shape[0]), int(f["width"]), at_least_rows=pooled)
+        if any(g is not None for g in grads):
+            gdesc = make_mlr_grads(grads, z.device)
+            b.grads = gdesc.data_ptr()
+    _dev_check(desc, z, d_out, dz, status, *[g for g in (grads or []) if g is not None])
+    if desc is not None:
+        b.fwd.fields = desc.data_ptr()
+    if status is not None:
+        b.fwd.status = status.data_ptr()
+    _C.check(_C.lib().dctr_mlr_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_mlr_bwd")
+    del keep, gdesc
+    return dz
+
+
+class MLRFunction(torch.autograd.Function):
+    """MLR's forward as one differentiable op: mlr() forward with z kept, mlr_bwd() backward, one launch each.
+    ``apply(plan, region_num, bias, task, status, dense, dense_w, *inputs)``.  ``plan``: per field a dict(master = the fused rows
+    [V, pitch] or None for a field that arrives pooled, ids = its 1-D id view, first = the master column of its first logit column,
+    col0, width); ``inputs`` in field order — a table field's ``width`` per-name views ``master[:, first + k : first + k + 1]``
+    (``inputs_of`` checks that they are), a pooled field's [B, width] rows.  ``dense`` [B, n_dense] and ``dense_w`` [n_dense, K] (or both
+    None): dense_w's gradient is dense^T dz, a torch matmul; dense gets none.  Returns the prediction [B].  The backward zeroes ONE
+    [V, pitch] gradient per distinct master and hands each view its column of it (fields that share a master add into the same
+    gradient; the views of the later ones get None), a pooled field its d_rows; table gradients leave the kernel through float atomics
+    and may differ in the last bits from call to call."""
+
+    @staticmethod
+    def inputs_of(plan, views):
+        """The gate: ``views[j]`` = field j's per-name tensors in column order, or its pooled rows (a callable is called for them once
+        every table view has passed).  Returns ``inputs`` for apply(), or None when a view is not the column of its master."""
+        flat = []
+        for f, vs in zip(plan, views):
+            m = f["master"]
+            if m is None:
+                flat.append(vs)
+                continue
+            if not m.is_cuda or m.dim() != 2 or not m.is_contiguous() or m.dtype != torch.float32 or len(vs) != f["width"]:
+                return None
+            V, pitch = m.shape
+            for k, v in enumerate(vs):
+                if (v.data_ptr() != m.data_ptr() + (f["first"] + k) * 4 or tuple(v.shape) != (V, 1) or v.dtype != torch.float32
+                        or v.device != m.device or (V > 1 and v.stride(0) != pitch)):
+                    return None
+            flat.extend(vs)
+        return [v() if callable(v) else v for v in flat]
+
+    @staticmethod
+    def _fields(plan, pooled_rows):
+        fields, at = [], 0
+        for f in plan:
+            if f["master"] is None:
+                fields.append(dict(rows=pooled_rows[at], ids=None, col0=f["col0"], width=f["width"]))
+                at += 1
+            else:
+                fields.append(dict(rows=f["master"].detach()[:, f["first"]:], ids=f["ids"], col0=f["col0"], width=f["width"]))
+        return fields
+
+    @staticmethod
+    def forward(ctx, plan, region_num, bias, task, status, dense, dense_w, *inputs):
+        ctx.set_materialize_grads(False)
+        pooled, at = [], 0
+        for f in plan:
+            if f["master"] is None:
+                pooled.append(_f32c(inputs[at].detach(), "pooled rows"))
+                at += 1
+            else:
+                at += f["width"]
+        B = int(plan[0]["ids"].shape[0] if plan and plan[0]["master"] is not None else (pooled[0].shape[0] if pooled else dense.shape[0]))
+        ctx.plan, ctx.meta, ctx.status = plan, (int(region_num), bool(bias), task, B), status
+        dw = None if dense_w is None else _f32c(dense_w.detach(), "dense_w")
+        out, z = mlr(MLRFunction._fields(plan, pooled), region_num, bias, task, dense=dense, dense_w=dw, z=True, status=status, batch=B,
+                     device=(dense if dense is not None else pooled[0] if pooled else plan[0]["master"]).device)
+        ctx.save_for_backward(z, *([dense] if dense is not None else []), *pooled)
+        ctx.has_dense = dense is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        plan, (R, bias, task, B) = ctx.plan, ctx.meta
+        needs = ctx.needs_input_grad[7:]
+        none = (None,) * (7 + len(needs))
+        if d_out is None:
+            return none
+        saved = list(ctx.saved_tensors)
+        z = saved[0]
+        dense = saved[1] if ctx.has_dense else None
+        pooled = saved[2 if ctx.has_dense else 1:]
+        d_out = _grad_operand(d_out, False)
+        masters, grads, at, pat = {}, [], 0, 0           # data_ptr of a master -> its zeroed gradient
+        for f in plan:
+            m = f["master"]
+            if m is None:
+                grads.append(torch.empty(B, f["width"], dtype=torch.float32, device=z.device) if needs[at] else None)
+                at += 1
+                pat += 1
+            else:
+                if any(needs[at:at + f["width"]]):
+                    g = masters.get(m.data_ptr())
+                    if g is None:
+                        g = masters[m.data_ptr()] = torch.zeros_like(m)
+                    grads.append(g[:, f["first"]:])
+                else:
+                    grads.append(None)
+                at += f["width"]
+        dz = mlr_bwd(MLRFunction._fields(plan, pooled), R, z, d_out, bias=bias, task=task, grads=grads, status=ctx.status, batch=B)
+        d_dense_w = dense.t() @ dz if (dense is not None and ctx.needs_input_grad[6]) else None
+        ret, at, handed = [None] * 6 + [d_dense_w], 0, set()
+        for f, g in zip(plan, grads):
+            if f["master"] is None:
+                ret.append(g)
+                at += 1
+                continue
+            for k in range(f["width"]):
+                key = (f["master"].data_ptr(), f["first"] + k)
+                if g is not None and needs[at + k] and key not in handed:
+                    handed.add(key)
+                    ret.append(g[:, k:k + 1])
+                else:
+                    ret.append(None)
+            at += f["width"]
+        return tuple(ret)
+
+
 _IFM_ROUTES = {None: _C.ifm.ROUTE_AUTO, "auto": _C.ifm.ROUTE_AUTO, "workspace": _C.ifm.ROUTE_WORKSPACE}
 
 

@@ -190,7 +190,8 @@ def frozen_weights(model):
     """data_ptr()s of the tables built from SparseFeat(trainable=False) (reference inputs.py:25: ``emb.trainable =
     feat.trainable``; docs FAQ "pretrained embeddings"): neither training path may touch them."""
     out = set()
-    for embs in (getattr(model, "tables", None) or {}, getattr(model, "linear_tables", None) or {}, getattr(model, "fg_tables", None) or {}):
+    for embs in (getattr(model, "tables", None) or {}, getattr(model, "linear_tables", None) or {}, getattr(model, "fg_tables", None) or {},
+                 getattr(model, "mlr_tables", None) or {}):
         for emb in embs.values():
             if not getattr(emb, "trainable", True):
                 out.add(emb.embeddings.data_ptr())
@@ -232,6 +233,10 @@ def regularized_weights(model):
         add(emb.embeddings, reg.get("linear", 0.0))
     if getattr(model, "linear", None) is not None:
         add(model.linear.w("linear_kernel"), reg.get("linear", 0.0))
+    for emb in (getattr(model, "mlr_tables", None) or {}).values():        # MLR: every one-wide table and every Linear of its 2R (+1)
+        add(emb.embeddings, reg.get("linear", 0.0))                        # logits carries l2(l2_reg_linear) (mlr.py:60-72)
+    for lin in getattr(model, "mlr_linears", None) or []:
+        add(lin._weights.get("linear_kernel"), reg.get("linear", 0.0))
     dnn = getattr(model, "dnn", None)
     if dnn is not None:
         for k in dnn.kernels:
@@ -375,6 +380,58 @@ def _ffm_on_hip(masters, views, rows, min_rows=0):
             and all(m.is_cuda and m.dtype == torch.float32 for m in tables)):
         return None
     return ops.FieldAwareFunction.inputs_of(masters, views)
+
+
+# MLR has no row threshold: at the Criteo shape the autograd step with ops.MLRFunction took 0.20 .. 0.22x of the torch ops' time at 4,096
+# rows and 0.16 .. 0.20x at 65,536, and with half of every column on one id 0.15 .. 0.16x down to 0.03x (profiles/mlr.txt; no smaller
+# row count was measured).  The name stays so that a measurement at another shape has somewhere to put its answer.
+MLR_HIP_MIN_ROWS = 0
+
+
+def _mlr_mix(z, region_num, bias, task):
+    """z [B, K] (columns region 0..R-1, learner R..2R-1, bias 2R) -> MLR's prediction [B] (reference models/mlr.py:45-54)."""
+    R = int(region_num)
+    s = torch.softmax(z[:, :R], dim=-1)
+    a = torch.sigmoid(z[:, R:2 * R]) if task == "binary" else z[:, R:2 * R]
+    out = (s * a).sum(-1)
+    return out * torch.sigmoid(z[:, 2 * R]) if bias else out
+
+
+def _mlr_output(model, staged, lo, hi, dtype=None):
+    """MLR's PREDICTION [B] of rows [lo, hi) in torch ops from the per-name weights (models/mlr.py: ``groups`` = its 2R (+1) linear
+    logits): the CPU suite's restatement, the autograd step on the CPU / under no_grad / with HIP_AUTOGRAD_OPS off, and the baseline of
+    scripts/bench_mlr.py.  ``dtype``: compute in that dtype (the tests' float64)."""
+    B = hi - lo
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    dense = cast(staged.dense[lo:hi]) if staged.dense is not None else None
+    zs = []
+    for g in model.groups:
+        z = torch.zeros(B, dtype=dtype or torch.float32, device=model.device)
+        for fc in g.features:
+            w = cast(g.tables[fc.embedding_name].embeddings)
+            if isinstance(fc, SparseFeat):
+                z = z + w[model.sparse_rows(staged, fc, lo, hi)].reshape(-1)
+            else:
+                rows = _rows_for(fc, staged.seq[fc.name][lo:hi], True)
+                length = staged.length[fc.length_name][lo:hi] if fc.length_name is not None else None
+                weight = cast(staged.weight[fc.weight_name][lo:hi]) if fc.weight_name is not None else None
+                z = z + _pool(w[rows], fc, rows != 0, length, weight).reshape(-1)
+        if g.dense_pos is not None:
+            z = z + (dense.index_select(1, g.dense_pos) @ cast(g.linear.w("linear_kernel"))).reshape(-1)
+        zs.append(z)
+    return _mlr_mix(torch.stack(zs, dim=1), model.region_num, model.has_bias, model.learner_task)
+
+
+def _mlr_on_hip(plan, views, rows, region_num, bias, min_rows=0):
+    """The gate of MLR inside the autograd step (models/mlr.py), _ffm_on_hip's: on the GPU, with gradients enabled, HIP_AUTOGRAD_OPS on,
+    at least ``min_rows`` rows, K <= 64 and every view the column of its fused table, returns the inputs of ops.MLRFunction —
+    dctr_mlr_fwd forward and dctr_mlr_bwd backward, one launch each in place of K gathers and index-put backwards per feature — else
+    None: the torch ops of _mlr_output."""
+    tables = [f["master"] for f in plan if f["master"] is not None]
+    if not (torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and rows >= min_rows
+            and all(m.is_cuda and m.dtype == torch.float32 for m in tables) and ops.mlr_supported(region_num, bias)):
+        return None
+    return ops.MLRFunction.inputs_of(plan, views)
 
 
 def senet_bilinear(model, xcat):
@@ -1302,7 +1359,17 @@ def _fit_torch(model, staged, yt, n_tr, bs, epochs, shuffle, epoch_end, wt=None,
                     continue
                 model._begin()
                 logit = model_logits(model, staged, int(lo), int(hi), training=True)
-                if loss_name in ("binary_crossentropy", "logloss") and model.task == "binary":
+                if getattr(model, "output_kind", "logit") == "prediction":
+                    # the model's output is not the sigmoid of a logit (MLR): Keras then clips the probability and takes the logs, so a
+                    # clamped row has zero gradient — the formula `shown` has below, differentiated as written (Keras' + 1e-7 inside
+                    # the logs is left out there too)
+                    if loss_name in ("binary_crossentropy", "logloss") and model.task == "binary":
+                        pc = logit.clamp(1e-7, 1.0 - 1e-7)
+                        loss = -(yt[lo:hi] * torch.log(pc) + (1.0 - yt[lo:hi]) * torch.log(1.0 - pc))
+                    else:
+                        loss = torch.nn.functional.mse_loss(logit, yt[lo:hi], reduction="none")
+                    shown = loss.detach()
+                elif loss_name in ("binary_crossentropy", "logloss") and model.task == "binary":
                     # gradient (p - y) / B from the logit; the VALUE as keras' backend.binary_crossentropy reports it on probabilities
                     # (clipped to [1e-7, 1 - 1e-7]: a saturated row costs 16.1, not |logit|) — the pair the HIP step's dctr_bce_grad forms
                     loss = torch.nn.functional.binary_cross_entropy_with_logits(logit, yt[lo:hi], reduction="none")

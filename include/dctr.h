@@ -702,6 +702,94 @@ int dctr_ffm_bwd_route(const dctr_ffm_bwd_args_t* args);
 int dctr_ffm_bwd(const dctr_ffm_bwd_args_t* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MLR (mixed logistic regression, piece-wise linear model) — deepctr/models/mlr.py:17-74 (no layer class in the reference)
+ *     R = region_num >= 2 pieces.  K = 2R (+ 1 with has_bias) linear logits per sample, in the column order region 0..R-1,
+ *     learner R..2R-1, bias 2R.  A feature's K one-wide tables are stored as ONE row [vocab, row_pitch]: the reference's
+ *     region_<r>0sparse_emb_<name>/embeddings is the strided view [:, c:c+1].  A field adds the first `width` floats of its row (the row
+ *     of the sample's id; the sample index for identity != 0: a VarLenSparseFeat pre-pooled by dctr_embed_pool) to the columns
+ *     col0 .. col0 + width - 1.  Per sample:
+ *         z[c]   = sum over the fields covering c of row[c - col0], in field order, + sum_k dense[k] * dense_w[k * K + c]
+ *         s      = softmax(z[0 .. R-1])            (the row maximum subtracted)
+ *         a[r]   = sigmoid(z[R + r])               (learner_act = DCTR_MLR_LEARNER_SIGMOID: task 'binary'; _LINEAR: a[r] = z[R + r])
+ *         out    = sum_r s[r] * a[r]               (* sigmoid(z[2R]) with has_bias)
+ *     out is the model's PREDICTION: nothing follows it.  z (optional) is what dctr_mlr_bwd reads.
+ *     One lane per column, a group of 8 / 16 / 32 / 64 lanes per sample: a (sample, field) row is one contiguous request, softmax and
+ *     the sums run on cross-lane moves inside the group; no LDS, no barrier, no workspace.  fp32 throughout.
+ *     An id outside [0, vocab) raises DCTR_STATUS_INDEX_OOR and counts as a row of zeros; nothing outside the tables is read.
+ *     K <= 64 (region_num <= 31 with a bias part, 32 without); beyond that dctr_mlr_fwd / dctr_mlr_bwd answer DCTR_E_UNSUPPORTED before
+ *     anything is launched (dctr_mlr_supported: 1 / 0, host only, reads region_num and has_bias only).
+ *     Argument errors (nothing launched or written): NULL args / out / fields with n_fields > 0 / dense or dense_w with n_dense > 0
+ *     (DCTR_E_NULL); region_num < 2, negative batch / n_fields / n_dense / z_offset, out_stride < 1, dense_stride < n_dense,
+ *     z_stride < z_offset + K (DCTR_E_DIM); has_bias not 0 / 1, unknown learner_act (DCTR_E_ENUM); a fields array that is not 8-byte
+ *     aligned (DCTR_E_ALIGN).  Field contents (col0 / width inside [0, K]) live on the device and are the caller's contract.
+ * ------------------------------------------------------------------------------------------------ */
+enum { DCTR_MLR_LEARNER_SIGMOID = 0, DCTR_MLR_LEARNER_LINEAR = 1 };
+#define DCTR_MLR_MAX_COLUMNS 64
+typedef struct {
+    const float* rows;            /* [vocab, row_pitch] fp32: the fused rows (or the pre-pooled buffer), already advanced to the field's first column */
+    const void* ids;              /* sample b's id at ids[b * ids_stride]; unused when identity */
+    int64_t vocab;
+    int64_t row_pitch;            /* floats between rows, >= width */
+    int64_t ids_stride;           /* elements */
+    int32_t ids_is_i64;           /* 0: int32 ids, 1: int64 ids */
+    int32_t identity;             /* 1: row = sample index b */
+    int32_t col0;                 /* first logit column the field adds to, 0 <= col0 */
+    int32_t width;                /* columns it adds to, col0 + width <= K */
+} dctr_mlr_field_t;
+typedef struct {
+    const dctr_mlr_field_t* fields;   /* DEVICE array [n_fields]; may be NULL when n_fields = 0 */
+    int64_t batch;
+    int32_t n_fields;             /* >= 0 */
+    int32_t region_num;           /* R >= 2 */
+    int32_t has_bias;             /* 0 | 1 */
+    int32_t learner_act;          /* DCTR_MLR_LEARNER_* */
+    int32_t n_dense;              /* columns of the dense matrix (0 = none) */
+    int32_t reserved;             /* 0 */
+    const float* dense;           /* [B, dense_stride] or NULL */
+    int64_t dense_stride;
+    const float* dense_w;         /* [n_dense, K] row-major: zeros where a logit does not use a dense column */
+    float* out;                   /* sample b's prediction at out[b * out_stride] */
+    int64_t out_stride;           /* >= 1 */
+    float* z;                     /* NULL, or row b at z + b * z_stride + z_offset: K floats; other columns are not touched */
+    int64_t z_stride;
+    int64_t z_offset;             /* >= 0 */
+    int32_t* status;              /* optional device word, DCTR_STATUS_* bits are OR-ed in */
+} dctr_mlr_args_t;
+int dctr_mlr_supported(const dctr_mlr_args_t* args);      /* host only: 1 when K <= DCTR_MLR_MAX_COLUMNS, else 0 */
+int dctr_mlr_fwd(const dctr_mlr_args_t* args, void* stream);
+
+/* Backward of dctr_mlr_fwd, one launch, ONE route, no workspace (nothing to query: every intermediate lives in a lane group's
+ * registers).  fwd: fields, batch, n_fields, region_num, has_bias, learner_act, status are read as the forward reads them; fwd.z /
+ * z_stride / z_offset is the z the forward SAVED (read, REQUIRED); out, dense and dense_w are ignored (the dense weights' gradient is
+ * dense^T dz: the caller's matmul).  With d = d_out[b * d_out_stride], s / a as the forward, u = sum_r s[r] a[r], g = sigmoid(z[2R])
+ * (1 without a bias part):
+ *     dz[r]      = d g s[r] (a[r] - u)                                 r < R
+ *     dz[R + r]  = d g s[r] a[r] (1 - a[r])        (_LINEAR: d g s[r])
+ *     dz[2R]     = d u g (1 - g)
+ * dz row b is written to dz + b * dz_stride (K floats; REQUIRED).  Then, per field, the slice dz[col0 .. col0 + width) goes where
+ * grads[f] says (grads may be NULL: no field gradient at all):
+ *   a table field: ACCUMULATED with float atomics into [vocab, row_stride] at the row of the sample's id (zero it first; last bits may
+ *     differ from call to call) — one row per (sample, field), one dword per lane; columns behind `width` are never touched;
+ *   an identity (pre-pooled) field: plain stores into the first `width` floats of row b of a [batch, row_stride] buffer;
+ *   grad = NULL (a frozen field): skipped.
+ * An id outside [0, vocab) receives no gradient and raises DCTR_STATUS_INDEX_OOR.  Argument errors as the forward (plus DCTR_E_NULL
+ * for a missing z / d_out / dz, DCTR_E_DIM for d_out_stride < 1 or dz_stride < K); nothing is launched or written then. */
+typedef struct {
+    float* grad;                  /* table field: [vocab, row_stride], ACCUMULATED into, already advanced to the field's first column;
+                                     identity field: [batch, row_stride], written; NULL: skipped */
+    int64_t row_stride;           /* floats between rows, >= width */
+} dctr_mlr_grad_t;
+typedef struct {
+    dctr_mlr_args_t fwd;
+    const float* d_out;           /* sample b's gradient at d_out[b * d_out_stride] */
+    int64_t d_out_stride;         /* >= 1 */
+    float* dz;                    /* [B, dz_stride], K floats written per row */
+    int64_t dz_stride;            /* >= K */
+    const dctr_mlr_grad_t* grads; /* DEVICE array [n_fields], in field order; NULL: no field gradients */
+} dctr_mlr_bwd_args_t;
+int dctr_mlr_bwd(const dctr_mlr_bwd_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * IFM / DIFM: the input-aware factor, the refined FM and linear terms, the prediction — deepctr/models/ifm.py:55-72, difm.py:59-80
  *     F >= 1 fields of one embedding_dim d, read in place from the leading F*d columns of x (e.g. dnn_in) at x_stride.  Per sample b:
  *       m'[f] = mprime[b, f] (0 when NULL) + sum over the n_src sources of act[b, 0..K) . kernel[0..K, f]   (Keras layout [K, F], no bias)
