@@ -257,6 +257,15 @@ ifm.Args = type("Args", (ctypes.Structure,), {"_fields_": [
     ("factor_stride", c_i64), ("status", c_vp), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
 
 
+# dctr_ifm_bwd_args_t (tests/test_ifm_bwd_oracle_cpu.py checks the layout)
+ifm.BwdArgs = type("BwdArgs", (ctypes.Structure,), {"_fields_": [
+    ("batch", c_i64), ("n_fields", c_i32), ("dim", c_i32), ("x", c_vp), ("x_stride", c_i64), ("factor", c_vp), ("factor_stride", c_i64),
+    ("terms", c_vp), ("terms_stride", c_i64), ("d_out", c_vp), ("n_src", c_i32), ("softmax", c_i32), ("src", ifm.Src * 2),
+    ("dx", c_vp), ("dx_stride", c_i64), ("dterms", c_vp), ("dterms_stride", c_i64), ("dmprime", c_vp), ("dmprime_stride", c_i64),
+    ("dact", c_vp * 2), ("dact_stride", c_i64 * 2), ("dkernel", c_vp * 2), ("dkernel_stride", c_i64 * 2), ("slices", c_i32),
+    ("reserved", c_i32), ("workspace", c_vp), ("workspace_bytes", c_sz)]})
+
+
 class fieldwise(object):
     """dctr_fieldwise_group_t / dctr_fieldwise_args_t / dctr_fieldwise_bwd_args_t, one level down for the same reason as
     interacting.Args (tests/test_flen_cpu.py checks the layout)."""
@@ -541,6 +550,9 @@ SYMBOLS = {
     "dctr_ifm_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_route": (ctypes.c_int, [ctypes.POINTER(ifm.Args)]),
     "dctr_ifm_fwd": (ctypes.c_int, [ctypes.POINTER(ifm.Args), c_vp]),
+    "dctr_ifm_bwd_supported": (ctypes.c_int, [ctypes.POINTER(ifm.BwdArgs)]),
+    "dctr_ifm_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(ifm.BwdArgs)]),
+    "dctr_ifm_bwd": (ctypes.c_int, [ctypes.POINTER(ifm.BwdArgs), c_vp]),
     "dctr_fieldwise_route": (ctypes.c_int, [ctypes.POINTER(fieldwise.Args)]),
     "dctr_fieldwise_fwd": (ctypes.c_int, [ctypes.POINTER(fieldwise.Args), c_vp]),
     "dctr_fieldwise_bwd_supported": (ctypes.c_int, [ctypes.POINTER(fieldwise.BwdArgs)]),

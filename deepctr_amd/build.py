@@ -59,6 +59,7 @@ SOURCES = [
     "mlr_kernels.hip",
     "mlr_bwd_kernels.hip",
     "ifm_kernels.hip",
+    "ifm_bwd_kernels.hip",
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",
     "mtl_kernels.hip",

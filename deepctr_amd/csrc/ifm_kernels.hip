@@ -17,21 +17,11 @@
 // groups of dp = pow2(d) lanes, group g walks the fields g, g + G, ... with a lane per embedding column, so a wave reads 256
 // contiguous bytes of the row per step; the groups meet in xor-shuffles.  m is formed where it is used and reaches HBM only through
 // factor_out.  An id outside [0, vocab) raises DCTR_STATUS_INDEX_OOR and contributes zero; nothing outside the tables is read.
-#include <math.h>
-#include <stdint.h>
-#include "dctr_common.h"
-#include "tile_route.h"
+#include "ifm_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int IFM_THREADS = 256;
-constexpr int IFM_ROWS = 16;                      // samples of a wave
-constexpr int IFM_WG_ROWS = 64;                   // samples of a workgroup
-constexpr int IFM_KC = 64;                        // source columns per LDS chunk
-constexpr int IFM_APITCH = IFM_KC + 4;            // bank = 4 * row + k-slot: the 64 operand reads of an MFMA hit 64 banks
-constexpr int IFM_SMALL_WG_BELOW = 2;             // one-wave workgroups while four-wave ones would number fewer than this many per CU
+using namespace dctr_ifm;
 
 enum { IFM_FUSED = 0, IFM_PROJECT = 1, IFM_EPILOGUE = 2 };
 
@@ -54,18 +44,6 @@ struct IfmParams {
     int64_t factor_stride;
     int32_t* status;
 };
-
-__device__ __forceinline__ float ifm_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float ifm_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // m' of the wave's 16 samples: columns [0, F) to dst (LDS tile or workspace rows), row pitch dst_pitch.  Every wave of the workgroup
 // runs the same trip counts (the barriers are workgroup-wide); samples past the batch enter as zeros and are not stored to global.
@@ -299,8 +277,7 @@ extern "C" int dctr_ifm_fwd(const dctr_ifm_args_t* a, void* stream) {
     p.batch = a->batch;
     p.F = a->n_fields;
     p.d = a->dim;
-    p.dp = 1;
-    while (p.dp < a->dim && p.dp < 64) p.dp <<= 1;
+    p.dp = ifm_group_lanes(a->dim);
     p.Fpad = (a->n_fields + 15) / 16 * 16;
     p.x = a->x;
     p.x_stride = a->x_stride;

@@ -50,6 +50,13 @@ class _DIFM(InputAwareModel):
         att = tops.interacting_stack([self.att], x)
         return att.reshape(att.shape[0], -1) @ self.dense.w("kernel") + h @ self.dense_1.w("kernel")
 
+    def _factor_sources(self, x, h):
+        att = tops.interacting_stack([self.att], x)
+        return [(att.reshape(att.shape[0], -1), self.dense.w("kernel")), (h, self.dense_1.w("kernel"))], False
+
+    def _hip_min_rows(self):
+        return tops.DIFM_HIP_MIN_ROWS
+
     def _forward(self, staged, lo, hi, out):
         ws, bufs, add, desc = self._stage_run(staged, lo, hi)
         ops.interacting(ws["dnn_in"], [self.att.weights_qkvr], self.att_embedding_size, self.att_head_num, self.att_res, True,

@@ -12,7 +12,11 @@ Unlike the reference, a linear part whose number of sparse / sequence features i
 model is built (the reference fails in the first batch with a broadcast error, or broadcasts silently when one of the counts is 1).
 
 Forward: fused gather -> dnn_in (= the F*d embedding columns; the dense linear term as its own [B] vector) -> the DNN kernel, last
-hidden layer to HBM -> ONE ``dctr_ifm_fwd`` launch: factor projection, softmax, refined FM and linear terms, bias, sigmoid."""
+hidden layer to HBM -> ONE ``dctr_ifm_fwd`` launch: factor projection, softmax, refined FM and linear terms, bias, sigmoid.
+
+fit() runs the autograd step; in it the factor projection, the softmax, the refined FM and the refined first-order terms are one
+differentiable HIP op (``training.input_aware_fm``: dctr_ifm_fwd forward, dctr_ifm_bwd backward) from ``training.IFM_HIP_MIN_ROWS`` rows
+on (DIFM: ``DIFM_HIP_MIN_ROWS``), and the torch ops of ``_autograd_logit`` everywhere else (profiles/ifm_bwd.txt)."""
 from collections import OrderedDict
 
 import numpy as np
@@ -157,6 +161,9 @@ class InputAwareModel(FeatureModel):
     def _autograd_logit(self, staged, lo, hi, parts, extra, training):       # ifm.py:55-72, difm.py:59-80
         x = torch.stack(parts[:self.n_fields], dim=1)              # [B,F,d]
         h = tops.dnn_forward(self.dnn, x.reshape(x.shape[0], -1), training)
+        if tops._ifm_on_hip(x, self._hip_min_rows()):              # one differentiable HIP op: dctr_ifm_fwd / dctr_ifm_bwd
+            sources, softmax = self._factor_sources(x, h)
+            return tops.input_aware_fm(x, sources, softmax, terms=self.linear_terms(staged, lo, hi))
         m = self._autograd_factor(x, h)
         r = x * m.unsqueeze(-1)
         logit = 0.5 * (r.sum(1).pow(2) - (r * r).sum(1)).sum(-1)
@@ -202,6 +209,12 @@ class _IFM(InputAwareModel):
 
     def _autograd_factor(self, x, h):
         return x.shape[1] * torch.softmax(h @ self.dense.w("kernel"), dim=1)
+
+    def _factor_sources(self, x, h):
+        return [(h, self.dense.w("kernel"))], True
+
+    def _hip_min_rows(self):
+        return tops.IFM_HIP_MIN_ROWS
 
     def _forward(self, staged, lo, hi, out):
         ws, bufs, add, desc = self._stage_run(staged, lo, hi)

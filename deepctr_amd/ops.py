@@ -5,6 +5,7 @@ Every function requires HIP-resident tensors and the built extension; nothing he
 the CPU and nothing falls back to eager PyTorch math.
 """
 import ctypes
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -1888,7 +1889,171 @@ def ifm(x, fields, dim, sources=(), mprime=None, softmax=False, lin=(), add=(), 
     return out
 
 
-_FIELDWISE_ROUTES = {None: _C.fieldwise.ROUTE_AUTO, "auto": _C.fieldwise.ROUTE_AUTO, "reread": _C.fieldwise.ROUTE_REREAD}
+def _ifm_bwd_shape(batch, fields, dim, Ks=(), dmprime=False, dact=True, dkernel=True, slices=0):
+    """dctr_ifm_bwd_args_t of the shapes alone, for the host-only queries: a wanted output is any non-NULL pointer."""
+    F, d = int(fields), int(dim)
+    if F < 1 or d < 1:
+        raise ValueError("ifm_bwd: fields = %d, dim = %d" % (F, d))
+    if len(Ks) > 2:
+        raise ValueError("ifm_bwd: %d factor sources: 0, 1 or 2" % len(Ks))
+    b = _C.ifm.BwdArgs(batch=int(batch), n_fields=F, dim=d, x_stride=F * d, factor_stride=F, n_src=len(Ks), slices=int(slices))
+    if dmprime:
+        b.dmprime, b.dmprime_stride = 16, F
+    for s, K in enumerate(Ks):
+        b.src[s].K, b.src[s].act_stride = int(K), int(K)
+        if dact:
+            b.dact[s], b.dact_stride[s] = 16, int(K)
+        if dkernel:
+            b.dkernel[s], b.dkernel_stride[s] = 16, F
+    return b
+
+
+def ifm_bwd_supported(fields, dim):
+    """Does dctr_ifm_bwd take these shapes (read from the library: a row of ``fields`` floats has to fit the LDS)?"""
+    if int(fields) < 1 or int(dim) < 1:
+        return False
+    return bool(_C.lib().dctr_ifm_bwd_supported(ctypes.byref(_C.ifm.BwdArgs(batch=1, n_fields=int(fields), dim=int(dim)))))
+
+
+def ifm_bwd_workspace_bytes(batch, fields, dim, Ks=(), dmprime=False, dact=True, dkernel=True, slices=0):
+    """Bytes of workspace dctr_ifm_bwd needs (read from the library): ``Ks`` = K per factor source; ``dmprime`` / ``dact`` / ``dkernel``:
+    is that gradient wanted (dm' waits in the workspace when a source's gradient is wanted and dmprime is not; the dkernel partials
+    of ``slices`` batch slices, 0 = the library's choice)."""
+    return int(_C.lib().dctr_ifm_bwd_workspace_bytes(ctypes.byref(_ifm_bwd_shape(batch, fields, dim, Ks, dmprime, dact, dkernel, slices))))
+
+
+def _ifm_bwd_out(name, want, rows, cols, device):
+    """An output of ifm_bwd: None / False (not wanted), True (allocated here) or the caller's float32 2-D view -> (tensor, row stride)."""
+    if want is None or want is False:
+        return None, 0
+    if want is True:
+        want = torch.empty(rows, cols, dtype=torch.float32, device=device)
+    return want, _rows2d("ifm_bwd", name, want, rows, cols)
+
+
+def ifm_bwd(x, fields, dim, factor, d_out, sources=(), terms=None, softmax=False, dx=None, dterms=None, dmprime=None, dact=None,
+            dkernel=None, slices=0, workspace=None):
+    """Backward of the differentiable part of ifm() (include/dctr.h: dctr_ifm_bwd): the logit without add vectors, bias and sigmoid.
+    ``x`` / ``fields`` / ``dim`` / ``sources`` / ``softmax`` as ifm(); ``factor`` [B, >= fields]: the m the forward wrote to
+    factor_out; ``terms`` [B, >= fields] or None: the first-order terms by position; ``d_out`` [B].  Outputs — each None / False (not
+    wanted, its work is skipped), True (allocated here) or a float32 2-D view that is OVERWRITTEN in its leading columns: ``dx``
+    [B, >= fields*dim], ``dterms`` and ``dmprime`` [B, >= fields], and per source ``dact[s]`` [B, >= K_s] and ``dkernel[s]``
+    [K_s, >= fields].  ``slices``: the batch slices of the dkernel sum (0: the library's choice, 1 .. 256 forces it).  No atomics:
+    bit-identical from call to call.  Returns (dx, dterms, dmprime, [dact], [dkernel])."""
+    F, d = int(fields), int(dim)
+    B = int(x.shape[0])
+    sources = list(sources)
+    if len(sources) > 2:
+        raise ValueError("ifm_bwd: %d factor sources: 0, 1 or 2" % len(sources))
+    if not 0 <= int(slices) <= 256:
+        raise ValueError("ifm_bwd: slices = %d: 0 or 1 .. 256" % int(slices))
+    b = _C.ifm.BwdArgs(batch=B, n_fields=F, dim=d, n_src=len(sources), softmax=int(bool(softmax)), slices=int(slices))
+    b.x, b.x_stride = x.data_ptr(), _rows2d("ifm_bwd", "x", x, B, F * d)
+    b.factor, b.factor_stride = factor.data_ptr(), _rows2d("ifm_bwd", "factor", factor, B, F)
+    if terms is not None:
+        b.terms, b.terms_stride = terms.data_ptr(), _rows2d("ifm_bwd", "terms", terms, B, F)
+    _vec("ifm_bwd", "d_out", d_out, B)
+    b.d_out = d_out.data_ptr()
+    dev = x.device
+    dx, b.dx_stride = _ifm_bwd_out("dx", dx, B, F * d, dev)
+    dterms, b.dterms_stride = _ifm_bwd_out("dterms", dterms, B, F, dev)
+    dmprime, b.dmprime_stride = _ifm_bwd_out("dmprime", dmprime, B, F, dev)
+    for t, n in ((dx, "dx"), (dterms, "dterms"), (dmprime, "dmprime")):
+        if t is not None:
+            setattr(b, n, t.data_ptr())
+    dact = list(dact) if dact is not None else [None] * len(sources)
+    dkernel = list(dkernel) if dkernel is not None else [None] * len(sources)
+    if len(dact) != len(sources) or len(dkernel) != len(sources):
+        raise ValueError("ifm_bwd: dact / dkernel take one entry per factor source (%d)" % len(sources))
+    keep = []
+    for s, (act, kernel) in enumerate(sources):
+        act_stride = _rows2d("ifm_bwd", "a source's act", act, B, 1)
+        K = int(act.shape[1])
+        if kernel.dtype != torch.float32 or tuple(kernel.shape) != (K, F):
+            raise ValueError("ifm_bwd: source %d: kernel must be float32 [%d, %d], got %s" % (s, K, F, tuple(kernel.shape)))
+        kernel = _f32c(kernel, "kernel")
+        keep.append(kernel)
+        b.src[s].act, b.src[s].act_stride, b.src[s].K, b.src[s].kernel = act.data_ptr(), act_stride, K, kernel.data_ptr()
+        dact[s], b.dact_stride[s] = _ifm_bwd_out("dact[%d]" % s, dact[s], B, K, dev)
+        dkernel[s], b.dkernel_stride[s] = _ifm_bwd_out("dkernel[%d]" % s, dkernel[s], K, F, dev)
+        if dact[s] is not None:
+            b.dact[s] = dact[s].data_ptr()
+        if dkernel[s] is not None:
+            b.dkernel[s] = dkernel[s].data_ptr()
+    _dev_check(x, factor, terms, d_out, dx, dterms, dmprime, workspace, *(dact + dkernel + keep + [s_[0] for s_ in sources]))
+    _workspace("ifm_bwd", b, int(_C.lib().dctr_ifm_bwd_workspace_bytes(ctypes.byref(b))), workspace, dev)
+    _C.check(_C.lib().dctr_ifm_bwd(ctypes.byref(b), _C.stream_ptr()), "dctr_ifm_bwd")
+    del keep
+    return dx, dterms, dmprime, dact, dkernel
+
+
+_IFM_TERM_DESCS = OrderedDict()
+
+
+def _ifm_term_columns(terms, F):
+    """The dctr_ifm_lin_t array that hands ifm() the columns of ``terms`` [B, F] as F pre-pooled vectors at vec_stride = its row stride.
+    The array is a function of (pointer, F, row stride, device) alone: cached on them."""
+    stride = row_stride(terms)
+    key = (terms.data_ptr(), F, stride, str(terms.device))
+    desc = _IFM_TERM_DESCS.get(key)
+    if desc is None:
+        arr = (_C.ifm.Lin * F)()
+        for k in range(F):
+            arr[k].vec, arr[k].vec_stride = terms.data_ptr() + 4 * k, stride
+        while len(_IFM_TERM_DESCS) >= 64:
+            _IFM_TERM_DESCS.popitem(last=False)
+        desc = _IFM_TERM_DESCS[key] = _upload(arr, terms.device)
+    return desc
+
+
+class InputAwareFMFunction(torch.autograd.Function):
+    """The input-aware FM of IFM / DIFM as one differentiable op (once differentiable): ifm() forward with the factor kept, ifm_bwd()
+    backward.  ``apply(x, terms, mprime, softmax, *flat)``: x [B,F,d]; ``terms`` [B,F] (the first-order terms by position) or None;
+    ``mprime`` [B,F] or None; ``flat`` = act_0, kernel_0 (, act_1, kernel_1): the factor sources.  Returns the logit [B] without the
+    unrefined tail (no add vectors, no bias, no sigmoid).  Gradients are formed only for the inputs that need them; none leaves
+    through atomics."""
+
+    @staticmethod
+    def forward(ctx, x, terms, mprime, softmax, *flat):
+        ctx.set_materialize_grads(False)
+        if x.dim() != 3 or len(flat) not in (0, 2, 4):
+            raise ValueError("InputAwareFMFunction: x must be [B,F,d] and the sources (act, kernel) pairs")
+        B, F, d = x.shape
+        x2 = _f32c(x.detach(), "x").view(B, F * d)
+        srcs = [(_grad_operand(flat[i].detach(), True), _f32c(flat[i + 1].detach(), "kernel")) for i in range(0, len(flat), 2)]
+        t = None if terms is None else _grad_operand(terms.detach(), True)
+        mp = None if mprime is None else _grad_operand(mprime.detach(), True)
+        factor = torch.empty(B, F, dtype=torch.float32, device=x.device)
+        lin_desc = None if t is None else _ifm_term_columns(t, F)
+        out = ifm(x2, F, d, sources=srcs, mprime=mp, softmax=softmax, lin=() if t is None else (None,) * F, lin_desc=lin_desc,
+                  factor_out=factor, sigmoid_out=False)
+        ctx.softmax, ctx.n_src, ctx.has_terms, ctx.shape = bool(softmax), len(srcs), t is not None, (B, F, d)
+        ctx.save_for_backward(x2, factor, *([t] if t is not None else []), *[v for s in srcs for v in s])
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        B, F, d = ctx.shape
+        n = 4 + 2 * ctx.n_src
+        if d_out is None:
+            return (None,) * n
+        saved = list(ctx.saved_tensors)
+        x2, factor = saved[0], saved[1]
+        t = saved[2] if ctx.has_terms else None
+        flat = saved[3 if ctx.has_terms else 2:]
+        srcs = [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
+        need = ctx.needs_input_grad
+        dx, dterms, dmprime, dact, dkernel = ifm_bwd(
+            x2, F, d, factor, _grad_operand(d_out, False), sources=srcs, terms=t, softmax=ctx.softmax, dx=bool(need[0]),
+            dterms=bool(need[1]) and t is not None, dmprime=bool(need[2]), dact=[bool(need[4 + 2 * s]) for s in range(ctx.n_src)],
+            dkernel=[bool(need[5 + 2 * s]) for s in range(ctx.n_src)])
+        ret = [None if dx is None else dx.view(B, F, d), dterms, dmprime, None]
+        for s in range(ctx.n_src):
+            ret += [dact[s], dkernel[s]]
+        return tuple(ret)
+
+
+_FIELDWISE_ROUTES ={None: _C.fieldwise.ROUTE_AUTO, "auto": _C.fieldwise.ROUTE_AUTO, "reread": _C.fieldwise.ROUTE_REREAD}
 _FIELDWISE_TABLES = {}
 
 

@@ -388,6 +388,34 @@ def _ffm_on_hip(masters, views, rows, min_rows=0):
 MLR_HIP_MIN_ROWS = 0
 
 
+# Below this many rows IFM's / DIFM's autograd step keeps the torch ops of InputAwareModel._autograd_logit.  From profiles/ifm_bwd.txt
+# (Criteo shape, two runs in one call, ms a step with the switch on and the op off / on):
+#   IFM   4,096 rows   6.88 / 6.45 and  6.43 / 5.10      65,536 rows  14.61 / 14.32 and 14.52 / 14.37
+#   DIFM  4,096 rows   7.49 / 7.83 and  6.62 / 7.05      65,536 rows  50.45 / 51.04 and 50.38 / 50.91
+# IFM's op is no slower at both row counts in both runs: no threshold.  DIFM's loses at both (0.94 - 0.96x and 0.99x): its K = 2,496
+# product and both of its gradients are three rocBLAS GEMMs on the torch route, and dctr_ifm_fwd + dctr_ifm_bwd's MFMA passes (a wave
+# per 16 samples reading kernel^T from L2, 0.97 ms for the backward alone at 65,536 rows) do not beat them.  The default keeps DIFM on
+# the torch ops behind an unreachable threshold; its attention stack stays on ops.InteractingFunction.
+IFM_HIP_MIN_ROWS = 0
+DIFM_HIP_MIN_ROWS = 1 << 62
+
+
+def _ifm_on_hip(x, min_rows=0):
+    """The gate of input_aware_fm inside the autograd step (models/ifm.py), worded as _fieldpair_on_hip: on the GPU, with gradients
+    enabled, HIP_AUTOGRAD_OPS on, float32, at least ``min_rows`` rows and a field count dctr_ifm_bwd takes.  x: [B,F,d]."""
+    return bool(x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32 and x.dim() == 3
+                and x.shape[0] >= min_rows and ops.ifm_bwd_supported(x.shape[1], x.shape[2]))
+
+
+def input_aware_fm(x, sources, softmax, terms=None, mprime=None):
+    """The input-aware FM over x [B,F,d] inside the autograd step as ONE differentiable op (ops.InputAwareFMFunction: dctr_ifm_fwd
+    forward with the factor kept, dctr_ifm_bwd backward): ``sources`` = the (act [B,K], kernel [K,F]) pairs whose products sum to m',
+    m = F * softmax(m') with ``softmax`` else m', ``terms`` [B,F] the first-order terms by position or None.  Returns the logit [B]
+    without the unrefined tail.  The caller asks _ifm_on_hip first: there is no torch form of this entry."""
+    flat = [t for act, kernel in sources for t in (act, kernel)]
+    return ops.InputAwareFMFunction.apply(x, terms, mprime, bool(softmax), *flat)
+
+
 def _mlr_mix(z, region_num, bias, task):
     """z [B, K] (columns region 0..R-1, learner R..2R-1, bias 2R) -> MLR's prediction [B] (reference models/mlr.py:45-54)."""
     R = int(region_num)

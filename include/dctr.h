@@ -856,6 +856,61 @@ size_t dctr_ifm_workspace_bytes(const dctr_ifm_args_t* args);
 int dctr_ifm_route(const dctr_ifm_args_t* args);
 int dctr_ifm_fwd(const dctr_ifm_args_t* args, void* stream);
 
+/* Backward of the differentiable part of dctr_ifm_fwd: the logit without the unrefined tail (no add vectors, no bias, no sigmoid),
+ *     y[b] = 0.5 * sum_c ((sum_f m[f] e[f,c])^2 - sum_f (m[f] e[f,c])^2) + sum_f m[f] t[f]
+ * with t = terms [B, F], the first-order terms already gathered / pooled (NULL: none).  factor is the m the forward SAVED (its
+ * factor_out): nothing is projected again and no exponential is taken again.  With g = d_out[b]:
+ *     S[c]    = sum_f m[f] e[f,c]              u[f,c] = S[c] - m[f] e[f,c]
+ *     dm[f]   = sum_c e[f,c] u[f,c] + t[f]
+ *     dx[f,c] = g m[f] u[f,c]                  dterms[f] = g m[f]
+ *     dm'[f]  = softmax ? g m[f] (dm[f] - (1/F) sum_h m[h] dm[h]) : g dm[f]
+ *     dmprime = dm'          dact_s = dm' kernel_s^T  [B, K_s]          dkernel_s = act_s^T dm'  [K_s, F]  (a sum over the batch)
+ * Outputs: a NULL pointer means the gradient is not wanted and its work is skipped; every wanted output is OVERWRITTEN (never
+ * accumulated into) and nothing is written behind the width of a row (F*d of dx, F of dterms / dmprime / dkernel_s, K_s of dact_s).
+ * Launches, all on the caller's stream: the row pass (a wave per sample: dx, dterms, dm'), per wanted dact one MFMA pass (a wave per
+ * 16 samples), and for the wanted dkernel one MFMA pass over `S` batch slices into partials[S] in the workspace followed by a small
+ * launch that adds the S partials of every element in the order 0 .. S-1.  v_mfma_f32_16x16x4_f32 throughout (exact fp32), no float
+ * atomics: every output is bit-identical from call to call.  slices = 0: S is a function of the shapes alone; 1 .. 256 forces it.
+ * dx, dterms, dmprime and dact do not depend on S.
+ * Workspace (dctr_ifm_bwd_workspace_bytes: shapes, n_src, slices and which of dmprime / dact / dkernel are NULL are read): [B, F] floats
+ * of dm' when a dact or dkernel is wanted and dmprime is not, plus the partials when a dkernel is wanted; REQUIRED then (DCTR_E_NULL).
+ * dctr_ifm_bwd_supported: 1, or 0 where one row of pad16(F) floats exceeds the LDS (F > 40,960; n_fields and dim are read);
+ * dctr_ifm_bwd answers DCTR_E_UNSUPPORTED there.  Argument errors launch and write nothing: NULL args / x / factor / d_out, a wanted
+ * dact without the source's kernel or a wanted dkernel without its act (DCTR_E_NULL); n_fields or dim < 1, negative batch, F*d >= 2^27, a stride below its width, n_src outside
+ * 0 .. 2, K < 1, slices outside 0 .. 256 (DCTR_E_DIM); a workspace that is not 16-B aligned (DCTR_E_ALIGN). */
+typedef struct {
+    int64_t batch;
+    int32_t n_fields;             /* F >= 1 */
+    int32_t dim;                  /* d >= 1 */
+    const float* x;               /* [B, x_stride]: the forward's x */
+    int64_t x_stride;             /* floats, >= F*d */
+    const float* factor;          /* [B, factor_stride]: m, the forward's factor_out */
+    int64_t factor_stride;        /* floats, >= F */
+    const float* terms;           /* NULL, or [B, terms_stride]: the first-order terms by position */
+    int64_t terms_stride;         /* floats, >= F */
+    const float* d_out;           /* [B] */
+    int32_t n_src;                /* 0, 1 or 2 */
+    int32_t softmax;              /* 0 | 1: as the forward */
+    dctr_ifm_src_t src[2];        /* as the forward (act is read for dkernel, kernel for dact) */
+    float* dx;                    /* NULL, or [B, dx_stride]: F*d floats of a row written */
+    int64_t dx_stride;
+    float* dterms;                /* NULL, or [B, dterms_stride]: F floats of a row written */
+    int64_t dterms_stride;
+    float* dmprime;               /* NULL, or [B, dmprime_stride]: dm', F floats of a row written */
+    int64_t dmprime_stride;
+    float* dact[2];               /* NULL, or [B, dact_stride[s]]: K_s floats of a row written */
+    int64_t dact_stride[2];
+    float* dkernel[2];            /* NULL, or [K_s, dkernel_stride[s]]: F floats of a row written */
+    int64_t dkernel_stride[2];
+    int32_t slices;               /* 0: the library's choice (a function of the shapes); 1 .. 256: that many batch slices for dkernel */
+    int32_t reserved;             /* 0 */
+    void* workspace;              /* NULL, or device scratch of dctr_ifm_bwd_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_ifm_bwd_args_t;
+int dctr_ifm_bwd_supported(const dctr_ifm_bwd_args_t* args);            /* host only: 1 / 0 */
+size_t dctr_ifm_bwd_workspace_bytes(const dctr_ifm_bwd_args_t* args);   /* host only; 0 for arguments dctr_ifm_bwd refuses */
+int dctr_ifm_bwd(const dctr_ifm_bwd_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FieldWiseBiInteraction.call (FLEN) — deepctr/layers/interaction.py:1224-1348, one launch
  *     x [B, x_stride] read in place from column x_offset; G >= 2 embedding groups, group g = n_fields fields of width dim from column
