@@ -303,6 +303,15 @@ class edcn(object):
                     ("out_offset", c_i64), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+# dctr_edcn_train_args_t (tests/test_edcn_bwd_oracle_cpu.py checks the layout)
+edcn.BWD_MAX_ROUNDS = 32
+edcn.TrainArgs = type("TrainArgs", (ctypes.Structure,), {"_fields_": [
+    ("fwd", edcn.Args), ("tape", c_vp), ("d_logit", c_vp), ("d_out", c_vp), ("d_out_stride", c_i64), ("dx", c_vp), ("dx_stride", c_i64),
+    ("dx_offset", c_i64), ("accumulate", c_i32), ("slices", c_i32), ("d_gates", c_vp), ("d_cross_w", c_vp), ("d_cross_b", c_vp),
+    ("d_dnn_w", c_vp), ("d_dnn_b", c_vp), ("d_bridge_w", c_vp), ("d_bridge_b", c_vp), ("d_head_w", c_vp), ("workspace", c_vp),
+    ("workspace_bytes", c_sz)]})
+
+
 class transformer(object):
     """dctr_transformer_args_t, one level down for the same reason as interacting.Args (tests/test_bst_cpu.py checks the layout)."""
     OUT_NONE, OUT_MEAN, OUT_SUM = 0, 1, 2
@@ -560,6 +569,11 @@ SYMBOLS = {
     "dctr_edcn_workspace_bytes": (c_sz, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_route": (ctypes.c_int, [ctypes.POINTER(edcn.Args)]),
     "dctr_edcn_fwd": (ctypes.c_int, [ctypes.POINTER(edcn.Args), c_vp]),
+    "dctr_edcn_bwd_supported": (ctypes.c_int, [ctypes.POINTER(edcn.TrainArgs)]),
+    "dctr_edcn_tape_bytes": (c_sz, [ctypes.POINTER(edcn.TrainArgs)]),
+    "dctr_edcn_bwd_workspace_bytes": (c_sz, [ctypes.POINTER(edcn.TrainArgs)]),
+    "dctr_edcn_train_fwd": (ctypes.c_int, [ctypes.POINTER(edcn.TrainArgs), c_vp]),
+    "dctr_edcn_bwd": (ctypes.c_int, [ctypes.POINTER(edcn.TrainArgs), c_vp]),
     "dctr_transformer_workspace_bytes": (c_sz, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_route": (ctypes.c_int, [ctypes.POINTER(transformer.Args)]),
     "dctr_transformer_fwd": (ctypes.c_int, [ctypes.POINTER(transformer.Args), c_vp]),

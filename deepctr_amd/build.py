@@ -62,6 +62,7 @@ SOURCES = [
     "ifm_bwd_kernels.hip",
     "fieldwise_kernels.hip",
     "edcn_kernels.hip",
+    "edcn_bwd_kernels.hip",
     "mtl_kernels.hip",
     "mtl_bwd_kernels.hip",
     "transformer_kernels.hip",

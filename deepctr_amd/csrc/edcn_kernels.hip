@@ -26,13 +26,10 @@
 #include "dctr_common.h"
 #include "tile_route.h"
 #include "mfma_tile.h"
+#include "edcn_device.h"
 
 namespace {
 
-constexpr int ED_THREADS = 512;
-constexpr int ED_WAVES = ED_THREADS / 64;
-constexpr int ED_MAX_ROUNDS = 32;                 // rounds per launch (kernel-argument space)
-constexpr size_t ED_LDS_TARGET = 80 * 1024;       // two workgroups per CU where the rows allow it
 constexpr int ED_EW_THREADS = 256;
 constexpr int ED_GATE_LDS_FIELDS = 8192;          // dctr_edcn_regulate keeps its gates in LDS up to this many fields
 
@@ -55,38 +52,11 @@ struct EdParams {
     float* out;                   // already advanced by out_offset
     int64_t out_stride;
     float* br_out;                // chained launches: [B, D]
+    float* tape;                  // TAPE: [rounds, B, 3D], c / h / br of every round
 };
 
-__device__ __forceinline__ float ed_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float ed_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// softmax over the F values g * inv_tau by one wave -> G[F]
-__device__ __forceinline__ void ed_gate(const float* __restrict__ g, int F, float inv_tau, float* G, int lane) {
-    float m = -INFINITY;
-    for (int f = lane; f < F; f += 64) m = fmaxf(m, g[f] * inv_tau);
-    m = ed_wave_max(m);
-    float s = 0.f;
-    for (int f = lane; f < F; f += 64) {
-        const float e = expf(g[f] * inv_tau - m);
-        G[f] = e;
-        s += e;
-    }
-    s = ed_wave_sum(s);
-    for (int f = lane; f < F; f += 64) G[f] = G[f] / s;
-}
-
-__device__ __forceinline__ float ed_act(float v, int act) { return act == DCTR_ACT_RELU ? fmaxf(v, 0.f) : v; }
-
-template <int TPW>
+// TAPE: the training forward (dctr_edcn_train_fwd) also writes c, h, br of every round; the arithmetic is the inference kernel's
+template <int TPW, bool TAPE>
 __global__ __launch_bounds__(ED_THREADS) void edcn_fwd_kernel(EdParams p) {
     extern __shared__ __attribute__((aligned(16))) float ed_lds[];
     const int R = p.R, ld = p.ld, D = p.D, F = p.F, d = p.d;
@@ -202,6 +172,15 @@ __global__ __launch_bounds__(ED_THREADS) void edcn_fwd_kernel(EdParams p) {
                 }
             }
             __syncthreads();
+            if (TAPE) {         // (reads only: the next round's gating follows its own barrier)
+                for (int e = tid; e < nvalid * D; e += ED_THREADS) {
+                    const int r = e / D, k = e - r * D;
+                    float* o = p.tape + ((int64_t)i * p.batch + b0 + r) * (3 * (int64_t)D) + k;
+                    o[0] = C[r * ld + k];
+                    o[D] = H[r * ld + k];
+                    o[2 * (int64_t)D] = X1[r * ld + k];
+                }
+            }
         }
         if (p.out) {
             for (int e = tid; e < nvalid * D; e += ED_THREADS) {
@@ -313,61 +292,6 @@ __global__ __launch_bounds__(ED_EW_THREADS) void edcn_bridge_kernel(int kind, co
     }
 }
 
-struct EdPlan {
-    bool fused;
-    int R, ld, tpw;
-    size_t lds;
-    int launches;
-    size_t ws_bytes;
-};
-
-bool ed_fused_act(int act) { return act == DCTR_ACT_LINEAR || act == DCTR_ACT_RELU; }
-
-int edcn_check(const dctr_edcn_args_t* a) {
-    DCTR_REQUIRE(a, DCTR_E_NULL, "edcn_fwd: null args");
-    DCTR_REQUIRE(a->batch >= 0 && a->fields >= 1 && a->dim >= 1 && a->cross_num >= 1, DCTR_E_DIM,
-                 "edcn_fwd: batch = %lld, fields = %d, dim = %d, cross_num = %d", (long long)a->batch, a->fields, a->dim, a->cross_num);
-    const int64_t D = (int64_t)a->fields * a->dim;
-    DCTR_REQUIRE(D <= (1 << 24), DCTR_E_DIM, "edcn_fwd: fields * dim = %lld exceeds 2^24", (long long)D);
-    DCTR_REQUIRE(a->x_offset >= 0 && a->x_stride >= 0 && a->x_offset + D <= a->x_stride, DCTR_E_DIM,
-                 "edcn_fwd: columns [%lld, %lld) in rows of %lld", (long long)a->x_offset, (long long)(a->x_offset + D), (long long)a->x_stride);
-    DCTR_REQUIRE(a->mode == DCTR_CROSS_VECTOR || a->mode == DCTR_CROSS_MATRIX, DCTR_E_ENUM, "edcn_fwd: unknown parameterization %d", a->mode);
-    DCTR_REQUIRE(a->bridge >= DCTR_EDCN_BRIDGE_ADD && a->bridge <= DCTR_EDCN_BRIDGE_ATTENTION, DCTR_E_ENUM, "edcn_fwd: unknown bridge %d",
-                 a->bridge);
-    DCTR_REQUIRE(a->activation >= DCTR_ACT_LINEAR && a->activation <= DCTR_ACT_DICE && a->bridge_activation >= DCTR_ACT_LINEAR &&
-                     a->bridge_activation <= DCTR_ACT_DICE, DCTR_E_ENUM, "edcn_fwd: unknown activation %d / %d", a->activation,
-                 a->bridge_activation);
-    DCTR_REQUIRE(a->route >= DCTR_EDCN_ROUTE_AUTO && a->route <= DCTR_EDCN_ROUTE_LAYERED, DCTR_E_ENUM, "edcn_fwd: unknown route %d", a->route);
-    DCTR_REQUIRE(a->sigmoid_out == 0 || a->sigmoid_out == 1, DCTR_E_ENUM, "edcn_fwd: sigmoid_out = %d", a->sigmoid_out);
-    DCTR_REQUIRE(a->inv_tau == a->inv_tau && a->inv_tau - a->inv_tau == 0.f, DCTR_E_DIM, "edcn_fwd: 1 / tau is not finite");
-    return DCTR_OK;
-}
-
-void edcn_plan(const dctr_edcn_args_t* a, EdPlan* pl) {
-    const int D = a->fields * a->dim;
-    pl->ld = ((D + 15) & ~15) + 4;
-    pl->tpw = D % 64 == 0 ? 4 : D % 32 == 0 ? 2 : 1;
-    pl->fused = false;
-    pl->R = 16;
-    pl->lds = 0;
-    pl->launches = (a->cross_num + ED_MAX_ROUNDS - 1) / ED_MAX_ROUNDS;
-    pl->ws_bytes = 0;
-    if (a->route == DCTR_EDCN_ROUTE_LAYERED || a->bridge == DCTR_EDCN_BRIDGE_ATTENTION || !ed_fused_act(a->activation) ||
-        (a->bridge == DCTR_EDCN_BRIDGE_CONCAT && !ed_fused_act(a->bridge_activation)))
-        return;
-    const size_t gates = 2 * (size_t)a->fields;
-    for (int R = 64; R >= 16; R >>= 1) {
-        const size_t need = (4 * (size_t)R * pl->ld + gates) * sizeof(float);
-        if (need <= (R == 16 ? DCTR_LDS_MAX : ED_LDS_TARGET)) {
-            pl->fused = true;
-            pl->R = R;
-            pl->lds = need;
-            break;
-        }
-    }
-    if (pl->fused && pl->launches > 1) pl->ws_bytes = (size_t)(a->batch > 0 ? a->batch : 0) * D * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" int dctr_edcn_route(const dctr_edcn_args_t* a) {
@@ -385,7 +309,8 @@ extern "C" size_t dctr_edcn_workspace_bytes(const dctr_edcn_args_t* a) {
     return pl.ws_bytes;
 }
 
-extern "C" int dctr_edcn_fwd(const dctr_edcn_args_t* a, void* stream) {
+// dctr_edcn_fwd (tape = NULL) and dctr_edcn_train_fwd (the tape kernel; one launch: cross_num <= ED_MAX_ROUNDS)
+static int edcn_run(const dctr_edcn_args_t* a, float* tape, void* stream) {
     int rc = edcn_check(a);
     if (rc != DCTR_OK) return rc;
     EdPlan pl;
@@ -421,9 +346,12 @@ extern "C" int dctr_edcn_fwd(const dctr_edcn_args_t* a, void* stream) {
     }
     if (a->batch == 0) return DCTR_OK;
     const int tpw = aligned ? pl.tpw : 1;        // (the 8- / 16-byte weight loads need aligned kernels; D % (16 TPW) == 0 keeps the rows so)
-    const void* fn = tpw == 4 ? (const void*)edcn_fwd_kernel<4> : tpw == 2 ? (const void*)edcn_fwd_kernel<2> : (const void*)edcn_fwd_kernel<1>;
-    static thread_local size_t granted[3][DCTR_MAX_DEVICES] = {{0}};
-    hipError_t e = dctr_grant_lds(fn, pl.lds, granted[tpw == 4 ? 2 : tpw == 2 ? 1 : 0]);
+    const void* fn = tape ? (tpw == 4 ? (const void*)edcn_fwd_kernel<4, true> : tpw == 2 ? (const void*)edcn_fwd_kernel<2, true>
+                                                                                         : (const void*)edcn_fwd_kernel<1, true>)
+                          : (tpw == 4 ? (const void*)edcn_fwd_kernel<4, false> : tpw == 2 ? (const void*)edcn_fwd_kernel<2, false>
+                                                                                          : (const void*)edcn_fwd_kernel<1, false>);
+    static thread_local size_t granted[6][DCTR_MAX_DEVICES] = {{0}};
+    hipError_t e = dctr_grant_lds(fn, pl.lds, granted[(tape ? 3 : 0) + (tpw == 4 ? 2 : tpw == 2 ? 1 : 0)]);
     DCTR_REQUIRE(e == hipSuccess, (int)e, "edcn_fwd: cannot raise dynamic LDS: %s", hipGetErrorString(e));
     const int64_t n_tiles = dctr_ceil_div(a->batch, (int64_t)pl.R), cap = 4 * (int64_t)dctr_n_cus();
     const dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap)), block(ED_THREADS);
@@ -471,16 +399,40 @@ extern "C" int dctr_edcn_fwd(const dctr_edcn_args_t* a, void* stream) {
         } else {
             p.br_out = (float*)a->workspace;        // a tile reads its rows before it writes them: in place
         }
-        if (tpw == 4)
-            DCTR_LAUNCH(edcn_fwd_kernel<4>, grid, block, pl.lds, st, p);
-        else if (tpw == 2)
-            DCTR_LAUNCH(edcn_fwd_kernel<2>, grid, block, pl.lds, st, p);
-        else
-            DCTR_LAUNCH(edcn_fwd_kernel<1>, grid, block, pl.lds, st, p);
+        p.tape = tape;
+#define ED_FWD_LAUNCH(T, TAPE) DCTR_LAUNCH((edcn_fwd_kernel<T, TAPE>), grid, block, pl.lds, st, p)
+        if (tape) {
+            if (tpw == 4) ED_FWD_LAUNCH(4, true);
+            else if (tpw == 2) ED_FWD_LAUNCH(2, true);
+            else ED_FWD_LAUNCH(1, true);
+        } else {
+            if (tpw == 4) ED_FWD_LAUNCH(4, false);
+            else if (tpw == 2) ED_FWD_LAUNCH(2, false);
+            else ED_FWD_LAUNCH(1, false);
+        }
+#undef ED_FWD_LAUNCH
         rc = dctr_launch_status("dctr_edcn_fwd");
         if (rc != DCTR_OK) return rc;
     }
     return DCTR_OK;
+}
+
+extern "C" int dctr_edcn_fwd(const dctr_edcn_args_t* a, void* stream) { return edcn_run(a, nullptr, stream); }
+
+extern "C" size_t dctr_edcn_tape_bytes(const dctr_edcn_train_args_t* t) {
+    if (!t || edcn_check(&t->fwd) != DCTR_OK) return 0;
+    return (size_t)t->fwd.cross_num * (size_t)t->fwd.batch * 3 * (size_t)t->fwd.fields * t->fwd.dim * sizeof(float);
+}
+
+extern "C" int dctr_edcn_train_fwd(const dctr_edcn_train_args_t* t, void* stream) {
+    DCTR_REQUIRE(t, DCTR_E_NULL, "edcn_train_fwd: null args");
+    int rc = edcn_check(&t->fwd);
+    if (rc != DCTR_OK) return rc;
+    DCTR_REQUIRE(dctr_edcn_bwd_supported(t), DCTR_E_UNSUPPORTED,
+                 "edcn_train_fwd: these shapes / options are not the backward's (dctr_edcn_bwd_supported)");
+    DCTR_REQUIRE(t->fwd.batch == 0 || t->tape, DCTR_E_NULL, "edcn_train_fwd: null tape (dctr_edcn_tape_bytes)");
+    DCTR_REQUIRE(t->fwd.batch == 0 || dctr_aligned16(t->tape), DCTR_E_ALIGN, "edcn_train_fwd: tape not 16-B aligned");
+    return edcn_run(&t->fwd, t->tape, stream);
 }
 
 extern "C" int dctr_edcn_regulate(const float* x, int64_t x_stride, int64_t batch, int32_t fields, int32_t dim, const float* g_deep,

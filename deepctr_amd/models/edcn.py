@@ -4,7 +4,8 @@ run side by side, a BridgeModule joins their outputs, and two RegulationModules 
 the next round's inputs; Dense(1, use_bias=False) over [cross_out, deep_out, bridge_out] of the last round + the linear logit.
 
 Forward: fused gather (+ linear logit) -> dnn_in -> ``ops.edcn``: ONE ``dctr_edcn_fwd`` launch for the whole tower, head, linear logit,
-bias and sigmoid where the library takes the shape on chip, else the layered route.  Training: the autograd step."""
+bias and sigmoid where the library takes the shape on chip, else the layered route.  Training: the autograd step, with
+the tower as one differentiable HIP op (``ops.EDCNTowerFunction``) where ``training._edcn_on_hip`` says so, else in torch ops."""
 import torch
 
 from .. import ops
@@ -91,6 +92,8 @@ class _EDCN(FeatureModel):
         F, d = self.n_fields, self.emb_dim
         x = torch.stack(parts[:F], dim=1)                            # [B, F, d]
         B = x.shape[0]
+        if tops._edcn_on_hip(self, x, training):
+            return tops.edcn_tower(self, x)                          # one differentiable HIP op
         deep = (x * self._autograd_gate(self.regulations[0])).reshape(B, F * d)
         cross = (x * self._autograd_gate(self.regulations[1])).reshape(B, F * d)
         for i in range(self.cross_num):

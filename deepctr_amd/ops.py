@@ -2468,6 +2468,264 @@ def edcn(x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_bi
     return logit, out
 
 
+def _edcn_train_shape(batch, fields, dim, cross_num, bridge_type, parameterization, activation, bridge_activation, bn=False, weights=True,
+                      slices=0):
+    """dctr_edcn_train_args_t with the fields the host-only queries read (shapes, options, which gradients are wanted)."""
+    t = _C.edcn.TrainArgs(slices=int(slices))
+    t.fwd = _edcn_args(batch, fields, dim, cross_num, bridge_type, parameterization, 1.0, activation, bridge_activation, None)
+    if bn:
+        t.fwd.bn_scale = t.fwd.bn_shift = 16          # (compared with NULL only)
+    if weights:
+        t.d_dnn_w = t.d_cross_w = t.d_bridge_w = 16
+    return t
+
+
+def edcn_bwd_supported(fields, dim, cross_num=1, bridge_type="hadamard_product", parameterization="vector", activation="relu",
+                       bridge_activation="relu", bn=False):
+    """Do dctr_edcn_train_fwd / dctr_edcn_bwd take these shapes and options (read from the library: it knows its LDS plan)?  ``bn``: the
+    DNNs carry a BatchNormalization affine."""
+    if int(fields) < 1 or int(dim) < 1 or int(cross_num) < 1 or bridge_type not in _C.edcn.BRIDGES \
+            or parameterization not in ("vector", "matrix") or activation not in _C.ACT_CODES or bridge_activation not in _C.ACT_CODES:
+        return False
+    t = _edcn_train_shape(0, fields, dim, cross_num, bridge_type, parameterization, activation, bridge_activation, bn)
+    return bool(_C.lib().dctr_edcn_bwd_supported(ctypes.byref(t)))
+
+
+def edcn_tape_bytes(batch, fields, dim, cross_num):
+    """Bytes of the tape edcn_train writes: [cross_num, batch, 3 * fields * dim] float32 (read from the library)."""
+    t = _edcn_train_shape(batch, fields, dim, cross_num, "hadamard_product", "vector", "relu", "relu")
+    return int(_C.lib().dctr_edcn_tape_bytes(ctypes.byref(t)))
+
+
+def edcn_bwd_workspace_bytes(batch, fields, dim, cross_num=1, bridge_type="hadamard_product", parameterization="vector", activation="relu",
+                             bridge_activation="relu", weights=True, slices=0):
+    """Bytes of workspace dctr_edcn_bwd needs (read from the library; 0 for what it refuses).  ``weights``: are the [D, D] weight
+    gradients wanted (their operands and the partials of ``slices`` batch slices wait in the workspace; 0 = the library's choice)."""
+    t = _edcn_train_shape(batch, fields, dim, cross_num, bridge_type, parameterization, activation, bridge_activation, False, weights, slices)
+    return int(_C.lib().dctr_edcn_bwd_workspace_bytes(ctypes.byref(t)))
+
+
+def _edcn_train_operands(op, x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, bridge_type, parameterization, tau,
+                         activation, bridge_weights, bridge_activation, x_offset, head_w):
+    """What edcn_train() and edcn_bwd() read alike: x (_x_in_place) and the live weights of every round, checked as edcn() checks them.
+    Returns (t, x, B, F, E, L, keep, tensors): ``t`` the dctr_edcn_train_args_t with t.fwd filled, ``keep`` the host pointer arrays."""
+    x, B, F, E, x_stride, x_offset = _x_in_place(op, x, int(fields), int(dim), x_offset)
+    D, L = F * E, len(dnn_kernels)
+    t = _C.edcn.TrainArgs()
+    t.fwd = _edcn_args(B, F, E, L, bridge_type, parameterization, tau, activation, bridge_activation, None, x_stride, x_offset)
+    if not (len(gates) == 2 * L and len(cross_kernels) == len(cross_biases) == len(dnn_biases) == L):
+        raise ValueError("%s: %d rounds take %d gates and %d of every other weight" % (op, L, 2 * L, L))
+    for k, g in enumerate(gates):
+        _vec(op, "gates[%d]" % k, g, F)
+    for i in range(L):
+        _vec(op, "cross_kernels[%d]" % i, cross_kernels[i], D if parameterization == "vector" else D * D)
+        _vec(op, "cross_biases[%d]" % i, cross_biases[i], D)
+        _vec(op, "dnn_kernels[%d]" % i, dnn_kernels[i], D * D)
+        _vec(op, "dnn_biases[%d]" % i, dnn_biases[i], D)
+    tensors = [x] + list(gates) + list(cross_kernels) + list(cross_biases) + list(dnn_kernels) + list(dnn_biases)
+    keep = [_ptr_array(ts) for ts in (gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases)]
+    a = t.fwd
+    a.x = x.data_ptr()
+    a.gates, a.cross_w, a.cross_b, a.dnn_w, a.dnn_b = (ctypes.cast(p, ctypes.c_void_p) for p in keep)
+    if bridge_type == "concatenation":
+        if bridge_weights is None or len(bridge_weights) != L:
+            raise ValueError("%s: bridge_type %r takes bridge_weights per round" % (op, bridge_type))
+        for i, bw in enumerate(bridge_weights):
+            _vec(op, "bridge_weights[%d] kernel" % i, bw[0], 2 * D * D)
+            _vec(op, "bridge_weights[%d] bias" % i, bw[1], D)
+            tensors += list(bw)
+        keep += [_ptr_array([bw[j] for bw in bridge_weights]) for j in range(2)]
+        a.bridge_w, a.bridge_b = (ctypes.cast(p, ctypes.c_void_p) for p in keep[-2:])
+    if head_w is not None:
+        _vec(op, "head_w", head_w, 3 * D)
+        a.head_w = head_w.data_ptr()
+        tensors.append(head_w)
+    if not _C.lib().dctr_edcn_bwd_supported(ctypes.byref(t)):
+        raise ValueError("%s: %d fields of dim %d, %d rounds, bridge %r, activations %r / %r: not what dctr_edcn_bwd takes "
+                         "(ops.edcn_bwd_supported)" % (op, F, E, L, bridge_type, activation, bridge_activation))
+    return t, x, B, F, E, L, keep, tensors
+
+
+def edcn_train(x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, bridge_type="hadamard_product",
+               parameterization="vector", tau=1.0, activation="relu", bridge_weights=None, bridge_activation="relu", x_offset=0, head_w=None,
+               logit=None, out=None, out_offset=0, tape=None):
+    """edcn() for training (include/dctr.h: dctr_edcn_train_fwd): the same launch under one more flag, which also writes ``tape``
+    [cross_num, B, 3D] = c, h, br of every round (a contiguous float32 tensor, default: a new one).  Operands as edcn(), without bn /
+    dice / add / global_bias / sigmoid: what ops.edcn_bwd_supported accepts.  ``logit`` / ``out`` as edcn() (default: the logit with
+    head_w, else out); their bits are edcn()'s.  Returns (logit, out, tape)."""
+    t, x, B, F, E, L, keep, tensors = _edcn_train_operands("edcn_train", x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels,
+                                                           dnn_biases, bridge_type, parameterization, tau, activation, bridge_weights,
+                                                           bridge_activation, x_offset, head_w)
+    D = F * E
+    if logit is None and out is None:
+        logit, out = (True, None) if head_w is not None else (None, True)
+    if logit is True:
+        logit = torch.empty(B, dtype=torch.float32, device=x.device)
+    if out is True:
+        out, out_offset = torch.empty(B, 3 * D, dtype=torch.float32, device=x.device), 0
+    if logit is not None:
+        _vec("edcn_train", "logit", logit, B)
+        if head_w is None:
+            raise ValueError("edcn_train: a logit needs head_w [3 * fields * dim]")
+        t.fwd.logit = logit.data_ptr()
+    if out is not None:
+        t.fwd.out, t.fwd.out_stride, t.fwd.out_offset = out.data_ptr(), _rows2d("edcn_train", "out", out, B, 3 * D, out_offset), int(out_offset)
+    if tape is None:
+        tape = torch.empty(L, B, 3 * D, dtype=torch.float32, device=x.device)
+    _vec("edcn_train", "tape", tape, L * B * 3 * D)
+    t.tape = tape.data_ptr()
+    _dev_check(logit, out, tape, *tensors)
+    _C.check(_C.lib().dctr_edcn_train_fwd(ctypes.byref(t), _C.stream_ptr()), "dctr_edcn_train_fwd")
+    del keep
+    return logit, out, tape
+
+
+def _edcn_grad_list(op, name, want, like, sizes, device):
+    """A per-round gradient output of edcn_bwd: None / False (not wanted), True (allocated here in the shapes of ``like``) or a list
+    with a contiguous float32 tensor of ``sizes[i]`` elements, or None, per entry -> (list or None, host pointer array or None)."""
+    if want is None or want is False:
+        return None, None
+    if want is True:
+        want = [torch.empty(w.shape, dtype=torch.float32, device=device) for w in like]
+    want = list(want)
+    if len(want) != len(sizes):
+        raise ValueError("%s: %s takes %d entries" % (op, name, len(sizes)))
+    for i, g in enumerate(want):
+        if g is not None:
+            _vec(op, "%s[%d]" % (name, i), g, sizes[i])
+    return want, _ptr_array(want)
+
+
+def edcn_bwd(x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels, dnn_biases, tape, d_logit=None, d_out=None,
+             bridge_type="hadamard_product", parameterization="vector", tau=1.0, activation="relu", bridge_weights=None,
+             bridge_activation="relu", x_offset=0, head_w=None, dx=None, dx_offset=0, accumulate=False, d_gates=None, d_cross_w=None,
+             d_cross_b=None, d_dnn_w=None, d_dnn_b=None, d_bridge_w=None, d_bridge_b=None, d_head_w=None, slices=0, workspace=None):
+    """Backward of edcn_train() (include/dctr.h: dctr_edcn_bwd): x and the live weights as the forward read them, ``tape`` as it wrote
+    it; ``d_logit`` [B] (needs head_w) and / or ``d_out`` [B, >= 3D] (unit column stride): the seed of the last round is
+    d_out + d_logit * head_w.  Outputs — each None / False (not wanted, skipped) or True (allocated here): ``dx`` a float32 view that
+    holds the F*E columns from ``dx_offset`` (_dx_operand; added to with ``accumulate``); ``d_gates`` [2L], ``d_cross_w`` / ``d_cross_b``
+    / ``d_dnn_w`` / ``d_dnn_b`` / ``d_bridge_w`` / ``d_bridge_b`` [L]: lists of contiguous float32 tensors (an entry may be None);
+    ``d_head_w`` [3D] (True: head_w's shape).  All are OVERWRITTEN.  ``slices``: the batch slices of the weight-gradient pass (0: the library's choice,
+    1 .. 256 forces it).  No atomics: bit-identical from call to call.  Returns (dx, d_gates, d_cross_w, d_cross_b, d_dnn_w, d_dnn_b,
+    d_bridge_w, d_bridge_b, d_head_w)."""
+    t, x, B, F, E, L, keep, tensors = _edcn_train_operands("edcn_bwd", x, fields, dim, gates, cross_kernels, cross_biases, dnn_kernels,
+                                                           dnn_biases, bridge_type, parameterization, tau, activation, bridge_weights,
+                                                           bridge_activation, x_offset, head_w)
+    D, dev = F * E, x.device
+    if not 0 <= int(slices) <= 256:
+        raise ValueError("edcn_bwd: slices = %d: 0 or 1 .. 256" % int(slices))
+    t.slices, t.accumulate = int(slices), int(bool(accumulate))
+    if tape is None or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() != L * B * 3 * D:
+        raise ValueError("edcn_bwd: tape must be the contiguous float32 [%d, %d, %d] tensor edcn_train wrote" % (L, B, 3 * D))
+    t.tape = tape.data_ptr()
+    if d_logit is None and d_out is None:
+        raise ValueError("edcn_bwd: give d_logit, d_out or both")
+    if d_logit is not None:
+        if head_w is None:
+            raise ValueError("edcn_bwd: d_logit needs head_w [3 * fields * dim]")
+        _vec("edcn_bwd", "d_logit", d_logit, B)
+        t.d_logit = d_logit.data_ptr()
+    if d_out is not None:
+        t.d_out, t.d_out_stride = d_out.data_ptr(), _rows2d("edcn_bwd", "d_out", d_out, B, 3 * D)
+    if dx is True:
+        dx, dx_offset = torch.empty(B, D, dtype=torch.float32, device=dev), 0
+        if accumulate:
+            dx.zero_()
+    elif dx is False:
+        dx = None
+    if dx is not None:
+        t.dx, t.dx_stride, t.dx_offset = dx.data_ptr(), _dx_operand("edcn_bwd", dx, B, F, E, dx_offset), int(dx_offset)
+    matrix, concat = parameterization == "matrix", bridge_type == "concatenation"
+    if not concat and (d_bridge_w or d_bridge_b):
+        raise ValueError("edcn_bwd: d_bridge_w / d_bridge_b exist with the concatenation bridge only")
+    bw = [b[0] for b in bridge_weights] if concat else []
+    bb = [b[1] for b in bridge_weights] if concat else []
+    outs = []
+    for name, want, like, size in (("d_gates", d_gates, gates, F), ("d_cross_w", d_cross_w, cross_kernels, D * D if matrix else D),
+                                   ("d_cross_b", d_cross_b, cross_biases, D), ("d_dnn_w", d_dnn_w, dnn_kernels, D * D),
+                                   ("d_dnn_b", d_dnn_b, dnn_biases, D), ("d_bridge_w", d_bridge_w, bw, 2 * D * D),
+                                   ("d_bridge_b", d_bridge_b, bb, D)):
+        lst, arr = _edcn_grad_list("edcn_bwd", name, want, like, [size] * len(like), dev)
+        outs.append(lst)
+        if arr is not None:
+            keep.append(arr)
+            setattr(t, name, ctypes.cast(arr, ctypes.c_void_p))
+            tensors += [g for g in lst if g is not None]
+    if d_head_w is True:
+        d_head_w = torch.empty(3 * D if head_w is None else tuple(head_w.shape), dtype=torch.float32, device=dev)
+    elif d_head_w is False:
+        d_head_w = None
+    if d_head_w is not None:
+        if d_logit is None:
+            raise ValueError("edcn_bwd: d_head_w needs d_logit")
+        _vec("edcn_bwd", "d_head_w", d_head_w, 3 * D)
+        t.d_head_w = d_head_w.data_ptr()
+    _dev_check(tape, d_logit, d_out, dx, d_head_w, workspace, *tensors)
+    _keep_ws = _workspace("edcn_bwd", t, int(_C.lib().dctr_edcn_bwd_workspace_bytes(ctypes.byref(t))), workspace, dev)
+    _C.check(_C.lib().dctr_edcn_bwd(ctypes.byref(t), _C.stream_ptr()), "dctr_edcn_bwd")
+    del keep
+    return (dx,) + tuple(outs) + (d_head_w,)
+
+
+class EDCNTowerFunction(torch.autograd.Function):
+    """EDCN's tower with its head as one differentiable op (once differentiable): edcn_train() forward with the tape kept, ONE edcn_bwd()
+    call backward.  ``apply(x, opts, head_w, *weights)``: x [B,F,d]; ``opts`` = (bridge_type, parameterization, tau, activation,
+    bridge_activation); head_w: Dense(1)'s kernel [3D, 1]; ``weights`` = the 2L gates, then L each of the cross kernels, cross biases,
+    DNN kernels, DNN biases (, bridge kernels, bridge biases with 'concatenation'), the live tensors in their own shapes.  Returns the
+    tower's logit [B] = [c, h, br] . head_w.  Gradients are formed only for the inputs that need them; none leaves through atomics."""
+
+    @staticmethod
+    def _split(weights, concat):
+        n = len(weights) // (8 if concat else 6)
+        if n < 1 or len(weights) != n * (8 if concat else 6):
+            raise ValueError("EDCNTowerFunction: %d weights: 2L gates and L of each other kind" % len(weights))
+        parts = [list(weights[:2 * n])] + [list(weights[(2 + j) * n:(3 + j) * n]) for j in range(6 if concat else 4)]
+        return n, parts
+
+    @staticmethod
+    def forward(ctx, x, opts, head_w, *weights):
+        ctx.set_materialize_grads(False)
+        bridge_type, parameterization, tau, activation, bridge_activation = opts
+        if x.dim() != 3:
+            raise ValueError("EDCNTowerFunction: x must be [B,F,d]")
+        B, F, d = x.shape
+        x2 = _f32c(x.detach(), "x").view(B, F * d)
+        ws = [_f32c(w.detach(), "weight") for w in weights]
+        hw = _f32c(head_w.detach(), "head_w")
+        concat = bridge_type == "concatenation"
+        L, parts = EDCNTowerFunction._split(ws, concat)
+        bw = list(zip(parts[5], parts[6])) if concat else None
+        logit, _, tape = edcn_train(x2, F, d, parts[0], parts[1], parts[2], parts[3], parts[4], bridge_type, parameterization, tau,
+                                    activation, bw, bridge_activation, head_w=hw, logit=True)
+        ctx.opts, ctx.shape, ctx.n_w = opts, (B, F, d), len(ws)
+        ctx.save_for_backward(x2, tape, hw, *ws)
+        return logit
+
+    @staticmethod
+    def backward(ctx, d_logit):
+        n = 3 + ctx.n_w
+        if d_logit is None:
+            return (None,) * n
+        bridge_type, parameterization, tau, activation, bridge_activation = ctx.opts
+        B, F, d = ctx.shape
+        saved = list(ctx.saved_tensors)
+        x2, tape, hw, ws = saved[0], saved[1], saved[2], saved[3:]
+        concat = bridge_type == "concatenation"
+        L, parts = EDCNTowerFunction._split(ws, concat)
+        need = ctx.needs_input_grad
+        _, views = _zeroed_grads(ws, [bool(v) for v in need[3:]], x2.device)
+        _, gparts = EDCNTowerFunction._split(views, concat)
+        wanted = [g if any(v is not None for v in g) else None for g in gparts]
+        bw = list(zip(parts[5], parts[6])) if concat else None
+        res = edcn_bwd(x2, F, d, parts[0], parts[1], parts[2], parts[3], parts[4], tape, d_logit=_grad_operand(d_logit, False),
+                       bridge_type=bridge_type, parameterization=parameterization, tau=tau, activation=activation, bridge_weights=bw,
+                       bridge_activation=bridge_activation, head_w=hw, dx=bool(need[0]), d_gates=wanted[0], d_cross_w=wanted[1],
+                       d_cross_b=wanted[2], d_dnn_w=wanted[3], d_dnn_b=wanted[4], d_bridge_w=wanted[5] if concat else None,
+                       d_bridge_b=wanted[6] if concat else None, d_head_w=bool(need[2]))
+        dx, d_head = res[0], res[8]
+        return (None if dx is None else dx.view(B, F, d), None, None if d_head is None else d_head.view(hw.shape)) + tuple(views)
+
+
 _MTL_ROUTES = {None: _C.mtl.ROUTE_AUTO, "auto": _C.mtl.ROUTE_AUTO, "layered": _C.mtl.ROUTE_LAYERED}
 _MTL_ROUTE_NAMES = {_C.mtl.ROUTE_FUSED: "fused", _C.mtl.ROUTE_LAYERED: "layered"}
 _MTL_MEMBERS = {}               # (device, members) -> int32 device copy of a gate-member list (dctr_mtl_mix reads it on the device)

@@ -416,6 +416,50 @@ def input_aware_fm(x, sources, softmax, terms=None, mprime=None):
     return ops.InputAwareFMFunction.apply(x, terms, mprime, bool(softmax), *flat)
 
 
+# The row counts at which EDCN's autograd step takes ops.EDCNTowerFunction; outside them it keeps the torch ops of
+# _EDCN._autograd_logit.  From profiles/edcn_bwd.txt (26 x 16, cross_num 2, two runs in one call, ms a step with the op off / on):
+#                                  4,096 rows                      65,536 rows
+#   addition       vector   5.14 / 4.62 and 4.13 / 3.53     11.72 / 14.14 and 11.78 / 14.36
+#   addition       matrix   5.24 / 4.56 and 4.17 / 3.88     12.62 / 24.65 and 12.60 / 24.61
+#   product        vector   5.14 / 4.57 and 4.20 / 3.50     12.02 / 14.30 and 11.96 / 14.28
+#   product        matrix   5.21 / 4.59 and 4.17 / 3.87     12.70 / 24.61 and 12.73 / 24.68
+#   concatenation  vector   5.46 / 4.62 and 4.38 / 4.16     15.02 / 28.00 and 15.10 / 28.20
+#   concatenation  matrix   5.44 / 4.80 and 4.39 / 4.79     15.83 / 38.04 and 15.88 / 38.24
+# The op is no slower at 4,096 rows in 11 of the 12 measurements (1.05 - 1.20x; concatenation x matrix 1.13x and 0.92x) and loses at
+# 65,536 in all of them (0.83x down to 0.41x): its row pass holds 16 rows a workgroup, one workgroup per CU, and sits at 0.04 - 0.10 of
+# its f32-MFMA bound, while rocBLAS runs the large batch near its own.  A lower threshold alone cannot say "wins at the smaller count,
+# loses at the larger": EDCN_HIP_MIN_ROWS is 0 (it wins at the smallest count measured) and EDCN_HIP_MAX_ROWS, the largest count at which
+# it was measured to win, closes the range from above.  Not measured: any other row count or shape.
+EDCN_HIP_MIN_ROWS = 0
+EDCN_HIP_MAX_ROWS = 4096
+
+
+def _edcn_on_hip(model, x, training):
+    """The gate of edcn_tower inside the autograd step (models/edcn.py), worded as _ifm_on_hip: on the GPU, with gradients enabled,
+    HIP_AUTOGRAD_OPS on, float32, no BatchNormalization (its training statistics are not the kernel's affine), no active dropout,
+    EDCN_HIP_MIN_ROWS .. EDCN_HIP_MAX_ROWS rows, and shapes and options dctr_edcn_bwd takes.  x: [B,F,d]."""
+    if not (x.is_cuda and torch.is_grad_enabled() and HIP_AUTOGRAD_OPS and x.dtype == torch.float32 and x.dim() == 3
+            and EDCN_HIP_MIN_ROWS <= x.shape[0] <= EDCN_HIP_MAX_ROWS):
+        return False
+    dnns = model.dnn_layers
+    if any(dn.bn_layers for dn in dnns) or (training and any(getattr(dn, "dropout_rate", 0) for dn in dnns)):
+        return False
+    return ops.edcn_bwd_supported(x.shape[1], x.shape[2], model.cross_num, model.bridge_type, model.parameterization, dnns[0].activation,
+                                  model.bridges[0].activation)
+
+
+def edcn_tower(model, x):
+    """EDCN's tower with its head over x [B,F,d] inside the autograd step as ONE differentiable op (ops.EDCNTowerFunction:
+    dctr_edcn_train_fwd forward with the tape kept, dctr_edcn_bwd backward).  Returns the logit [B] of Dense(1) over [c, h, br].  The
+    caller asks _edcn_on_hip first: there is no torch form of this entry."""
+    (gates, cross_w, cross_b, dnn_w, dnn_b), kw = model._tower_args()
+    flat = list(gates) + list(cross_w) + list(cross_b) + list(dnn_w) + list(dnn_b)
+    if model.bridge_type == "concatenation":
+        flat += [b[0] for b in kw["bridge_weights"]] + [b[1] for b in kw["bridge_weights"]]
+    opts = (model.bridge_type, model.parameterization, model.tau, kw["activation"], kw["bridge_activation"])
+    return ops.EDCNTowerFunction.apply(x, opts, model.dense.w("kernel"), *flat)
+
+
 def _mlr_mix(z, region_num, bias, task):
     """z [B, K] (columns region 0..R-1, learner R..2R-1, bias 2R) -> MLR's prediction [B] (reference models/mlr.py:45-54)."""
     R = int(region_num)

@@ -1047,6 +1047,52 @@ size_t dctr_edcn_workspace_bytes(const dctr_edcn_args_t* args);
  * looked at. */
 int dctr_edcn_route(const dctr_edcn_args_t* args);
 int dctr_edcn_fwd(const dctr_edcn_args_t* args, void* stream);
+/* EDCN's tower for training: a forward that keeps a tape, and its backward.
+ *   dctr_edcn_train_fwd: dctr_edcn_fwd on `fwd` (the same kernel under one more flag: logit and out have dctr_edcn_fwd's bits) that also
+ *     writes tape [cross_num, B, 3D] = c, h, br of every round (out is the last round's slice of the same data).
+ *   dctr_edcn_bwd: from x (read in place at fwd.x_offset), the live weights of `fwd` and the tape, the gradient of
+ *     sum_b d_logit[b] * ([c, h, br]_last[b] . head_w) + sum d_out * [c, h, br]_last: the seed of the last round is
+ *     d_out + d_logit * head_w.  fwd.add / global_bias / sigmoid_out / logit / out are not read: the op is the tower with its head.
+ *     A workgroup owns 16 rows and walks the rounds in reverse with four [16, pad16(D) + 4] tiles in LDS; the input-gradient products
+ *     run on v_mfma_f32_16x16x4_f32.  The row pass leaves the pre-activation gradients in the workspace; a second pass forms the
+ *     [D, D] / [2D, D] weight gradients over `slices` batch slices, and a last step adds the partials in a fixed order; the F-, D- and
+ *     3D-sized gradients are summed per workgroup and added the same way.  No atomics: two calls give the same bits; another slice
+ *     count changes the [D, D] / [2D, D] gradients only (by rounding).
+ *   Both take what dctr_edcn_bwd_supported accepts: the fused route's bridges (ADD / HADAMARD / CONCAT), both parameterizations,
+ *   activation / bridge_activation in {LINEAR, RELU}, no bn_scale, at most 32 rounds, while the backward's LDS plan fits 160 KiB
+ *   (D <= 624 at dim 16).  Everything else answers DCTR_E_UNSUPPORTED: the host keeps its torch ops.
+ *   Every gradient is OVERWRITTEN (dx: added to with `accumulate`); a NULL pointer (array or entry) skips that output. */
+typedef struct {
+    dctr_edcn_args_t fwd;         /* shapes, options, x and the live weights as dctr_edcn_fwd reads them; fwd.workspace is not used */
+    float* tape;                  /* [cross_num, B, 3D] contiguous, 16-B aligned: train_fwd writes it, bwd reads it */
+    const float* d_logit;         /* bwd: NULL or [B]; needs fwd.head_w */
+    const float* d_out;           /* bwd: NULL or [B, d_out_stride]: the gradient of c, h, br of the last round in its first 3D columns */
+    int64_t d_out_stride;         /* floats between rows, >= 3D */
+    float* dx;                    /* NULL or [B, dx_stride]: columns [dx_offset, dx_offset + D) written */
+    int64_t dx_stride;
+    int64_t dx_offset;
+    int32_t accumulate;           /* 0: dx is overwritten | 1: added to */
+    int32_t slices;               /* batch slices of the weight-gradient pass: 0 (the library's choice) or 1 .. 256 */
+    float* const* d_gates;        /* NULL, or HOST array [2 * cross_num] of DEVICE pointers (entries may be NULL) -> [F] */
+    float* const* d_cross_w;      /* NULL, or [cross_num] -> [D] (vector) or [D, D] (matrix) */
+    float* const* d_cross_b;      /* NULL, or [cross_num] -> [D] */
+    float* const* d_dnn_w;        /* NULL, or [cross_num] -> [D, D] */
+    float* const* d_dnn_b;        /* NULL, or [cross_num] -> [D] */
+    float* const* d_bridge_w;     /* DCTR_EDCN_BRIDGE_CONCAT: NULL, or [cross_num] -> [2D, D] */
+    float* const* d_bridge_b;     /* DCTR_EDCN_BRIDGE_CONCAT: NULL, or [cross_num] -> [D] */
+    float* d_head_w;              /* NULL or [3D]: sum_b d_logit[b] * [c, h, br]_last[b]; needs d_logit */
+    void* workspace;              /* bwd: device scratch of dctr_edcn_bwd_workspace_bytes() bytes, 16-B aligned */
+    size_t workspace_bytes;
+} dctr_edcn_train_args_t;
+/* 1 when dctr_edcn_train_fwd / dctr_edcn_bwd take these shapes and options, else 0.  Host only: no pointer is followed (fwd.bn_scale is
+ * compared with NULL). */
+int dctr_edcn_bwd_supported(const dctr_edcn_train_args_t* args);
+/* Bytes of the tape (batch, fields, dim, cross_num are read). */
+size_t dctr_edcn_tape_bytes(const dctr_edcn_train_args_t* args);
+/* Bytes dctr_edcn_bwd needs (shapes, options, slices and which weight gradients are wanted are read); 0 for what it refuses. */
+size_t dctr_edcn_bwd_workspace_bytes(const dctr_edcn_train_args_t* args);
+int dctr_edcn_train_fwd(const dctr_edcn_train_args_t* args, void* stream);
+int dctr_edcn_bwd(const dctr_edcn_train_args_t* args, void* stream);
 /* RegulationModule over one read of x [B, x_stride] (F fields of width dim): deep = x * softmax_f(g_deep * inv_tau)[field],
  * cross = x * softmax_f(g_cross * inv_tau)[field].  Either output (with its weights) may be NULL. */
 int dctr_edcn_regulate(const float* x, int64_t x_stride, int64_t batch, int32_t fields, int32_t dim, const float* g_deep,
