@@ -795,6 +795,48 @@ def _field_conv(x, kernels, biases, pools):
     return maps[-1], maps
 
 
+def field_conv_selected(x, kernels, biases, pools, sels=None):
+    """The conv / pool stack of _field_conv with its pooling written as an explicit SELECTION, the arguments of _field_conv.  Per stage
+    ``sel`` [B,rout,E,C] (int64) is the row of the stage's conv output every pooled element comes from, by the reference's own rules on
+    ties: ('kmax', k) the k largest in descending order with equal values in row order (tf.nn.top_k: "if two elements are equal, the
+    lower-index element appears first"), ('max', p) the FIRST maximum of every window (what MaxPool's gradient routes to).  The pooled
+    map is ``gather(conv output, sel)``, so the gradient of a pooled element reaches exactly the row it was taken from: on an exact tie
+    tf.keras and this function move one element, where _field_conv's ``amax`` spreads the gradient evenly over the tied rows and
+    ``topk`` promises no order.  Away from exact ties the values and gradients are _field_conv's up to rounding (the convolution is
+    summed tap by tap here).  ``sels``: None, or the selection of every stage to pool by instead of choosing (a tape: the pooling then
+    makes no choice of its own, whatever the precision).  Returns (last pooled map, every stage's, every stage's sel), the maps
+    channel-last [B,rows,E,C]."""
+    h = x.unsqueeze(-1) if x.dim() == 3 else x              # [B,rows,E,C]
+    maps, chosen = [], []
+    for s, (kern, bias, (kind, arg)) in enumerate(zip(kernels, biases, pools)):
+        if kern.dim() == 4:
+            kern = kern[:, 0]
+        w, rows, arg = kern.shape[0], h.shape[1], int(arg)
+        before = (w - 1) // 2
+        hp = torch.nn.functional.pad(h, (0, 0, 0, 0, before, w - 1 - before))
+        z = bias + hp[:, 0:rows] @ kern[0]
+        for d in range(1, w):
+            z = z + hp[:, d:d + rows] @ kern[d]
+        y = torch.tanh(z)
+        if sels is not None:
+            sel = sels[s].long()
+        else:
+            with torch.no_grad():
+                if kind == "kmax":
+                    sel = torch.sort(y, dim=1, descending=True, stable=True).indices[:, :arg]
+                else:
+                    n = rows // arg
+                    win = y[:, :n * arg].reshape(y.shape[0], n, arg, y.shape[2], y.shape[3])
+                    # the first maximum, spelled out: the smallest position in the window that holds the window's maximum
+                    pos = torch.arange(arg, device=y.device).view(1, 1, arg, 1, 1)
+                    first = torch.where(win == win.amax(dim=2, keepdim=True), pos, arg).amin(dim=2)
+                    sel = first + (torch.arange(n, device=y.device) * arg).view(1, n, 1, 1)
+        h = torch.gather(y, 1, sel)
+        maps.append(h)
+        chosen.append(sel)
+    return maps[-1], maps, chosen
+
+
 def _fgcnn_layer(layer, x):
     """FGCNNLayer.call (reference interaction.py:994-1020) in torch ops: x [B,F,E] -> the new features [B, new, E]."""
     B, E = x.shape[0], x.shape[2]
