@@ -136,6 +136,18 @@ class CrossMixBwdArgs(ctypes.Structure):
                 ("dx_stride", c_i64), ("dx_accumulate", c_i32), ("pad_", c_i32), ("workspace", c_vp), ("workspace_bytes", c_sz)]
 
 
+class gemm(object):
+    """dctr_gemm_group_t (dctr_sgemm_grouped), one level down for the same reason as interacting.Args (tests/test_gemm_cpu.py checks
+    its layout)."""
+    MAX_GROUPS = 8
+
+    class Group(ctypes.Structure):
+        _fields_ = [("A", c_vp), ("B", c_vp), ("C", c_vp), ("stride_a", c_i64), ("stride_b", c_i64), ("stride_c", c_i64),
+                    ("slice_stride_c", c_i64), ("trans_a", c_i32), ("trans_b", c_i32), ("m", c_i32), ("n", c_i32), ("k", c_i32),
+                    ("lda", c_i32), ("ldb", c_i32), ("ldc", c_i32), ("batch", c_i32), ("ones_last", c_i32), ("accumulate", c_i32),
+                    ("k_slices", c_i32)]
+
+
 class interacting(object):
     """dctr_interacting_args_t.  Its mirror sits one level down (interacting.Args): tests/test_cabi.py pairs the module-level mirrors
     with header structs by a fixed list, and tests/test_autoint_cpu.py checks this one against the C compiler's layout the same way."""
@@ -516,6 +528,10 @@ SYMBOLS = {
     "dctr_embed_gather_fm": (ctypes.c_int, [ctypes.POINTER(GatherFmArgs), c_vp]),
     "dctr_sgemm": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, ctypes.c_float, c_vp, c_i32,
                                   c_i64, c_i32, c_vp]),
+    "dctr_sgemm_plan": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                       ctypes.POINTER(c_i32)]),
+    "dctr_gemm_k_slices": (c_i32, [c_i32, c_i32]),
+    "dctr_sgemm_grouped": (ctypes.c_int, [ctypes.POINTER(gemm.Group), c_i32, c_vp]),
     "dctr_hash_fields": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_i32, c_vp]),
     "dctr_embed_pool": (ctypes.c_int, [ctypes.POINTER(PoolArgs), c_vp]),
     "dctr_embed_lookup": (ctypes.c_int, [ctypes.POINTER(LookupArgs), c_vp]),

@@ -270,28 +270,17 @@ static int launch(hipStream_t stream, Op op_a, Op op_b, int m, int n, int k, con
     DCTR_REQUIRE(A != nullptr && B != nullptr && C != nullptr, DCTR_E_NULL, "sgemm: null pointer");
     Params p{};
     fill_params(p, op_a, op_b, m, n, k, A, lda, stride_a, B, ldb, stride_b, beta, C, ldc, stride_c);
-    const int64_t t128 = dctr_ceil_div(p.M, 128) * dctr_ceil_div(p.N, 128) * batch;
-    const bool small = t128 < 2 * (int64_t)dctr_n_cus();       // the 128 x 128 tiling would leave CUs (or their second workgroup slot) idle: 64 x 64 tiles
-    const int bt = small ? 64 : 128;
-    // a small output with a long reduction (dW = X^T dZ over the batch, the CrossNetMix projections' gradients): split K over
-    // workgroups until the chip is filled (>= 256 k per slice), partial products added with float atomics
-    const int64_t tiles = dctr_ceil_div(p.N, bt) * dctr_ceil_div(p.M, bt) * batch;
-    int ksplit = 1;
-    if (tiles * 2 <= (int64_t)dctr_n_cus() && k >= 1024) {
-        int64_t want = 2 * (int64_t)dctr_n_cus() / tiles;
-        if (want > k / 256) want = k / 256;
-        if (want > 32) want = 32;
-        ksplit = want > 1 ? (int)want : 1;
-    }
+    // tile edge and k split: dctr_sgemm_plan (below) is the one statement of the rule, for this launch and for whoever asks
+    int32_t bt = 64, ksplit = 1, kchunk = k;
+    const int rc = dctr_sgemm_plan(m, n, k, batch, 0, &bt, &ksplit, &kchunk);
+    if (rc != DCTR_OK) return rc;
+    const bool small = bt == 64;
     p.ksplit = ksplit;
-    p.kchunk = ksplit > 1 ? (int)(dctr_ceil_div(dctr_ceil_div(k, ksplit), 32) * 32) : k;
-    if (ksplit > 1) {
-        p.ksplit = (int)dctr_ceil_div(k, p.kchunk);            // (no empty slices)
-        if (!p.accumulate) {                                   // atomics add to zero
-            for (int b = 0; b < batch; ++b) {
-                hipError_t e = hipMemset2DAsync(C + (int64_t)b * stride_c, (size_t)ldc * sizeof(float), 0, (size_t)m * sizeof(float), (size_t)n, stream);
-                DCTR_REQUIRE(e == hipSuccess, (int)e, "sgemm: clearing C failed: %s", hipGetErrorString(e));
-            }
+    p.kchunk = kchunk;
+    if (ksplit > 1 && !p.accumulate) {                         // atomics add to zero
+        for (int b = 0; b < batch; ++b) {
+            hipError_t e = hipMemset2DAsync(C + (int64_t)b * stride_c, (size_t)ldc * sizeof(float), 0, (size_t)m * sizeof(float), (size_t)n, stream);
+            DCTR_REQUIRE(e == hipSuccess, (int)e, "sgemm: clearing C failed: %s", hipGetErrorString(e));
         }
     }
     const dim3 grid((unsigned)dctr_ceil_div(p.N, bt), (unsigned)dctr_ceil_div(p.M, bt), (unsigned)(batch * p.ksplit));
@@ -372,4 +361,54 @@ extern "C" int dctr_sgemm(int32_t trans_a, int32_t trans_b, int32_t m, int32_t n
     return dctr_gemm::sgemm_strided_batched((hipStream_t)stream, trans_a ? dctr_gemm::OP_T : dctr_gemm::OP_N,
                                             trans_b ? dctr_gemm::OP_T : dctr_gemm::OP_N, m, n, k, A, lda, stride_a, B, ldb, stride_b, beta, C,
                                             ldc, stride_c, batch);
+}
+
+// The plan of a dctr_sgemm call, host arithmetic only (launch() above runs on what this returns).
+extern "C" int dctr_sgemm_plan(int32_t m, int32_t n, int32_t k, int32_t batch, int32_t n_cus, int32_t* tile, int32_t* k_slices,
+                               int32_t* k_chunk) {
+    DCTR_REQUIRE(m >= 0 && n >= 0 && k >= 0 && batch >= 0 && n_cus >= 0, DCTR_E_DIM, "dctr_sgemm_plan: m=%d n=%d k=%d batch=%d n_cus=%d", m, n,
+                 k, batch, n_cus);
+    DCTR_REQUIRE(tile != nullptr && k_slices != nullptr && k_chunk != nullptr, DCTR_E_NULL, "dctr_sgemm_plan: null pointer");
+    *tile = 64;
+    *k_slices = 1;
+    *k_chunk = k;
+    if (m == 0 || n == 0 || batch == 0) return DCTR_OK;        // nothing is launched
+    const int64_t cus = n_cus > 0 ? n_cus : dctr_n_cus();
+    const int64_t t128 = dctr_ceil_div(n, 128) * dctr_ceil_div(m, 128) * batch;
+    const bool small = t128 < 2 * cus;                         // the 128 x 128 tiling would leave CUs (or their second workgroup slot) idle: 64 x 64 tiles
+    const int bt = small ? 64 : 128;
+    // a small output with a long reduction (dW = X^T dZ over the batch, the CrossNetMix projections' gradients): split K over
+    // workgroups until the chip is filled (>= 256 k per slice), partial products added with float atomics
+    const int64_t tiles = dctr_ceil_div(m, bt) * dctr_ceil_div(n, bt) * batch;
+    int ksplit = 1;
+    if (tiles * 2 <= cus && k >= 1024) {
+        int64_t want = 2 * cus / tiles;
+        if (want > k / 256) want = k / 256;
+        if (want > 32) want = 32;
+        ksplit = want > 1 ? (int)want : 1;
+    }
+    *tile = bt;
+    if (ksplit > 1) {
+        *k_chunk = (int32_t)(dctr_ceil_div(dctr_ceil_div(k, ksplit), 32) * 32);
+        *k_slices = (int32_t)dctr_ceil_div(k, *k_chunk);       // (no empty slices)
+    }
+    return DCTR_OK;
+}
+
+extern "C" int32_t dctr_gemm_k_slices(int32_t k, int32_t rows_per_slice) { return dctr_gemm::k_slices(k, rows_per_slice); }
+
+extern "C" int dctr_sgemm_grouped(const dctr_gemm_group_t* groups, int32_t n_groups, void* stream) {
+    DCTR_REQUIRE(n_groups >= 1 && n_groups <= dctr_gemm::MAX_GROUPS, DCTR_E_DIM, "dctr_sgemm_grouped: %d groups (1..%d)", n_groups,
+                 dctr_gemm::MAX_GROUPS);
+    DCTR_REQUIRE(groups != nullptr, DCTR_E_NULL, "dctr_sgemm_grouped: null pointer");
+    dctr_gemm::GroupDesc g[dctr_gemm::MAX_GROUPS];
+    for (int i = 0; i < n_groups; ++i) {
+        const dctr_gemm_group_t& s = groups[i];
+        DCTR_REQUIRE(s.lda >= 1 && s.ldb >= 1 && s.ldc >= s.m, DCTR_E_DIM, "dctr_sgemm_grouped[%d]: leading dimensions lda=%d ldb=%d ldc=%d (m=%d)", i,
+                     s.lda, s.ldb, s.ldc, s.m);
+        g[i] = dctr_gemm::GroupDesc{s.trans_a ? dctr_gemm::OP_T : dctr_gemm::OP_N, s.trans_b ? dctr_gemm::OP_T : dctr_gemm::OP_N, s.m, s.n, s.k,
+                                    s.A, s.lda, s.stride_a, s.B, s.ldb, s.stride_b, s.C, s.ldc, s.stride_c, s.batch, s.ones_last, s.accumulate,
+                                    s.k_slices, s.slice_stride_c};
+    }
+    return dctr_gemm::sgemm_grouped((hipStream_t)stream, g, n_groups);
 }

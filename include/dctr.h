@@ -2324,6 +2324,51 @@ int dctr_sgemm(int32_t trans_a, int32_t trans_b, int32_t m, int32_t n, int32_t k
                const float* B, int32_t ldb, int64_t stride_b, float beta, float* C, int32_t ldc, int64_t stride_c, int32_t batch,
                void* stream);
 
+/* What a dctr_sgemm call of these sizes runs on (host arithmetic only, no device call unless n_cus == 0; the launcher plans through
+ * this same function): *tile = edge of the square output tile, 64 or 128 — 128 when ceil(m/128) ceil(n/128) batch >= 2 n_cus;
+ * *k_slices > 1: the reduction is cut into that many slices of *k_chunk (a multiple of 32; the last one shorter) which ADD their
+ * products with float atomics — chosen when the tiles fill at most half the CUs and k >= 1024 (>= 256 k per slice, <= 32 slices);
+ * otherwise 1 and *k_chunk = k.  n_cus: the compute-unit count to plan for, 0 = the current device's.  DCTR_E_DIM / DCTR_E_NULL. */
+int dctr_sgemm_plan(int32_t m, int32_t n, int32_t k, int32_t batch, int32_t n_cus, int32_t* tile, int32_t* k_slices, int32_t* k_chunk);
+
+/* Slices a reduction of length k is cut into at about rows_per_slice each: want = min(32, ceil(k / rows_per_slice)),
+ * chunk = ceil(ceil(k / want) / 32) * 32, slices = ceil(k / chunk).  The k_slices a dctr_gemm_group_t takes.  k <= 0: 1. */
+int32_t dctr_gemm_k_slices(int32_t k, int32_t rows_per_slice);
+
+/* Up to 8 independent products in ONE launch (64 x 64 tiles), each C (m x n, ldc) = op(A) op(B) as in dctr_sgemm (the dW products of
+ * every layer of a DNN, the gate products of a BiLSTM backward).  A group with m, n or batch 0 is skipped.
+ *   ones_last   op(B) holds only n - 1 columns in memory; column n - 1 reads as 1.0 for every k, so that column n - 1 of C is
+ *               sum_k op(A)(:, k) (a bias gradient beside its dW).
+ *   accumulate  C += the product (beta = 1).
+ *   k_slices    > 1: must equal ceil(k / chunk) with chunk = ceil(ceil(k / k_slices) / 32) * 32 (dctr_gemm_k_slices gives such a count).
+ *               With slice_stride_c != 0 and no accumulate, slice s STORES the product of its own k range [s chunk, (s + 1) chunk) at
+ *               C + s * slice_stride_c — the caller sums them: no atomics, the same bits on every call.  With slice_stride_c == 0 and
+ *               accumulate the slices add to the one C with float atomics.  Any other pairing: DCTR_E_UNSUPPORTED.
+ * DCTR_E_DIM: n_groups outside 1..8, a negative size, ldc < m, a k_slices the rule does not give;  DCTR_E_NULL: groups, or A / B / C
+ * of a group that is not empty.  All of these are answered before any device call. */
+typedef struct {
+    const float* A;
+    const float* B;
+    float* C;
+    int64_t stride_a;             /* element strides between the `batch` problems of the group             */
+    int64_t stride_b;
+    int64_t stride_c;
+    int64_t slice_stride_c;
+    int32_t trans_a;
+    int32_t trans_b;
+    int32_t m;
+    int32_t n;
+    int32_t k;
+    int32_t lda;
+    int32_t ldb;
+    int32_t ldc;
+    int32_t batch;
+    int32_t ones_last;
+    int32_t accumulate;
+    int32_t k_slices;             /* 0 / 1: one slice                                                       */
+} dctr_gemm_group_t;
+int dctr_sgemm_grouped(const dctr_gemm_group_t* groups, int32_t n_groups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
